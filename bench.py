@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: retargeted frames/s, Unitree G1 29-DoF, SMPL-X mapping (BASELINE.json).
 
-    python bench.py [--gpus N --steps K --warmup W] [--clips S --frames T]
+    python bench.py [--gpus N --steps K --warmup W] [--clips S --frames T] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (two-stage box-constrained IK of every frame, warm start carried
 along each clip exactly as the reference's caller loop does) over one batch of synthetic AMASS-shaped
@@ -11,11 +11,19 @@ torch.distributed.run, spawned before this process touches the GPU) and relays r
 independent, so ranks own disjoint clips and there is no collective inside the timed region (weak
 scaling: S clips per GPU); rank 0 broadcasts the packed model once before it.
 
-One JSON line on stdout (rank 0).  Besides the driver's contract it carries
-  value_unshaped  the same metric on the un-shaped workload: every clip distinct, any initial heading, variable lengths
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times the K steps of the headline workload, writes their
+outputs if --dump-outputs is given and prints the line.  Besides the driver's contract (metric, value, unit, higher_is_better,
+dtype, ms_per_step) it carries
   roofline        dominant kernel (ik_kernel) vs the bound that binds it, FP64 vector issue: SURVEY 8(d)'s flop per solve x
-                  measured solves, over the kernel time from HIP events; `hbm` is the same kernel against the HBM roofline
-                  (north_star asks for it; ~0.3 % by construction, not the bound)
+                  measured solves, over the kernel time from HIP events of the timed steps; `hbm` is the same kernel against
+                  the HBM roofline (north_star asks for it; ~0.3 % by construction, not the bound).  Traffic: the committed
+                  PMC figure, or (--full) child rocprofv3 passes of this run
+--dump-outputs DIR writes what the last timed step returned: DIR/qpos.npy (float64 [n, nq]) and DIR/iters.npy (the int32
+solve word -- solves in bits 0-29, QP iteration cap hit in bit 30 -- as float64 [n]), every frame, or the same seeded sample
+of DUMP_ROWS frames (in frame order) when there are more.  The inputs are the same in every run with the same arguments.
+--full adds everything else:
+  value_unshaped  the same metric on the un-shaped workload: every clip distinct, any initial heading, variable lengths
+  roofline        launch_order.array_order_kernel_ms: the same launch once more in array order
   fk (+ kin_ops), adapters, dataset_path (+ from_joint_files), host_fed, single_clip, long_clips (+ from_files), heterogeneous,
   live_session (+ class_api)                                          the other kernels / modes of the path (N = 1), each kernel
                                                                       against its roofline with PMC traffic where a child pass measures it
@@ -48,6 +56,9 @@ ROBOT, SRC = "unitree_g1", "smplx"
 MEASURED_TRAFFIC = {"robot": "unitree_g1", "src": "smplx", "in_itemsize": 4,
                     "bytes_per_frame": (2 * 942970.5 * 1024 + 1401604.3 * 1024) / 4915200.0, "source": "profiles/r02_v18_pmc_*"}
 
+# --dump-outputs: frames written when the output has more (qpos + solve word: 296 B per G1 frame, 39 MB in all)
+DUMP_ROWS = 1 << 17
+
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
@@ -57,9 +68,13 @@ def parse_args(argv=None):
     ap.add_argument("--clips", type=int, default=8192, help="clips per GPU (AMASS holds >1e4 sequences; several clips per wavefront slot -- 2048 slots on a MI355X -- let the hardware dispatcher balance clips that need more solves than others)")
     ap.add_argument("--frames", type=int, default=3000, help="frames per clip (one AMASS sequence ~3k frames @30fps)")
     ap.add_argument("--distinct", type=int, default=64, help="distinct synthetic clips of the shaped workload, tiled to --clips")
+    ap.add_argument("--full", action="store_true", help="after the headline steps, every other leg of the record: the un-shaped workload, the "
+                    "CPU baseline and parity, the other kernels and modes (N = 1), the exchange steps (N > 1), live PMC traffic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's qpos / solve words to DIR/*.npy "
+                    f"(float64; a fixed seeded sample of {DUMP_ROWS} frames when there are more)")
     ap.add_argument("--cpu-clips", type=int, default=0, help="clips solved by the CPU oracle per workload (baseline + parity); 0 = 4 per host core, capped at 512")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-unshaped", action="store_true", help="skip the un-shaped workload (value_unshaped)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--no-unshaped", action="store_true", help="with --full: skip the un-shaped workload (value_unshaped)")
     ap.add_argument("--hot-only", action="store_true", help="only the warmup + timed launches of the headline workload (no other legs): the "
                     "form profiled under rocprofv3 so the kernel's average duration is that of the timed launch")
     ap.add_argument("--hot-adapters", action="store_true", help="with --hot-only: also run the two input-adapter kernels (profiles/r03_adapters_*)")
@@ -67,8 +82,11 @@ def parse_args(argv=None):
     ap.add_argument("--traffic", choices=["auto", "pmc", "const"], default="auto",
                     help="roofline.traffic: 'pmc' measures HBM bytes of ik_kernel in this run (two child rocprofv3 --pmc passes over a short "
                          "--hot-only launch, FETCH_SIZE x 2 + WRITE_SIZE as MI355X_MICROARCH.md prescribes); 'const' uses the figure of the "
-                         "committed profile; 'auto' = pmc when rocprofv3 is available and this is a plain 1-GPU run, else const")
-    return ap.parse_args(argv)
+                         "committed profile; 'auto' = pmc when rocprofv3 is available and this is a --full 1-GPU run, else const")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> int:
@@ -194,14 +212,33 @@ def bytes_per_frame(cm, in_itemsize=4) -> int:
     return cm.nslot * 7 * in_itemsize + cm.robot.nq * 8 + 4
 
 
+def dump_outputs(path, qpos, iters, rows=DUMP_ROWS):
+    """--dump-outputs: what ik_solve returned in the last timed step -- qpos [N, nq] float64 and the solve word int32 [N] -- as
+    DIR/qpos.npy and DIR/iters.npy, float64; every frame when N <= rows, else `rows` frames drawn with a fixed seed (the same
+    frames in every run of the same size), in frame order.  Outside the timed region."""
+    import numpy as np
+    import torch
+    n = int(qpos.shape[0])
+    if n <= rows:
+        idx = None
+    else:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(20251016).choice(n, size=rows, replace=False))).to(qpos.device)
+    q = qpos if idx is None else qpos.index_select(0, idx)
+    it = iters if idx is None else iters.index_select(0, idx)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "qpos.npy"), q.cpu().numpy().astype(np.float64, copy=False))
+    np.save(os.path.join(path, "iters.npy"), it.cpu().numpy().astype(np.float64))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
+    full = args.full and not args.hot_only   # every leg of the record, not only the headline steps
     # HBM traffic of the dominant kernel, measured in this run by child profiler passes -- taken first, before this process
     # imports torch or touches the GPU
     live_traffic = (None, "not requested", None)
-    if args.traffic == "pmc" or (args.traffic == "auto" and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.hot_only):
+    if args.traffic == "pmc" or (args.traffic == "auto" and args.gpus == 1 and "WORLD_SIZE" not in os.environ and full):
         live_traffic = measure_traffic_pmc()
 
     import numpy as np
@@ -307,9 +344,11 @@ def main():
     mids = mids[-args.steps:]
     probe_ms = float(np.mean([a.elapsed_time(m_) for (a, _), m_ in zip(timed_steps.events, mids)]))
     kern_ms = float(np.mean([m_.elapsed_time(b) for (_, b), m_ in zip(timed_steps.events, mids)]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, iters)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     array_order_ms = None
-    if planned and not args.hot_only:  # what the order is worth: the same launch in array order
+    if planned and full:  # what the order is worth: the same launch in array order
         e0.record(); eng.ik_solve(pos, quat, sc, items, out=out, launch_order=None); e1.record(); torch.cuda.synchronize()
         array_order_ms = e0.elapsed_time(e1)
     mean_solves, solves_hist, qp_capped = solve_stats(iters)
@@ -319,7 +358,7 @@ def main():
     # ---- workload 2 (un-shaped): every clip distinct, initial heading anywhere in (-pi, pi], lengths U(T/3, 5T/3), half the clips
     #      noisy / over-reaching; generated on the GPU (gmr_amd.synth.synth_clips_torch) ----
     un = None
-    if not args.no_unshaped and not args.hot_only:
+    if not args.no_unshaped and full:
         rng = np.random.default_rng(7)
         lens = rng.integers(max(1, T // 3), max(2, 5 * T // 3) + 1, size=S)
         hard_mask = np.arange(S) % 2 == 1
@@ -360,7 +399,7 @@ def main():
             "metric": "retargeted frames/sec (whole node), Unitree G1 29-DoF SMPLX; max qpos err vs CPU",
             "value": value, "n1_equivalent_value": value / world, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
+            "dtype": "f64", "data": "synthetic", "full": full,
             "config": {
                 "workload": f"AMASS-shaped smplx->unitree_g1 (29 DoF, nq 36): {S} clips x {T} frames @30fps per GPU, equal lengths, "
                             f"{D} distinct clips tiled (half exactly reachable, half 2cm/5deg noise + 1.1x arm reach), initial heading within "
@@ -441,7 +480,7 @@ def main():
             result["parity"]["unshaped"] = parity(uout[:e].cpu().numpy(), (uiters[:e] & 0x3FFFFFFF).cpu().numpy(), uq_ref, uit_ref)
             result["cpu_baseline"]["unshaped_value"] = e / t_u
 
-    if rank == 0 and not args.no_cpu and not args.hot_only:
+    if rank == 0 and not args.no_cpu and full:
         try:
             cpu_leg()
         except Exception as ex:  # (the other ranks are waiting at the barrier below: never leave them there)
@@ -452,7 +491,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ N > 1: the exchange steps, on the real outputs
-    if world > 1 and not args.hot_only:
+    if world > 1 and full:
         try:
             cdev = dev if on_rccl else torch.device("cpu")
             ones = torch.ones(1, dtype=torch.float64, device=cdev)
@@ -504,7 +543,7 @@ def main():
                 result["multi_gpu_legs_error"] = repr(ex)
 
     # ------------------------------------------------------------------ N = 1: the other kernels and modes of the path
-    if rank == 0 and world == 1 and (not args.hot_only or args.hot_fk):
+    if rank == 0 and world == 1 and (full or args.hot_fk):
         # fk_kernel (KinematicsModel.forward_kinematics): HBM-bound; positions only, as the dataset path calls it
         nf = n_frames
         root_pos32 = out[:, 0:3].to(torch.float32).contiguous()
@@ -524,7 +563,7 @@ def main():
             "with_rotations": {"frames": nf // 2, "kernel_ms": fk_ms2, "bytes_per_frame": fk_bytes2,
                                "frac": fk_bytes2 * (nf // 2) / (fk_ms2 * 1e-3) / 1e9 / HBM_PEAK_GBS},
         }
-        if not args.no_cpu and not args.hot_only:
+        if not args.no_cpu and full:
             # the CPU path beside it: the oracle's float32 restatement of KinematicsModel.forward_kinematics (positions only) on this
             # host's cores, frames split over threads (the ctypes call releases the GIL); a bounded sample of the same frames
             try:
@@ -557,7 +596,7 @@ def main():
             result["fk"]["kin_ops"] = {"error": repr(ex)}
         attach_fk_traffic(result["fk"], live_traffic[2])
         del root_pos32, root_rot32, dof32, bp_out, br_out
-    if rank == 0 and world == 1 and (not args.hot_only or args.hot_adapters):
+    if rank == 0 and world == 1 and (full or args.hot_adapters):
         # the two input-adapter kernels (rows f-1, f-2): HBM-bound by construction (1.9 - 8.4 KB per frame)
         if args.hot_only:   # the PMC child passes: one timed dispatch per configuration, smaller arrays
             adapters_leg(dev, *ADAPTER_PMC_SIZES, steps=1)
@@ -567,7 +606,7 @@ def main():
                 attach_adapter_traffic(result["adapters"], live_traffic[2])
             except Exception as ex:
                 result["adapters"] = {"error": repr(ex)}
-    if rank == 0 and world == 1 and not args.hot_only:
+    if rank == 0 and world == 1 and full:
         from gmr_amd import dataset
 
         def timed(fn, reps=5):

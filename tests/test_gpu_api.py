@@ -518,7 +518,7 @@ def test_bench_two_rank_path_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(GMR_BENCH_BACKEND="gloo", GMR_BENCH_SHARE_GPU="1")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--clips", "64", "--frames", "60"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--clips", "64", "--frames", "60", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -539,6 +539,39 @@ def test_bench_two_rank_path_rehearsal():
     assert d["strong"]["clips_total"] == 64 and d["strong"]["value"] > 0
     lc = d["long_clips_sharded"]
     assert lc["ranks"] == 2 and lc["clips"] == 77 and lc["frames_per_s"] > 0 and lc["resolved_frames"] < 0.05 * lc["frames"]  # (initial headings within 1 rad: speculative starts hit the right basin)
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) times the headline steps and nothing else; --dump-outputs writes what the last timed step
+    returned, the same in two runs, and those are the solver's results: the first clip against the oracle."""
+    import subprocess
+    import sys
+    S, T = 64, 60
+    runs = []
+    for k in range(2):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--clips", str(S),
+               "--frames", str(T), "--dump-outputs", str(tmp_path / f"run{k}")]
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False and d["unit"] == "frames/s" and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] - S * T / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["roofline"]["kernel_ms"] > 0 and d["roofline"]["launch_order"]["array_order_kernel_ms"] is None
+    for key in ("value_unshaped", "cpu_baseline", "parity", "fk", "adapters", "dataset_path", "single_clip", "long_clips", "live_session", "host_fed"):
+        assert key not in d, key
+    q, it = np.load(tmp_path / "run0" / "qpos.npy"), np.load(tmp_path / "run0" / "iters.npy")
+    assert q.dtype == np.float64 and it.dtype == np.float64 and q.shape == (S * T, 36) and it.shape == (S * T,)
+    assert np.isfinite(q).all() and ((it.astype(np.int64) & 0x3FFFFFFF) >= 1).all()
+    np.testing.assert_array_equal(q, np.load(tmp_path / "run1" / "qpos.npy"))
+    np.testing.assert_array_equal(it, np.load(tmp_path / "run1" / "iters.npy"))
+    cm = compiled("smplx", "unitree_g1")
+    pos, quat, names, offs, _ = synth.synth_clips(cm, 1, T, seed=1000, hard=False, dtype=np.float32)  # bench.py's first clip
+    q_ref, it_ref, _ = Oracle(cm.blob).ik_solve(pos, quat, cm.slot_columns(names), make_items(offs))
+    assert np.abs(q[:T] - q_ref).max() < 1e-6
+    np.testing.assert_array_equal(it[:T].astype(np.int64) & 0x3FFFFFFF, it_ref)
 
 
 def test_c_abi_bvh_file_from_plain_c(golden_dir, tmp_path):

@@ -13,8 +13,9 @@ from gmr_amd.model import HEADER_BYTES
 from gmr_amd.schedule import make_items, partition_clips
 from tests.util import CONFIG_ROBOTS, compiled
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the model XMLs and IK configs of a GMR checkout that these tests read, laid out like one (tests/golden/gmr_root)
+REF = os.path.join(ROOT, "tests", "golden", "gmr_root")
 
 
 def test_header_size_matches_c_struct():
@@ -33,7 +34,6 @@ def test_expected_sizes(robot):
     assert len(compiled("smplx", robot).tasks[0]) == 14
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 @pytest.mark.parametrize("robot", sorted(params._ROBOT_XML_REL))
 def test_packs_are_fresh(robot, monkeypatch):
     """The shipped packs equal what the MJCF compiler produces from the reference's XML today."""
@@ -74,7 +74,6 @@ def test_planar_base_model_and_qpos_layout(tmp_path):
         load_mjcf(str(p))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_gmr_root_switches_registry(monkeypatch):
     monkeypatch.setenv("GMR_ROOT", REF)
     assert str(params.ROBOT_XML_DICT["unitree_g1"]).endswith("g1_mocap_29dof.xml")
@@ -589,8 +588,36 @@ def test_package_exports_the_reference_package_names(monkeypatch):
     assert set(gmr_amd.VIEWER_CAM_DISTANCE_DICT) == set(gmr_amd.ROBOT_XML_DICT.keys()) == set(gmr_amd.ROBOT_BASE_DICT)
     with pytest.raises(AttributeError, match="viewer"):
         gmr_amd.RobotMotionViewer
-    root = os.environ.get("GMR_ROOT") or "/root/reference"
-    if os.path.isdir(os.path.join(root, "assets")):   # (the build container: ASSET_ROOT follows GMR_ROOT like the registry paths)
-        monkeypatch.setenv("GMR_ROOT", root)
-        from gmr_amd import params
-        assert str(params.asset_root()) == os.path.join(root, "assets")
+    # ASSET_ROOT follows GMR_ROOT like the registry paths
+    monkeypatch.setenv("GMR_ROOT", REF)
+    from gmr_amd import params
+    assert str(params.asset_root()) == os.path.join(REF, "assets")
+
+
+def test_bench_options_and_dumped_sample(tmp_path):
+    """bench.py: --full is off by default, --steps is the number of timed steps (>= 1); dump_outputs writes float64 arrays, every
+    frame or the same seeded sample in frame order, within 64 MB for the headline robot."""
+    import torch
+    import bench
+    a = bench.parse_args(["--steps", "4", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (4, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert bench.DUMP_ROWS * (36 + 1) * 8 <= 64 << 20
+    n, nq = 1000, 36
+    q = torch.arange(n * nq, dtype=torch.float64).reshape(n, nq)
+    it = torch.arange(n, dtype=torch.int32) | (1 << 30)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), q, it, rows=100)
+    qa, ia = np.load(tmp_path / "a" / "qpos.npy"), np.load(tmp_path / "a" / "iters.npy")
+    assert qa.dtype == ia.dtype == np.float64 and qa.shape == (100, nq) and ia.shape == (100,)
+    rows = ia.astype(np.int64) & 0x3FFFFFFF
+    assert (np.diff(rows) > 0).all() and (ia.astype(np.int64) >> 30 == 1).all()
+    np.testing.assert_array_equal(qa, q.numpy()[rows])
+    np.testing.assert_array_equal(qa, np.load(tmp_path / "b" / "qpos.npy"))
+    np.testing.assert_array_equal(ia, np.load(tmp_path / "b" / "iters.npy"))
+    bench.dump_outputs(str(tmp_path / "c"), q, it, rows=n)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "qpos.npy"), q.numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "iters.npy"), it.numpy().astype(np.float64))

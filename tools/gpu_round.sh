@@ -3,6 +3,8 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+# the round's bench record carries every leg; the profiled run below stays --hot-only, which --full does not widen
+BENCH_ARGS="--full ${BENCH_ARGS}"
 echo "== pytest -m gpu" | tee gpurun_out/round.log
 timeout -k 10 600 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee -a gpurun_out/round.log
 echo "== smoke" | tee -a gpurun_out/round.log
