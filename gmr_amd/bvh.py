@@ -17,13 +17,13 @@ only flips signs; every consumer is sign-insensitive).
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _native
+from ._filebatch import ClipBatch, Staged, pinned, read_ahead, read_files
 
 _CHANNEL = {"Xrotation": 0, "Yrotation": 1, "Zrotation": 2}
 
@@ -138,16 +138,28 @@ def _layout(names, chan, filename: str):
     return channels, {3: 3 + 3 * J, 6: 6 * J, 9: 3 + 9 * (J - 1)}[channels]
 
 
+def _header(raw, filename: str) -> Tuple[BvhAnim, int, int]:
+    """The HIERARCHY section and MOTION header of a file the loader can lay out: (its skeleton with no rows, frame count, motion offset).
+    A frame count the rest of the file cannot hold is rejected before anything is sized by it: every number takes a byte and a
+    separator (the last one may go without)."""
+    names, parents, offsets, chan, order, fnum, frametime, moff = _parse_header(raw, filename)
+    channels, ncol = _layout(names, chan, filename)
+    if fnum > (len(raw) - moff + 1) // (2 * ncol):
+        raise ValueError(f"{filename}: header says {fnum} frames, more than the motion block can hold")
+    anim = BvhAnim(names, np.asarray(parents, dtype=np.int32), np.asarray(offsets, dtype=np.float64), order, np.zeros((0, ncol)), channels, frametime)
+    return anim, fnum, moff
+
+
 def read_bvh(filename: str) -> BvhAnim:
     with open(filename, "rb") as f:
         raw = f.read()
-    names, parents, offsets, chan, order, fnum, frametime, moff = _parse_header(raw, filename)
-    channels, want = _layout(names, chan, filename)
-    J = len(names)
-    data = _parse_motion(raw[moff:], fnum, 9 * J + 3, filename)  # the ctypes call releases the GIL: files parse in parallel threads
+    anim, fnum, moff = _header(raw, filename)
+    want = anim.rows.shape[1]
+    data = _parse_motion(raw[moff:], fnum, 9 * len(anim.bones) + 3, filename)  # the ctypes call releases the GIL: files parse in parallel threads
     if data.shape[1] != want:
         raise ValueError(f"{filename}: expected {want} columns, found {data.shape[1]}")
-    return BvhAnim(names, np.asarray(parents, dtype=np.int32), np.asarray(offsets, dtype=np.float64), order, data, channels, frametime)
+    anim.rows = data
+    return anim
 
 
 class BvhClip:
@@ -262,149 +274,65 @@ def load_lafan1_file(bvh_file: str, device: int = 0, columns=None) -> BvhClip:
     ``columns``: emit only these entries (e.g. the bones an IK config consumes), in this order."""
     anim = read_bvh(bvh_file)
     dev = torch.device("cuda", device)
-    rows = torch.from_numpy(np.ascontiguousarray(anim.rows)).to(dev)
-    pos, quat, names = _device_fk(anim, rows, dev, columns)
-    offs = np.array([0, len(anim)], dtype=np.int64)
-    height = _clip_heights(anim, rows, offs, dev, full=(pos, names) if columns is None else None)[0]
+    with torch.cuda.device(dev):
+        rows = torch.from_numpy(np.ascontiguousarray(anim.rows)).to(dev)
+        pos, quat, names = _device_fk(anim, rows, dev, columns)
+        offs = np.array([0, len(anim)], dtype=np.int64)
+        height = _clip_heights(anim, rows, offs, dev, full=(pos, names) if columns is None else None)[0]
     return BvhClip(pos, quat, names, height, anim.frametime)
 
 
-class BvhBatch:
-    """Several BVH clips on the GPU as one batch: ``pos [N, B, 3]``, ``quat [N, B, 4]`` (concatenated clips), ``seq_offsets``,
-    one height estimate per clip -- the arguments ``retarget_batch(..., seq_offsets=..., human_heights=...)`` takes.  ``files`` are the
-    clips' files in batch order; ``skipped`` lists (file, reason) of files left out (``skip_errors=True``)."""
+class BvhBatch(ClipBatch):
+    """A ``ClipBatch`` of BVH clips; ``frametimes``: each clip's frame time."""
 
     def __init__(self, pos, quat, names, seq_offsets, heights, frametimes, files, skipped=None):
-        self.pos, self.quat, self.body_names = pos, quat, names
-        self.seq_offsets, self.human_heights, self.frametimes, self.files = seq_offsets, heights, frametimes, files
-        self.skipped = skipped or []
-
-    def __len__(self):
-        return len(self.files)
+        super().__init__(pos, quat, names, seq_offsets, heights, files, skipped)
+        self.frametimes = frametimes
 
 
-def _check_one_skeleton(files, anims):
-    a0 = anims[0]
-    for f, a in zip(files, anims):
-        if a.bones != a0.bones or not np.array_equal(a.parents, a0.parents) or a.order != a0.order or a.channels != a0.channels \
-                or not np.array_equal(a.offsets, a0.offsets):
-            raise ValueError(f"{f}: skeleton differs from {files[0]} (one batch = one skeleton)")
+def _same_skeleton(a: BvhAnim, b: BvhAnim) -> bool:
+    return a.bones == b.bones and np.array_equal(a.parents, b.parents) and tuple(a.order) == tuple(b.order) and a.channels == b.channels \
+        and np.array_equal(a.offsets, b.offsets)
 
 
-class _FileText:
-    """What the host keeps of a batch of files whose MOTION blocks are parsed on the device: the files' bytes in ONE page-locked
-    array (read straight into it) and each file's parsed header."""
-
-    def __init__(self, files, buf, starts, sizes, heads, total, skipped=None):
-        self.files, self.buf, self.starts, self.sizes, self.heads, self.total = files, buf, starts, sizes, heads, total   # starts: per file
-        self.skipped: List[Tuple[str, str]] = skipped or []   # (file, reason) of files left out (skip_errors)
-
-    def anim0(self) -> BvhAnim:
-        names, parents, offsets, chan, order, fnum, frametime, moff = self.heads[0]
-        channels, ncol = _layout(names, chan, self.files[0])
-        return BvhAnim(names, np.asarray(parents, dtype=np.int32), np.asarray(offsets, dtype=np.float64), order, np.zeros((0, ncol)), channels, frametime)
+def _stage(files: List[str], dev: torch.device, threads: int, slot: int, skip_errors: bool) -> Staged:
+    """The files in the BVH loader's pinned ``slot``, each on a 64-byte boundary, with their checked headers (``_header``)."""
+    with torch.cuda.device(dev):
+        return read_files(files, pinned("bvh", slot), 64, _header, threads, skip_errors)
 
 
-_PINNED_TEXT: Dict[int, torch.Tensor] = {}
-
-
-def _pinned_bytes(n: int, slot: int) -> torch.Tensor:
-    """A grow-only page-locked byte buffer per slot (two slots alternate when batches are read ahead): page-locking is what a
-    fresh pinned allocation costs, so it is paid once per process, not once per batch."""
-    t = _PINNED_TEXT.get(slot)
-    if t is None or t.numel() < n:
-        t = torch.empty(max(n, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-        _PINNED_TEXT[slot] = t
-    return t
-
-
-def _read_files(files: List[str], threads: int, slot: int = 0, skip_errors: bool = False) -> _FileText:
-    """Read the files into one pinned byte array (``readinto``: no intermediate bytes objects) and parse their HIERARCHY sections,
-    on ``threads`` host threads (file reads and the native header parser release the GIL).  ``skip_errors``: a file that cannot be
-    read or whose header / layout the loader does not understand is left out and reported in ``.skipped`` -- the per-file
-    ``try / except: print; continue`` of scripts/bvh_to_robot_dataset.py:75-80 -- instead of failing the batch."""
-    from concurrent.futures import ThreadPoolExecutor
-    skipped = []
-    if skip_errors:
-        ok = []
-        for f in files:
-            try:
-                os.path.getsize(f)
-                ok.append(f)
-            except OSError as ex:
-                skipped.append((f, str(ex)))
-        files = ok
-    sizes = np.array([os.path.getsize(f) for f in files], dtype=np.int64)
-    starts = np.concatenate([[0], np.cumsum((sizes + 63) // 64 * 64)]).astype(np.int64)  # every file on a 64-byte boundary
-    buf = _pinned_bytes(int(starts[-1]) + 64, slot)
-    host = buf.numpy()
-
-    def one(k):
-        a, n = int(starts[k]), int(sizes[k])
-        view = host[a:a + n]
-        with open(files[k], "rb", buffering=0) as f:
-            got = 0
-            while got < n:
-                r = f.readinto(memoryview(view)[got:])
-                if not r:
-                    raise ValueError(f"{files[k]}: file shrank while it was read")
-                got += r
-        head = _parse_header(view, files[k])
-        _layout(head[0], head[3], files[k])
-        return head
-
-    def guarded(k):
-        try:
-            return one(k)
-        except (ValueError, NotImplementedError, OSError) as ex:
-            if not skip_errors:
-                raise
-            return ex
-
-    with ThreadPoolExecutor(max_workers=max(1, min(threads, max(1, len(files))))) as ex:
-        heads = list(ex.map(guarded, range(len(files))))
-    if skip_errors and any(isinstance(h, Exception) for h in heads):
-        # the first readable file sets the batch's skeleton; files of another skeleton are left out like broken ones
-        keep = [k for k, h in enumerate(heads) if not isinstance(h, Exception)]
-        skipped += [(files[k], str(h)) for k, h in enumerate(heads) if isinstance(h, Exception)]
-        return _FileText([files[k] for k in keep], buf, starts[:-1][keep], sizes[keep], [heads[k] for k in keep], int(starts[-1]), skipped)
-    return _FileText(files, buf, starts[:-1], sizes, heads, int(starts[-1]), skipped)
-
-
-def _rows_on_device(ft: _FileText, dev: torch.device, stats: Optional[dict] = None, skip_errors: bool = False):
+def _rows_on_device(st: Staged, dev: torch.device, stats: Optional[dict] = None, skip_errors: bool = False):
     """The batch's MOTION blocks -> ``rows [N, ncol]`` float64 on the device (``gmr_bvh_parse_motion_device``): one H2D copy of the
     files as they are, three launches.  Tokens off the exact fast path are parsed by the host parser and patched in; a file whose
     structure the device rejects goes through the host parser whole (which raises what it always raised -- or, with ``skip_errors``,
     has the file left out and reported).  Returns (a0, rows, offs, files, frame times, skipped)."""
     lib = _native.load()
-    skipped = list(ft.skipped)
-    if not ft.files:
+    skipped = list(st.skipped)
+    if not st.files:
         raise ValueError("no readable BVH file in the batch: " + "; ".join(f"{f}: {r}" for f, r in skipped))
-    a0 = ft.anim0()
+    a0 = st.parsed[0][0]
     ncol = int(a0.rows.shape[1])
     keep = []
-    for k, (f, h) in enumerate(zip(ft.files, ft.heads)):
-        names, parents, offsets, chan, order, fnum, frametime, moff = h
-        ch, nc = _layout(names, chan, f)
-        if names != a0.bones or not np.array_equal(parents, a0.parents) or tuple(order) != tuple(a0.order) or ch != a0.channels \
-                or not np.array_equal(np.asarray(offsets, dtype=np.float64), a0.offsets):
-            if not skip_errors:
-                raise ValueError(f"{f}: skeleton differs from {ft.files[0]} (one batch = one skeleton)")
-            skipped.append((f, f"skeleton differs from {ft.files[0]}"))
-        else:
+    for k, (f, (a, _, _)) in enumerate(zip(st.files, st.parsed)):
+        if _same_skeleton(a, a0):
             keep.append(k)
-    if len(keep) != len(ft.files):
-        ft = _FileText([ft.files[k] for k in keep], ft.buf, ft.starts[keep], ft.sizes[keep], [ft.heads[k] for k in keep], ft.total)
-    files, heads = ft.files, ft.heads
-    lens = np.array([h[5] for h in heads], dtype=np.int64)
+        elif not skip_errors:
+            raise ValueError(f"{f}: skeleton differs from {st.files[0]} (one batch = one skeleton)")
+        else:
+            skipped.append((f, f"skeleton differs from {st.files[0]}"))
+    files, starts, sizes, frametimes = [st.files[k] for k in keep], st.starts[keep], st.sizes[keep], [st.parsed[k][0].frametime for k in keep]
+    lens = np.array([st.parsed[k][1] for k in keep], dtype=np.int64)
+    moffs = np.array([st.parsed[k][2] for k in keep], dtype=np.int64)
     offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     N, nf = int(offs[-1]), len(files)
-    total = int(ft.total)
+    if N == 0:  # every clip is empty (the device parser rejects a launch without rows)
+        return a0, torch.empty((0, ncol), dtype=torch.float64, device=dev), offs, files, frametimes, skipped
+    total = int(st.total)
     text = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    text[:total].copy_(ft.buf[:total], non_blocking=True)
+    text[:total].copy_(st.buf[:total], non_blocking=True)
     rows = torch.empty((N, ncol), dtype=torch.float64, device=dev)
-    seg_b = (ft.starts + np.array([h[7] for h in heads], dtype=np.int64)).astype(np.int64)
-    seg_e = (ft.starts + ft.sizes).astype(np.int64)
+    seg_b = (starts + moffs).astype(np.int64)
+    seg_e = (starts + sizes).astype(np.int64)
     status = np.zeros(nf, dtype=np.int32)
     ntok = np.zeros(nf, dtype=np.int64)
     max_slow = 1 << 16
@@ -417,7 +345,7 @@ def _rows_on_device(ft: _FileText, dev: torch.device, stats: Optional[dict] = No
                                          slow.ctypes.data_as(vp), max_slow, C.byref(n_slow), vp(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise RuntimeError(f"gmr_bvh_parse_motion_device failed with status {rc}")
-    host = ft.buf.numpy()
+    host = st.buf.numpy()
     redo = set(int(k) for k in np.nonzero(status)[0])
     ns = int(n_slow.value)
     if ns > max_slow:
@@ -444,7 +372,7 @@ def _rows_on_device(ft: _FileText, dev: torch.device, stats: Optional[dict] = No
             rows.view(-1)[torch.from_numpy(np.asarray(idx, dtype=np.int64)).to(dev)] = torch.from_numpy(np.asarray(val, dtype=np.float64)).to(dev)
     bad = {}
     for k in sorted(redo):  # the host parser decides (and words the error for a malformed file)
-        a, n, moff = int(ft.starts[k]), int(ft.sizes[k]), int(heads[k][7])
+        a, n, moff = int(starts[k]), int(sizes[k]), int(moffs[k])
         try:
             data = _parse_motion(host[a + moff:a + n], int(lens[k]), 9 * len(a0.bones) + 3, files[k])
             if data.shape[1] != ncol:
@@ -456,8 +384,7 @@ def _rows_on_device(ft: _FileText, dev: torch.device, stats: Optional[dict] = No
             continue
         rows[int(offs[k]):int(offs[k + 1])] = torch.from_numpy(data).to(dev)
     if stats is not None:
-        stats.update({"text_bytes": int(ft.sizes.sum()), "numbers": int(N * ncol), "slow_tokens": ns, "files_reparsed_on_host": len(redo)})
-    frametimes = [h[6] for h in heads]
+        stats.update({"text_bytes": int(sizes.sum()), "numbers": int(N * ncol), "slow_tokens": ns, "files_reparsed_on_host": len(redo)})
     if bad:  # leave the broken files' rows out (rare: one device copy of the good ones)
         good = [k for k in range(nf) if k not in bad]
         skipped += [(files[k], bad[k]) for k in sorted(bad)]
@@ -468,7 +395,7 @@ def _rows_on_device(ft: _FileText, dev: torch.device, stats: Optional[dict] = No
 
 
 def load_lafan1_files(bvh_files, device: int = 0, threads: int = 8, columns=None, parse: str = "device", stats: Optional[dict] = None,
-                      skip_errors: bool = False, _slot: int = 0) -> BvhBatch:
+                      skip_errors: bool = False) -> BvhBatch:
     """A folder's worth of BVH files -> one GPU batch (the file loop of scripts/bvh_to_robot_dataset.py:59-80, where every file
     is parsed with regexes and turned into per-frame dicts one after the other).  All files must share one skeleton (names,
     parents, offsets, Euler order, channel layout), as a dataset does; the height estimate of every clip (lafan1.py:45-69, from its
@@ -486,29 +413,31 @@ def load_lafan1_files(bvh_files, device: int = 0, threads: int = 8, columns=None
         raise ValueError("no files")
     dev = torch.device("cuda", device)
     skipped = []
-    if parse == "device":
-        ft = _read_files(files, threads, _slot, skip_errors)
-        a0, rows, offs, files, frametimes, skipped = _rows_on_device(ft, dev, stats, skip_errors)
-    elif parse == "host":
-        if skip_errors:
-            raise ValueError("skip_errors needs parse='device'")
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=max(1, min(threads, len(files)))) as ex:
-            anims = list(ex.map(read_bvh, files))
-        a0 = anims[0]
-        _check_one_skeleton(files, anims)
-        lens = np.array([len(a) for a in anims], dtype=np.int64)
-        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        N, ncol = int(offs[-1]), int(a0.rows.shape[1])
-        rows_h = torch.empty((N, ncol), dtype=torch.float64, pin_memory=True)
-        for a, o in zip(anims, offs[:-1]):
-            rows_h[o:o + len(a)] = torch.from_numpy(a.rows)
-        rows = rows_h.to(dev, non_blocking=True)
-        frametimes = [a.frametime for a in anims]
-    else:
-        raise ValueError("parse must be 'device' or 'host'")
-    pos, quat, names = _device_fk(a0, rows, dev, columns)
-    heights = _clip_heights(a0, rows, offs, dev, full=(pos, names) if columns is None else None)
+    with torch.cuda.device(dev):
+        if parse == "device":
+            a0, rows, offs, files, frametimes, skipped = _rows_on_device(_stage(files, dev, threads, 0, skip_errors), dev, stats, skip_errors)
+        elif parse == "host":
+            if skip_errors:
+                raise ValueError("skip_errors needs parse='device'")
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=max(1, min(threads, len(files)))) as ex:
+                anims = list(ex.map(read_bvh, files))
+            a0 = anims[0]
+            for f, a in zip(files, anims):
+                if not _same_skeleton(a, a0):
+                    raise ValueError(f"{f}: skeleton differs from {files[0]} (one batch = one skeleton)")
+            lens = np.array([len(a) for a in anims], dtype=np.int64)
+            offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            N, ncol = int(offs[-1]), int(a0.rows.shape[1])
+            rows_h = torch.empty((N, ncol), dtype=torch.float64, pin_memory=True)
+            for a, o in zip(anims, offs[:-1]):
+                rows_h[o:o + len(a)] = torch.from_numpy(a.rows)
+            rows = rows_h.to(dev, non_blocking=True)
+            frametimes = [a.frametime for a in anims]
+        else:
+            raise ValueError("parse must be 'device' or 'host'")
+        pos, quat, names = _device_fk(a0, rows, dev, columns)
+        heights = _clip_heights(a0, rows, offs, dev, full=(pos, names) if columns is None else None)
     return BvhBatch(pos, quat, names, offs, heights, frametimes, files, skipped)
 
 
@@ -516,30 +445,22 @@ def iter_lafan1_batches(bvh_files, batch_files: int = 32, device: int = 0, threa
     """The folder in batches of ``batch_files`` files, read ahead: while the caller works on batch k (its ``retarget_batch`` call,
     writing the results), a background thread reads batch k + 1's files and parses their headers into the other pinned buffer.
     ``skip_errors``: broken files are left out of their batch and listed in ``batch.skipped``; a batch without a good file is skipped."""
-    from concurrent.futures import ThreadPoolExecutor
     files = [str(f) for f in bvh_files]
-    groups = [files[i:i + batch_files] for i in range(0, len(files), max(1, batch_files))]
-    if not groups:
-        return
     dev = torch.device("cuda", device)
-    with ThreadPoolExecutor(max_workers=1) as bg:
-        nxt = bg.submit(_read_files, groups[0], threads, 0, skip_errors)
-        for g in range(len(groups)):
-            ft = nxt.result()
-            if g + 1 < len(groups):
-                nxt = bg.submit(_read_files, groups[g + 1], threads, (g + 1) & 1, skip_errors)
-            if skip_errors and not ft.files:
-                yield BvhBatch(torch.empty((0, 0, 3), dtype=torch.float64, device=dev), torch.empty((0, 0, 4), dtype=torch.float64, device=dev), [],
-                               np.zeros(1, dtype=np.int64), [], [], [], list(ft.skipped))
-                continue
-            a0, rows, offs, files_g, frametimes, skipped = _rows_on_device(ft, dev, None, skip_errors)
+
+    def finish(st: Staged) -> BvhBatch:
+        if not st.files:
+            return BvhBatch.empty(dev, st.skipped)
+        with torch.cuda.device(dev):
+            a0, rows, offs, files_g, frametimes, skipped = _rows_on_device(st, dev, None, skip_errors)
             try:
                 pos, quat, names = _device_fk(a0, rows, dev, columns)
             except KeyError as ex:  # the skeleton lacks a bone the caller asked for (the reference fails at its first retarget(): KeyError)
                 if not skip_errors:
                     raise
-                yield BvhBatch(torch.empty((0, 0, 3), dtype=torch.float64, device=dev), torch.empty((0, 0, 4), dtype=torch.float64, device=dev), [],
-                               np.zeros(1, dtype=np.int64), [], [], [], list(skipped) + [(f, str(ex.args[0])) for f in files_g])
-                continue
+                return BvhBatch.empty(dev, skipped + [(f, str(ex.args[0])) for f in files_g])
             heights = _clip_heights(a0, rows, offs, dev, full=(pos, names) if columns is None else None)
-            yield BvhBatch(pos, quat, names, offs, heights, frametimes, files_g, skipped)
+        return BvhBatch(pos, quat, names, offs, heights, frametimes, files_g, skipped)
+
+    groups = [files[i:i + batch_files] for i in range(0, len(files), max(1, batch_files))]
+    yield from read_ahead(groups, lambda group, slot: _stage(group, dev, threads, slot, skip_errors), finish)

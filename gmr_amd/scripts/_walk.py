@@ -1,4 +1,4 @@
-"""The folder walk both dataset scripts share: which files to convert and where each result goes."""
+"""What both dataset scripts share: their common flags, which files to convert and where each result goes, and the batch -> pickles loop."""
 from __future__ import annotations
 
 import os
@@ -42,3 +42,40 @@ def hard_motion_names(paths: Sequence[str]) -> List[str]:
                     continue
                 out.append(line.split(":")[1].strip().split(",")[0].strip().split(".")[0])
     return out
+
+
+def add_common_flags(ap) -> None:
+    ap.add_argument("--override", default=False, action="store_true")
+    ap.add_argument("--device", default=None, type=int, help="GPU to use (default: LOCAL_RANK under torch.distributed.run, else 0)")
+    ap.add_argument("--clip_start", default="qpos0", choices=["qpos0", "root_target"],
+                    help="qpos0: the reference (every clip starts from the model's rest pose); root_target: start with the floating base on the first root target (not the reference's numbers for the first frames; spares clips that face away from qpos0 their slow start)")
+    ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
+
+
+def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callable, retarget_kw: Callable, workers: int, done: str) -> int:
+    """This rank's share of the (source, target) pairs -> pickles: ``batches(sources, columns)`` yields the loader's batches, each one
+    goes through ``dataset.retarget_clips(..., **retarget_kw(batch))`` and to the writer pool; files that could not be loaded are
+    reported and counted like the reference's ``except: print; continue``."""
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    if args.device is None:
+        args.device = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.shard_by_rank and world > 1:
+        pairs = pairs[rank::world]
+        print(f"rank {rank} of {world}: {len(pairs)} of them")
+    if pairs:
+        from .. import GeneralMotionRetargeting as GMR, dataset
+        g = GMR(src_human=src_human, tgt_robot=args.robot, device=args.device)
+        target_of, failed = dict(pairs), 0
+        with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
+            for batch in batches([s for s, _ in pairs], g.ik_columns):
+                for f, why in batch.skipped:
+                    print(f"Error loading {f}: {why}")
+                    failed += 1
+                if not len(batch):
+                    continue
+                motions = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                                 clip_start=args.clip_start, **retarget_kw(batch))
+                writer.submit(motions, [target_of[f] for f in batch.files])
+        print(f"{writer.written} files written, {failed} could not be loaded")
+    print(done, args.tgt_folder)
+    return 0

@@ -454,6 +454,58 @@ def test_bvh_folder_skip_errors(golden_dir, tmp_path):
     assert [len(bb) for bb in only_bad] == [0, 0] and len(only_bad[0].skipped) == 1
 
 
+def test_bvh_batch_of_zero_frame_files(golden_dir, tmp_path):
+    """A batch whose files all say ``Frames: 0`` is a batch of clips without frames (the device parser is not launched for no rows)."""
+    import os
+    from gmr_amd.bvh import iter_lafan1_batches, load_lafan1_files
+    raw = open(os.path.join(golden_dir, "bvh_lafan_like.bvh"), "rb").read()
+    head = raw[:raw.index(b"Frames:")] + b"Frames: 0\nFrame Time: 0.033333\n"
+    files = [str(tmp_path / f"empty{k}.bvh") for k in range(3)]
+    for f in files:
+        open(f, "wb").write(head)
+    b = load_lafan1_files(files)
+    assert len(b) == 3 and b.pos.shape[0] == 0 and b.seq_offsets.tolist() == [0, 0, 0, 0] and b.human_heights == [1.75] * 3 and b.skipped == []
+    got = list(iter_lafan1_batches(files, batch_files=2, columns=["Hips", "Head"], skip_errors=True))
+    assert [len(bb) for bb in got] == [2, 1] and [tuple(bb.pos.shape) for bb in got] == [(0, 2, 3), (0, 2, 3)]
+
+
+def test_loaders_and_script_twins_on_the_second_device(golden_dir, tmp_path, capsys):
+    """device=1 with cuda:0 current: both folder loaders and both script twins put their work on cuda:1 and compute, bit for bit, what
+    they compute on cuda:0; the caller's current device is left as it was."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    import os
+    import shutil
+    from gmr_amd import GeneralMotionRetargeting as GMR, synth
+    from gmr_amd import smplx_adapter as sa
+    from gmr_amd.bvh import load_lafan1_files
+    from gmr_amd.scripts import bvh_to_robot_dataset, smplx_to_robot_dataset
+    torch.cuda.set_device(0)
+    b_in, s_in = tmp_path / "bvh_in", tmp_path / "sm_in"
+    b_in.mkdir()
+    s_in.mkdir()
+    bfiles = [str(b_in / f"c{k}.bvh") for k in range(3)]
+    for f in bfiles:
+        shutil.copy(os.path.join(golden_dir, "bvh_lafan_like.bvh"), f)
+    g = GMR(src_human="smplx", tgt_robot="unitree_g1", device=0)
+    pos, quat, names, offs = synth.synth_clips_torch(g._cm, np.array([40, 25, 60]), seed=5, device=torch.device("cuda", 0), yaw0=1.0, dtype=torch.float64)
+    sfiles = synth.write_smplx_joint_files(str(s_in), pos, quat, names, offs, fps=30.0, heights=[1.7, 1.6, 1.8])
+    for load, files in ((load_lafan1_files, bfiles), (sa.load_joint_files, sfiles)):
+        b0, b1 = load(files, device=0), load(files, device=1)
+        assert torch.cuda.current_device() == 0 and b1.pos.device == torch.device("cuda", 1)
+        assert torch.equal(b0.pos, b1.pos.to(b0.pos.device)) and torch.equal(b0.quat, b1.quat.to(b0.quat.device))
+        assert np.array_equal(b0.seq_offsets, b1.seq_offsets) and b0.human_heights == b1.human_heights
+    for script, src in ((bvh_to_robot_dataset, b_in), (smplx_to_robot_dataset, s_in)):
+        outs = []
+        for d in ("0", "1"):
+            tgt = str(tmp_path / f"{src.name}_out{d}")
+            extra = ["--hard_motions"] if script is smplx_to_robot_dataset else []
+            assert script.main(["--src_folder", str(src), "--tgt_folder", tgt, "--robot", "unitree_g1", "--device", d] + extra) == 0
+            outs.append({f: open(os.path.join(tgt, f), "rb").read() for f in sorted(os.listdir(tgt))})
+        assert len(outs[0]) == 3 and outs[0] == outs[1]
+    capsys.readouterr()
+
+
 def test_smplx_joint_files_equal_per_clip_adapter_calls(tmp_path):
     """smplx_adapter.load_joint_files / iter_joint_batches (the file side of row f-2): every clip of the batch is, bit for bit, what
     get_smplx_data_offline_fast returns for that clip's arrays -- 120 -> 30 fps and 1:1 clips in one batch, float32 files (a body model's
