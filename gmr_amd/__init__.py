@@ -18,6 +18,9 @@ def __getattr__(name):
     if name == "KinematicsModel":
         from .kinematics_model import KinematicsModel
         return KinematicsModel
+    if name == "MultiRobotRetargeting":
+        from .multi_robot import MultiRobotRetargeting
+        return MultiRobotRetargeting
     if name == "load_robot_motion":
         from .dataset import load_robot_motion
         return load_robot_motion

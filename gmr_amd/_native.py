@@ -27,7 +27,8 @@ INIT_QPOS0, INIT_ROOT_TARGET = -1, -2
 EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last_error", "gmr_model_info_get",
            "gmr_ik_solve", "gmr_fk", "gmr_fk_shape", "gmr_dof_to_rot", "gmr_rot_to_dof", "gmr_local_rot_to_global", "gmr_fk_min_height", "gmr_bvh_fk", "gmr_bvh_parse_header", "gmr_bvh_parse_motion", "gmr_evaluate", "gmr_smplx_keypoints", "gmr_smplx_keypoints_cols", "gmr_smplx_keypoints_in", "gmr_bvh_fk_rows", "gmr_bvh_parse_motion_device",
            "gmr_session_create", "gmr_session_destroy", "gmr_session_reset", "gmr_session_step", "gmr_session_state", "gmr_session_set_persistent", "gmr_ik_plan_order", "gmr_ik_solve_ordered",
-           "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve"]
+           "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
+           "gmr_group_plan_order", "gmr_group_ik_solve_ordered"]
 
 
 class IKParams(C.Structure):
@@ -123,6 +124,10 @@ def load():
     L.gmr_ik_solve_ordered.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, C.POINTER(IKParams), vp, vp, vp, vp, vp,
                                        C.POINTER(IKStats), vp, vp]
     L.gmr_group_ik_solve.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp]
+    L.gmr_group_plan_order.restype = C.c_int
+    L.gmr_group_plan_order.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), C.c_int, vp, vp]
+    L.gmr_group_ik_solve_ordered.restype = C.c_int
+    L.gmr_group_ik_solve_ordered.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp, vp]
     L.gmr_bvh_parse_header.restype = C.c_int
     L.gmr_bvh_parse_header.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.gmr_evaluate.restype = C.c_int

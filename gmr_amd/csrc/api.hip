@@ -202,13 +202,22 @@ int launch_ik_variant(gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool
   return GMR_OK;
 }
 
+// perm: NULL or the global launch order (gmr_group_ik_solve_ordered); probe: the cost probe (gmr_group_plan_order)
 template <int NVP>
-void launch_ik_group(const gmr_group *g, const gmr::IkGroupEntry *entries, const int *block_entry, int n_blocks, int lds_bytes, hipStream_t st) {
+void launch_ik_group(const gmr_group *g, const gmr::IkGroupEntry *entries, const int *block_entry, int n_blocks, int lds_bytes, hipStream_t st,
+                     const int *perm = nullptr, bool probe = false) {
+  if (probe) {
+    if (g->sq) hipLaunchKernelGGL((gmr::ik_group_probe_kernel<NVP, true>), dim3(n_blocks), dim3(64), lds_bytes, st, entries, block_entry);
+#ifndef GMR_IK_DEV_ONLY36
+    else hipLaunchKernelGGL((gmr::ik_group_probe_kernel<NVP, false>), dim3(n_blocks), dim3(64), lds_bytes, st, entries, block_entry);
+#endif
+    return;
+  }
   if (g->sq)
-    hipLaunchKernelGGL((gmr::ik_group_kernel<NVP, true>), dim3(n_blocks), dim3(64), lds_bytes, st, entries, block_entry);
+    hipLaunchKernelGGL((gmr::ik_group_kernel<NVP, true>), dim3(n_blocks), dim3(64), lds_bytes, st, entries, block_entry, perm, n_blocks);
 #ifndef GMR_IK_DEV_ONLY36
   else
-    hipLaunchKernelGGL((gmr::ik_group_kernel<NVP, false>), dim3(n_blocks), dim3(64), lds_bytes, st, entries, block_entry);
+    hipLaunchKernelGGL((gmr::ik_group_kernel<NVP, false>), dim3(n_blocks), dim3(64), lds_bytes, st, entries, block_entry, perm, n_blocks);
 #endif
 }
 
@@ -871,11 +880,13 @@ int build_device_model(gmr_model *m) {
   // opt in to > 64 KiB of dynamic LDS where a variant needs it
 #define GMR_LDS_OPT_IN(k) hipFuncSetAttribute(reinterpret_cast<const void *>(&k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #ifdef GMR_IK_DEV_ONLY36
-#define GMR_X(v) GMR_LDS_OPT_IN((gmr::ik_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_probe_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_group_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_session_kernel<v, true>))
+#define GMR_X(v) GMR_LDS_OPT_IN((gmr::ik_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_probe_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_group_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_group_probe_kernel<v, true>)) \
+  GMR_LDS_OPT_IN((gmr::ik_session_kernel<v, true>))
 #else
 #define GMR_X(v)                                                                                                                         \
   GMR_LDS_OPT_IN((gmr::ik_kernel<v, false>)) GMR_LDS_OPT_IN((gmr::ik_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_probe_kernel<v, false>))       \
   GMR_LDS_OPT_IN((gmr::ik_probe_kernel<v, true>)) GMR_LDS_OPT_IN((gmr::ik_group_kernel<v, false>)) GMR_LDS_OPT_IN((gmr::ik_group_kernel<v, true>)) \
+  GMR_LDS_OPT_IN((gmr::ik_group_probe_kernel<v, false>)) GMR_LDS_OPT_IN((gmr::ik_group_probe_kernel<v, true>))                            \
   GMR_LDS_OPT_IN((gmr::ik_session_kernel<v, false>)) GMR_LDS_OPT_IN((gmr::ik_session_kernel<v, true>))
 #endif
   GMR_FOR_EACH_NVP(GMR_X)
@@ -1157,15 +1168,12 @@ int gmr_group_size(const gmr_group *g) { return g ? (int)g->models.size() : 0; }
 gmr_model *gmr_group_model(gmr_group *g, int i) { return g && i >= 0 && i < (int)g->models.size() ? g->models[i] : nullptr; }
 const char *gmr_group_last_error(const gmr_group *g) { return g ? g->err.c_str() : "null group"; }
 
-int gmr_group_ik_solve(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, void *stream) {
-  if (!g || !inputs || !params) return GMR_EINVAL;
-  g->err.clear();
+// Validate every member's batch and fill its entry (prepare_ik_launch per member).  Members without work get an empty entry.
+static int prepare_group(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, hipStream_t st, bool keep_order,
+                         std::vector<CallScratch> &scratch, std::vector<gmr::IkGroupEntry> &entries,
+                         std::vector<std::vector<gmr_work_item>> &sorted, int &total, int &lds_bytes) {
   const int n = (int)g->models.size();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<CallScratch> scratch(n);
-  std::vector<gmr::IkGroupEntry> entries(n);
-  std::vector<std::vector<gmr_work_item>> sorted(n);
-  int total = 0, lds_bytes = 0;
+  total = 0; lds_bytes = 0;
   for (int i = 0; i < n; ++i) {
     gmr_model *m = g->models[i];
     m->err.clear();
@@ -1174,25 +1182,30 @@ int gmr_group_ik_solve(gmr_group *g, const gmr_group_input *inputs, const gmr_ik
     entries[i] = gmr::IkGroupEntry{};
     if (in.n_items == 0) continue;  // no work for this member
     int rc = prepare_ik_launch(m, in.human_pos, in.human_quat, in.in_dtype, in.n_cols, in.slot_col, in.n_frames, in.items, in.n_items, params,
-                               in.qpos_init, in.qpos_final, in.qpos_out, in.iters_out, in.frames_done, nullptr, st, scratch[i], L, sorted[i]);
+                               in.qpos_init, in.qpos_final, in.qpos_out, in.iters_out, in.frames_done, nullptr, st, scratch[i], L, sorted[i],
+                               keep_order);
     if (rc != GMR_OK) { g->err = "member " + std::to_string(i) + ": " + m->err; return rc; }
+    if (in.n_items > INT32_MAX - total) { g->err = "more than 2^31 - 1 work items in one group launch"; return GMR_EINVAL; }
     entries[i].m = m->dm_dev; entries[i].L = L; entries[i].lay = m->lay; entries[i].item_base = 0; entries[i].pad = 0;
     total += in.n_items;
     if (in.n_items > 0) lds_bytes = std::max(lds_bytes, m->lds_bytes);
   }
-  if (total == 0) return GMR_OK;
-  // one grid over all members' items: a block finds its entry in block_entry[] and its item as blockIdx - item_base, so the
-  // blocks of an entry are contiguous (its items longest first); the entry with the longest items goes first
-  std::vector<int> block_entry(total);
-  std::vector<int> eorder(n);
-  std::iota(eorder.begin(), eorder.end(), 0);
-  auto longest = [&](int e) { return sorted[e].empty() ? -1 : sorted[e][0].n_burn + sorted[e][0].n_out; };
-  std::stable_sort(eorder.begin(), eorder.end(), [&](int a, int b) { return longest(a) > longest(b); });
+  return GMR_OK;
+}
+
+// Global item numbering of the ordered calls: member i's items at base_i = the sum of n_items over the members before it.
+static void group_bases(const gmr_group_input *inputs, int n, std::vector<gmr::IkGroupEntry> &entries, std::vector<int> &block_entry) {
   int blk = 0;
-  for (int e : eorder) {
-    entries[e].item_base = blk;
-    for (size_t k = 0; k < sorted[e].size(); ++k) block_entry[blk++] = e;
+  for (int i = 0; i < n; ++i) {
+    entries[i].item_base = blk;
+    for (int k = 0; k < inputs[i].n_items; ++k) block_entry[blk++] = i;
   }
+}
+
+// Upload the entries and the block -> entry table into stream-ordered scratch and launch one grid of `total` workgroups.
+static int launch_group(gmr_group *g, const std::vector<gmr::IkGroupEntry> &entries, const std::vector<int> &block_entry, int total,
+                        int lds_bytes, hipStream_t st, const int32_t *perm, bool probe) {
+  const int n = (int)g->models.size();
   gmr_model *m0 = g->models[0];
   if (hipSetDevice(g->device) != hipSuccess) { g->err = "hipSetDevice failed"; return GMR_EDEVICE; }
   CallScratch gs;
@@ -1208,13 +1221,123 @@ int gmr_group_ik_solve(gmr_group *g, const gmr_group_input *inputs, const gmr_ik
   const auto *d_entries = reinterpret_cast<const gmr::IkGroupEntry *>(ws);
   const int *d_be = reinterpret_cast<const int *>(ws + be_off);
   switch (g->nvp) {
-#define GMR_X(v) case v: launch_ik_group<v>(g, d_entries, d_be, total, lds_bytes, st); break;
+#define GMR_X(v) case v: launch_ik_group<v>(g, d_entries, d_be, total, lds_bytes, st, perm, probe); break;
     GMR_FOR_EACH_NVP(GMR_X)
 #undef GMR_X
     default: g->err = "internal: no kernel variant"; return GMR_EUNSUPPORTED;
   }
   if (hipGetLastError() != hipSuccess) { g->err = "kernel launch failed"; return GMR_EDEVICE; }
   return GMR_OK;
+}
+
+int gmr_group_ik_solve(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, void *stream) {
+  if (!g || !inputs || !params) return GMR_EINVAL;
+  g->err.clear();
+  const int n = (int)g->models.size();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<CallScratch> scratch(n);
+  std::vector<gmr::IkGroupEntry> entries(n);
+  std::vector<std::vector<gmr_work_item>> sorted(n);
+  int total = 0, lds_bytes = 0;
+  int rc = prepare_group(g, inputs, params, st, /*keep_order=*/false, scratch, entries, sorted, total, lds_bytes);
+  if (rc != GMR_OK) return rc;
+  if (total == 0) return GMR_OK;
+  // one grid over all members' items: a block finds its entry in block_entry[] and its item as blockIdx - item_base, so the
+  // blocks of an entry are contiguous (its items longest first); the entry with the longest items goes first
+  std::vector<int> block_entry(total);
+  std::vector<int> eorder(n);
+  std::iota(eorder.begin(), eorder.end(), 0);
+  auto longest = [&](int e) { return sorted[e].empty() ? -1 : sorted[e][0].n_burn + sorted[e][0].n_out; };
+  std::stable_sort(eorder.begin(), eorder.end(), [&](int a, int b) { return longest(a) > longest(b); });
+  int blk = 0;
+  for (int e : eorder) {
+    entries[e].item_base = blk;
+    for (size_t k = 0; k < sorted[e].size(); ++k) block_entry[blk++] = e;
+  }
+  return launch_group(g, entries, block_entry, total, lds_bytes, st, nullptr, false);
+}
+
+// Launch order across robots: gmr_ik_plan_order's probe for every member's items in one grid, costs in the global item space
+// (entry i's cost array starts at base_i), one device sort over all of them.
+int gmr_group_plan_order(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, int probe_frames, int32_t *order_out,
+                         void *stream) {
+  if (!g || !inputs || !params) return GMR_EINVAL;
+  g->err.clear();
+  if (!order_out || probe_frames < 1) { g->err = "order_out is NULL or probe_frames < 1"; return GMR_EINVAL; }
+  const int n = (int)g->models.size();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<gmr_group_input> pin(inputs, inputs + n);
+  std::vector<std::vector<gmr_work_item>> probe(n);
+  double dummy_out = 0.0;  // (prepare_ik_launch insists on an output array; a probe item has no output frame to write)
+  int64_t total64 = 0;
+  for (int i = 0; i < n; ++i) total64 += std::max(0, inputs[i].n_items);
+  if (total64 > INT32_MAX) { g->err = "more than 2^31 - 1 work items in one group launch"; return GMR_EINVAL; }
+  std::vector<int> meta(3 * (size_t)std::max<int64_t>(total64, 1));  // [cost | frames | probed], global item index
+  const int tot = (int)total64;
+  for (int i = 0, base = 0; i < n; ++i) {
+    const gmr_group_input &in = inputs[i];
+    if (in.n_items < 0 || (!in.items && in.n_items > 0)) { g->err = "member " + std::to_string(i) + ": null argument"; return GMR_EINVAL; }
+    probe[i].assign(in.items, in.items + in.n_items);
+    for (int k = 0; k < in.n_items; ++k) {  // as gmr_ik_plan_order builds its probe items
+      gmr_work_item &w = probe[i][k];
+      if (w.check_stride != 0) { g->err = "member " + std::to_string(i) + ": work item " + std::to_string(k) + ": verification walks cannot be probed"; return GMR_EINVAL; }
+      if (w.n_burn < 0 || w.n_out < 0) { g->err = "member " + std::to_string(i) + ": work item " + std::to_string(k) + " has a negative frame count"; return GMR_EINVAL; }
+      const int total = w.n_burn + w.n_out, p = std::min(total, probe_frames);
+      meta[tot + base + k] = total; meta[2 * (size_t)tot + base + k] = p;
+      w.n_burn = p; w.n_out = 0; w.final_row = -1; w.burn_row = -1;  // frames solved, nothing written
+    }
+    pin[i].items = probe[i].data();
+    pin[i].qpos_final = nullptr; pin[i].qpos_out = &dummy_out; pin[i].iters_out = nullptr; pin[i].frames_done = nullptr;
+    base += in.n_items;
+  }
+  if (tot == 0) return GMR_OK;
+  std::vector<CallScratch> scratch(n);
+  std::vector<gmr::IkGroupEntry> entries(n);
+  std::vector<std::vector<gmr_work_item>> sorted(n);
+  int total = 0, lds_bytes = 0;
+  int rc = prepare_group(g, pin.data(), params, st, /*keep_order=*/false, scratch, entries, sorted, total, lds_bytes);
+  if (rc != GMR_OK) return rc;
+  gmr_model *m0 = g->models[0];
+  if (hipSetDevice(g->device) != hipSuccess) { g->err = "hipSetDevice failed"; return GMR_EDEVICE; }
+  CallScratch ms;
+  rc = scratch_alloc(m0, ms, sizeof(int) * meta.size(), st);
+  if (rc != GMR_OK) { g->err = m0->err; return rc; }
+  int *meta_dev = static_cast<int *>(ms.p);
+  if (hipMemcpyAsync(meta_dev, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, st) != hipSuccess) {
+    g->err = "hipMemcpyAsync failed";
+    return GMR_EDEVICE;
+  }
+  std::vector<int> block_entry(total);
+  group_bases(pin.data(), n, entries, block_entry);
+  for (int i = 0; i < n; ++i) {
+    entries[i].L.qout = nullptr;
+    entries[i].L.cost = meta_dev + entries[i].item_base;  // (item k of member i: cost[order[k]] = global item base_i + k)
+  }
+  rc = launch_group(g, entries, block_entry, total, lds_bytes, st, nullptr, /*probe=*/true);
+  if (rc != GMR_OK) return rc;
+  hipLaunchKernelGGL(gmr::plan_order_kernel, dim3(1), dim3(1024), 0, st, meta_dev, meta_dev + tot, meta_dev + 2 * (size_t)tot, tot, order_out);
+  if (hipGetLastError() != hipSuccess) { g->err = "kernel launch failed"; return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_group_ik_solve_ordered(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, const int32_t *launch_order,
+                               void *stream) {
+  if (!g || !inputs || !params) return GMR_EINVAL;
+  g->err.clear();
+  const int n = (int)g->models.size();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<CallScratch> scratch(n);
+  std::vector<gmr::IkGroupEntry> entries(n);
+  std::vector<std::vector<gmr_work_item>> sorted(n);
+  int total = 0, lds_bytes = 0;
+  // every member's items in the caller's order, so that a global index is base_i + the caller's index
+  int rc = prepare_group(g, inputs, params, st, /*keep_order=*/true, scratch, entries, sorted, total, lds_bytes);
+  if (rc != GMR_OK) return rc;
+  if (total == 0) return GMR_OK;
+  if (!launch_order) { g->err = "launch_order is NULL"; return GMR_EINVAL; }
+  std::vector<int> block_entry(total);
+  group_bases(inputs, n, entries, block_entry);
+  return launch_group(g, entries, block_entry, total, lds_bytes, st, launch_order, false);
 }
 
 // ------------------------------------------------------------------ single-sequence sessions (teleop)

@@ -1663,12 +1663,12 @@ struct IkGroupEntry {
   LdsLayout lay;
   int item_base, pad;  // first workgroup of this entry
 };
-template <int NVP, bool SQ>
-__global__ void __launch_bounds__(64, SQ ? GMR_IK_WAVES_PER_SIMD : 1) ik_group_kernel(const IkGroupEntry *__restrict__ entries,
-                                                                             const int *__restrict__ block_entry) {
-#if defined(__HIP_DEVICE_COMPILE__)  // (the host pass only needs the kernel's stub; address-space-qualified copies do not parse there)
+// Items are numbered globally: block_entry[gi] is the entry of global item gi, and gi - item_base its index in that entry.
+#if defined(__HIP_DEVICE_COMPILE__)  // (the host pass only needs the kernels' stubs; address-space-qualified copies do not parse there)
+template <int NVP, bool SQ, bool PROBE>
+__device__ __forceinline__ void ik_group_item(const IkGroupEntry *__restrict__ entries, const int *__restrict__ block_entry, const int gi) {
   // (readfirstlane: tell the compiler these are wave-uniform, so that everything derived from them stays in SGPRs)
-  const int e = __builtin_amdgcn_readfirstlane(block_entry[blockIdx.x]);
+  const int e = __builtin_amdgcn_readfirstlane(block_entry[gi]);
   const uintptr_t ea = (uintptr_t)(entries + e);
   const uintptr_t eu = (uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ea) |
                        ((uintptr_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ea >> 32)) << 32);
@@ -1678,7 +1678,28 @@ __global__ void __launch_bounds__(64, SQ ? GMR_IK_WAVES_PER_SIMD : 1) ik_group_k
   GMR_LAY(zero) GMR_LAY(hplan) GMR_LAY(cplan) GMR_LAY(q) GMR_LAY(tp) GMR_LAY(tq) GMR_LAY(S) GMR_LAY(F) GMR_LAY(Lb) GMR_LAY(bodyc)
   GMR_LAY(xpos) GMR_LAY(xquat) GMR_LAY(B) GMR_LAY(Bc) GMR_LAY(H) GMR_LAY(total_doubles)
 #undef GMR_LAY
-  ik_body<NVP, SQ>(*(DevModelG *)E->m, &E->L, lay, (int)blockIdx.x - E->item_base);
+  ik_body<NVP, SQ, false, PROBE>(*(DevModelG *)E->m, &E->L, lay, gi - E->item_base);
+}
+#endif
+// perm: NULL = workgroup b runs global item b (gmr_group_ik_solve); else global item perm[b] (gmr_group_ik_solve_ordered).
+template <int NVP, bool SQ>
+__global__ void __launch_bounds__(64, SQ ? GMR_IK_WAVES_PER_SIMD : 1) ik_group_kernel(const IkGroupEntry *__restrict__ entries,
+                                                                             const int *__restrict__ block_entry,
+                                                                             const int *__restrict__ perm, int n_total) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int gi = perm ? __builtin_amdgcn_readfirstlane(perm[blockIdx.x]) : (int)blockIdx.x;
+  if ((unsigned)gi >= (unsigned)n_total) return;  // (an order that is not a permutation must not reach outside the item arrays)
+  ik_group_item<NVP, SQ, false>(entries, block_entry, gi);
+#endif
+}
+
+// The probe in front of an ordered group launch (gmr_group_plan_order): ik_probe_kernel's body behind the group's entry lookup;
+// each entry's cost array points at its members' slice of the global cost array.
+template <int NVP, bool SQ>
+__global__ void __launch_bounds__(64, SQ ? GMR_IK_WAVES_PER_SIMD : 1) ik_group_probe_kernel(const IkGroupEntry *__restrict__ entries,
+                                                                                   const int *__restrict__ block_entry) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  ik_group_item<NVP, SQ, true>(entries, block_entry, (int)blockIdx.x);
 #endif
 }
 

@@ -26,6 +26,35 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _state_arrays(nq: int, device, items: np.ndarray, qpos_init: Optional[torch.Tensor], qpos_final: Optional[torch.Tensor], n_final: int,
+                  frames_done: Optional[torch.Tensor], what: str = ""):
+    """Host-side checks of a batch's state arrays against its work items -- the C side cannot check row counts, and on the device a
+    wrong row is an out-of-bounds write.  Returns (qpos_init, qpos_final): qpos_init made contiguous, qpos_final allocated with
+    ``n_final`` rows (zeros) when the caller gives none.  ``what`` prefixes the error messages (a group member)."""
+    if qpos_final is not None:
+        if qpos_final.dtype != torch.float64 or qpos_final.dim() != 2 or qpos_final.shape[1] != nq or not qpos_final.is_contiguous() \
+                or qpos_final.device != device:
+            raise EngineError(what + "qpos_final must be a contiguous float64 [R, nq] tensor on the engine's device")
+        qfin, n_final = qpos_final, int(qpos_final.shape[0])
+    else:
+        qfin = torch.zeros((n_final, nq), dtype=torch.float64, device=device) if n_final > 0 else None
+    if qpos_init is not None:
+        if qpos_init.dtype != torch.float64 or qpos_init.dim() != 2 or qpos_init.shape[1] != nq or qpos_init.device != device:
+            raise EngineError(what + "qpos_init must be float64 [R, nq] on the engine's device")
+        if not qpos_init.is_contiguous():
+            qpos_init = qpos_init.contiguous()
+        if len(items) and int(items["init_row"].max()) >= qpos_init.shape[0]:
+            raise EngineError(what + "init_row outside qpos_init")
+    if len(items):
+        reach = np.where(items["check_stride"] > 0, (np.maximum(items["n_out"], 1) - 1) // np.maximum(items["check_stride"], 1), 0)
+        if int(max((items["final_row"] + reach).max(), (items["burn_row"] + reach).max())) >= n_final:
+            raise EngineError(what + "final_row outside qpos_final")
+    if frames_done is not None and (frames_done.dtype != torch.int32 or frames_done.device != device or not frames_done.is_contiguous()
+                                    or frames_done.numel() < len(items)):
+        raise EngineError(what + "frames_done must be a contiguous int32 [n_items] tensor on the engine's device")
+    return qpos_init, qfin
+
+
 class Engine:
     def __init__(self, cm: CompiledModel, device: int = 0, _borrowed_handle=None):
         if not torch.cuda.is_available():
@@ -104,27 +133,7 @@ class Engine:
             raise EngineError("out must be a contiguous float64 [N, nq] tensor on the engine's device")
         if iters is None:
             iters = torch.zeros(N, dtype=torch.int32, device=self.device) if want_iters else None
-        if qpos_final is not None:
-            if qpos_final.dtype != torch.float64 or qpos_final.dim() != 2 or qpos_final.shape[1] != self.nq or not qpos_final.is_contiguous() \
-                    or qpos_final.device != self.device:
-                raise EngineError("qpos_final must be a contiguous float64 [R, nq] tensor on the engine's device")
-            qfin, n_final = qpos_final, int(qpos_final.shape[0])
-        else:
-            qfin = torch.zeros((n_final, self.nq), dtype=torch.float64, device=self.device) if n_final > 0 else None
-        if qpos_init is not None:
-            if qpos_init.dtype != torch.float64 or qpos_init.dim() != 2 or qpos_init.shape[1] != self.nq or qpos_init.device != self.device:
-                raise EngineError("qpos_init must be float64 [R, nq] on the engine's device")
-            if not qpos_init.is_contiguous():
-                qpos_init = qpos_init.contiguous()
-            if len(items) and int(items["init_row"].max()) >= qpos_init.shape[0]:
-                raise EngineError("init_row outside qpos_init")
-        if len(items):
-            reach = np.where(items["check_stride"] > 0, (np.maximum(items["n_out"], 1) - 1) // np.maximum(items["check_stride"], 1), 0)
-            if int(max((items["final_row"] + reach).max(), (items["burn_row"] + reach).max())) >= n_final:
-                raise EngineError("final_row outside qpos_final")
-        if frames_done is not None and (frames_done.dtype != torch.int32 or frames_done.device != self.device or not frames_done.is_contiguous()
-                                        or frames_done.numel() < len(items)):
-            raise EngineError("frames_done must be a contiguous int32 [n_items] tensor on the engine's device")
+        qpos_init, qfin = _state_arrays(self.nq, self.device, items, qpos_init, qpos_final, n_final, frames_done)
         stats = IKStats()
         self.last_stats = stats
         if N == 0 or len(items) == 0:  # nothing to launch (empty tensors have no device pointer)
@@ -495,18 +504,28 @@ class EngineGroup:
         except Exception:
             pass
 
-    def ik_solve(self, batches, params: Optional[IKParams] = None):
-        """``batches[i] = (pos, quat, slot_col, items)`` for member i (or ``None``: no work) -> list of (qpos, iters) per member."""
+    STATE_KEYS = ("qpos_init", "qpos_final", "n_final", "frames_done", "out", "iters")
+
+    def _inputs(self, batches, with_outputs: bool = True):
+        """Validate every member's batch and fill the C input array.  Returns (inputs, per-member results, per-member items, keep-alive)."""
         if len(batches) != len(self.engines):
             raise EngineError("one batch (or None) per group member")
-        prm = params or IKParams()
         inputs = (_native.GroupInput * len(batches))()
-        keep, outs = [], []
+        keep, outs, all_items = [], [], []
         for i, (eng, b) in enumerate(zip(self.engines, batches)):
+            all_items.append(np.zeros(0, dtype=_native.WORK_ITEM_DTYPE))
             if b is None:
                 outs.append((None, None))
                 continue
-            pos, quat, slot_col, items = b
+            what = f"member {i}: "
+            state = isinstance(b, dict)
+            if state:
+                unknown = set(b) - {"pos", "quat", "slot_col", "items"} - set(self.STATE_KEYS)
+                if unknown:
+                    raise EngineError(what + f"unknown batch keys {sorted(unknown)}")
+                pos, quat, slot_col, items = b["pos"], b["quat"], b["slot_col"], b["items"]
+            else:
+                pos, quat, slot_col, items = b
             if pos.device != self.device or quat.device != self.device or pos.dtype != quat.dtype or pos.dtype not in (torch.float32, torch.float64) \
                     or pos.dim() != 3 or quat.dim() != 3 or pos.shape[2] != 3 or quat.shape[2] != 4 or pos.shape[:2] != quat.shape[:2]:
                 raise EngineError(f"member {i}: bad key-point tensors")
@@ -516,24 +535,148 @@ class EngineGroup:
             slot_col = np.ascontiguousarray(slot_col, dtype=np.int32)
             if slot_col.shape != (eng.info.nslot,):
                 raise EngineError(f"member {i}: slot_col has the wrong length")
-            if len(items) and (int(items["init_row"].max()) >= 0 or int(items["final_row"].max()) >= 0 or int(items["burn_row"].max()) >= 0):
-                raise EngineError("group launches take plain per-clip items (no state rows)")
-            out = torch.full((N, eng.nq), float("nan"), dtype=torch.float64, device=self.device)
-            iters = torch.zeros(N, dtype=torch.int32, device=self.device)
-            outs.append((out, iters))
-            keep += [pos, quat, items, slot_col]
+            qinit = qfin = done = None
+            if state:
+                qinit, qfin = _state_arrays(eng.nq, self.device, items, b.get("qpos_init"), b.get("qpos_final"), int(b.get("n_final", 0) or 0),
+                                            b.get("frames_done"), what)
+                done = b.get("frames_done")
+                if len(items) and qinit is None and int(items["init_row"].max()) >= 0:
+                    raise EngineError(what + "init_row outside qpos_init")
+            elif len(items) and (int(items["init_row"].max()) >= 0 or int(items["final_row"].max()) >= 0 or int(items["burn_row"].max()) >= 0):
+                raise EngineError("group launches take plain per-clip items (no state rows) unless the batch supplies the state arrays")
+            out = iters = None
+            if with_outputs:
+                out, iters = (b.get("out"), b.get("iters")) if state else (None, None)
+                if out is None:
+                    out = torch.full((N, eng.nq), float("nan"), dtype=torch.float64, device=self.device)
+                elif out.shape != (N, eng.nq) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != self.device:
+                    raise EngineError(what + "out must be a contiguous float64 [N, nq] tensor on the engine's device")
+                if iters is None:
+                    iters = torch.zeros(N, dtype=torch.int32, device=self.device)
+                elif iters.shape != (N,) or iters.dtype != torch.int32 or not iters.is_contiguous() or iters.device != self.device:
+                    raise EngineError(what + "iters must be a contiguous int32 [N] tensor on the engine's device")
+            outs.append((out, iters, qfin) if state else (out, iters))
+            keep += [pos, quat, items, slot_col, qinit]
             if N == 0 or len(items) == 0:
                 continue
+            all_items[i] = items
             inputs[i].human_pos, inputs[i].human_quat = pos.data_ptr(), quat.data_ptr()
             inputs[i].in_dtype = _native.GMR_DTYPE_F64 if pos.dtype == torch.float64 else _native.GMR_DTYPE_F32
             inputs[i].n_cols, inputs[i].slot_col, inputs[i].n_frames = B, slot_col.ctypes.data, N
             inputs[i].items, inputs[i].n_items = items.ctypes.data, len(items)
-            inputs[i].qpos_out, inputs[i].iters_out = out.data_ptr(), iters.data_ptr()
-        rc = self._lib.gmr_group_ik_solve(self._g, inputs, C.byref(prm), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            inputs[i].qpos_init = None if qinit is None else qinit.data_ptr()
+            inputs[i].qpos_final = None if qfin is None else qfin.data_ptr()
+            inputs[i].frames_done = None if done is None else done.data_ptr()
+            if with_outputs:
+                inputs[i].qpos_out, inputs[i].iters_out = out.data_ptr(), iters.data_ptr()
+        return inputs, outs, all_items, keep
+
+    def _check(self, rc: int, what: str):
         if rc != 0:
             msg = self._lib.gmr_group_last_error(self._g)
-            raise EngineError(f"gmr_group_ik_solve: {_ERR.get(rc, rc)}: {msg.decode() if msg else ''}")
+            raise EngineError(f"{what}: {_ERR.get(rc, rc)}: {msg.decode() if msg else ''}")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def ik_solve(self, batches, params: Optional[IKParams] = None, launch_order=None):
+        """``batches[i]`` for member i: ``(pos, quat, slot_col, items)``, or ``None`` (no work), or a dict with the keys ``pos``, ``quat``,
+        ``slot_col``, ``items`` and any of ``qpos_init``, ``qpos_final`` (or ``n_final``), ``frames_done``, ``out``, ``iters`` -- the
+        state arrays and outputs of ``Engine.ik_solve``, validated the same way; only such a batch may carry items with state rows
+        (chunks, verification walks).  Returns per member (qpos, iters) for a tuple batch, (qpos, iters, qpos_final) for a dict.
+
+        ``launch_order``: ``None`` (default: one grid, the member with the longest item first, each member's items longest first),
+        an int32 device tensor from :meth:`plan_order` over all members' items (item k of member i has the global index
+        base_i + k, base_i = the items of the members before it), or ``"auto"`` -- plan an order when ``Engine``'s probe policy
+        says it pays for all members' items together (they share the wavefront slots).  The order only moves work in time."""
+        prm = params or IKParams()
+        from .schedule import group_item_bases
+        inputs, outs, all_items, keep = self._inputs(batches)
+        total = int(group_item_bases([inputs[i].n_items for i in range(len(batches))])[-1])
+        if isinstance(launch_order, str):
+            if launch_order != "auto":
+                raise EngineError("launch_order must be a tensor, None or 'auto'")
+            pf = self.engines[0]._probe_frames(np.concatenate(all_items)) if total else 0
+            launch_order = self.plan_order(batches, prm, probe_frames=pf) if pf else None
+        if launch_order is None:
+            self._check(self._lib.gmr_group_ik_solve(self._g, inputs, C.byref(prm), self._stream()), "gmr_group_ik_solve")
+        else:
+            if not isinstance(launch_order, torch.Tensor) or launch_order.dtype != torch.int32 or launch_order.device != self.device \
+                    or not launch_order.is_contiguous() or launch_order.numel() != total:
+                raise EngineError(f"launch_order must be a contiguous int32 [{total}] tensor on the group's device (one entry per work item)")
+            self._check(self._lib.gmr_group_ik_solve_ordered(self._g, inputs, C.byref(prm), _ptr(launch_order), self._stream()),
+                        "gmr_group_ik_solve_ordered")
         return outs
+
+    def plan_order(self, batches, params: Optional[IKParams] = None, probe_frames: Optional[int] = None) -> torch.Tensor:
+        """All members' items by predicted cost, most expensive first, across robots: int32 ``[sum of n_items]`` on the device (global
+        item indices, see :meth:`ik_solve`).  Probes the first ``probe_frames`` frames of every item in one grid; asynchronous."""
+        prm = params or IKParams()
+        from .schedule import group_item_bases
+        inputs, _, _, keep = self._inputs(batches, with_outputs=False)
+        total = int(group_item_bases([inputs[i].n_items for i in range(len(batches))])[-1])
+        order = torch.empty(total, dtype=torch.int32, device=self.device)
+        if total == 0:
+            return order
+        self._check(self._lib.gmr_group_plan_order(self._g, inputs, C.byref(prm), int(probe_frames or Engine.PROBE_FRAMES), _ptr(order),
+                                                   self._stream()), "gmr_group_plan_order")
+        return order
+
+    def ik_solve_chunked(self, batches, chunk, burn_in: int, params: Optional[IKParams] = None, eps: float = 1e-7, height_scales=None,
+                         chunk_init: int = _native.INIT_ROOT_TARGET, clip_init: int = _native.INIT_QPOS0):
+        """``Engine.ik_solve_chunked`` for every member at once: ``batches[i] = (pos, quat, slot_col, seq_offsets)`` or ``None``;
+        ``height_scales``: ``None`` or one entry (per-clip factors or ``None``) per member.  Launch 1 runs every member's tracked
+        chunk items in one grid, launch 2 every member's verification walks in another.  Returns per member (qpos, iters, info) --
+        info as the single-model call's -- or ``(None, None, None)``.
+
+        ``chunk="auto"``: ``schedule.auto_chunk`` over the clips of ALL members (they share the wavefront slots); ``(0, 0)`` means
+        whole clips, through :meth:`ik_solve` with ``launch_order="auto"``.  The choice is kept in ``last_chunk``."""
+        from .schedule import auto_chunk, group_chunk_offsets, make_items, plan_walks
+        if len(batches) != len(self.engines):
+            raise EngineError("one batch (or None) per group member")
+        if height_scales is not None and len(height_scales) != len(batches):
+            raise EngineError("height_scales: one entry (or None) per group member")
+        hs = [None] * len(batches) if height_scales is None else list(height_scales)
+        offs = [None if b is None else np.asarray(b[3], dtype=np.int64) for b in batches]
+        if isinstance(chunk, str):
+            if chunk != "auto":
+                raise EngineError("chunk must be an integer or 'auto'")
+            chunk, burn_in = auto_chunk(group_chunk_offsets(offs), 8 * torch.cuda.get_device_properties(self.device).multi_processor_count)
+        self.last_chunk = (int(chunk), int(burn_in))
+        prm = params or IKParams()
+        prm = IKParams(prm.damping, prm.tol, prm.limit_gain, prm.lm_damping, prm.max_iter, prm.offset_to_ground, eps)
+        if chunk <= 0:
+            items = [None if b is None else make_items(o, height_scales=h, clip_init=clip_init) for b, o, h in zip(batches, offs, hs)]
+            res = self.ik_solve([None if b is None else (b[0], b[1], b[2], it) for b, it in zip(batches, items)], prm, launch_order="auto")
+            return [(None, None, None) if b is None else (r[0], r[1], {"chunks": len(it), "passes": 0, "resolved_frames": 0})
+                    for b, r, it in zip(batches, res, items)]
+        items = [None if b is None else make_items(o, chunk=chunk, burn_in=burn_in, track=True, height_scales=h, chunk_init=chunk_init,
+                                                   clip_init=clip_init) for b, o, h in zip(batches, offs, hs)]
+        first = self.ik_solve([None if b is None else {"pos": b[0], "quat": b[1], "slot_col": b[2], "items": it, "n_final": 2 * len(it)}
+                               for b, it in zip(batches, items)], prm)
+        second, done = [], []
+        for b, it, o, r in zip(batches, items, offs, first):
+            w = None if b is None or len(it) == 0 else plan_walks(it, o, chunk)
+            if w is None or len(w) == 0:
+                second.append(None)
+                done.append(None)
+                continue
+            d = torch.zeros(len(w), dtype=torch.int32, device=self.device)
+            done.append(d)
+            second.append({"pos": b[0], "quat": b[1], "slot_col": b[2], "items": w, "qpos_init": r[2], "qpos_final": r[2], "out": r[0],
+                           "iters": r[1], "frames_done": d})
+        if any(x is not None for x in second):
+            self.ik_solve(second, prm)
+        res = []
+        for b, it, r, d in zip(batches, items, first, done):
+            if b is None:
+                res.append((None, None, None))
+                continue
+            info = {"chunks": len(it), "passes": 0, "resolved_frames": 0}
+            if d is not None:
+                info["resolved_frames"], info["passes"] = int(d.sum().item()), 1
+            res.append((r[0], r[1], info))
+        return res
 
 
 class Session:

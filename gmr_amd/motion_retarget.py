@@ -29,6 +29,25 @@ from .params import IK_CONFIG_DICT, ROBOT_XML_DICT
 from .schedule import make_items
 
 
+def caller_layout_batch(model, out: torch.Tensor, offs: np.ndarray) -> torch.Tensor:
+    """``[N, nq]`` engine output of ``model`` (a ``RobotModel``) -> the XML's layout; a planar base's heading is unwrapped along every
+    clip from its first frame's principal value (the hinge coordinate of the reference accumulates from ``qpos0``'s 0)."""
+    if not model.planar_base or out.shape[0] == 0:
+        return out
+    mj = model.to_mj_qpos(out)
+    yaw = mj[:, 2]
+    jump = torch.round((yaw[1:] - yaw[:-1]) / (2 * np.pi))
+    starts = torch.as_tensor(np.asarray(offs[:-1], dtype=np.int64), device=out.device)
+    starts = starts[starts < out.shape[0]]
+    inner = starts[starts > 0]
+    jump[inner - 1] = 0  # no unwrapping across a clip boundary
+    c = torch.cat([torch.zeros(1, dtype=yaw.dtype, device=yaw.device), torch.cumsum(jump, 0)])
+    lens = torch.diff(torch.cat([starts, torch.tensor([out.shape[0]], device=out.device)]))
+    base = torch.repeat_interleave(c[starts], lens)
+    mj[:, 2] = yaw - 2 * np.pi * (c - base)
+    return mj
+
+
 class _Data:
     def __init__(self, owner):
         self._o = owner
@@ -184,22 +203,7 @@ class GeneralMotionRetargeting:
         return self.model.to_mj_qpos(self._qpos, yaw_ref=np.float64(self._yaw))
 
     def _caller_layout_batch(self, out: torch.Tensor, offs: np.ndarray) -> torch.Tensor:
-        """``[N, nq]`` engine output -> the XML's layout; a planar base's heading is unwrapped along every clip from its first
-        frame's principal value (the hinge coordinate of the reference accumulates from ``qpos0``'s 0)."""
-        if not self.model.planar_base or out.shape[0] == 0:
-            return out
-        mj = self.model.to_mj_qpos(out)
-        yaw = mj[:, 2]
-        jump = torch.round((yaw[1:] - yaw[:-1]) / (2 * np.pi))
-        starts = torch.as_tensor(np.asarray(offs[:-1], dtype=np.int64), device=out.device)
-        starts = starts[starts < out.shape[0]]
-        inner = starts[starts > 0]
-        jump[inner - 1] = 0  # no unwrapping across a clip boundary
-        c = torch.cat([torch.zeros(1, dtype=yaw.dtype, device=yaw.device), torch.cumsum(jump, 0)])
-        lens = torch.diff(torch.cat([starts, torch.tensor([out.shape[0]], device=out.device)]))
-        base = torch.repeat_interleave(c[starts], lens)
-        mj[:, 2] = yaw - 2 * np.pi * (c - base)
-        return mj
+        return caller_layout_batch(self.model, out, offs)
 
     def _session(self, names: Sequence[str]):
         """The live session for this frame layout; the warm start follows the object, not the session."""

@@ -1,0 +1,148 @@
+"""``MultiRobotRetargeting`` -- one human motion set retargeted to several robots in shared launches.
+
+The reference retargets to one robot per process (scripts/smplx_to_robot_dataset.py:79-83: one ``GeneralMotionRetargeting`` per
+file and robot).  Here the robots form one ``EngineGroup`` (a common kernel variant, ``gmr_group_*``): every robot's clips -- or
+their parallel-in-time chunks and verification walks -- run in ONE grid, reading the same human key-points through each robot's
+own slot columns.  Every argument of :meth:`MultiRobotRetargeting.retarget_batch` means what it means in
+``GeneralMotionRetargeting.retarget_batch``, and each robot's result is what that call gives for the robot alone.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from ._native import IKParams
+from .params import IK_CONFIG_DICT, ROBOT_XML_DICT
+
+MAX_ROBOTS = 64  # gmr_group_create's limit
+
+
+class MultiRobotRetargeting:
+    """Several robots retargeted from one human source in shared launches.
+
+    ``mr.robots``: the robot names, in the order given; ``mr.engines``: the group's per-robot ``Engine`` (FK, evaluation, the dataset
+    post-processing); ``mr.ik_columns``: the union of the robots' ``ik_columns`` (what a narrowed input needs);
+    ``mr.last_chunk_info``: per robot, ``GeneralMotionRetargeting.last_chunk_info`` of the last batch.
+    """
+
+    def __init__(self, src_human: str, tgt_robots: Sequence[str], actual_human_height: float = None, damping: float = 5e-1,
+                 device: int = 0, verbose: bool = False) -> None:
+        robots = list(tgt_robots)
+        # every refusal before any device work
+        if not robots:
+            raise ValueError("no robots given")
+        if len(robots) > MAX_ROBOTS:
+            raise ValueError(f"{len(robots)} robots: a group holds at most {MAX_ROBOTS}")
+        if len(set(robots)) != len(robots):
+            raise ValueError(f"duplicate robots in {robots}")
+        cfgs = IK_CONFIG_DICT[src_human]  # KeyError where the reference raises (motion_retarget.py:24-33)
+        for r in robots:
+            _ = ROBOT_XML_DICT[r], cfgs[r]
+        from .engine import EngineGroup
+        from .ik_config import load_ik_config
+        from .mjcf import load_robot
+        from .model import compile_model
+        self.src_human = src_human
+        self.robots = robots
+        self.damping = damping
+        self.max_iter = 10
+        self.models, self._cms = [], []
+        for r in robots:
+            if verbose:
+                print("Use robot model: ", ROBOT_XML_DICT[r], " IK config: ", cfgs[r])
+            model = load_robot(str(ROBOT_XML_DICT[r]), name=r)
+            self.models.append(model)
+            self._cms.append(compile_model(model, load_ik_config(cfgs[r]), actual_human_height))
+        self.group = EngineGroup(self._cms, device)
+        self.engines = self.group.engines
+        self.device = self.group.device
+        self.last_chunk_info: Dict[str, dict] = {}
+
+    def close(self):
+        self.group.close()
+
+    @property
+    def ik_columns(self) -> List[str]:
+        """The human bodies any of the robots consumes, in first-appearance order over the robots."""
+        out: List[str] = []
+        for cm in self._cms:
+            out += [n for n in cm.slot_names if n not in out]
+        return out
+
+    def _params(self, offset_to_ground: bool) -> IKParams:
+        return IKParams(damping=self.damping, max_iter=self.max_iter, offset_to_ground=int(bool(offset_to_ground)))
+
+    def retarget_batch(self, pos, quat, body_names: Sequence[str], seq_offsets=None, chunk=0, burn_in: int = 0,
+                       offset_to_ground: bool = False, return_iters: bool = False, verify: bool = True,
+                       human_heights: Optional[Sequence[float]] = None, check: bool = True, clip_start: str = "qpos0"):
+        """``GeneralMotionRetargeting.retarget_batch`` for every robot at once: pos ``[N, B, 3]``, quat ``[N, B, 4]`` (wxyz),
+        float32/float64, numpy or CUDA torch, one input for all robots.  Returns ``{robot: qpos [N, nq]}`` (numpy for numpy input,
+        planar bases in the XML's layout) and, with ``return_iters``, ``{robot: solves per frame}`` as a second value.
+
+        ``chunk > 0`` with ``verify``: every robot's chunks in one launch, every robot's verification walks in a second
+        (``EngineGroup.ik_solve_chunked``).  ``chunk="auto"`` chooses chunk and burn-in (``schedule.auto_chunk``) from all robots'
+        clips together, since they share the wavefront slots; ``(0, 0)`` means whole clips.  Whole clips go in one launch,
+        cost-ordered across robots when the probe pays (``EngineGroup.ik_solve(launch_order="auto")``).  ``human_heights[s]`` applies to clip s of every robot,
+        through each robot's own ``human_height_assumption`` and scale ratio.  ``check`` inspects every robot's solve-count flags.
+        Numpy inputs with more columns than ``ik_columns`` are narrowed on the host first; there is no overlapped host pipeline
+        (``Engine.ik_solve_host``) for several robots: large numpy batches are copied to the device in one piece.
+        """
+        from ._native import INIT_QPOS0, INIT_ROOT_TARGET
+        from .motion_retarget import caller_layout_batch
+        from .schedule import make_items
+        if clip_start not in ("qpos0", "root_target"):
+            raise ValueError("clip_start must be 'qpos0' (the reference) or 'root_target'")
+        clip_init = INIT_ROOT_TARGET if clip_start == "root_target" else INIT_QPOS0
+        names = list(body_names)
+        cols = [cm.slot_columns(names) for cm in self._cms]  # KeyError where the reference raises
+        is_np = isinstance(pos, np.ndarray)
+        if is_np and isinstance(quat, np.ndarray) and pos.ndim == 3:
+            used = np.unique(np.concatenate(cols))
+            if pos.shape[1] > len(used):
+                # host arrays with more bodies than the robots consume: gather the used columns on the host first
+                pos, quat = pos[:, used], quat[:, used]
+                cols = [np.searchsorted(used, c).astype(np.int32) for c in cols]
+        tpos = torch.from_numpy(np.ascontiguousarray(pos)) if is_np else pos
+        tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
+        tpos, tquat = tpos.to(self.device).contiguous(), tquat.to(self.device).contiguous()
+        N = int(tpos.shape[0])
+        offs = np.asarray([0, N] if seq_offsets is None else seq_offsets, dtype=np.int64)
+        if offs[0] != 0 or offs[-1] != N:
+            raise ValueError("seq_offsets must span [0, N]")
+        hs = [None] * len(self.robots)
+        if human_heights is not None:
+            hh = np.asarray(human_heights, dtype=np.float64)
+            if hh.shape != (len(offs) - 1,):
+                raise ValueError("human_heights must hold one height per clip")
+            hs = [hh / cm.config.human_height_assumption / cm.ratio for cm in self._cms]
+        if isinstance(chunk, str):
+            if chunk != "auto":
+                raise ValueError("chunk must be an integer or 'auto'")
+            from .schedule import auto_chunk, group_chunk_offsets
+            slots = 8 * torch.cuda.get_device_properties(self.device).multi_processor_count
+            chunk, burn_in = auto_chunk(group_chunk_offsets([offs] * len(self.robots)), slots)
+        prm = self._params(offset_to_ground)
+        if chunk > 0 and verify:
+            res = self.group.ik_solve_chunked([(tpos, tquat, c, offs) for c in cols], chunk, burn_in, params=prm, height_scales=hs,
+                                              clip_init=clip_init)
+            outs = [(q, it) for q, it, _ in res]
+            infos = [info for _, _, info in res]
+        else:
+            items = [make_items(offs, chunk=chunk, burn_in=burn_in, height_scales=h, clip_init=clip_init) for h in hs]
+            outs = self.group.ik_solve([(tpos, tquat, c, it) for c, it in zip(cols, items)], params=prm, launch_order="auto")
+            infos = [{"chunks": len(it), "passes": 0, "resolved_frames": 0} for it in items]
+        self.last_chunk_info = dict(zip(self.robots, infos))
+        if check and N > 0:
+            flags = torch.stack([torch.stack([(it >> 31).ne(0).any(), ((it >> 30) & 1).ne(0).any()]) for _, it in outs]).cpu().numpy()
+            for r, bad in zip(self.robots, flags):
+                if bad[0]:
+                    raise FloatingPointError(f"{r}: retarget_batch produced non-finite qpos")
+                if bad[1]:
+                    raise RuntimeError(f"{r}: a box QP hit its iteration cap (the reference would assert on a failed QP)")
+        qpos, iters = {}, {}
+        for r, model, (q, it) in zip(self.robots, self.models, outs):
+            q = caller_layout_batch(model, q, offs)
+            qpos[r], iters[r] = (q.cpu().numpy(), it.cpu().numpy()) if is_np else (q, it)
+        return (qpos, iters) if return_iters else qpos

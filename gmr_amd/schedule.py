@@ -89,6 +89,23 @@ def auto_chunk(seq_offsets: Sequence[int], slots: int = 2048):
     return int(min(128, max(16, c_latency, c_fill))), 24
 
 
+def group_item_bases(n_items: Sequence[int]) -> np.ndarray:
+    """Global item numbering of a group launch (gmr_group_plan_order / gmr_group_ik_solve_ordered): item k of member i has the index
+    ``bases[i] + k``, ``bases[i]`` = the items of the members before i (members without work add nothing); ``bases[-1]`` is the total."""
+    n = np.asarray(n_items, dtype=np.int64).reshape(-1)
+    if np.any(n < 0):
+        raise ValueError("n_items must be >= 0")
+    return np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+
+
+def group_chunk_offsets(seq_offsets_per_member) -> np.ndarray:
+    """The clips of all members of a group (``None``: a member without work) as one set of offsets, lengths in member order: the
+    input of ``auto_chunk`` for a group launch, whose members share the wavefront slots."""
+    lens = [np.diff(np.asarray(o, dtype=np.int64)) for o in seq_offsets_per_member if o is not None]
+    lens = np.concatenate(lens) if lens else np.zeros(0, dtype=np.int64)
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+
 def plan_walks(items: np.ndarray, seq_offsets: Sequence[int], chunk: int) -> np.ndarray:
     """Verification walks for the tracked chunk items of ``make_items(..., chunk, track=True)``: one item per clip that has
     more than one chunk, running from the clip's second chunk to its end with ``check_stride = chunk`` (gmr_blob.h): it starts

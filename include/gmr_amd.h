@@ -142,7 +142,16 @@ int gmr_ik_solve_ordered(gmr_model *m, const void *human_pos, const void *human_
  *   gmr_group_model    borrowed handle of member i for everything else (gmr_fk, gmr_evaluate, sessions, gmr_ik_solve alone);
  *                      members are destroyed with the group
  *   gmr_group_ik_solve inputs host [n_models], member i's arguments exactly as gmr_ik_solve takes them (n_items = 0: no work
- *                      for that member); params are shared; asynchronous on `stream`                                        */
+ *                      for that member); params are shared; asynchronous on `stream`
+ * Cost-ordered group launch: gmr_ik_plan_order / gmr_ik_solve_ordered over all members' items together.  Both number the items
+ * globally: item k of member i is base_i + k, base_i = the sum of n_items over the members before i (members without work add
+ * nothing); order_out / launch_order are device int32 [sum of n_items].
+ *   gmr_group_plan_order       probes the first probe_frames frames of every member's items in one grid and orders all of them
+ *                              by probe solves per frame x frames, most expensive first, across robots; plain items only
+ *                              (check_stride != 0: GMR_EINVAL)
+ *   gmr_group_ik_solve_ordered gmr_group_ik_solve with workgroup b running global item launch_order[b] (a permutation of
+ *                              0 .. total-1: entries outside that range are skipped, a repeated entry leaves another item
+ *                              unsolved); results are those of gmr_group_ik_solve bit for bit                                  */
 typedef struct gmr_group gmr_group;
 typedef struct gmr_group_input {
   const void *human_pos, *human_quat; /* device */
@@ -161,6 +170,10 @@ int gmr_group_size(const gmr_group *g);
 gmr_model *gmr_group_model(gmr_group *g, int i);
 const char *gmr_group_last_error(const gmr_group *g);
 int gmr_group_ik_solve(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, void *stream);
+int gmr_group_plan_order(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, int probe_frames, int32_t *order_out,
+                         void *stream);
+int gmr_group_ik_solve_ordered(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, const int32_t *launch_order,
+                               void *stream);
 
 /* Single-sequence sessions ("teleop"): one frame per call, warm start carried in the session -- the semantics of calling
  * GeneralMotionRetargeting.retarget once per captured frame (motion_retarget.py:139-185).  Inputs and outputs are HOST
