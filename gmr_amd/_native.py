@@ -28,7 +28,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_ik_solve", "gmr_fk", "gmr_fk_shape", "gmr_dof_to_rot", "gmr_rot_to_dof", "gmr_local_rot_to_global", "gmr_fk_min_height", "gmr_bvh_fk", "gmr_bvh_parse_header", "gmr_bvh_parse_motion", "gmr_evaluate", "gmr_smplx_keypoints", "gmr_smplx_keypoints_cols", "gmr_smplx_keypoints_in", "gmr_bvh_fk_rows", "gmr_bvh_parse_motion_device",
            "gmr_session_create", "gmr_session_destroy", "gmr_session_reset", "gmr_session_step", "gmr_session_state", "gmr_session_set_persistent", "gmr_ik_plan_order", "gmr_ik_solve_ordered",
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
-           "gmr_group_plan_order", "gmr_group_ik_solve_ordered"]
+           "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue"]
 
 
 class IKParams(C.Structure):
@@ -59,6 +59,19 @@ class GroupInput(C.Structure):
         ("human_pos", C.c_void_p), ("human_quat", C.c_void_p), ("in_dtype", C.c_int32), ("n_cols", C.c_int32),
         ("slot_col", C.c_void_p), ("n_frames", C.c_int64), ("items", C.c_void_p), ("n_items", C.c_int32), ("reserved", C.c_int32),
         ("qpos_init", C.c_void_p), ("qpos_final", C.c_void_p), ("qpos_out", C.c_void_p), ("iters_out", C.c_void_p), ("frames_done", C.c_void_p),
+    ]
+
+
+MOTION_HEIGHT_ADJUST, MOTION_ROOT_ORIGIN = 1, 2
+
+
+class MotionInput(C.Structure):
+    """``gmr_motion_input`` (include/gmr_amd.h): one model's arguments of the dataset epilogue."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("n_seq", C.c_int32), ("flags", C.c_int32),
+        ("ground_offset", C.c_double), ("root_pos_out", C.c_void_p), ("root_rot_out", C.c_void_p), ("dof_pos_out", C.c_void_p),
+        ("local_body_pos_out", C.c_void_p), ("min_z_out", C.c_void_p),
     ]
 
 
@@ -128,6 +141,10 @@ def load():
     L.gmr_group_plan_order.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), C.c_int, vp, vp]
     L.gmr_group_ik_solve_ordered.restype = C.c_int
     L.gmr_group_ik_solve_ordered.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp, vp]
+    L.gmr_motion_epilogue.restype = C.c_int
+    L.gmr_motion_epilogue.argtypes = [vp, C.POINTER(MotionInput), vp]
+    L.gmr_group_motion_epilogue.restype = C.c_int
+    L.gmr_group_motion_epilogue.argtypes = [vp, C.POINTER(MotionInput), vp]
     L.gmr_bvh_parse_header.restype = C.c_int
     L.gmr_bvh_parse_header.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.gmr_evaluate.restype = C.c_int

@@ -24,6 +24,7 @@
 #include "smplx_kernel.hip.h"
 #include "bvh_parse_kernel.hip.h"
 #include "kin_ops_kernel.hip.h"
+#include "motion_kernel.hip.h"
 #include "bvh_text.h"
 
 using gmr::u64;
@@ -894,6 +895,7 @@ int build_device_model(gmr_model *m) {
   GMR_LDS_OPT_IN(gmr::eval_kernel)
   GMR_LDS_OPT_IN(gmr::fk_pos_kernel<1>) GMR_LDS_OPT_IN(gmr::fk_pos_kernel<2>)
   GMR_LDS_OPT_IN(gmr::fk_kernel<0>) GMR_LDS_OPT_IN(gmr::fk_kernel<1>)
+  GMR_LDS_OPT_IN(gmr::motion_epilogue_kernel)
 #undef GMR_LDS_OPT_IN
   (void)hipGetLastError();
   return GMR_OK;
@@ -1685,6 +1687,104 @@ int gmr_fk_min_height(gmr_model *m, const float *root_pos, const float *root_rot
   hipLaunchKernelGGL(gmr::fk_minkey_decode, dim3((n_seq + 255) / 256), dim3(256), 0, st, keys, min_z_out, n_seq);
   HIP_TRY(m, hipGetLastError());
   return GMR_OK;
+}
+
+// ------------------------------------------------------------------ dataset epilogue (motion_kernel.hip.h)
+// Validate every member with work, upload the entries, clip offsets and minimum keys in one block of stream-ordered scratch,
+// and run pass 1 over all members' tiles in one grid, pass 2 (height adjust, decoded minima) in a second when any member needs it.
+// `models[i]` goes with `inputs[i]`; a group call names the member in its messages.  Errors land in `err`.
+static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, int n, int device, hipStream_t st, bool group, std::string &err) {
+  std::vector<gmr::MotionEntry> ent(n);
+  size_t n_offs = 0, n_keys = 0;
+  int64_t tiles = 0, finish = 0, lds = 0;
+  bool any = false, any_finish = false;
+  for (int i = 0; i < n; ++i) {
+    const gmr_motion_input &in = inputs[i];
+    const gmr_model *m = models[i];
+    const std::string who = group ? "member " + std::to_string(i) + ": " : "";
+    gmr::MotionEntry &e = ent[i];
+    e = gmr::MotionEntry{};
+    e.tile_base = tiles; e.finish_base = finish;
+    if (in.n_frames < 0) { err = who + "negative n_frames"; return GMR_EINVAL; }
+    if (in.n_frames == 0) continue;  // no work for this member
+    if (m->dm.root_planar) { err = who + "the motion schema needs a free-joint root; a planar base is not supported"; return GMR_EUNSUPPORTED; }
+    const int ndof = m->fk.ndof;
+    if (!in.qpos || !in.seq_offsets || !in.root_pos_out || !in.root_rot_out || !in.local_body_pos_out || (!in.dof_pos_out && ndof > 0)) {
+      err = who + "null argument"; return GMR_EINVAL;
+    }
+    if (in.flags & ~(GMR_MOTION_HEIGHT_ADJUST | GMR_MOTION_ROOT_ORIGIN)) { err = who + "unknown flags"; return GMR_EINVAL; }
+    if (in.n_seq < 1 || in.seq_offsets[0] != 0 || in.seq_offsets[in.n_seq] != in.n_frames) {
+      err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL;
+    }
+    for (int s = 0; s < in.n_seq; ++s)
+      if (in.seq_offsets[s + 1] < in.seq_offsets[s]) { err = who + "seq_offsets must not decrease"; return GMR_EINVAL; }
+    const int64_t need = gmr::motion_lds_bytes(m->fk.nbody, ndof, m->fk.nslots);
+    if (need > 160 * 1024) { err = who + "the epilogue tile needs " + std::to_string(need) + " bytes of LDS"; return GMR_EUNSUPPORTED; }
+    lds = std::max(lds, need);
+    e.fk = m->fk;
+    e.qpos = in.qpos;
+    e.root_pos = in.root_pos_out; e.root_rot = in.root_rot_out; e.dof_pos = in.dof_pos_out;
+    e.local_body_pos = in.local_body_pos_out; e.min_z = in.min_z_out;
+    e.ground_offset = in.ground_offset;
+    e.n_frames = in.n_frames; e.n_seq = in.n_seq;
+    e.flags = in.flags | (in.min_z_out ? gmr::kMotionWantMin : 0);
+    // offsets and keys: byte offsets into the scratch block for now, device pointers once it exists
+    e.seq_offsets = reinterpret_cast<const int64_t *>(n_offs);
+    e.keys = reinterpret_cast<int *>(n_keys);
+    n_offs += (size_t)in.n_seq + 1;
+    n_keys += (size_t)in.n_seq;
+    tiles += (in.n_frames + gmr::kFkWave - 1) / gmr::kFkWave;
+    const int64_t items = ((e.flags & gmr::kMotionHeight) ? in.n_frames : 0) + ((e.flags & gmr::kMotionWantMin) ? in.n_seq : 0);
+    finish += (items + gmr::kMotionFinishThreads - 1) / gmr::kMotionFinishThreads;
+    any = true;
+    any_finish = any_finish || items > 0;
+  }
+  if (!any) return GMR_OK;
+  if (tiles > 0x7fffffff || finish > 0x7fffffff || n_keys > 0x7fffffff) { err = "too many frames for one launch"; return GMR_EINVAL; }
+  if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
+  const size_t ent_bytes = sizeof(gmr::MotionEntry) * (size_t)n, off_at = (ent_bytes + 15) & ~size_t(15);
+  const size_t key_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15), total = key_at + sizeof(int) * std::max<size_t>(n_keys, 1);
+  CallScratch sc;
+  gmr_model *m0 = models[0];
+  if (scratch_alloc(m0, sc, total, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
+  uint8_t *ws = static_cast<uint8_t *>(sc.p);
+  std::vector<uint8_t> host(key_at, 0);
+  for (int i = 0; i < n; ++i) {
+    gmr::MotionEntry &e = ent[i];
+    if (inputs[i].n_frames <= 0) continue;
+    const size_t o = reinterpret_cast<size_t>(e.seq_offsets), k = reinterpret_cast<size_t>(e.keys);
+    memcpy(host.data() + off_at + sizeof(int64_t) * o, inputs[i].seq_offsets, sizeof(int64_t) * ((size_t)inputs[i].n_seq + 1));
+    e.seq_offsets = reinterpret_cast<const int64_t *>(ws + off_at) + o;
+    e.keys = reinterpret_cast<int *>(ws + key_at) + k;
+  }
+  memcpy(host.data(), ent.data(), ent_bytes);
+  if (hipMemcpyAsync(ws, host.data(), key_at, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
+  const auto *d_ent = reinterpret_cast<const gmr::MotionEntry *>(ws);
+  if (n_keys > 0)
+    hipLaunchKernelGGL(gmr::fk_minkey_init, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, st, reinterpret_cast<int *>(ws + key_at), (int)n_keys);
+  hipLaunchKernelGGL(gmr::motion_epilogue_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, st, d_ent, n);
+  if (any_finish)
+    hipLaunchKernelGGL(gmr::motion_finish_kernel, dim3((unsigned)finish), dim3(gmr::kMotionFinishThreads), 0, st, d_ent, n);
+  if (hipGetLastError() != hipSuccess) { err = "kernel launch failed"; return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_epilogue(gmr_model *m, const gmr_motion_input *in, void *stream) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  std::string err;
+  const int rc = motion_run(&m, in, 1, m->device, static_cast<hipStream_t>(stream), false, err);
+  if (rc != GMR_OK) m->err = err;
+  return rc;
+}
+
+int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void *stream) {
+  if (!g) return GMR_EINVAL;
+  g->err.clear();
+  if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
+  const int rc = motion_run(g->models.data(), inputs, (int)g->models.size(), g->device, static_cast<hipStream_t>(stream), true, g->err);
+  return rc;
 }
 
 /* Frames per wavefront of the adapter kernels: runs long enough that a wavefront's setup (plan, tables) is amortised and its

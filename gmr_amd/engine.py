@@ -55,6 +55,43 @@ def _state_arrays(nq: int, device, items: np.ndarray, qpos_init: Optional[torch.
     return qpos_init, qfin
 
 
+def _motion_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, height_adjust: bool, root_origin_offset: bool, ground_offset: float,
+                  out, min_z: Optional[torch.Tensor], what: str = ""):
+    """Check one model's epilogue arguments and fill its ``MotionInput``.  Returns (input, (root_pos, root_rot, dof_pos,
+    local_body_pos), keep-alive)."""
+    if not isinstance(qpos, torch.Tensor) or qpos.device != eng.device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or qpos.shape[1] != eng.nq:
+        raise EngineError(what + f"qpos must be a float64 [N, {eng.nq}] tensor on the engine's device")
+    qpos = qpos.contiguous()
+    N = int(qpos.shape[0])
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != N:
+        raise ValueError(what + "seq_offsets must span [0, N]")
+    if (np.diff(offs) < 0).any():
+        raise ValueError(what + "seq_offsets must not decrease")
+    shapes = ((N, 3, torch.float64), (N, 4, torch.float64), (N, eng.nq - 7, torch.float64), (N, eng.nbody, 3, torch.float32))
+    if out is None:
+        res = tuple(torch.empty(sh[:-1], dtype=sh[-1], device=eng.device) for sh in shapes)
+    else:
+        res = tuple(out)
+        if len(res) != 4 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != sh[:-1] or t.dtype != sh[-1] or t.device != eng.device
+                                or not t.is_contiguous() for t, sh in zip(res, shapes)):
+            raise EngineError(what + "out must be contiguous (root_pos f64 [N, 3], root_rot f64 [N, 4], dof_pos f64 [N, nq-7], "
+                                     "local_body_pos f32 [N, nbody, 3]) on the engine's device")
+    if min_z is not None and (min_z.device != eng.device or min_z.dtype != torch.float32 or tuple(min_z.shape) != (len(offs) - 1,)
+                              or not min_z.is_contiguous()):
+        raise EngineError(what + "min_z must be a contiguous float32 [n_seq] tensor on the engine's device")
+    mi = _native.MotionInput()
+    mi.qpos, mi.n_frames = qpos.data_ptr(), N
+    mi.seq_offsets, mi.n_seq = offs.ctypes.data, len(offs) - 1
+    mi.flags = (_native.MOTION_HEIGHT_ADJUST if height_adjust else 0) | (_native.MOTION_ROOT_ORIGIN if root_origin_offset else 0)
+    mi.ground_offset = float(ground_offset)
+    mi.root_pos_out, mi.root_rot_out, mi.dof_pos_out = (t.data_ptr() for t in res[:3])
+    mi.local_body_pos_out = res[3].data_ptr()
+    mi.min_z_out = None if min_z is None else min_z.data_ptr()
+    return mi, res, (qpos, offs)
+
+
 class Engine:
     def __init__(self, cm: CompiledModel, device: int = 0, _borrowed_handle=None):
         if not torch.cuda.is_available():
@@ -469,6 +506,18 @@ class Engine:
         return out
 
 
+    def motion_epilogue(self, qpos: torch.Tensor, seq_offsets, height_adjust: bool = True, root_origin_offset: bool = True,
+                        ground_offset: float = 0.0, out=None, min_z: Optional[torch.Tensor] = None):
+        """The dataset post-processing of ``dataset.motions_from_qpos`` in one native call (``gmr_motion_epilogue``): qpos
+        ``[N, nq]`` float64 (free-joint layout, concatenated clips) -> device tensors (root_pos f64 [N, 3], root_rot f64 [N, 4]
+        xyzw, dof_pos f64 [N, nq-7], local_body_pos f32 [N, nbody, 3]), bit for bit what the two FK launches and the torch ops
+        give.  ``out``: caller-owned result tensors in that order; ``min_z``: a float32 [n_seq] tensor that also receives the
+        per-clip minimum body height (``fk_min_height``).  Asynchronous on the current stream."""
+        mi, res, keep = _motion_input(self, qpos, seq_offsets, height_adjust, root_origin_offset, ground_offset, out, min_z)
+        self._check(self._lib.gmr_motion_epilogue(self._h, C.byref(mi), self._stream()), "gmr_motion_epilogue")
+        return res
+
+
 class EngineGroup:
     """Several robots' batches in ONE launch (``gmr_group_*``; BASELINE config 4, "heterogeneous trees in one launch").
 
@@ -621,6 +670,29 @@ class EngineGroup:
         self._check(self._lib.gmr_group_plan_order(self._g, inputs, C.byref(prm), int(probe_frames or Engine.PROBE_FRAMES), _ptr(order),
                                                    self._stream()), "gmr_group_plan_order")
         return order
+
+    def motion_epilogue(self, batches, height_adjust: bool = True, root_origin_offset: bool = True, ground_offset: float = 0.0, min_z=None):
+        """:meth:`Engine.motion_epilogue` for every member in shared launches (``gmr_group_motion_epilogue``).  ``batches[i]``:
+        ``(qpos, seq_offsets)`` of member i, or ``None`` (no work); ``min_z``: ``None`` or one float32 [n_seq] tensor (or ``None``)
+        per member.  Returns per member the four device tensors, or ``None``."""
+        if len(batches) != len(self.engines):
+            raise EngineError("one batch (or None) per group member")
+        mz = [None] * len(batches) if min_z is None else list(min_z)
+        if len(mz) != len(batches):
+            raise EngineError("min_z: one tensor (or None) per group member")
+        inputs = (_native.MotionInput * len(batches))()
+        outs, keep = [], []
+        for i, (eng, b) in enumerate(zip(self.engines, batches)):
+            if b is None:
+                outs.append(None)
+                continue
+            qpos, offs = b
+            mi, res, k = _motion_input(eng, qpos, offs, height_adjust, root_origin_offset, ground_offset, None, mz[i], f"member {i}: ")
+            inputs[i] = mi
+            outs.append(res)
+            keep.append(k)
+        self._check(self._lib.gmr_group_motion_epilogue(self._g, inputs, self._stream()), "gmr_group_motion_epilogue")
+        return outs
 
     def ik_solve_chunked(self, batches, chunk, burn_in: int, params: Optional[IKParams] = None, eps: float = 1e-7, height_scales=None,
                          chunk_init: int = _native.INIT_ROOT_TARGET, clip_init: int = _native.INIT_QPOS0):

@@ -89,8 +89,78 @@ class MultiRobotRetargeting:
         Numpy inputs with more columns than ``ik_columns`` are narrowed on the host first; there is no overlapped host pipeline
         (``Engine.ik_solve_host``) for several robots: large numpy batches are copied to the device in one piece.
         """
-        from ._native import INIT_QPOS0, INIT_ROOT_TARGET
         from .motion_retarget import caller_layout_batch
+        is_np = isinstance(pos, np.ndarray)
+        outs, offs = self._solve(pos, quat, body_names, seq_offsets, chunk, burn_in, offset_to_ground, verify, human_heights, check, clip_start)
+        qpos, iters = {}, {}
+        for r, model, (q, it) in zip(self.robots, self.models, outs):
+            q = caller_layout_batch(model, q, offs)
+            qpos[r], iters[r] = (q.cpu().numpy(), it.cpu().numpy()) if is_np else (q, it)
+        return (qpos, iters) if return_iters else qpos
+
+    def _refuse_planar(self):
+        planar = [r for r, m in zip(self.robots, self.models) if m.planar_base]
+        if planar:
+            # dataset.motions_from_qpos's refusal: the motion schema reads a free-joint root out of qpos
+            raise NotImplementedError(f"{planar}: the dataset post-processing assumes a free-joint root; use retarget_batch for a planar-base robot")
+
+    def motions_from_qpos(self, qpos: Dict[str, torch.Tensor], seq_offsets: Sequence[int], fps, height_adjust: bool = True,
+                          root_origin_offset: bool = True, ground_offset: float = 0.0) -> Dict[str, List[Dict]]:
+        """``dataset.motions_from_qpos`` for every robot, post-processed in shared launches (``EngineGroup.motion_epilogue``):
+        ``qpos[robot]`` ``[N, nq]`` float64 on the group's device, the same clips for every robot -> ``{robot: [motion dict per
+        clip]}``, the same keys, dtypes and arrays as the single-robot call.  The arrays are row slices of per-robot page-locked
+        host arrays; every copy is in flight before the one synchronisation."""
+        self._refuse_planar()
+        offs = np.asarray(seq_offsets, dtype=np.int64)
+        missing = [r for r in self.robots if r not in qpos]
+        if missing:
+            raise KeyError(f"no qpos for {missing}")
+        batches = []
+        for r in self.robots:
+            q = qpos[r]
+            q = torch.from_numpy(np.ascontiguousarray(q)).to(self.device) if isinstance(q, np.ndarray) else q
+            if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != int(q.shape[0]):
+                raise ValueError("seq_offsets must span [0, N]")
+            batches.append((q, offs))
+        fps_list = list(fps) if isinstance(fps, (list, tuple, np.ndarray)) else [fps] * (len(offs) - 1)
+        res = self.group.motion_epilogue(batches, height_adjust=height_adjust, root_origin_offset=root_origin_offset, ground_offset=ground_offset)
+        hosts = []
+        for arrays in res:
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in arrays]
+            for h, t in zip(host, arrays):
+                h.copy_(t, non_blocking=True)
+            hosts.append(host)
+        torch.cuda.current_stream(self.device).synchronize()
+        out: Dict[str, List[Dict]] = {}
+        for r, model, host in zip(self.robots, self.models, hosts):
+            rp, rr, dp, lb = (h.numpy() for h in host)
+            names = list(model.body_names)
+            clips = []
+            for s in range(len(offs) - 1):
+                a, b = int(offs[s]), int(offs[s + 1])
+                clips.append({"fps": fps_list[s], "root_pos": rp[a:b], "root_rot": rr[a:b], "dof_pos": dp[a:b],
+                              "local_body_pos": lb[a:b], "link_body_list": names})
+            out[r] = clips
+        return out
+
+    def retarget_clips(self, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30, height_adjust: bool = True,
+                       root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
+                       clip_start: str = "qpos0") -> Dict[str, List[Dict]]:
+        """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
+        solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
+        ``dataset.MotionWriter.submit`` as they are."""
+        self._refuse_planar()
+        tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
+        tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
+        outs, offs = self._solve(tpos.to(self.device), tquat.to(self.device), body_names, seq_offsets, chunk, burn_in, False, True,
+                                 human_heights, True, clip_start)
+        return self.motions_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, height_adjust=height_adjust,
+                                      root_origin_offset=root_origin_offset)
+
+    def _solve(self, pos, quat, body_names, seq_offsets, chunk, burn_in, offset_to_ground, verify, human_heights, check, clip_start):
+        """The solve of :meth:`retarget_batch`: per robot (qpos [N, nq] in the engine's layout, solves per frame) on the device, and
+        the clip offsets."""
+        from ._native import INIT_QPOS0, INIT_ROOT_TARGET
         from .schedule import make_items
         if clip_start not in ("qpos0", "root_target"):
             raise ValueError("clip_start must be 'qpos0' (the reference) or 'root_target'")
@@ -141,8 +211,4 @@ class MultiRobotRetargeting:
                     raise FloatingPointError(f"{r}: retarget_batch produced non-finite qpos")
                 if bad[1]:
                     raise RuntimeError(f"{r}: a box QP hit its iteration cap (the reference would assert on a failed QP)")
-        qpos, iters = {}, {}
-        for r, model, (q, it) in zip(self.robots, self.models, outs):
-            q = caller_layout_batch(model, q, offs)
-            qpos[r], iters[r] = (q.cpu().numpy(), it.cpu().numpy()) if is_np else (q, it)
-        return (qpos, iters) if return_iters else qpos
+        return outs, offs

@@ -30,6 +30,47 @@ def plan_files(src_folder: str, tgt_folder: str, want: Callable[[str], bool], sr
     return srcs, tgts, skipped
 
 
+def plan_robot_targets(srcs: Sequence[str], src_folder: str, tgt_folder: str, robots: Sequence[str], src_ext: str,
+                       override: bool) -> Tuple[List[str], List[Tuple[str, ...]], int]:
+    """``--robots``: robot r's target of a source is ``<tgt_folder>/<r>/<relative path>.pkl`` (``plan_files``'s rule with
+    ``tgt_folder/r`` as the target folder).  A source is converted when any robot lacks its target, or with ``override``.
+    Returns (sources, per-source tuples of targets in robot order, skipped)."""
+    out_s, out_t, skipped = [], [], 0
+    for s in srcs:
+        ts = tuple(s.replace(src_folder, os.path.join(tgt_folder, r)).replace(src_ext, ".pkl") for r in robots)
+        if not override and all(os.path.exists(t) for t in ts):
+            skipped += 1
+            continue
+        out_s.append(s)
+        out_t.append(ts)
+    return out_s, out_t, skipped
+
+
+def resolve_robots(ap, args, default: str = "unitree_g1") -> None:
+    """``--robot`` xor ``--robots``: sets ``args.robot_list`` (the ``--robots`` names, or ``None``) and ``args.robot`` (its default
+    when neither is given)."""
+    if args.robots is not None and args.robot is not None:
+        ap.error("--robot and --robots exclude each other")
+    args.robot_list = None
+    if args.robots is not None:
+        names = [r.strip() for r in args.robots.split(",") if r.strip()]
+        if not names:
+            ap.error("--robots needs at least one robot name")
+        if len(set(names)) != len(names):
+            ap.error(f"--robots names a robot twice: {args.robots}")
+        args.robot_list = names
+    elif args.robot is None:
+        args.robot = default
+
+
+def plan(args, src_ext: str, want: Callable[[str], bool], natural: bool = False) -> Tuple[List[str], list, int]:
+    """The sources to convert and their targets: one path each (``--robot``), or a tuple per source in ``--robots`` order."""
+    if args.robot_list is None:
+        return plan_files(args.src_folder, args.tgt_folder, want, src_ext, args.override, natural=natural)
+    srcs, _, _ = plan_files(args.src_folder, args.tgt_folder, want, src_ext, True, natural=natural)
+    return plan_robot_targets(srcs, args.src_folder, args.tgt_folder, args.robot_list, src_ext, args.override)
+
+
 def hard_motion_names(paths: Sequence[str]) -> List[str]:
     """Motion names listed in the reference's ``assets/hard_motions/*.txt`` (``Motion: <path>, ...`` lines; smplx_to_robot_dataset.py:193-203)."""
     out = []
@@ -49,6 +90,8 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--device", default=None, type=int, help="GPU to use (default: LOCAL_RANK under torch.distributed.run, else 0)")
     ap.add_argument("--clip_start", default="qpos0", choices=["qpos0", "root_target"],
                     help="qpos0: the reference (every clip starts from the model's rest pose); root_target: start with the floating base on the first root target (not the reference's numbers for the first frames; spares clips that face away from qpos0 their slow start)")
+    ap.add_argument("--robots", default=None, type=str,
+                    help="comma-separated robots solved together from each batch (MultiRobotRetargeting); robot r's files go to <tgt_folder>/<r>/...")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -62,6 +105,8 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
     if args.shard_by_rank and world > 1:
         pairs = pairs[rank::world]
         print(f"rank {rank} of {world}: {len(pairs)} of them")
+    if pairs and getattr(args, "robot_list", None):
+        return _convert_robots(args, pairs, src_human, batches, retarget_kw, workers, done)
     if pairs:
         from .. import GeneralMotionRetargeting as GMR, dataset
         g = GMR(src_human=src_human, tgt_robot=args.robot, device=args.device)
@@ -77,5 +122,27 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
                                                  clip_start=args.clip_start, **retarget_kw(batch))
                 writer.submit(motions, [target_of[f] for f in batch.files])
         print(f"{writer.written} files written, {failed} could not be loaded")
+    print(done, args.tgt_folder)
+    return 0
+
+
+def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw: Callable, workers: int, done: str) -> int:
+    """``convert`` for ``--robots``: each batch is loaded once and solved for every robot (``MultiRobotRetargeting.retarget_clips``);
+    a target that exists already is skipped by the writer unless ``--override``."""
+    from .. import MultiRobotRetargeting, dataset
+    mr = MultiRobotRetargeting(src_human, args.robot_list, device=args.device)
+    target_of, failed = dict(pairs), 0
+    with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
+        for batch in batches([s for s, _ in pairs], mr.ik_columns):
+            for f, why in batch.skipped:
+                print(f"Error loading {f}: {why}")
+                failed += 1
+            if not len(batch):
+                continue
+            motions = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                        clip_start=args.clip_start, **retarget_kw(batch))
+            for i, r in enumerate(mr.robots):
+                writer.submit(motions[r], [target_of[f][i] for f in batch.files])
+    print(f"{writer.written} files written, {failed} could not be loaded")
     print(done, args.tgt_folder)
     return 0

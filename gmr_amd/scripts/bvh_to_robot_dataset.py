@@ -8,20 +8,21 @@ from __future__ import annotations
 
 import argparse
 
-from ._walk import add_common_flags, convert, plan_files
+from ._walk import add_common_flags, convert, plan, resolve_robots
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--src_folder", required=True, type=str, help="Folder containing BVH motion files to load.")
     ap.add_argument("--tgt_folder", default="../../motion_data/LAFAN1_g1_gmr", help="Folder to save the retargeted motion files.")
-    ap.add_argument("--robot", default="unitree_g1")
+    ap.add_argument("--robot", default=None, help="(default: unitree_g1)")
     ap.add_argument("--target_fps", default=30, type=int, help="(accepted like the reference, which stores 30 whatever it is given)")
     ap.add_argument("--batch_files", default=64, type=int, help="files per GPU batch (one skeleton per batch)")
     ap.add_argument("--threads", default=8, type=int, help="host threads reading files / writing pickles")
     add_common_flags(ap)
     args = ap.parse_args(argv)
-    srcs, tgts, skipped = plan_files(args.src_folder, args.tgt_folder, lambda n: n.endswith(".bvh"), ".bvh", args.override)
+    resolve_robots(ap, args)
+    srcs, tgts, skipped = plan(args, ".bvh", lambda n: n.endswith(".bvh"))
     print(f"{len(srcs)} files to retarget ({skipped} skipped: target exists)")
 
     def batches(todo, columns):

@@ -11,14 +11,14 @@ from __future__ import annotations
 import argparse
 import os
 
-from ._walk import add_common_flags, convert, hard_motion_names, plan_files
+from ._walk import add_common_flags, convert, hard_motion_names, plan, resolve_robots
 
 EXCLUDE_FILE_CONTENT = ["BMLrub", "EKUT", "crawl", "_lie", "upstairs", "downstairs"]  # smplx_to_robot_dataset.py:218
 
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--robot", default="unitree_g1")
+    ap.add_argument("--robot", default=None, help="(default: unitree_g1)")
     ap.add_argument("--src_folder", type=str, required=True, help="folder of joint-array .npz files (smplx_adapter.save_joint_file)")
     ap.add_argument("--tgt_folder", type=str, required=True)
     ap.add_argument("--num_cpus", default=4, type=int, help="host threads reading files / writing pickles (the reference's worker processes)")
@@ -26,7 +26,8 @@ def main(argv=None) -> int:
     ap.add_argument("--batch_files", default=1024, type=int)
     add_common_flags(ap)
     args = ap.parse_args(argv)
-    srcs, tgts, skipped = plan_files(args.src_folder, args.tgt_folder, lambda n: n.endswith(".npz") and not n.endswith("_stagei.npz"), ".npz", args.override, natural=True)
+    resolve_robots(ap, args)
+    srcs, tgts, skipped = plan(args, ".npz", lambda n: n.endswith(".npz") and not n.endswith("_stagei.npz"), natural=True)
     print("full args_list:", len(srcs))
     lists = args.hard_motions
     if lists is None:

@@ -32,6 +32,9 @@
  *   gmr_fk_shape       the same with `fitted_shape` (per-body scale of the local translations, kinematics_model.py:225)
  *   gmr_fk_min_height  the clip-global `torch.min(body_pos[..., 2])` of the height adjust
  *                      (scripts/smplx_to_robot_dataset.py:118-126)
+ *   gmr_motion_epilogue, gmr_group_motion_epilogue  the whole post-processing after the retarget loop
+ *                      (scripts/smplx_to_robot_dataset.py:93-131): root_rot / dof_pos out of qpos, local_body_pos, the height
+ *                      adjust and the root-origin offset -- for one model, or for every member of a group in shared launches
  *   gmr_dof_to_rot     KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -174,6 +177,33 @@ int gmr_group_plan_order(gmr_group *g, const gmr_group_input *inputs, const gmr_
                          void *stream);
 int gmr_group_ik_solve_ordered(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, const int32_t *launch_order,
                                void *stream);
+
+/* The dataset epilogue (what follows the solve in scripts/smplx_to_robot_dataset.py:93-131): per frame of a free-joint qpos
+ * (layout [x y z qw qx qy qz hinges]), the arrays of the motion-file schema, bit for bit what the separate calls give:
+ *   root_rot_out        qpos[:, [4,5,6,3]] (xyzw)                 dof_pos_out   qpos[:, 7:]
+ *   local_body_pos_out  gmr_fk with root position 0 and the identity root rotation, dof = (float)qpos[:, 7:]
+ *   root_pos_out        qpos[:, :3]; GMR_MOTION_HEIGHT_ADJUST: z = (z - (double)low_s) + ground_offset, low_s = the value
+ *                       gmr_fk_min_height gives clip s for ((float)qpos[:, :3], (float)root_rot, (float)dof);
+ *                       GMR_MOTION_ROOT_ORIGIN: xy minus the xy of the clip's first frame
+ *   min_z_out           low_s per clip (+inf for an empty clip), or NULL
+ * seq_offsets (host) start at 0, end at n_frames and never decrease (empty clips are allowed).  A planar-base model is refused
+ * with GMR_EUNSUPPORTED, a model whose tile does not fit in LDS too.  Asynchronous on `stream`; the handle's device is selected.
+ *   gmr_motion_epilogue        one model
+ *   gmr_group_motion_epilogue  inputs host [group size]: member i's arguments (n_frames = 0: no work), all members in one grid  */
+#define GMR_MOTION_HEIGHT_ADJUST 1
+#define GMR_MOTION_ROOT_ORIGIN 2
+typedef struct gmr_motion_input {
+  const double *qpos;          /* device [n_frames][nq] f64, free-joint layout                    */
+  int64_t n_frames;
+  const int64_t *seq_offsets;  /* host [n_seq+1], 0 .. n_frames, non-decreasing (empty clips ok)  */
+  int32_t n_seq, flags;        /* GMR_MOTION_* */
+  double ground_offset;
+  double *root_pos_out, *root_rot_out, *dof_pos_out;   /* device [n][3], [n][4] xyzw, [n][nq-7] f64 */
+  float *local_body_pos_out;   /* device [n][nbody][3] f32 */
+  float *min_z_out;            /* device [n_seq] f32 or NULL: low_s as gmr_fk_min_height gives it */
+} gmr_motion_input;
+int gmr_motion_epilogue(gmr_model *m, const gmr_motion_input *in, void *stream);
+int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void *stream);
 
 /* Single-sequence sessions ("teleop"): one frame per call, warm start carried in the session -- the semantics of calling
  * GeneralMotionRetargeting.retarget once per captured frame (motion_retarget.py:139-185).  Inputs and outputs are HOST
