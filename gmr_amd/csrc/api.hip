@@ -1698,6 +1698,7 @@ static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, 
   size_t n_offs = 0, n_keys = 0;
   int64_t tiles = 0, finish = 0, lds = 0;
   bool any = false, any_finish = false;
+  std::vector<int> empty_min;  // members without frames that want min_z
   for (int i = 0; i < n; ++i) {
     const gmr_motion_input &in = inputs[i];
     const gmr_model *m = models[i];
@@ -1706,7 +1707,10 @@ static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, 
     e = gmr::MotionEntry{};
     e.tile_base = tiles; e.finish_base = finish;
     if (in.n_frames < 0) { err = who + "negative n_frames"; return GMR_EINVAL; }
-    if (in.n_frames == 0) continue;  // no work for this member
+    if (in.n_frames == 0) {  // no work for this member; its clips (all empty) still report fk_min_height's +inf
+      if (in.min_z_out && in.n_seq > 0) empty_min.push_back(i);
+      continue;
+    }
     if (m->dm.root_planar) { err = who + "the motion schema needs a free-joint root; a planar base is not supported"; return GMR_EUNSUPPORTED; }
     const int ndof = m->fk.ndof;
     if (!in.qpos || !in.seq_offsets || !in.root_pos_out || !in.root_rot_out || !in.local_body_pos_out || (!in.dof_pos_out && ndof > 0)) {
@@ -1738,6 +1742,13 @@ static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, 
     finish += (items + gmr::kMotionFinishThreads - 1) / gmr::kMotionFinishThreads;
     any = true;
     any_finish = any_finish || items > 0;
+  }
+  if (!empty_min.empty()) {
+    if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
+    for (int i : empty_min)
+      if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(inputs[i].min_z_out), 0x7f800000, (size_t)inputs[i].n_seq, st) != hipSuccess) {
+        err = "hipMemsetD32Async failed"; return GMR_EDEVICE;
+      }
   }
   if (!any) return GMR_OK;
   if (tiles > 0x7fffffff || finish > 0x7fffffff || n_keys > 0x7fffffff) { err = "too many frames for one launch"; return GMR_EINVAL; }

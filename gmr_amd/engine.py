@@ -512,7 +512,7 @@ class Engine:
         ``[N, nq]`` float64 (free-joint layout, concatenated clips) -> device tensors (root_pos f64 [N, 3], root_rot f64 [N, 4]
         xyzw, dof_pos f64 [N, nq-7], local_body_pos f32 [N, nbody, 3]), bit for bit what the two FK launches and the torch ops
         give.  ``out``: caller-owned result tensors in that order; ``min_z``: a float32 [n_seq] tensor that also receives the
-        per-clip minimum body height (``fk_min_height``).  Asynchronous on the current stream."""
+        per-clip minimum body height (``fk_min_height``; +inf for a clip without frames, also when N = 0).  Asynchronous on the current stream."""
         mi, res, keep = _motion_input(self, qpos, seq_offsets, height_adjust, root_origin_offset, ground_offset, out, min_z)
         self._check(self._lib.gmr_motion_epilogue(self._h, C.byref(mi), self._stream()), "gmr_motion_epilogue")
         return res

@@ -8,6 +8,7 @@ vectors; IK side "parity unpinned" (mink/mujoco/daqp absent) -- see the C header
 from __future__ import annotations
 
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -38,8 +39,17 @@ WORK_ITEM_DTYPE = np.dtype(
 def build(force: bool = False) -> str:
     src = os.path.join(HERE, "gmr_oracle.c")
     hdr = os.path.join(os.path.dirname(HERE), "include", "gmr_blob.h")
-    if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["make", "-C", HERE, "-s"])
+
+    def stale():
+        return not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(src), os.path.getmtime(hdr))
+    if force or stale():
+        # processes that start together (the spawned ranks of a test) take turns: the first rebuilds, the others find the
+        # library fresh; the Makefile renames the finished file into place, so a concurrent load never sees half of it
+        os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
+        with open(os.path.join(os.path.dirname(LIB_PATH), ".build.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            if force or stale():
+                subprocess.check_call(["make", "-C", HERE, "-s"])
     return LIB_PATH
 
 

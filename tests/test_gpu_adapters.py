@@ -163,20 +163,26 @@ def test_bvh_fk_split_arrays_entry_equals_rows_entry():
     assert bad is not None
 
 
-def _smplx_restatement(go, fp, jt, parents, T_out, resample):
-    """smpl.py:75-107,127-196 in numpy (scipy for the rotation-vector conversions, as the reference)."""
+def _smplx_restatement(go, fp, jt, parents, T_out, resample, ks=None):
+    """smpl.py:75-107,127-196 in numpy (scipy for the rotation-vector conversions, as the reference).  ``ks``: only these output
+    frames (row n of the result is frame ks[n]); the input rows are read one frame at a time, so a long clip costs what the samples do."""
     from scipy.spatial.transform import Rotation as R
     T, J = fp.shape[:2]
-    rv = fp.copy()
-    rv[:, 0] = go
-    pos = np.zeros((T_out, J, 3))
-    quat = np.zeros((T_out, J, 4))
+    ks = range(T_out) if ks is None else ks
+    pos = np.zeros((len(ks), J, 3))
+    quat = np.zeros((len(ks), J, 4))
     tt = np.linspace(0, T - 1, T_out) if resample else np.arange(T, dtype=np.float64)
-    for k, t in enumerate(tt):
+
+    def rv(i):  # the frame's rotation vectors, global_orient first
+        r = fp[i].copy()
+        r[0] = go[i]
+        return r
+    for n, k in enumerate(ks):
+        t = tt[k]
         i1 = int(np.floor(t)); i2 = min(i1 + 1, T - 1); a = t - i1
-        q1 = R.from_rotvec(rv[i1]).as_quat()
+        q1 = R.from_rotvec(rv(i1)).as_quat()
         if resample:
-            q2 = R.from_rotvec(rv[i2]).as_quat()
+            q2 = R.from_rotvec(rv(i2)).as_quat()
             dot = np.sum(q1 * q2, axis=1)
             q2 = np.where(dot[:, None] < 0, -q2, q2)
             dot = np.abs(dot)
@@ -187,12 +193,12 @@ def _smplx_restatement(go, fp, jt, parents, T_out, resample):
             q = s0[:, None] * q1 + s1[:, None] * q2
             lq = R.from_rotvec(R.from_quat(q).as_rotvec())
         else:
-            lq = R.from_rotvec(rv[i1])
+            lq = R.from_rotvec(rv(i1))
         rots = []
         for i in range(J):
             rots.append(lq[i] if i == 0 else rots[parents[i]] * lq[i])
-            quat[k, i] = rots[i].as_quat(scalar_first=True)
-        pos[k] = jt[i1, :J] + a * (jt[i2, :J] - jt[i1, :J])
+            quat[n, i] = rots[i].as_quat(scalar_first=True)
+        pos[n] = jt[i1, :J] + a * (jt[i2, :J] - jt[i1, :J])
     return pos, quat
 
 
