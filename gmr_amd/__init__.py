@@ -21,6 +21,9 @@ def __getattr__(name):
     if name == "MultiRobotRetargeting":
         from .multi_robot import MultiRobotRetargeting
         return MultiRobotRetargeting
+    if name == "SmplxBodyModel":
+        from .smplx_body import SmplxBodyModel
+        return SmplxBodyModel
     if name == "load_robot_motion":
         from .dataset import load_robot_motion
         return load_robot_motion

@@ -111,3 +111,33 @@ def read_ahead(groups: List[List[str]], read: Callable, finish: Callable):
             if k + 1 < len(groups):
                 nxt = bg.submit(read, groups[k + 1], (k + 1) & 1)
             yield finish(got)
+
+
+def read_planned(files: List[str], alloc: Callable[[int], torch.Tensor], align: int, plan_one: Callable, fill_one: Callable, threads: int,
+                 skip_errors: bool) -> Staged:
+    """``read_files`` for loaders that want PARTS of their files: ``plan_one(path) -> (parsed, nbytes)`` looks at a file's directory and
+    says how many bytes of the buffer it needs, then ``fill_one(path, parsed, view)`` reads just those parts into its ``nbytes``-long,
+    ``align``-ed region (both on ``threads`` host threads).  ``sizes`` of the result are the regions' lengths; a file that fails in
+    either step is left out with ``skip_errors`` exactly as ``read_files`` leaves it out."""
+    def guarded(fn):
+        def run(*a):
+            try:
+                return fn(*a)
+            except SKIPPABLE as ex:
+                if not skip_errors:
+                    raise
+                return ex
+        return run
+    with ThreadPoolExecutor(max_workers=max(1, min(threads, len(files)))) as ex:
+        plans = list(ex.map(guarded(plan_one), files))
+        ok = [k for k, p in enumerate(plans) if not isinstance(p, Exception)]
+        sizes = np.array([plans[k][1] for k in ok], dtype=np.int64)
+        starts = np.concatenate([[0], np.cumsum((sizes + align - 1) // align * align)]).astype(np.int64)
+        buf = alloc(int(starts[-1]) + align)
+        host = buf.numpy()
+        filled = list(ex.map(guarded(lambda i: fill_one(files[ok[i]], plans[ok[i]][0], host[int(starts[i]):int(starts[i]) + int(sizes[i])])), range(len(ok))))
+    bad = {ok[i]: f for i, f in enumerate(filled) if isinstance(f, Exception)}
+    bad.update({k: p for k, p in enumerate(plans) if isinstance(p, Exception)})
+    keep = [i for i in range(len(ok)) if ok[i] not in bad]
+    skipped = [(files[k], str(bad[k])) for k in sorted(bad)]
+    return Staged([files[ok[i]] for i in keep], buf, starts[:-1][keep], sizes[keep], [plans[ok[i]][0] for i in keep], int(starts[-1]), skipped)

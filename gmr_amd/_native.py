@@ -25,7 +25,7 @@ assert WORK_ITEM_DTYPE.itemsize == 40
 INIT_QPOS0, INIT_ROOT_TARGET = -1, -2
 
 EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last_error", "gmr_model_info_get",
-           "gmr_ik_solve", "gmr_fk", "gmr_fk_shape", "gmr_dof_to_rot", "gmr_rot_to_dof", "gmr_local_rot_to_global", "gmr_fk_min_height", "gmr_bvh_fk", "gmr_bvh_parse_header", "gmr_bvh_parse_motion", "gmr_evaluate", "gmr_smplx_keypoints", "gmr_smplx_keypoints_cols", "gmr_smplx_keypoints_in", "gmr_bvh_fk_rows", "gmr_bvh_parse_motion_device",
+           "gmr_ik_solve", "gmr_fk", "gmr_fk_shape", "gmr_dof_to_rot", "gmr_rot_to_dof", "gmr_local_rot_to_global", "gmr_fk_min_height", "gmr_bvh_fk", "gmr_bvh_parse_header", "gmr_bvh_parse_motion", "gmr_evaluate", "gmr_smplx_keypoints", "gmr_smplx_keypoints_cols", "gmr_smplx_keypoints_in", "gmr_smplx_body", "gmr_bvh_fk_rows", "gmr_bvh_parse_motion_device",
            "gmr_session_create", "gmr_session_destroy", "gmr_session_reset", "gmr_session_step", "gmr_session_state", "gmr_session_set_persistent", "gmr_ik_plan_order", "gmr_ik_solve_ordered",
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue"]
@@ -72,6 +72,16 @@ class MotionInput(C.Structure):
         ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("n_seq", C.c_int32), ("flags", C.c_int32),
         ("ground_offset", C.c_double), ("root_pos_out", C.c_void_p), ("root_rot_out", C.c_void_p), ("dof_pos_out", C.c_void_p),
         ("local_body_pos_out", C.c_void_p), ("min_z_out", C.c_void_p),
+    ]
+
+
+class SmplxBodyClip(C.Structure):
+    """``gmr_smplx_body_clip`` (include/gmr_amd.h): one clip's arguments of the body-model launch."""
+
+    _fields_ = [
+        ("root_orient", C.c_void_p), ("pose_body", C.c_void_p), ("trans", C.c_void_p), ("j_template", C.c_void_p), ("j_dirs", C.c_void_p),
+        ("hand_mean", C.c_void_p), ("betas", C.c_void_p), ("n_frames", C.c_int64), ("in_dtype", C.c_int32 * 3), ("n_betas", C.c_int32),
+        ("dirs_stride", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
@@ -155,6 +165,8 @@ def load():
     L.gmr_smplx_keypoints_cols.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int, vp, vp, vp]
     L.gmr_smplx_keypoints_in.restype = C.c_int
     L.gmr_smplx_keypoints_in.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.gmr_smplx_body.restype = C.c_int
+    L.gmr_smplx_body.argtypes = [vp, C.c_int, C.POINTER(SmplxBodyClip), C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
     L.gmr_bvh_fk_rows.restype = C.c_int
     L.gmr_bvh_fk_rows.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int64, C.c_int64, C.c_double, vp, C.c_int, vp, vp, vp]
     L.gmr_bvh_parse_motion_device.restype = C.c_int

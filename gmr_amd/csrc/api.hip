@@ -22,6 +22,7 @@
 #include "ik_kernel.hip.h"
 #include "bvh_kernel.hip.h"
 #include "smplx_kernel.hip.h"
+#include "smplx_body_kernel.hip.h"
 #include "bvh_parse_kernel.hip.h"
 #include "kin_ops_kernel.hip.h"
 #include "motion_kernel.hip.h"
@@ -1808,23 +1809,9 @@ static int adapter_chunk(int64_t n_frames, int groups) {
   return (int)c;
 }
 
-int gmr_smplx_keypoints_cols(const int32_t *parents, int n_joints, int joints_stride, const double *global_orient, const double *full_pose,
-                             const double *joints, int64_t n_frames, int64_t n_frames_out, int resample, const int32_t *out_cols, int n_out,
-                             double *pos_out, double *quat_out, void *stream) {
-  return gmr_smplx_keypoints_in(parents, n_joints, joints_stride, global_orient, full_pose, joints, GMR_DTYPE_F64, n_frames, n_frames_out, resample,
-                                out_cols, n_out, pos_out, quat_out, stream);
-}
-
-int gmr_smplx_keypoints_in(const int32_t *parents, int n_joints, int joints_stride, const void *global_orient, const void *full_pose,
-                           const void *joints, int in_dtype, int64_t n_frames, int64_t n_frames_out, int resample, const int32_t *out_cols, int n_out,
-                           double *pos_out, double *quat_out, void *stream) {
-  if (!parents || !global_orient || !full_pose || !joints || !pos_out || !quat_out || n_frames < 0 || n_frames_out < 0) return GMR_EINVAL;
-  if (in_dtype != GMR_DTYPE_F32 && in_dtype != GMR_DTYPE_F64) return GMR_EINVAL;
-  if (n_joints < 1 || n_joints > gmr::kSmplMaxJoints || joints_stride < n_joints) return GMR_EUNSUPPORTED;
-  if (!resample && n_frames_out != n_frames) return GMR_EINVAL;
-  if (n_frames_out > 0 && n_frames == 0) return GMR_EINVAL;
-  gmr::SmplSkeleton sk{};
-  sk.joints_stride = joints_stride; sk.pose_stride = n_joints; sk.resample = resample ? 1 : 0;
+/* The skeleton the SMPL-X kernels work on: the joints emitted (out_cols, NULL = all) and their ancestors, renumbered in order
+ * (a parent precedes its children, the root stays first).  Fills n_joints, n_out, parent, out_col, src. */
+static int smpl_live_skeleton(const int32_t *parents, int n_joints, const int32_t *out_cols, int n_out, gmr::SmplSkeleton &sk) {
   if (parents[0] != -1) return GMR_EINVAL;
   for (int j = 1; j < n_joints; ++j)
     if (parents[j] < 0 || parents[j] >= j) return GMR_EINVAL;
@@ -1844,7 +1831,6 @@ int gmr_smplx_keypoints_in(const int32_t *parents, int n_joints, int joints_stri
     for (int j = 0; j < n_joints; ++j) { col_of[j] = (short)j; live[j] = 1; }
     sk.n_out = n_joints;
   }
-  /* the kernel's skeleton: the live joints only, renumbered in order (a parent precedes its children, the root stays first) */
   short cidx[gmr::kSmplMaxJoints];
   int nl = 0;
   for (int j = 0; j < n_joints; ++j) {
@@ -1857,6 +1843,28 @@ int gmr_smplx_keypoints_in(const int32_t *parents, int n_joints, int joints_stri
     ++nl;
   }
   sk.n_joints = nl;
+  return GMR_OK;
+}
+
+int gmr_smplx_keypoints_cols(const int32_t *parents, int n_joints, int joints_stride, const double *global_orient, const double *full_pose,
+                             const double *joints, int64_t n_frames, int64_t n_frames_out, int resample, const int32_t *out_cols, int n_out,
+                             double *pos_out, double *quat_out, void *stream) {
+  return gmr_smplx_keypoints_in(parents, n_joints, joints_stride, global_orient, full_pose, joints, GMR_DTYPE_F64, n_frames, n_frames_out, resample,
+                                out_cols, n_out, pos_out, quat_out, stream);
+}
+
+int gmr_smplx_keypoints_in(const int32_t *parents, int n_joints, int joints_stride, const void *global_orient, const void *full_pose,
+                           const void *joints, int in_dtype, int64_t n_frames, int64_t n_frames_out, int resample, const int32_t *out_cols, int n_out,
+                           double *pos_out, double *quat_out, void *stream) {
+  if (!parents || !global_orient || !full_pose || !joints || !pos_out || !quat_out || n_frames < 0 || n_frames_out < 0) return GMR_EINVAL;
+  if (in_dtype != GMR_DTYPE_F32 && in_dtype != GMR_DTYPE_F64) return GMR_EINVAL;
+  if (n_joints < 1 || n_joints > gmr::kSmplMaxJoints || joints_stride < n_joints) return GMR_EUNSUPPORTED;
+  if (!resample && n_frames_out != n_frames) return GMR_EINVAL;
+  if (n_frames_out > 0 && n_frames == 0) return GMR_EINVAL;
+  gmr::SmplSkeleton sk{};
+  sk.joints_stride = joints_stride; sk.pose_stride = n_joints; sk.resample = resample ? 1 : 0;
+  if (const int rc = smpl_live_skeleton(parents, n_joints, out_cols, n_out, sk)) return rc;
+  const int nl = sk.n_joints;
   if (n_frames_out == 0) return GMR_OK;
   const int chunk = adapter_chunk(n_frames_out, gmr::chain_geom(nl).groups);
   const int64_t nblk = (n_frames_out + chunk - 1) / chunk;
@@ -1877,6 +1885,76 @@ int gmr_smplx_keypoints(const int32_t *parents, int n_joints, int joints_stride,
                         void *stream) {
   return gmr_smplx_keypoints_cols(parents, n_joints, joints_stride, global_orient, full_pose, joints, n_frames, n_frames_out, resample,
                                   nullptr, 0, pos_out, quat_out, stream);
+}
+
+int gmr_smplx_body(const int32_t *parents, int n_joints, const gmr_smplx_body_clip *clips, int n_clips, const int32_t *out_cols, int n_out,
+                   double *global_orient, double *full_pose, double *joints, double *rest_out, void *stream) {
+  if (!parents || n_clips < 0 || (n_clips > 0 && !clips)) return GMR_EINVAL;
+  if (n_joints != gmr::kBodyJoints) return GMR_EUNSUPPORTED;
+  gmr::SmplSkeleton sk{};
+  sk.joints_stride = n_joints; sk.pose_stride = n_joints;
+  if (const int rc = smpl_live_skeleton(parents, n_joints, out_cols, n_out, sk)) return rc;
+  if (n_clips == 0) return GMR_OK;
+  const int groups = gmr::chain_geom(sk.n_joints).groups;
+  int64_t total = 0;
+  size_t n_betas = 0;
+  for (int c = 0; c < n_clips; ++c) {
+    const gmr_smplx_body_clip &in = clips[c];
+    if (in.n_frames < 0 || in.n_betas < 0 || in.dirs_stride < in.n_betas || !in.j_template || !in.hand_mean) return GMR_EINVAL;
+    if (in.n_betas > 0 && (!in.betas || !in.j_dirs)) return GMR_EINVAL;
+    if (in.n_frames > 0 && (!in.root_orient || !in.pose_body || !in.trans)) return GMR_EINVAL;
+    for (int k = 0; k < 3; ++k)
+      if (in.in_dtype[k] != GMR_DTYPE_F32 && in.in_dtype[k] != GMR_DTYPE_F64) return GMR_EINVAL;
+    total += in.n_frames;
+    n_betas += (size_t)in.n_betas;
+  }
+  if (total > 0 && (!global_orient || !full_pose || !joints)) return GMR_EINVAL;
+  /* the device the outputs live on (the rest skeletons' when there is not a single frame) */
+  const void *where = total > 0 ? static_cast<const void *>(full_pose) : static_cast<const void *>(rest_out);
+  if (!where) return GMR_OK;
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, where) != hipSuccess) { (void)hipGetLastError(); return GMR_EINVAL; }
+  if (hipSetDevice(attr.device) != hipSuccess) return GMR_EDEVICE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int chunk = adapter_chunk(total, groups);
+  const size_t clip_bytes = (sizeof(gmr::BodyClip) * (size_t)n_clips + 15) & ~size_t(15);
+  const size_t rest_at = clip_bytes + sizeof(double) * n_betas;
+  const size_t rest_doubles = (size_t)gmr::kBodyJoints * 3;
+  const size_t bytes = rest_at + (rest_out ? 0 : sizeof(double) * rest_doubles * (size_t)n_clips);
+  CallScratch sc;
+  sc.st = st;
+  hipMemPool_t pool = scratch_pool(attr.device);
+  if ((pool ? hipMallocFromPoolAsync(&sc.p, bytes, pool, st) : hipMallocAsync(&sc.p, bytes, st)) != hipSuccess) { (void)hipGetLastError(); return GMR_EDEVICE; }
+  uint8_t *ws = static_cast<uint8_t *>(sc.p);
+  std::vector<uint8_t> host(rest_at, 0);
+  gmr::BodyClip *hc = reinterpret_cast<gmr::BodyClip *>(host.data());
+  double *hb = reinterpret_cast<double *>(host.data() + clip_bytes);
+  double *rest = rest_out ? rest_out : reinterpret_cast<double *>(ws + rest_at);
+  int64_t row = 0, blk = 0;
+  size_t b_at = 0;
+  for (int c = 0; c < n_clips; ++c) {
+    const gmr_smplx_body_clip &in = clips[c];
+    gmr::BodyClip &e = hc[c];
+    e.root_orient = in.root_orient; e.pose_body = in.pose_body; e.trans = in.trans;
+    e.j_template = in.j_template; e.j_dirs = in.j_dirs; e.hand_mean = in.hand_mean;
+    e.betas = reinterpret_cast<const double *>(ws + clip_bytes) + b_at;
+    if (in.n_betas > 0) memcpy(hb + b_at, in.betas, sizeof(double) * (size_t)in.n_betas);
+    b_at += (size_t)in.n_betas;
+    e.rest = rest + rest_doubles * (size_t)c;
+    e.row0 = row; e.n_frames = in.n_frames; e.blk0 = blk;
+    for (int k = 0; k < 3; ++k) e.dt[k] = in.in_dtype[k] == GMR_DTYPE_F64 ? 1 : 0;
+    e.n_betas = in.n_betas; e.dirs_stride = in.dirs_stride;
+    row += in.n_frames;
+    blk += (in.n_frames + chunk - 1) / chunk;
+  }
+  if (blk > 0x7fffffff) return GMR_EINVAL;
+  if (hipMemcpyAsync(ws, host.data(), rest_at, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); return GMR_EDEVICE; }
+  const auto *d_clips = reinterpret_cast<const gmr::BodyClip *>(ws);
+  const int n_rest = n_clips * (int)rest_doubles;
+  hipLaunchKernelGGL(gmr::smplx_rest_kernel, dim3((unsigned)((n_rest + 255) / 256)), dim3(256), 0, st, d_clips, n_clips);
+  if (blk > 0)
+    hipLaunchKernelGGL(gmr::smplx_body_kernel, dim3((unsigned)blk), dim3(64), 0, st, sk, d_clips, n_clips, chunk, global_orient, full_pose, joints);
+  return hipGetLastError() == hipSuccess ? GMR_OK : GMR_EDEVICE;
 }
 
 int gmr_bvh_parse_header(const char *text, size_t len, int max_joints, char *names_out, size_t names_cap, int32_t *parents_out,

@@ -24,6 +24,9 @@ def main(argv=None) -> int:
     ap.add_argument("--num_cpus", default=4, type=int, help="host threads reading files / writing pickles (the reference's worker processes)")
     ap.add_argument("--hard_motions", nargs="*", default=None, help="lists of motions to leave out (default: $GMR_ROOT/assets/hard_motions/0.txt, 1.txt when present)")
     ap.add_argument("--batch_files", default=1024, type=int)
+    ap.add_argument("--smplx_model_folder", default=None, type=str,
+                    help="folder holding smplx/SMPLX_<GENDER>.npz|pkl: --src_folder then holds AMASS .npz files and the body model's joints are evaluated here")
+    ap.add_argument("--num_betas", default=None, type=int, help="with --smplx_model_folder: shape coefficients used per clip (default: all the file and the model share)")
     add_common_flags(ap)
     args = ap.parse_args(argv)
     resolve_robots(ap, args)
@@ -44,7 +47,10 @@ def main(argv=None) -> int:
     print(f"Total number of files to process: {len(keep)}")
 
     def batches(files, columns):
-        from ..smplx_adapter import iter_joint_batches
+        from ..smplx_adapter import iter_amass_batches, iter_joint_batches
+        if args.smplx_model_folder is not None:
+            return iter_amass_batches(files, args.smplx_model_folder, batch_files=args.batch_files, device=args.device, threads=max(1, args.num_cpus),
+                                      columns=columns, skip_errors=True, num_betas=args.num_betas)
         return iter_joint_batches(files, batch_files=args.batch_files, device=args.device, threads=max(1, args.num_cpus), columns=columns, skip_errors=True)
     return convert(args, keep, "smplx", batches, lambda batch: dict(fps=batch.fps), args.num_cpus, "Done. Saved to ")  # :97-141
 

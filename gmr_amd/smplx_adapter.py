@@ -14,14 +14,16 @@ from __future__ import annotations
 
 import ast
 import ctypes as C
+import os
 import struct
+import zlib
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _native
-from ._filebatch import ClipBatch, Staged, pinned, read_ahead, read_files
+from ._filebatch import ClipBatch, Staged, pinned, read_ahead, read_files, read_planned
 
 # smplx.joint_names.JOINT_NAMES[:55] (body, jaw, eyes, hands) -- the names the smplx_to_*.json configs refer to
 SMPLX_JOINT_NAMES: List[str] = [
@@ -265,3 +267,264 @@ def iter_joint_batches(files, batch_files: int = 256, device: int = 0, tgt_fps: 
     groups = [files[i:i + batch_files] for i in range(0, len(files), max(1, batch_files))]
     yield from read_ahead(groups, lambda group, slot: _stage(group, dev, threads, len(parents), skip_errors, slot),
                           lambda st: _joint_batch(st, dev, tgt_fps, columns, parents, joint_names))
+
+
+# --------------------------------------------------------------------------------------------------------------------- AMASS files
+# The whole of scripts/smplx_to_robot_dataset.py:63-146 from the user's own folder: AMASS / OMOMO .npz files plus the SMPL-X model
+# files.  The body model's joints come from gmr_amd.smplx_body (one launch per batch), the rest is the joint-file path above.
+# Of a file only root_orient, pose_body, trans (69 numbers per frame) and the small betas / gender / mocap_frame_rate are read --
+# an AMASS archive also carries poses, pose_hand, dmpls, markers ... (several times as much), which stay on the disk.
+AMASS_ARRAYS = (("root_orient", 3), ("pose_body", 63), ("trans", 3))
+AMASS_SMALL = ("betas", "gender", "mocap_frame_rate")
+_MEMBER_ALIGN = 64
+
+
+def _npy_header(head: bytes, path: str, name: str):
+    """(dtype, shape, header length) of a .npy member from its first bytes."""
+    if head[:6] != b"\x93NUMPY" or len(head) < 12:
+        raise ValueError(f"{path}: member {name} is not a .npy array")
+    hlen, hoff = (struct.unpack_from("<H", head, 8)[0], 10) if head[6] == 1 else (struct.unpack_from("<I", head, 8)[0], 12)
+    if hoff + hlen > len(head):
+        raise ValueError(f"{path}: member {name} has a malformed .npy header")
+    try:
+        d = ast.literal_eval(head[hoff:hoff + hlen].decode("latin1"))
+        dt, shape, plain = np.dtype(d["descr"]), tuple(int(x) for x in d["shape"]), not d["fortran_order"]
+    except (SyntaxError, ValueError, TypeError, KeyError) as ex:
+        raise ValueError(f"{path}: member {name} has a malformed .npy header ({ex})") from None
+    if dt.hasobject or not (plain or len(shape) < 2):
+        raise ValueError(f"{path}: member {name} is not a plain C-ordered array")
+    return dt, shape, hoff + hlen
+
+
+def _pread(fh, n: int, at: int, path: str) -> bytes:
+    b = os.pread(fh.fileno(), n, at) if n > 0 else b""
+    if len(b) != n:
+        raise ValueError(f"{path}: truncated")
+    return b
+
+
+def _amass_plan(path: str):
+    """``plan_one`` of the AMASS loader: the archive's directory, the small members' values and where the three per-frame arrays lie --
+    ``(meta, bytes needed)``.  Only the members named above are looked at: an object array or a member of another kind elsewhere in the
+    archive does not matter.  Members may be stored (np.savez) or deflated (np.savez_compressed)."""
+    size = os.path.getsize(path)
+    with open(path, "rb", buffering=0) as fh:
+        try:
+            tail_at = max(0, size - 65557)
+            tail = _pread(fh, size - tail_at, tail_at, path)
+            k = tail.rfind(b"PK\x05\x06")
+            if k < 0 or k + 22 > len(tail):
+                raise ValueError(f"{path}: not a zip archive")
+            total, cd_size, cd_off = struct.unpack_from("<HII", tail, k + 10)
+            if cd_off == 0xFFFFFFFF or total == 0xFFFF:
+                raise ValueError(f"{path}: zip64 directory")
+            if cd_off + cd_size > size:
+                raise ValueError(f"{path}: truncated")
+            cd = _pread(fh, cd_size, cd_off, path)
+            want = {a for a, _ in AMASS_ARRAYS} | set(AMASS_SMALL)
+            mem, p = {}, 0
+            for _ in range(total):
+                sig, method, csize, usize, nlen, xlen, clen, lho = struct.unpack_from("<4s6xH8xIIHHH8xI", cd, p)
+                if sig != b"PK\x01\x02":
+                    raise ValueError(f"{path}: bad central directory")
+                name = cd[p + 46:p + 46 + nlen].decode("utf-8", "replace")
+                p += 46 + nlen + xlen + clen
+                key = name[:-4] if name.endswith(".npy") else name
+                if key not in want:
+                    continue
+                if method not in (0, 8):
+                    raise ValueError(f"{path}: member {name} uses compression method {method}")
+                if usize == 0xFFFFFFFF or csize == 0xFFFFFFFF or lho == 0xFFFFFFFF:
+                    raise ValueError(f"{path}: zip64 member")
+                sig2, nlen2, xlen2 = struct.unpack_from("<4s22xHH", _pread(fh, 30, lho, path), 0)
+                if sig2 != b"PK\x03\x04":
+                    raise ValueError(f"{path}: bad local header")
+                d0 = lho + 30 + nlen2 + xlen2
+                if d0 + csize > size:
+                    raise ValueError(f"{path}: truncated")
+                mem[key] = (method, d0, csize, usize)
+        except (struct.error, IndexError) as ex:
+            raise ValueError(f"{path}: malformed zip archive ({ex})") from None
+        for key in [a for a, _ in AMASS_ARRAYS] + list(AMASS_SMALL):
+            if key not in mem:
+                raise ValueError(f"{path}: no '{key}' array (an AMASS file holds {', '.join(a for a, _ in AMASS_ARRAYS)}, {', '.join(AMASS_SMALL)})")
+        small = {}
+        for key in AMASS_SMALL:
+            method, d0, csize, usize = mem[key]
+            raw = _pread(fh, csize, d0, path)
+            raw = _inflate(raw, usize, path, key) if method == 8 else raw
+            dt, shape, hl = _npy_header(raw[:4096], path, key)
+            cnt = int(np.prod(shape)) if shape else 1
+            if hl + cnt * dt.itemsize > len(raw):
+                raise ValueError(f"{path}: truncated")
+            small[key] = np.frombuffer(raw, dtype=dt, count=cnt, offset=hl).reshape(shape).copy()
+        arrays, need, T = {}, 0, None
+        for key, width in AMASS_ARRAYS:
+            method, d0, csize, usize = mem[key]
+            if method == 8:  # (the header sits inside the deflate stream: shape and dtype are checked when the member is inflated)
+                dt, shape, hl = None, None, None
+            else:
+                dt, shape, hl = _npy_header(_pread(fh, min(usize, 4096), d0, path), path, key)
+                _check_amass_array(path, key, width, dt, shape, hl, usize)
+                if T is not None and shape[0] != T:
+                    raise ValueError(f"{path}: {key} has {shape[0]} frames, root_orient {T}")
+                T = shape[0] if T is None else T
+            arrays[key] = dict(method=method, at=d0, csize=csize, usize=usize, dtype=dt, shape=shape, hl=hl, off=need)
+            room = usize if method == 8 else shape[0] * width * dt.itemsize  # (a deflated member's .npy header is at most that much too much)
+            need += (room + _MEMBER_ALIGN - 1) // _MEMBER_ALIGN * _MEMBER_ALIGN
+    g = small["gender"]
+    if g.size != 1 or g.dtype.kind not in "US":
+        raise ValueError(f"{path}: gender must be one string")
+    g = g.reshape(-1)[0]
+    gender = (g.decode("utf-8", "replace") if isinstance(g, bytes) else str(g)).strip().lower()
+    if small["mocap_frame_rate"].size < 1 or small["mocap_frame_rate"].dtype.kind not in "fiu":
+        raise ValueError(f"{path}: mocap_frame_rate must be a number")
+    fps = float(small["mocap_frame_rate"].reshape(-1)[0])
+    if not (fps > 0):
+        raise ValueError(f"{path}: mocap_frame_rate must be positive")
+    if small["betas"].dtype.kind != "f" or small["betas"].size < 1:
+        raise ValueError(f"{path}: betas must be floating point")
+    betas = small["betas"].astype(np.float64).reshape(-1)
+    return dict(T=T, fps=fps, gender=gender, betas=betas, height=human_height_from_betas(betas), arrays=arrays), need
+
+
+def _check_amass_array(path, key, width, dt, shape, hl, usize):
+    if dt not in (np.dtype("<f4"), np.dtype("<f8")):
+        raise ValueError(f"{path}: {key} must be float32 or float64")
+    if len(shape) != 2 or shape[1] != width:
+        raise ValueError(f"{path}: {key} has shape {shape}, expected [T, {width}]")
+    if hl + shape[0] * width * dt.itemsize > usize:
+        raise ValueError(f"{path}: truncated")
+
+
+def _inflate(raw: bytes, usize: int, path: str, key: str) -> bytes:
+    try:
+        out = zlib.decompressobj(-15).decompress(raw, usize + 1)
+    except zlib.error as ex:
+        raise ValueError(f"{path}: member {key} does not inflate ({ex})") from None
+    if len(out) != usize:
+        raise ValueError(f"{path}: member {key} inflates to {len(out)} bytes, the directory says {usize}")
+    return out
+
+
+def _amass_fill(path: str, meta: dict, view: np.ndarray) -> None:
+    """``fill_one``: the three arrays' numbers into the file's region of the pinned buffer, each on a 64-byte boundary.  A stored
+    member is read from the disk straight to its place (one copy); a deflated one is inflated on this thread and copied there."""
+    T = meta["T"]
+    with open(path, "rb", buffering=0) as fh:
+        for key, width in AMASS_ARRAYS:
+            a = meta["arrays"][key]
+            if a["method"] == 8:
+                raw = _inflate(_pread(fh, a["csize"], a["at"], path), a["usize"], path, key)
+                a["dtype"], a["shape"], a["hl"] = _npy_header(raw[:4096], path, key)
+                _check_amass_array(path, key, width, a["dtype"], a["shape"], a["hl"], a["usize"])
+                n = a["shape"][0] * width * a["dtype"].itemsize
+                view[a["off"]:a["off"] + n] = np.frombuffer(raw, dtype=np.uint8, count=n, offset=a["hl"])
+            else:
+                n = a["shape"][0] * width * a["dtype"].itemsize
+                dst, got = memoryview(view)[a["off"]:a["off"] + n], 0
+                while got < n:
+                    r = os.preadv(fh.fileno(), [dst[got:]], a["at"] + a["hl"] + got)
+                    if not r:
+                        raise ValueError(f"{path}: truncated")
+                    got += r
+            if T is not None and a["shape"][0] != T:
+                raise ValueError(f"{path}: {key} has {a['shape'][0]} frames, another array {T}")
+            T = a["shape"][0]
+    meta["T"] = T
+
+
+def read_amass_members(files, alloc, threads: int = 8, skip_errors: bool = False) -> Staged:
+    """The files' per-frame arrays in one byte buffer from ``alloc(nbytes)`` (each file's region on a 256-byte boundary), their
+    directories' findings in ``.parsed``: the host half of the AMASS loader, usable without a device."""
+    return read_planned([str(f) for f in files], alloc, 256, _amass_plan, _amass_fill, threads, skip_errors)
+
+
+def read_amass_file(path) -> dict:
+    """One AMASS file's ``root_orient``, ``pose_body``, ``trans`` (as stored), ``betas`` (float64), ``gender``, ``mocap_frame_rate``
+    through the loader's own parser (numpy arrays on the host)."""
+    st = read_amass_members([path], lambda n: torch.empty(n, dtype=torch.uint8), 1, False)
+    m, host = st.parsed[0], st.buf.numpy()
+    out = dict(betas=m["betas"], gender=m["gender"], mocap_frame_rate=m["fps"])
+    for key, width in AMASS_ARRAYS:
+        a = m["arrays"][key]
+        out[key] = np.frombuffer(host, dtype=a["dtype"], count=m["T"] * width, offset=int(st.starts[0]) + a["off"]).reshape(m["T"], width).copy()
+    return out
+
+
+def _amass_stage(files, dev: torch.device, threads: int, skip_errors: bool, slot: int) -> Staged:
+    with torch.cuda.device(dev):
+        return read_amass_members(files, pinned("amass", slot), threads, skip_errors)
+
+
+def _amass_batch(st: Staged, dev, models, tgt_fps, columns, num_betas, skip_errors) -> SmplxBatch:
+    """Staged AMASS members -> body model (all clips, one launch) -> the adapter, clip by clip as ``_joint_batch`` runs it."""
+    from . import smplx_body
+    # clips whose gender has no model (or whose betas do not fit num_betas) leave the batch here: skippable like a parse error
+    good, clip_models, clip_betas, skipped = [], [], [], list(st.skipped)
+    for k, m in enumerate(st.parsed):
+        try:
+            model = models.get(m["gender"])
+            clip_betas.append(model.clip_betas(m["betas"], num_betas))
+            clip_models.append(model)
+            good.append(k)
+        except ValueError as ex:
+            if not skip_errors:
+                raise ValueError(f"{st.files[k]}: {ex}") from None
+            skipped.append((st.files[k], str(ex)))
+    if not good:
+        return SmplxBatch.empty(dev, skipped)
+    names = list(SMPLX_JOINT_NAMES) if columns is None else [str(c) for c in columns]
+    metas = [st.parsed[k] for k in good]
+    t_out = [m["T"] // int(m["fps"] / tgt_fps) if tgt_fps < m["fps"] else m["T"] for m in metas]  # smpl.py:119,127
+    offs = np.concatenate([[0], np.cumsum(t_out)]).astype(np.int64)
+    B = len(names)
+    with torch.cuda.device(dev):
+        pos = torch.empty((int(offs[-1]), B, 3), dtype=torch.float64, device=dev)
+        quat = torch.empty((int(offs[-1]), B, 4), dtype=torch.float64, device=dev)
+        raw = st.buf[: st.total].to(dev, non_blocking=True)  # ONE copy of the members as they lie in the files
+        clips = []
+        for i, k in enumerate(good):
+            m, base = metas[i], int(st.starts[k])
+            c = dict(model=clip_models[i], betas=clip_betas[i])
+            for key, width in AMASS_ARRAYS:
+                a = m["arrays"][key]
+                n = m["T"] * width * a["dtype"].itemsize
+                c[key] = raw[base + a["off"]:base + a["off"] + n].view(torch.float32 if a["dtype"].itemsize == 4 else torch.float64).reshape(m["T"], width)
+            clips.append(c)
+        go, fp, jt, src = smplx_body.evaluate_clips(clips, device=dev.index or 0, columns=columns)
+        out_fps = []
+        for i, m in enumerate(metas):
+            a, e = int(src[i]), int(src[i + 1])
+            _, _, _, afps = get_smplx_data_offline_fast(go[a:e], fp[a:e], jt[a:e], SMPLX_PARENTS, src_fps=m["fps"], tgt_fps=tgt_fps, device=dev.index or 0,
+                                                        columns=columns, out=(pos[offs[i]:offs[i + 1]], quat[offs[i]:offs[i + 1]]))
+            out_fps.append(afps)
+        torch.cuda.current_stream(dev).synchronize()  # the pinned buffer is reused by the batch after next
+    return SmplxBatch(pos, quat, names, offs, [m["height"] for m in metas], out_fps, [st.files[k] for k in good], skipped)
+
+
+def _model_set(body_models):
+    from .smplx_body import BodyModelSet
+    return body_models if isinstance(body_models, BodyModelSet) else BodyModelSet(body_models)
+
+
+def load_amass_files(files, body_models, device: int = 0, tgt_fps: float = 30.0, columns: Optional[Sequence[str]] = None, threads: int = 8,
+                     skip_errors: bool = False, num_betas: Optional[int] = None) -> SmplxBatch:
+    """AMASS ``.npz`` files -> one ``SmplxBatch`` on the GPU, the body model included.  ``body_models``: the folder holding
+    ``smplx/SMPLX_<GENDER>.npz|pkl`` (a gender's model is loaded when first needed) or a ``{gender: SmplxBodyModel}`` dict.
+    ``num_betas``: shape coefficients used per clip (``None``: as many as the file and the model share)."""
+    dev = torch.device("cuda", device)
+    return _amass_batch(_amass_stage([str(f) for f in files], dev, threads, skip_errors, 0), dev, _model_set(body_models), tgt_fps, columns,
+                        num_betas, skip_errors)
+
+
+def iter_amass_batches(files, body_models, batch_files: int = 256, device: int = 0, tgt_fps: float = 30.0, columns: Optional[Sequence[str]] = None,
+                       threads: int = 8, skip_errors: bool = False, num_betas: Optional[int] = None):
+    """``load_amass_files`` over a folder in batches of ``batch_files`` files, read ahead like ``iter_joint_batches``.  A batch without a
+    good file is yielded empty with its ``skipped`` list."""
+    files = [str(f) for f in files]
+    dev = torch.device("cuda", device)
+    models = _model_set(body_models)
+    groups = [files[i:i + batch_files] for i in range(0, len(files), max(1, batch_files))]
+    yield from read_ahead(groups, lambda group, slot: _amass_stage(group, dev, threads, skip_errors, slot),
+                          lambda st: _amass_batch(st, dev, models, tgt_fps, columns, num_betas, skip_errors))

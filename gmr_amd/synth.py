@@ -13,7 +13,8 @@ the engine and nothing in the solver calls it.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+import os
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -508,3 +509,92 @@ def write_smplx_joint_files(folder: str, pos, quat, names: List[str], seq_offset
         save_joint_file(f, jt[a:b].astype(dtype), go[a:b].astype(dtype), fp[a:b].astype(dtype), fps, betas)
         files.append(f)
     return files
+
+
+def write_smplx_model(path: str, seed: int, n_verts: int = 400, n_shape: int = 16, fmt: Optional[str] = None, sparse_like: bool = False) -> dict:
+    """A random stand-in for an SMPL-X model file (the only "model" tests use; nothing licensed): random ``v_template [V,3]`` and
+    ``shapedirs [V,3,n_shape]``, a row-normalised non-negative ``J_regressor [55,V]``, the real kinematic tree, random hand means, and
+    members of the kind a real file also carries and the loader must not look at.  ``.npz`` or ``.pkl`` by extension (or ``fmt``).
+    Returns the arrays written."""
+    import pickle
+    from .smplx_adapter import SMPLX_PARENTS
+    rng = np.random.default_rng(seed)
+    J = len(SMPLX_PARENTS)
+    reg = rng.random((J, n_verts)) * (rng.random((J, n_verts)) < 0.1)
+    reg[np.arange(J), rng.integers(0, n_verts, J)] += 0.5
+    reg /= reg.sum(axis=1, keepdims=True)
+    kin = np.stack([np.asarray(SMPLX_PARENTS, dtype=np.int64), np.arange(J)]).astype(np.uint32)  # (the files hold 2^32 - 1 for the root)
+    data = dict(v_template=rng.normal(0.0, 0.5, (n_verts, 3)), shapedirs=rng.normal(0.0, 0.03, (n_verts, 3, n_shape)), J_regressor=reg,
+                kintree_table=kin, hands_meanl=rng.normal(0.0, 0.3, 45), hands_meanr=rng.normal(0.0, 0.3, 45),
+                posedirs=rng.normal(0.0, 1e-3, (n_verts * 3, 8)), f=rng.integers(0, n_verts, (16, 3)))
+    if (fmt or os.path.splitext(path)[1].lstrip(".")) == "pkl":
+        out = dict(data)
+        if sparse_like:
+            out["J_regressor"] = _SparseLike(reg)
+        with open(path, "wb") as fh:
+            pickle.dump(out, fh, protocol=2)
+    else:
+        np.savez(path, **data)
+    return data
+
+
+class _SparseLike:
+    """A ``J_regressor`` that is not an ndarray but has ``.toarray()`` (what scipy.sparse gives the .pkl model files)."""
+
+    def __init__(self, a):
+        self.a = np.asarray(a)
+
+    def toarray(self):
+        return self.a
+
+
+def write_smplx_model_folder(folder: str, seed: int = 0, genders: Sequence[str] = ("neutral", "male", "female"), n_verts: int = 400) -> str:
+    """``<folder>/smplx/SMPLX_<GENDER>.npz`` for each gender (the layout ``SmplxBodyModel.from_folder`` reads); returns ``folder``."""
+    os.makedirs(os.path.join(folder, "smplx"), exist_ok=True)
+    for k, g in enumerate(genders):
+        write_smplx_model(os.path.join(folder, "smplx", f"SMPLX_{g.upper()}.npz"), seed + k, n_verts=n_verts)
+    return folder
+
+
+def amass_arrays(T: int, seed: int, dtype=np.float64, big: bool = False) -> dict:
+    """Random AMASS-shaped parameters of one clip: smooth ``root_orient [T,3]``, ``pose_body [T,63]``, ``trans [T,3]``, 16 betas.
+    ``big``: some rotation vectors beyond pi and some exactly / nearly zero."""
+    rng = np.random.default_rng(seed)
+    t = np.linspace(0.0, 1.0, max(T, 1))[:T, None]
+    wave = lambda n, amp: amp * (rng.normal(size=(1, n)) + np.sin(2 * np.pi * (t * rng.uniform(0.5, 3.0, (1, n)) + rng.random((1, n)))))  # noqa: E731
+    root, pose, trans = wave(3, 0.8), wave(63, 0.4), wave(3, 1.0)
+    if big and T:
+        pose[:, 3:6] *= 6.0        # angles beyond pi (the range-reducing sincos)
+        root[:, :] *= 2.5
+        pose[:, 6:9] = 0.0         # exactly zero
+        pose[:, 9:12] *= 1e-5      # the series arm of the exponential map
+        pose[::2, 12:15] = 0.0
+    return dict(root_orient=root.astype(dtype), pose_body=pose.astype(dtype), trans=trans.astype(dtype), betas=rng.normal(0.0, 1.0, 16))
+
+
+def write_amass_file(path: str, arrays: dict, gender="neutral", fps=120.0, compressed: bool = False, extras: bool = True) -> None:
+    """One AMASS-shaped ``.npz`` (``np.savez`` or ``np.savez_compressed``): the members the loader reads plus, with ``extras``, the kind
+    it must ignore (``poses``, ``pose_hand``, an object-dtype member, ``surface_model_type``)."""
+    T = arrays["root_orient"].shape[0]
+    d = dict(arrays)
+    d.update(gender=np.asarray(gender), mocap_frame_rate=np.asarray(fps))
+    if extras:
+        d.update(poses=np.zeros((T, 165), dtype=arrays["pose_body"].dtype), pose_hand=np.zeros((T, 90), dtype=np.float32),
+                 surface_model_type=np.asarray("smplx"), labels=np.asarray([{"a": 1}, None], dtype=object))
+    (np.savez_compressed if compressed else np.savez)(path, **d)
+
+
+def write_amass_files(folder: str, lengths, seed: int = 0, fps=120.0, dtypes=(np.float64,), genders=("neutral",), compressed=(False,),
+                      prefix: str = "amass", big: bool = False):
+    """``len(lengths)`` AMASS-shaped files; ``fps`` (one value or one per file), ``dtypes``, ``genders``, ``compressed`` cycle over the files.
+    -> (files, per-file array dicts as written, with ``gender`` and ``mocap_frame_rate`` added)."""
+    os.makedirs(folder, exist_ok=True)
+    files, out = [], []
+    for k, T in enumerate(lengths):
+        a = amass_arrays(int(T), seed + k, dtypes[k % len(dtypes)], big=big)
+        f = os.path.join(folder, f"{prefix}_{k:05d}.npz")
+        g, r = genders[k % len(genders)], float(fps[k] if np.ndim(fps) else fps)
+        write_amass_file(f, a, gender=g, fps=r, compressed=compressed[k % len(compressed)])
+        files.append(f)
+        out.append(dict(a, gender=g, mocap_frame_rate=r))
+    return files, out

@@ -1,7 +1,8 @@
 """``general_motion_retargeting.utils.smpl`` (utils/smpl.py) on this engine, behind the SMPL-X body model.
 
 ``load_smplx_file`` evaluates the licensed body model through the ``smplx`` package exactly as the reference does (:12-42) -- it needs that package
-and the model files, neither of which this repository ships; ``get_smplx_data_offline_fast`` takes what it returns."""
+and the model files, neither of which this repository ships; ``load_smplx_file_native`` needs the model files only (the 55 joints are
+evaluated by ``gmr_amd.smplx_body``); ``get_smplx_data_offline_fast`` takes what either returns."""
 from __future__ import annotations
 
 import numpy as np
@@ -30,6 +31,26 @@ def load_smplx_file(smplx_file, smplx_body_model_path):
                               body_pose=torch.tensor(smplx_data["pose_body"]).float(), transl=torch.tensor(smplx_data["trans"]).float(),
                               left_hand_pose=z(45), right_hand_pose=z(45), jaw_pose=z(3), leye_pose=z(3), reye_pose=z(3), return_full_pose=True)
     return smplx_data, body_model, smplx_output, human_height_from_betas(smplx_data["betas"])
+
+
+def load_smplx_file_native(smplx_file, smplx_body_model_path, num_betas=None):
+    """``load_smplx_file`` without the ``smplx`` package: the same 4-tuple, with the first 55 joints evaluated by this engine
+    (``gmr_amd.smplx_body``, float64 on the GPU) from the user's own model files under ``<smplx_body_model_path>/smplx``.
+    ``body_model`` is a ``SmplxBodyModel`` (``.parents``), the output object carries ``global_orient [T,3]``, ``full_pose [T,165]``,
+    ``joints [T,55,3]`` as float32 torch tensors (the dtype the package emits) -- what ``get_smplx_data_offline_fast`` below takes."""
+    import torch
+    from .. import smplx_body
+    from ..smplx_adapter import human_height_from_betas, read_amass_file
+    smplx_data = read_amass_file(smplx_file)
+    body_model = smplx_body.SmplxBodyModel.from_folder(smplx_body_model_path, smplx_data["gender"])
+    dev = torch.device("cuda", 0)
+    clip = dict(model=body_model, betas=body_model.clip_betas(smplx_data["betas"], num_betas))
+    for key in ("root_orient", "pose_body", "trans"):
+        clip[key] = torch.as_tensor(smplx_data[key]).to(dev)
+    go, fp, jt, _ = smplx_body.evaluate_clips([clip], device=0)
+    T = go.shape[0]
+    out = smplx_body.BodyOutput(go.float().cpu(), fp.reshape(T, -1).float().cpu(), jt.float().cpu())
+    return smplx_data, body_model, out, human_height_from_betas(smplx_data["betas"])
 
 
 def get_smplx_data_offline_fast(smplx_data, body_model, smplx_output, tgt_fps=30):

@@ -40,6 +40,8 @@
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
  *   gmr_smplx_keypoints, gmr_smplx_keypoints_cols, gmr_smplx_keypoints_in  the numeric part of get_smplx_data_offline_fast (general_motion_retargeting/utils/smpl.py:109-198)
  *                      after the SMPL-X body model: slerp/lerp to the target frame rate, orientation chaining
+ *   gmr_smplx_body     the SMPL-X body model's first 55 joints as load_smplx_file obtains them (general_motion_retargeting/utils/smpl.py:12-41):
+ *                      rest joints from betas, the rigid chain over root_orient / pose_body, + trans -- all clips of a batch at once
  *   gmr_bvh_parse_header the HIERARCHY section of read_bvh (general_motion_retargeting/utils/lafan_vendor/extract.py:60-139)
  *   gmr_bvh_parse_motion, gmr_bvh_parse_motion_device  the MOTION block of read_bvh (general_motion_retargeting/utils/lafan_vendor/extract.py:140-166): the
  *                      per-line regex + float() loop that dominates BVH loading in the reference
@@ -293,6 +295,33 @@ int gmr_smplx_keypoints_cols(const int32_t *parents, int n_joints, int joints_st
 int gmr_smplx_keypoints_in(const int32_t *parents, int n_joints, int joints_stride, const void *global_orient, const void *full_pose,
                            const void *joints, int in_dtype, int64_t n_frames, int64_t n_frames_out, int resample, const int32_t *out_cols,
                            int n_out, double *pos_out, double *quat_out, void *stream);
+
+/* The SMPL-X body model's joints from AMASS parameters, for every clip of a batch in one launch: what load_smplx_file
+ * (general_motion_retargeting/utils/smpl.py:12-41) takes from the `smplx` package for the first 55 joints, without the vertices.
+ * Per clip the rest joints J = j_template + j_dirs betas are formed on the device, then per frame
+ *   full_pose      row 0 root_orient, rows 1-21 pose_body, rows 22-24 zero, rows 25-54 hand_mean (the model's mean hand pose)
+ *   global_orient  root_orient
+ *   joints         R_0 = exp(root_orient), p_0 = J_0; R_i = R_parent exp(full_pose_i), p_i = p_parent + R_parent (J_i - J_parent); + trans
+ * with the exponential map and the products of gmr_smplx_keypoints_in, so the orientations that call derives from full_pose are
+ * the rotations these positions were built with.  Clip c's frames are rows sum(n_frames of the clips before it) ... of the outputs.
+ *   parents host [n_joints], n_joints = 55 (GMR_EUNSUPPORTED otherwise)
+ *   clips host [n_clips]; root_orient / pose_body / trans device [n_frames][3 / 63 / 3] of element type in_dtype[0 / 1 / 2];
+ *     j_template device [55][3], j_dirs device [55][3][dirs_stride], hand_mean device [90] (float64); betas HOST [n_betas <= dirs_stride]
+ *   out_cols / n_out as in gmr_smplx_keypoints_cols: only the named joints and their ancestors are evaluated AND WRITTEN (the rows
+ *     that call reads with the same selection); the other joints' entries of full_pose / joints are left as they are
+ *   global_orient device [N][3], full_pose device [N][55][3], joints device [N][55][3] (float64)
+ *   rest_out device [n_clips][55][3] or NULL: the clips' rest joints
+ * Asynchronous on `stream`; the device of the outputs is selected; scratch comes from the library's own pool.               */
+typedef struct gmr_smplx_body_clip {
+  const void *root_orient, *pose_body, *trans;
+  const double *j_template, *j_dirs, *hand_mean;
+  const double *betas;
+  int64_t n_frames;
+  int32_t in_dtype[3];
+  int32_t n_betas, dirs_stride, reserved;
+} gmr_smplx_body_clip;
+int gmr_smplx_body(const int32_t *parents, int n_joints, const gmr_smplx_body_clip *clips, int n_clips, const int32_t *out_cols, int n_out,
+                   double *global_orient, double *full_pose, double *joints, double *rest_out, void *stream);
 
 /* Host-side parse of a BVH file's HIERARCHY section and MOTION header (stateless, no device involved; grammar and the
  * reference semantics it keeps are documented in gmr_amd/csrc/bvh_text.h).  Replaces the hierarchy loop of read_bvh
