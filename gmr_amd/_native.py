@@ -119,9 +119,16 @@ def load():
     L.gmr_last_error.restype = C.c_char_p
     L.gmr_last_error.argtypes = [vp]
     L.gmr_model_info_get.argtypes = [vp, C.POINTER(ModelInfo)]
-    L.gmr_ik_solve.restype = C.c_int
-    L.gmr_ik_solve.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, C.POINTER(IKParams), vp, vp, vp, vp, vp,
-                               C.POINTER(IKStats), vp]
+    batch = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, C.POINTER(IKParams), vp]  # model .. qpos_init of the three IK calls
+    solve = batch + [vp, vp, vp, vp, C.POINTER(IKStats)]                                          # qpos_final .. stats
+    L.gmr_ik_solve.argtypes = solve + [vp]
+    L.gmr_ik_solve_ordered.argtypes = solve + [vp, vp]
+    L.gmr_ik_plan_order.argtypes = batch + [C.c_int, vp, vp]
+    L.gmr_group_ik_solve.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp]
+    L.gmr_group_ik_solve_ordered.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp, vp]
+    L.gmr_group_plan_order.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), C.c_int, vp, vp]
+    for f in ("gmr_ik_solve", "gmr_ik_solve_ordered", "gmr_ik_plan_order", "gmr_group_ik_solve", "gmr_group_ik_solve_ordered", "gmr_group_plan_order"):
+        getattr(L, f).restype = C.c_int
     L.gmr_fk.restype = C.c_int
     L.gmr_fk.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
     L.gmr_fk_shape.restype = C.c_int
@@ -140,17 +147,6 @@ def load():
     L.gmr_group_model.argtypes = [vp, C.c_int]
     L.gmr_group_last_error.restype = C.c_char_p
     L.gmr_group_last_error.argtypes = [vp]
-    L.gmr_group_ik_solve.restype = C.c_int
-    L.gmr_ik_plan_order.restype = C.c_int
-    L.gmr_ik_plan_order.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, C.POINTER(IKParams), vp, C.c_int, vp, vp]
-    L.gmr_ik_solve_ordered.restype = C.c_int
-    L.gmr_ik_solve_ordered.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, C.POINTER(IKParams), vp, vp, vp, vp, vp,
-                                       C.POINTER(IKStats), vp, vp]
-    L.gmr_group_ik_solve.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp]
-    L.gmr_group_plan_order.restype = C.c_int
-    L.gmr_group_plan_order.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), C.c_int, vp, vp]
-    L.gmr_group_ik_solve_ordered.restype = C.c_int
-    L.gmr_group_ik_solve_ordered.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp, vp]
     L.gmr_motion_epilogue.restype = C.c_int
     L.gmr_motion_epilogue.argtypes = [vp, C.POINTER(MotionInput), vp]
     L.gmr_group_motion_epilogue.restype = C.c_int

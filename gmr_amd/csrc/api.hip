@@ -91,11 +91,15 @@ void set_err(gmr_model *m, const char *fmt, ...) {
   if (m) m->err = buf;
 }
 
-#define HIP_TRY(m, expr)                                                              \
+// HIP_TRY's error sink: a model (its last error) or the message string a shared host path was given.
+std::string &err_of(gmr_model *m) { return m->err; }
+std::string &err_of(std::string &err) { return err; }
+
+#define HIP_TRY(sink, expr)                                                           \
   do {                                                                                \
     hipError_t e_ = (expr);                                                           \
     if (e_ != hipSuccess) {                                                           \
-      set_err(m, "%s failed: %s", #expr, hipGetErrorString(e_));                      \
+      err_of(sink) = std::string(#expr " failed: ") + hipGetErrorString(e_);          \
       return GMR_EDEVICE;                                                             \
     }                                                                                 \
   } while (0)
@@ -153,12 +157,13 @@ hipMemPool_t scratch_pool(int device) {
   pools[device] = pool;
   return pool;
 }
-int scratch_alloc(gmr_model *m, CallScratch &sc, size_t bytes, hipStream_t st) {
+int scratch_alloc(const gmr_model *m, CallScratch &sc, size_t bytes, hipStream_t st, std::string &err) {
   sc.st = st;
-  if (m->pool) HIP_TRY(m, hipMallocFromPoolAsync(&sc.p, std::max<size_t>(bytes, 256), m->pool, st));
-  else HIP_TRY(m, hipMallocAsync(&sc.p, std::max<size_t>(bytes, 256), st));
+  if (m->pool) HIP_TRY(err, hipMallocFromPoolAsync(&sc.p, std::max<size_t>(bytes, 256), m->pool, st));
+  else HIP_TRY(err, hipMallocAsync(&sc.p, std::max<size_t>(bytes, 256), st));
   return GMR_OK;
 }
+int scratch_alloc(gmr_model *m, CallScratch &sc, size_t bytes, hipStream_t st) { return scratch_alloc(m, sc, bytes, st, m->err); }
 
 // Kernel variants by padded system size.  GMR_IK_DEV_ONLY36 (experiments only, never the shipped library) builds just
 // ik_kernel<36, true> to cut compile time.
@@ -976,17 +981,17 @@ int gmr_model_info_get(const gmr_model *m, gmr_model_info *out) {
   return GMR_OK;
 }
 
-// Validate one model's batch, put its scheduling data (length-sorted work items, the caller's index of each, the slot columns)
-// into stream-ordered scratch and fill the launch arguments.  `order_host` receives the caller's index of every sorted item.
-static int prepare_ik_launch(gmr_model *m, const void *human_pos, const void *human_quat, int in_dtype, int n_cols, const int32_t *slot_col,
-                             int64_t n_frames, const gmr_work_item *items, int n_items, const gmr_ik_params *params,
-                             const double *qpos_init, double *qpos_final, double *qpos_out, int32_t *iters_out, int32_t *frames_done,
-                             gmr_ik_stats *stats, hipStream_t st, CallScratch &sc, gmr::IkLaunch &L, std::vector<gmr_work_item> &sorted,
-                             bool keep_order = false) {
+// Validate one model's batch (`in`: its arguments exactly as gmr_ik_solve takes them), put its scheduling data (length-sorted work
+// items, the caller's index of each, the slot columns) into stream-ordered scratch and fill the launch arguments.
+static int prepare_ik_launch(gmr_model *m, const gmr_group_input &in, const gmr_ik_params *params, gmr_ik_stats *stats, hipStream_t st,
+                             CallScratch &sc, gmr::IkLaunch &L, std::vector<gmr_work_item> &sorted, bool keep_order) {
+  const gmr_work_item *items = in.items;
+  const int32_t *slot_col = in.slot_col;
+  const int n_items = in.n_items, n_cols = in.n_cols;
   if (m->h.nslot == 0 || (m->h.ntask[0] == 0 && m->h.ntask[1] == 0)) { set_err(m, "model has no IK config"); return GMR_ENOCONFIG; }
-  if (!human_pos || !human_quat || !slot_col || !params || !qpos_out || (!items && n_items > 0)) { set_err(m, "null argument"); return GMR_EINVAL; }
-  if (in_dtype != GMR_DTYPE_F32 && in_dtype != GMR_DTYPE_F64) { set_err(m, "in_dtype must be f32 or f64"); return GMR_EINVAL; }
-  if (n_cols <= 0 || n_frames < 0 || n_items < 0) { set_err(m, "negative size"); return GMR_EINVAL; }
+  if (!in.human_pos || !in.human_quat || !slot_col || !params || !in.qpos_out || (!items && n_items > 0)) { set_err(m, "null argument"); return GMR_EINVAL; }
+  if (in.in_dtype != GMR_DTYPE_F32 && in.in_dtype != GMR_DTYPE_F64) { set_err(m, "in_dtype must be f32 or f64"); return GMR_EINVAL; }
+  if (n_cols <= 0 || in.n_frames < 0 || n_items < 0) { set_err(m, "negative size"); return GMR_EINVAL; }
   if (params->max_iter < 0 || !(params->damping > 0.0)) { set_err(m, "damping must be > 0 (H must be positive definite) and max_iter >= 0"); return GMR_EINVAL; }
   for (int s = 0; s < m->h.nslot; ++s)
     if (slot_col[s] < 0 || slot_col[s] >= n_cols) { set_err(m, "slot_col[%d]=%d outside [0,%d)", s, slot_col[s], n_cols); return GMR_EINVAL; }
@@ -994,8 +999,8 @@ static int prepare_ik_launch(gmr_model *m, const void *human_pos, const void *hu
   bool need_init = false, need_final = false;
   for (int i = 0; i < n_items; ++i) {
     const gmr_work_item &w = items[i];
-    if (w.n_burn < 0 || w.n_out < 0 || w.frame_begin < 0 || w.frame_begin + w.n_burn + w.n_out > n_frames) {
-      set_err(m, "work item %d covers frames outside [0,%lld)", i, (long long)n_frames);
+    if (w.n_burn < 0 || w.n_out < 0 || w.frame_begin < 0 || w.frame_begin + w.n_burn + w.n_out > in.n_frames) {
+      set_err(m, "work item %d covers frames outside [0,%lld)", i, (long long)in.n_frames);
       return GMR_EINVAL;
     }
     if (w.check_stride < 0 || (w.check_stride > 0 && (w.burn_row < 0 || w.final_row < 0 || w.n_burn != 0))) {
@@ -1009,13 +1014,13 @@ static int prepare_ik_launch(gmr_model *m, const void *human_pos, const void *hu
     tot += w.n_burn + w.n_out; out += w.n_out;
     need_init |= w.init_row >= 0; need_final |= w.final_row >= 0 || w.burn_row >= 0;
   }
-  if (need_init && !qpos_init) { set_err(m, "items reference qpos_init but it is NULL"); return GMR_EINVAL; }
-  if (need_final && !qpos_final) { set_err(m, "items reference qpos_final but it is NULL"); return GMR_EINVAL; }
+  if (need_init && !in.qpos_init) { set_err(m, "items reference qpos_init but it is NULL"); return GMR_EINVAL; }
+  if (need_final && !in.qpos_final) { set_err(m, "items reference qpos_final but it is NULL"); return GMR_EINVAL; }
   if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_items = n_items; stats->n_frames_total = tot; stats->n_frames_out = out; }
   L = gmr::IkLaunch{};
   L.n_items = n_items;
   sorted.clear();
-  if (n_items == 0) return GMR_OK;
+  if (n_items == 0) return GMR_OK;  // (before any device call)
 
   HIP_TRY(m, hipSetDevice(m->device));
   // longest item first so that the tail of the grid is made of short ones
@@ -1036,15 +1041,132 @@ static int prepare_ik_launch(gmr_model *m, const void *human_pos, const void *hu
   HIP_TRY(m, hipMemcpyAsync(ws + order_off, order.data(), order_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(m, hipMemcpyAsync(ws + col_off, slot_col, col_bytes, hipMemcpyHostToDevice, st));
 
-  L.hpos = human_pos; L.hquat = human_quat; L.slot_col = reinterpret_cast<const int *>(ws + col_off);
+  L.hpos = in.human_pos; L.hquat = in.human_quat; L.slot_col = reinterpret_cast<const int *>(ws + col_off);
   L.items = reinterpret_cast<const gmr_work_item *>(ws);
-  L.order = reinterpret_cast<const int *>(ws + order_off); L.frames_done = frames_done;
-  L.qinit = qpos_init; L.qfinal = qpos_final; L.qout = qpos_out; L.iters = iters_out;
-  L.in_f64 = in_dtype == GMR_DTYPE_F64; L.n_cols = n_cols; L.n_items = n_items; L.prm = *params;
+  L.order = reinterpret_cast<const int *>(ws + order_off); L.frames_done = in.frames_done;
+  L.qinit = in.qpos_init; L.qfinal = in.qpos_final; L.qout = in.qpos_out; L.iters = in.iters_out;
+  L.in_f64 = in.in_dtype == GMR_DTYPE_F64; L.n_cols = n_cols; L.n_items = n_items; L.prm = *params;
 #ifdef GMR_IK_STAMPS
   if (!m->dbg) { HIP_TRY(m, hipMalloc(&m->dbg, 16 * sizeof(unsigned long long))); HIP_TRY(m, hipMemset(m->dbg, 0, 16 * sizeof(unsigned long long))); }
 #endif
   L.dbg = m->dbg;
+  return GMR_OK;
+}
+
+// The probe copy of a batch (gmr_ik_plan_order): every item cut to its first probe_frames frames, solved for their cost alone.
+// `in` is redirected to the copy and loses its outputs; frames[k] / probed[k] receive item k's frames in total / in the probe.
+static int probe_batch(gmr_group_input &in, int probe_frames, std::vector<gmr_work_item> &probe, int *frames, int *probed, std::string &err) {
+  static double dummy_out;  // (prepare_ik_launch insists on an output array; a probe item has no output frame to write)
+  if (in.n_items < 0 || (!in.items && in.n_items > 0)) { err = "null argument"; return GMR_EINVAL; }
+  probe.assign(in.items, in.items + in.n_items);
+  for (int k = 0; k < in.n_items; ++k) {
+    gmr_work_item &w = probe[k];
+    if (w.check_stride != 0) { err = "work item " + std::to_string(k) + ": verification walks cannot be probed"; return GMR_EINVAL; }
+    if (w.n_burn < 0 || w.n_out < 0) { err = "work item " + std::to_string(k) + " has a negative frame count"; return GMR_EINVAL; }
+    const int total = w.n_burn + w.n_out, p = std::min(total, probe_frames);
+    frames[k] = total; probed[k] = p;
+    w.n_burn = p; w.n_out = 0; w.final_row = -1; w.burn_row = -1;  // frames solved, nothing written
+  }
+  in.items = probe.data();
+  in.qpos_final = nullptr; in.qpos_out = &dummy_out; in.iters_out = nullptr; in.frames_done = nullptr;
+  return GMR_OK;
+}
+
+enum IkMode { IK_PLAIN, IK_PROBE, IK_ORDERED };
+
+// Every batched IK call.  `models[i]` goes with `inputs[i]`.  With `g` NULL it is a model's own call (n = 1): ik_kernel / ik_probe_kernel
+// with the launch arguments by value; with a group, one grid of the ik_group_* kernels over all members' items -- a block finds its
+// entry in block_entry[] and its item as its global index - item_base.  Members without work get an empty entry.
+//   IK_PLAIN    each member's items longest first, the member with the longest item first
+//   IK_ORDERED  items in the caller's order, member i's at base_i = the sum of n_items over the members before it; workgroup b runs
+//               global item launch_order[b]
+//   IK_PROBE    the first probe_frames frames of every item for their cost (entry i's cost array starts at base_i), then one device
+//               sort over all of them into order_out
+// Errors land in `err` (a model's call passes its own); a group call names the member.
+static int ik_run(const gmr_group *g, gmr_model *const *models, const gmr_group_input *inputs, int n, const gmr_ik_params *params, hipStream_t st,
+                  IkMode mode, int probe_frames, int32_t *order_out, const int32_t *launch_order, gmr_ik_stats *stats, std::string &err) {
+  auto who = [&](int i) { return g ? "member " + std::to_string(i) + ": " : std::string(); };
+  std::vector<gmr_group_input> pin;
+  std::vector<std::vector<gmr_work_item>> probe(n), sorted(n);
+  std::vector<int> meta;  // IK_PROBE: [cost | frames | probed] by global item index
+  int tot = 0;
+  if (mode == IK_PROBE) {
+    if (!order_out || probe_frames < 1) { err = "order_out is NULL or probe_frames < 1"; return GMR_EINVAL; }
+    int64_t total64 = 0;
+    for (int i = 0; i < n; ++i) total64 += std::max(0, inputs[i].n_items);
+    if (total64 > INT32_MAX) { err = "more than 2^31 - 1 work items in one group launch"; return GMR_EINVAL; }
+    tot = (int)total64;
+    meta.resize(3 * (size_t)std::max(tot, 1));
+    pin.assign(inputs, inputs + n);
+    for (int i = 0, base = 0; i < n; ++i) {
+      int rc = probe_batch(pin[i], probe_frames, probe[i], meta.data() + tot + base, meta.data() + 2 * (size_t)tot + base, err);
+      if (rc != GMR_OK) { err = who(i) + err; return rc; }
+      base += pin[i].n_items;
+    }
+    if (tot == 0) return GMR_OK;
+    inputs = pin.data();
+  }
+  std::vector<CallScratch> scratch(n);
+  CallScratch ms, gs;
+  std::vector<gmr::IkGroupEntry> entries(n);
+  int total = 0, lds_bytes = 0;
+  for (int i = 0; i < n; ++i) {
+    gmr_model *m = models[i];
+    const gmr_group_input &in = inputs[i];
+    m->err.clear();
+    if (g && in.n_items == 0) continue;  // no work for this member (a model's own call of zero items is still checked)
+    int rc = prepare_ik_launch(m, in, params, stats, st, scratch[i], entries[i].L, sorted[i], mode == IK_ORDERED);
+    if (rc != GMR_OK) { err = who(i) + m->err; return rc; }
+    if (in.n_items > INT32_MAX - total) { err = "more than 2^31 - 1 work items in one group launch"; return GMR_EINVAL; }
+    entries[i].m = m->dm_dev; entries[i].lay = m->lay;
+    total += in.n_items;
+    if (in.n_items > 0) lds_bytes = std::max(lds_bytes, m->lds_bytes);
+  }
+  if (total == 0) return GMR_OK;
+  if (mode == IK_ORDERED && !launch_order) { err = "launch_order is NULL"; return GMR_EINVAL; }
+  int *meta_dev = nullptr;
+  if (mode == IK_PROBE) {
+    int rc = scratch_alloc(models[0], ms, sizeof(int) * meta.size(), st, err);
+    if (rc != GMR_OK) return rc;
+    meta_dev = static_cast<int *>(ms.p);
+    HIP_TRY(err, hipMemcpyAsync(meta_dev, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, st));
+  }
+  std::vector<int> eorder(n), block_entry(g ? total : 0);
+  std::iota(eorder.begin(), eorder.end(), 0);
+  auto longest = [&](int e) { return sorted[e].empty() ? -1 : sorted[e][0].n_burn + sorted[e][0].n_out; };
+  if (mode == IK_PLAIN) std::stable_sort(eorder.begin(), eorder.end(), [&](int a, int b) { return longest(a) > longest(b); });
+  int blk = 0;
+  for (int e : eorder) {
+    entries[e].item_base = blk;
+    if (g) std::fill_n(block_entry.begin() + blk, sorted[e].size(), e);
+    blk += (int)sorted[e].size();
+    if (mode == IK_PROBE) { entries[e].L.qout = nullptr; entries[e].L.cost = meta_dev + entries[e].item_base; }  // (cost[order[k]]: global item base + k)
+  }
+  if (!g) {
+    if (mode == IK_ORDERED) entries[0].L.perm = launch_order;
+    int rc = launch_ik_variant(models[0], entries[0].L, st, mode == IK_PROBE);
+    if (rc != GMR_OK) { err = models[0]->err; return rc; }
+  } else {  // the entries and the block -> entry table go into stream-ordered scratch
+    const size_t ent_bytes = sizeof(gmr::IkGroupEntry) * (size_t)n, be_off = (ent_bytes + 15) & ~size_t(15);
+    int rc = scratch_alloc(models[0], gs, be_off + sizeof(int) * (size_t)total, st, err);
+    if (rc != GMR_OK) return rc;
+    uint8_t *ws = static_cast<uint8_t *>(gs.p);
+    HIP_TRY(err, hipMemcpyAsync(ws, entries.data(), ent_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(err, hipMemcpyAsync(ws + be_off, block_entry.data(), sizeof(int) * (size_t)total, hipMemcpyHostToDevice, st));
+    const auto *d_entries = reinterpret_cast<const gmr::IkGroupEntry *>(ws);
+    const int *d_be = reinterpret_cast<const int *>(ws + be_off);
+    switch (g->nvp) {
+#define GMR_X(v) case v: launch_ik_group<v>(g, d_entries, d_be, total, lds_bytes, st, launch_order, mode == IK_PROBE); break;
+      GMR_FOR_EACH_NVP(GMR_X)
+#undef GMR_X
+      default: err = "internal: no kernel variant"; return GMR_EUNSUPPORTED;
+    }
+    HIP_TRY(err, hipGetLastError());
+  }
+  if (mode == IK_PROBE) {
+    hipLaunchKernelGGL(gmr::plan_order_kernel, dim3(1), dim3(1024), 0, st, meta_dev, meta_dev + tot, meta_dev + 2 * (size_t)tot, tot, order_out);
+    HIP_TRY(err, hipGetLastError());
+  }
   return GMR_OK;
 }
 
@@ -1053,14 +1175,9 @@ int gmr_ik_solve(gmr_model *m, const void *human_pos, const void *human_quat, in
                  double *qpos_final, double *qpos_out, int32_t *iters_out, int32_t *frames_done, gmr_ik_stats *stats, void *stream) {
   if (!m) return GMR_EINVAL;
   m->err.clear();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CallScratch sc;
-  gmr::IkLaunch L{};
-  std::vector<gmr_work_item> sorted;
-  int rc = prepare_ik_launch(m, human_pos, human_quat, in_dtype, n_cols, slot_col, n_frames, items, n_items, params, qpos_init, qpos_final,
-                             qpos_out, iters_out, frames_done, stats, st, sc, L, sorted);
-  if (rc != GMR_OK || n_items == 0) return rc;
-  return launch_ik_variant(m, L, st);
+  const gmr_group_input in = {human_pos, human_quat, in_dtype, n_cols, slot_col, n_frames, items, n_items, 0,
+                              qpos_init, qpos_final, qpos_out, iters_out, frames_done};
+  return ik_run(nullptr, &m, &in, 1, params, static_cast<hipStream_t>(stream), IK_PLAIN, 0, nullptr, nullptr, stats, m->err);
 }
 
 // ---- launch order by predicted cost.  Items of equal length still differ in cost (solves per frame: 1.15 max / mean on the
@@ -1073,39 +1190,9 @@ int gmr_ik_plan_order(gmr_model *m, const void *human_pos, const void *human_qua
                       int probe_frames, int32_t *order_out, void *stream) {
   if (!m) return GMR_EINVAL;
   m->err.clear();
-  if (!order_out || probe_frames < 1) { set_err(m, "order_out is NULL or probe_frames < 1"); return GMR_EINVAL; }
-  if (n_items < 0 || (!items && n_items > 0)) { set_err(m, "null argument"); return GMR_EINVAL; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<gmr_work_item> probe(items, items + n_items);
-  std::vector<int> meta(3 * (size_t)std::max(n_items, 1));  // [cost | frames | probed]
-  for (int i = 0; i < n_items; ++i) {
-    gmr_work_item &w = probe[i];
-    if (w.check_stride != 0) { set_err(m, "work item %d: verification walks cannot be probed", i); return GMR_EINVAL; }
-    if (w.n_burn < 0 || w.n_out < 0) { set_err(m, "work item %d has a negative frame count", i); return GMR_EINVAL; }
-    const int total = w.n_burn + w.n_out, p = std::min(total, probe_frames);
-    meta[n_items + i] = total; meta[2 * n_items + i] = p;
-    w.n_burn = p; w.n_out = 0; w.final_row = -1; w.burn_row = -1;  // frames solved, nothing written
-  }
-  if (n_items == 0) return GMR_OK;
-  HIP_TRY(m, hipSetDevice(m->device));
-  CallScratch sc, ms;
-  gmr::IkLaunch L{};
-  std::vector<gmr_work_item> sorted;
-  double dummy_out = 0.0;  // (prepare_ik_launch insists on an output array; a probe item has no output frame to write)
-  int rc = prepare_ik_launch(m, human_pos, human_quat, in_dtype, n_cols, slot_col, n_frames, probe.data(), n_items, params, qpos_init, nullptr,
-                             &dummy_out, nullptr, nullptr, nullptr, st, sc, L, sorted);
-  if (rc != GMR_OK) return rc;
-  rc = scratch_alloc(m, ms, sizeof(int) * meta.size(), st);
-  if (rc != GMR_OK) return rc;
-  int *meta_dev = static_cast<int *>(ms.p);
-  HIP_TRY(m, hipMemcpyAsync(meta_dev, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, st));
-  L.qout = nullptr;
-  L.cost = meta_dev;
-  rc = launch_ik_variant(m, L, st, /*probe=*/true);
-  if (rc != GMR_OK) return rc;
-  hipLaunchKernelGGL(gmr::plan_order_kernel, dim3(1), dim3(1024), 0, st, meta_dev, meta_dev + n_items, meta_dev + 2 * n_items, n_items, order_out);
-  HIP_TRY(m, hipGetLastError());
-  return GMR_OK;
+  const gmr_group_input in = {human_pos, human_quat, in_dtype, n_cols, slot_col, n_frames, items, n_items, 0,
+                              qpos_init, nullptr, nullptr, nullptr, nullptr};
+  return ik_run(nullptr, &m, &in, 1, params, static_cast<hipStream_t>(stream), IK_PROBE, probe_frames, order_out, nullptr, nullptr, m->err);
 }
 
 int gmr_ik_solve_ordered(gmr_model *m, const void *human_pos, const void *human_quat, int in_dtype, int n_cols, const int32_t *slot_col,
@@ -1115,15 +1202,9 @@ int gmr_ik_solve_ordered(gmr_model *m, const void *human_pos, const void *human_
   if (!m) return GMR_EINVAL;
   m->err.clear();
   if (!launch_order && n_items > 0) { set_err(m, "launch_order is NULL"); return GMR_EINVAL; }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  CallScratch sc;
-  gmr::IkLaunch L{};
-  std::vector<gmr_work_item> sorted;
-  int rc = prepare_ik_launch(m, human_pos, human_quat, in_dtype, n_cols, slot_col, n_frames, items, n_items, params, qpos_init, qpos_final,
-                             qpos_out, iters_out, frames_done, stats, st, sc, L, sorted, /*keep_order=*/true);
-  if (rc != GMR_OK || n_items == 0) return rc;
-  L.perm = launch_order;
-  return launch_ik_variant(m, L, st);
+  const gmr_group_input in = {human_pos, human_quat, in_dtype, n_cols, slot_col, n_frames, items, n_items, 0,
+                              qpos_init, qpos_final, qpos_out, iters_out, frames_done};
+  return ik_run(nullptr, &m, &in, 1, params, static_cast<hipStream_t>(stream), IK_ORDERED, 0, nullptr, launch_order, stats, m->err);
 }
 
 // ------------------------------------------------------------------ several models in one launch (BASELINE config 4)
@@ -1171,176 +1252,28 @@ int gmr_group_size(const gmr_group *g) { return g ? (int)g->models.size() : 0; }
 gmr_model *gmr_group_model(gmr_group *g, int i) { return g && i >= 0 && i < (int)g->models.size() ? g->models[i] : nullptr; }
 const char *gmr_group_last_error(const gmr_group *g) { return g ? g->err.c_str() : "null group"; }
 
-// Validate every member's batch and fill its entry (prepare_ik_launch per member).  Members without work get an empty entry.
-static int prepare_group(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, hipStream_t st, bool keep_order,
-                         std::vector<CallScratch> &scratch, std::vector<gmr::IkGroupEntry> &entries,
-                         std::vector<std::vector<gmr_work_item>> &sorted, int &total, int &lds_bytes) {
-  const int n = (int)g->models.size();
-  total = 0; lds_bytes = 0;
-  for (int i = 0; i < n; ++i) {
-    gmr_model *m = g->models[i];
-    m->err.clear();
-    const gmr_group_input &in = inputs[i];
-    gmr::IkLaunch L{};
-    entries[i] = gmr::IkGroupEntry{};
-    if (in.n_items == 0) continue;  // no work for this member
-    int rc = prepare_ik_launch(m, in.human_pos, in.human_quat, in.in_dtype, in.n_cols, in.slot_col, in.n_frames, in.items, in.n_items, params,
-                               in.qpos_init, in.qpos_final, in.qpos_out, in.iters_out, in.frames_done, nullptr, st, scratch[i], L, sorted[i],
-                               keep_order);
-    if (rc != GMR_OK) { g->err = "member " + std::to_string(i) + ": " + m->err; return rc; }
-    if (in.n_items > INT32_MAX - total) { g->err = "more than 2^31 - 1 work items in one group launch"; return GMR_EINVAL; }
-    entries[i].m = m->dm_dev; entries[i].L = L; entries[i].lay = m->lay; entries[i].item_base = 0; entries[i].pad = 0;
-    total += in.n_items;
-    if (in.n_items > 0) lds_bytes = std::max(lds_bytes, m->lds_bytes);
-  }
-  return GMR_OK;
-}
-
-// Global item numbering of the ordered calls: member i's items at base_i = the sum of n_items over the members before it.
-static void group_bases(const gmr_group_input *inputs, int n, std::vector<gmr::IkGroupEntry> &entries, std::vector<int> &block_entry) {
-  int blk = 0;
-  for (int i = 0; i < n; ++i) {
-    entries[i].item_base = blk;
-    for (int k = 0; k < inputs[i].n_items; ++k) block_entry[blk++] = i;
-  }
-}
-
-// Upload the entries and the block -> entry table into stream-ordered scratch and launch one grid of `total` workgroups.
-static int launch_group(gmr_group *g, const std::vector<gmr::IkGroupEntry> &entries, const std::vector<int> &block_entry, int total,
-                        int lds_bytes, hipStream_t st, const int32_t *perm, bool probe) {
-  const int n = (int)g->models.size();
-  gmr_model *m0 = g->models[0];
-  if (hipSetDevice(g->device) != hipSuccess) { g->err = "hipSetDevice failed"; return GMR_EDEVICE; }
-  CallScratch gs;
-  const size_t ent_bytes = sizeof(gmr::IkGroupEntry) * (size_t)n, be_off = (ent_bytes + 15) & ~size_t(15);
-  int rc = scratch_alloc(m0, gs, be_off + sizeof(int) * (size_t)total, st);
-  if (rc != GMR_OK) { g->err = m0->err; return rc; }
-  uint8_t *ws = static_cast<uint8_t *>(gs.p);
-  if (hipMemcpyAsync(ws, entries.data(), ent_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(ws + be_off, block_entry.data(), sizeof(int) * (size_t)total, hipMemcpyHostToDevice, st) != hipSuccess) {
-    g->err = "hipMemcpyAsync failed";
-    return GMR_EDEVICE;
-  }
-  const auto *d_entries = reinterpret_cast<const gmr::IkGroupEntry *>(ws);
-  const int *d_be = reinterpret_cast<const int *>(ws + be_off);
-  switch (g->nvp) {
-#define GMR_X(v) case v: launch_ik_group<v>(g, d_entries, d_be, total, lds_bytes, st, perm, probe); break;
-    GMR_FOR_EACH_NVP(GMR_X)
-#undef GMR_X
-    default: g->err = "internal: no kernel variant"; return GMR_EUNSUPPORTED;
-  }
-  if (hipGetLastError() != hipSuccess) { g->err = "kernel launch failed"; return GMR_EDEVICE; }
-  return GMR_OK;
-}
-
 int gmr_group_ik_solve(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, void *stream) {
   if (!g || !inputs || !params) return GMR_EINVAL;
   g->err.clear();
-  const int n = (int)g->models.size();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<CallScratch> scratch(n);
-  std::vector<gmr::IkGroupEntry> entries(n);
-  std::vector<std::vector<gmr_work_item>> sorted(n);
-  int total = 0, lds_bytes = 0;
-  int rc = prepare_group(g, inputs, params, st, /*keep_order=*/false, scratch, entries, sorted, total, lds_bytes);
-  if (rc != GMR_OK) return rc;
-  if (total == 0) return GMR_OK;
-  // one grid over all members' items: a block finds its entry in block_entry[] and its item as blockIdx - item_base, so the
-  // blocks of an entry are contiguous (its items longest first); the entry with the longest items goes first
-  std::vector<int> block_entry(total);
-  std::vector<int> eorder(n);
-  std::iota(eorder.begin(), eorder.end(), 0);
-  auto longest = [&](int e) { return sorted[e].empty() ? -1 : sorted[e][0].n_burn + sorted[e][0].n_out; };
-  std::stable_sort(eorder.begin(), eorder.end(), [&](int a, int b) { return longest(a) > longest(b); });
-  int blk = 0;
-  for (int e : eorder) {
-    entries[e].item_base = blk;
-    for (size_t k = 0; k < sorted[e].size(); ++k) block_entry[blk++] = e;
-  }
-  return launch_group(g, entries, block_entry, total, lds_bytes, st, nullptr, false);
+  return ik_run(g, g->models.data(), inputs, (int)g->models.size(), params, static_cast<hipStream_t>(stream), IK_PLAIN, 0, nullptr, nullptr,
+                nullptr, g->err);
 }
 
-// Launch order across robots: gmr_ik_plan_order's probe for every member's items in one grid, costs in the global item space
-// (entry i's cost array starts at base_i), one device sort over all of them.
+// Launch order across robots: gmr_ik_plan_order's probe for every member's items in one grid, one device sort over all of them.
 int gmr_group_plan_order(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, int probe_frames, int32_t *order_out,
                          void *stream) {
   if (!g || !inputs || !params) return GMR_EINVAL;
   g->err.clear();
-  if (!order_out || probe_frames < 1) { g->err = "order_out is NULL or probe_frames < 1"; return GMR_EINVAL; }
-  const int n = (int)g->models.size();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<gmr_group_input> pin(inputs, inputs + n);
-  std::vector<std::vector<gmr_work_item>> probe(n);
-  double dummy_out = 0.0;  // (prepare_ik_launch insists on an output array; a probe item has no output frame to write)
-  int64_t total64 = 0;
-  for (int i = 0; i < n; ++i) total64 += std::max(0, inputs[i].n_items);
-  if (total64 > INT32_MAX) { g->err = "more than 2^31 - 1 work items in one group launch"; return GMR_EINVAL; }
-  std::vector<int> meta(3 * (size_t)std::max<int64_t>(total64, 1));  // [cost | frames | probed], global item index
-  const int tot = (int)total64;
-  for (int i = 0, base = 0; i < n; ++i) {
-    const gmr_group_input &in = inputs[i];
-    if (in.n_items < 0 || (!in.items && in.n_items > 0)) { g->err = "member " + std::to_string(i) + ": null argument"; return GMR_EINVAL; }
-    probe[i].assign(in.items, in.items + in.n_items);
-    for (int k = 0; k < in.n_items; ++k) {  // as gmr_ik_plan_order builds its probe items
-      gmr_work_item &w = probe[i][k];
-      if (w.check_stride != 0) { g->err = "member " + std::to_string(i) + ": work item " + std::to_string(k) + ": verification walks cannot be probed"; return GMR_EINVAL; }
-      if (w.n_burn < 0 || w.n_out < 0) { g->err = "member " + std::to_string(i) + ": work item " + std::to_string(k) + " has a negative frame count"; return GMR_EINVAL; }
-      const int total = w.n_burn + w.n_out, p = std::min(total, probe_frames);
-      meta[tot + base + k] = total; meta[2 * (size_t)tot + base + k] = p;
-      w.n_burn = p; w.n_out = 0; w.final_row = -1; w.burn_row = -1;  // frames solved, nothing written
-    }
-    pin[i].items = probe[i].data();
-    pin[i].qpos_final = nullptr; pin[i].qpos_out = &dummy_out; pin[i].iters_out = nullptr; pin[i].frames_done = nullptr;
-    base += in.n_items;
-  }
-  if (tot == 0) return GMR_OK;
-  std::vector<CallScratch> scratch(n);
-  std::vector<gmr::IkGroupEntry> entries(n);
-  std::vector<std::vector<gmr_work_item>> sorted(n);
-  int total = 0, lds_bytes = 0;
-  int rc = prepare_group(g, pin.data(), params, st, /*keep_order=*/false, scratch, entries, sorted, total, lds_bytes);
-  if (rc != GMR_OK) return rc;
-  gmr_model *m0 = g->models[0];
-  if (hipSetDevice(g->device) != hipSuccess) { g->err = "hipSetDevice failed"; return GMR_EDEVICE; }
-  CallScratch ms;
-  rc = scratch_alloc(m0, ms, sizeof(int) * meta.size(), st);
-  if (rc != GMR_OK) { g->err = m0->err; return rc; }
-  int *meta_dev = static_cast<int *>(ms.p);
-  if (hipMemcpyAsync(meta_dev, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, st) != hipSuccess) {
-    g->err = "hipMemcpyAsync failed";
-    return GMR_EDEVICE;
-  }
-  std::vector<int> block_entry(total);
-  group_bases(pin.data(), n, entries, block_entry);
-  for (int i = 0; i < n; ++i) {
-    entries[i].L.qout = nullptr;
-    entries[i].L.cost = meta_dev + entries[i].item_base;  // (item k of member i: cost[order[k]] = global item base_i + k)
-  }
-  rc = launch_group(g, entries, block_entry, total, lds_bytes, st, nullptr, /*probe=*/true);
-  if (rc != GMR_OK) return rc;
-  hipLaunchKernelGGL(gmr::plan_order_kernel, dim3(1), dim3(1024), 0, st, meta_dev, meta_dev + tot, meta_dev + 2 * (size_t)tot, tot, order_out);
-  if (hipGetLastError() != hipSuccess) { g->err = "kernel launch failed"; return GMR_EDEVICE; }
-  return GMR_OK;
+  return ik_run(g, g->models.data(), inputs, (int)g->models.size(), params, static_cast<hipStream_t>(stream), IK_PROBE, probe_frames, order_out,
+                nullptr, nullptr, g->err);
 }
 
 int gmr_group_ik_solve_ordered(gmr_group *g, const gmr_group_input *inputs, const gmr_ik_params *params, const int32_t *launch_order,
                                void *stream) {
   if (!g || !inputs || !params) return GMR_EINVAL;
   g->err.clear();
-  const int n = (int)g->models.size();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<CallScratch> scratch(n);
-  std::vector<gmr::IkGroupEntry> entries(n);
-  std::vector<std::vector<gmr_work_item>> sorted(n);
-  int total = 0, lds_bytes = 0;
-  // every member's items in the caller's order, so that a global index is base_i + the caller's index
-  int rc = prepare_group(g, inputs, params, st, /*keep_order=*/true, scratch, entries, sorted, total, lds_bytes);
-  if (rc != GMR_OK) return rc;
-  if (total == 0) return GMR_OK;
-  if (!launch_order) { g->err = "launch_order is NULL"; return GMR_EINVAL; }
-  std::vector<int> block_entry(total);
-  group_bases(inputs, n, entries, block_entry);
-  return launch_group(g, entries, block_entry, total, lds_bytes, st, launch_order, false);
+  return ik_run(g, g->models.data(), inputs, (int)g->models.size(), params, static_cast<hipStream_t>(stream), IK_ORDERED, 0, nullptr,
+                launch_order, nullptr, g->err);
 }
 
 // ------------------------------------------------------------------ single-sequence sessions (teleop)

@@ -55,6 +55,82 @@ def _state_arrays(nq: int, device, items: np.ndarray, qpos_init: Optional[torch.
     return qpos_init, qfin
 
 
+def _ik_batch(eng: "Engine", pos: torch.Tensor, quat: torch.Tensor, slot_col, items, *, out=None, iters=None, want_iters: bool = True,
+              qpos_init=None, qpos_final=None, n_final: int = 0, frames_done=None, host_out: bool = False, with_outputs: bool = True,
+              what: str = ""):
+    """Check one model's key-point batch and give it the form the library takes: contiguous tensors, ``slot_col`` int32, ``items`` as
+    work-item records, ``out`` (NaN) / ``iters`` / ``qpos_final`` allocated where the caller gives none.  ``host_out``: ``out`` may be
+    pinned host memory; ``with_outputs=False`` (a probe) leaves ``out`` / ``iters`` alone.  ``what`` prefixes the error messages (a group
+    member).  Returns (pos, quat, slot_col, items, out, iters, qpos_init, qpos_final)."""
+    if pos.device != eng.device or quat.device != eng.device:
+        raise EngineError(what + "inputs must live on the engine's device")
+    if pos.dtype != quat.dtype or pos.dtype not in (torch.float32, torch.float64):
+        raise EngineError(what + "pos/quat must both be float32 or both float64")
+    if pos.dim() != 3 or quat.dim() != 3 or pos.shape[2] != 3 or quat.shape[2] != 4 or pos.shape[:2] != quat.shape[:2]:
+        raise EngineError(what + f"bad input shapes {tuple(pos.shape)} / {tuple(quat.shape)}")
+    pos, quat = pos.contiguous(), quat.contiguous()
+    N = int(pos.shape[0])
+    items = np.ascontiguousarray(items, dtype=_native.WORK_ITEM_DTYPE)
+    slot_col = np.ascontiguousarray(slot_col, dtype=np.int32)
+    if slot_col.shape != (eng.info.nslot,):
+        raise EngineError(what + "slot_col has the wrong length")
+    if with_outputs:
+        if out is None:
+            out = torch.full((N, eng.nq), float("nan"), dtype=torch.float64, device=eng.device)
+        elif out.shape != (N, eng.nq) or out.dtype != torch.float64 or not out.is_contiguous() or \
+                (out.device != eng.device and not (host_out and out.is_pinned())):
+            raise EngineError(what + "out must be a contiguous float64 [N, nq] tensor on the engine's device")
+        if iters is None:
+            iters = torch.zeros(N, dtype=torch.int32, device=eng.device) if want_iters else None
+        elif iters.shape != (N,) or iters.dtype != torch.int32 or not iters.is_contiguous() or iters.device != eng.device:
+            raise EngineError(what + "iters must be a contiguous int32 [N] tensor on the engine's device")
+    qpos_init, qfin = _state_arrays(eng.nq, eng.device, items, qpos_init, qpos_final, n_final, frames_done, what)
+    return pos, quat, slot_col, items, out, iters, qpos_init, qfin
+
+
+def _launch_order(eng: "Engine", launch_order, item_arrays, plan):
+    """What an ``ik_solve`` launches by: ``None`` or a checked order tensor.  ``item_arrays``: the work items of the launch (one array per
+    model); ``"auto"`` asks ``eng``'s probe policy about all of them together and has ``plan(probe_frames)`` make the order."""
+    total = sum(len(it) for it in item_arrays)
+    if isinstance(launch_order, str):
+        if launch_order != "auto":
+            raise EngineError("launch_order must be a tensor, None or 'auto'")
+        pf = eng._probe_frames(np.concatenate(item_arrays))
+        launch_order = plan(pf) if pf else None
+    if launch_order is not None and (not isinstance(launch_order, torch.Tensor) or launch_order.dtype != torch.int32
+                                     or launch_order.device != eng.device or not launch_order.is_contiguous() or launch_order.numel() != total):
+        raise EngineError(f"launch_order must be a contiguous int32 [{total}] tensor on the engine's device (one entry per work item)")
+    return launch_order
+
+
+def _chunk_params(params: Optional[IKParams], eps: float) -> IKParams:
+    """``params`` with the verification walks' tolerance ``eps``."""
+    prm = params or IKParams()
+    return IKParams(prm.damping, prm.tol, prm.limit_gain, prm.lm_damping, prm.max_iter, prm.offset_to_ground, eps)
+
+
+def _chunk_batch(pos, quat, slot_col, offs, chunk: int, burn_in: int, height_scales, chunk_init: int, clip_init: int) -> dict:
+    """Launch 1 of a chunked solve as an ``ik_solve`` batch: the tracked chunk items of the clips ``offs`` and room for their states."""
+    from .schedule import make_items
+    items = make_items(offs, chunk=chunk, burn_in=burn_in, track=True, height_scales=height_scales, chunk_init=chunk_init, clip_init=clip_init)
+    return {"pos": pos, "quat": quat, "slot_col": slot_col, "items": items, "n_final": 2 * len(items)}
+
+
+def _walk_batch(first: dict, res, offs, chunk: int):
+    """Launch 2 from launch 1's batch and its results (qpos, iters, qpos_final): the verification walks writing into the same arrays, or
+    ``None`` where there is nothing to walk.  Returns (batch, info); ``info()`` -- to be called after launch 2 -- is the chunked solve's
+    info dict."""
+    from .schedule import plan_walks
+    items = first["items"]
+    walks = plan_walks(items, offs, chunk) if len(items) else items
+    if len(walks) == 0:
+        return None, lambda: {"chunks": len(items), "passes": 0, "resolved_frames": 0}
+    done = torch.zeros(len(walks), dtype=torch.int32, device=res[0].device)
+    batch = {"pos": first["pos"], "quat": first["quat"], "slot_col": first["slot_col"], "items": walks, "qpos_init": res[2], "qpos_final": res[2],
+             "out": res[0], "iters": res[1], "frames_done": done}
+    return batch, lambda: {"chunks": len(items), "passes": 1, "resolved_frames": int(done.sum().item())}
+
+
 def _motion_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, height_adjust: bool, root_origin_offset: bool, ground_offset: float,
                   out, min_z: Optional[torch.Tensor], what: str = ""):
     """Check one model's epilogue arguments and fill its ``MotionInput``.  Returns (input, (root_pos, root_rot, dof_pos,
@@ -150,52 +226,24 @@ class Engine:
         -- plan an order when that pays: more plain items than wavefront slots, long enough for the probe to be a small fraction of
         the work (``PROBE_*`` below).  The order only moves work in time; results are identical.
         """
-        if pos.device != self.device or quat.device != self.device:
-            raise EngineError("inputs must live on the engine's device")
-        if pos.dtype != quat.dtype or pos.dtype not in (torch.float32, torch.float64):
-            raise EngineError("pos/quat must both be float32 or both float64")
-        if pos.dim() != 3 or quat.dim() != 3 or pos.shape[2] != 3 or quat.shape[2] != 4 or pos.shape[:2] != quat.shape[:2]:
-            raise EngineError(f"bad input shapes {tuple(pos.shape)} / {tuple(quat.shape)}")
-        pos, quat = pos.contiguous(), quat.contiguous()
+        pos, quat, slot_col, items, out, iters, qpos_init, qfin = _ik_batch(
+            self, pos, quat, slot_col, items, out=out, iters=iters, want_iters=want_iters, qpos_init=qpos_init, qpos_final=qpos_final,
+            n_final=n_final, frames_done=frames_done, host_out=_host_out)
         N, B = int(pos.shape[0]), int(pos.shape[1])
-        items = np.ascontiguousarray(items, dtype=_native.WORK_ITEM_DTYPE)
-        slot_col = np.ascontiguousarray(slot_col, dtype=np.int32)
-        if slot_col.shape != (self.info.nslot,):
-            raise EngineError("slot_col has the wrong length")
         prm = params or IKParams()
-        if out is None:
-            out = torch.full((N, self.nq), float("nan"), dtype=torch.float64, device=self.device)
-        elif out.shape != (N, self.nq) or out.dtype != torch.float64 or not out.is_contiguous() or \
-                (out.device != self.device and not (_host_out and out.is_pinned())):
-            raise EngineError("out must be a contiguous float64 [N, nq] tensor on the engine's device")
-        if iters is None:
-            iters = torch.zeros(N, dtype=torch.int32, device=self.device) if want_iters else None
-        qpos_init, qfin = _state_arrays(self.nq, self.device, items, qpos_init, qpos_final, n_final, frames_done)
         stats = IKStats()
         self.last_stats = stats
         if N == 0 or len(items) == 0:  # nothing to launch (empty tensors have no device pointer)
             return out, iters, qfin
-        if isinstance(launch_order, str):
-            if launch_order != "auto":
-                raise EngineError("launch_order must be a tensor, None or 'auto'")
-            pf = self._probe_frames(items)
-            launch_order = self.plan_order(pos, quat, slot_col, items, prm, qpos_init, probe_frames=pf) if pf else None
-        dt = _native.GMR_DTYPE_F64 if pos.dtype == torch.float64 else _native.GMR_DTYPE_F32
+        launch_order = _launch_order(self, launch_order, [items],
+                                     lambda pf: self.plan_order(pos, quat, slot_col, items, prm, qpos_init, probe_frames=pf))
+        args = (self._h, _ptr(pos), _ptr(quat), _native.GMR_DTYPE_F64 if pos.dtype == torch.float64 else _native.GMR_DTYPE_F32, B,
+                slot_col.ctypes.data_as(C.c_void_p), N, items.ctypes.data_as(C.c_void_p), len(items), C.byref(prm), _ptr(qpos_init), _ptr(qfin),
+                _ptr(out), _ptr(iters), _ptr(frames_done), C.byref(stats))
         if launch_order is None:
-            rc = self._lib.gmr_ik_solve(
-                self._h, _ptr(pos), _ptr(quat), dt, B, slot_col.ctypes.data_as(C.c_void_p), N, items.ctypes.data_as(C.c_void_p), len(items),
-                C.byref(prm), _ptr(qpos_init), _ptr(qfin), _ptr(out), _ptr(iters), _ptr(frames_done), C.byref(stats), self._stream())
-            self._check(rc, "gmr_ik_solve")
+            self._check(self._lib.gmr_ik_solve(*args, self._stream()), "gmr_ik_solve")
         else:
-            if launch_order.dtype != torch.int32 or launch_order.device != self.device or not launch_order.is_contiguous() \
-                    or launch_order.numel() != len(items):
-                raise EngineError("launch_order must be a contiguous int32 [n_items] tensor on the engine's device")
-            rc = self._lib.gmr_ik_solve_ordered(
-                self._h, _ptr(pos), _ptr(quat), dt, B, slot_col.ctypes.data_as(C.c_void_p), N, items.ctypes.data_as(C.c_void_p), len(items),
-                C.byref(prm), _ptr(qpos_init), _ptr(qfin), _ptr(out), _ptr(iters), _ptr(frames_done), C.byref(stats), _ptr(launch_order),
-                self._stream())
-            self._check(rc, "gmr_ik_solve_ordered")
-        self.last_stats = stats
+            self._check(self._lib.gmr_ik_solve_ordered(*args, _ptr(launch_order), self._stream()), "gmr_ik_solve_ordered")
         return out, iters, qfin
 
     # Launch order by predicted cost (gmr_ik_plan_order: solves of an item's first frames x its length): when it is worth a probe, and of
@@ -360,23 +408,14 @@ class Engine:
         good the speculative start was; its quality only decides how much of a clip the walk has to re-solve.
         Returns (qpos [N,nq], iters [N], info dict).
         """
-        from .schedule import make_items, plan_walks
         offs = np.asarray(seq_offsets, dtype=np.int64)
-        items = make_items(offs, chunk=chunk, burn_in=burn_in, track=True, height_scales=height_scales, chunk_init=chunk_init, clip_init=clip_init)
-        n = len(items)
-        prm = params or IKParams()
-        prm = IKParams(prm.damping, prm.tol, prm.limit_gain, prm.lm_damping, prm.max_iter, prm.offset_to_ground, eps)
-        out, iters, qf = self.ik_solve(pos, quat, slot_col, items, params=prm, n_final=2 * n)
-        info = {"chunks": n, "passes": 0, "resolved_frames": 0}
-        if n == 0:
-            return out, iters, info
-        walks = plan_walks(items, offs, chunk)
-        if len(walks):
-            done = torch.zeros(len(walks), dtype=torch.int32, device=self.device)
-            self.ik_solve(pos, quat, slot_col, walks, params=prm, qpos_init=qf, qpos_final=qf, out=out, iters=iters, frames_done=done)
-            info["resolved_frames"] = int(done.sum().item())
-            info["passes"] = 1
-        return out, iters, info
+        prm = _chunk_params(params, eps)
+        first = _chunk_batch(pos, quat, slot_col, offs, chunk, burn_in, height_scales, chunk_init, clip_init)
+        res = self.ik_solve(params=prm, **first)
+        walk, info = _walk_batch(first, res, offs, chunk)
+        if walk is not None:
+            self.ik_solve(params=prm, **walk)
+        return res[0], res[1], info()
 
     def ik_solve_chunked_sharded(self, pos: torch.Tensor, quat: torch.Tensor, slot_col: np.ndarray, seq_offsets, chunk: int, burn_in: int,
                                  params: Optional[IKParams] = None, eps: float = 1e-7, height_scales=None):
@@ -384,8 +423,7 @@ class Engine:
         (``distributed.solve_chunked_sharded``: BASELINE config 3, few long clips on several GPUs).  Every rank passes the
         same full inputs and receives the full result."""
         from .distributed import solve_chunked_sharded
-        prm = params or IKParams()
-        prm = IKParams(prm.damping, prm.tol, prm.limit_gain, prm.lm_damping, prm.max_iter, prm.offset_to_ground, eps)
+        prm = _chunk_params(params, eps)
 
         def solve(items, qinit, qfinal, out, iters, done):
             self.ik_solve(pos, quat, slot_col, items, params=prm, qpos_init=qinit, qpos_final=qfinal, out=out, iters=iters, frames_done=done)
@@ -568,42 +606,25 @@ class EngineGroup:
                 continue
             what = f"member {i}: "
             state = isinstance(b, dict)
+            kw = {}
             if state:
                 unknown = set(b) - {"pos", "quat", "slot_col", "items"} - set(self.STATE_KEYS)
                 if unknown:
                     raise EngineError(what + f"unknown batch keys {sorted(unknown)}")
                 pos, quat, slot_col, items = b["pos"], b["quat"], b["slot_col"], b["items"]
+                kw = {k: b[k] for k in self.STATE_KEYS if b.get(k) is not None}
+                kw["n_final"] = int(kw.get("n_final", 0))
             else:
                 pos, quat, slot_col, items = b
-            if pos.device != self.device or quat.device != self.device or pos.dtype != quat.dtype or pos.dtype not in (torch.float32, torch.float64) \
-                    or pos.dim() != 3 or quat.dim() != 3 or pos.shape[2] != 3 or quat.shape[2] != 4 or pos.shape[:2] != quat.shape[:2]:
-                raise EngineError(f"member {i}: bad key-point tensors")
-            pos, quat = pos.contiguous(), quat.contiguous()
+                items = np.ascontiguousarray(items, dtype=_native.WORK_ITEM_DTYPE)
+                if len(items) and (int(items["init_row"].max()) >= 0 or int(items["final_row"].max()) >= 0 or int(items["burn_row"].max()) >= 0):
+                    raise EngineError("group launches take plain per-clip items (no state rows) unless the batch supplies the state arrays")
+            pos, quat, slot_col, items, out, iters, qinit, qfin = _ik_batch(eng, pos, quat, slot_col, items, with_outputs=with_outputs,
+                                                                            what=what, **kw)
+            done = kw.get("frames_done")
+            if len(items) and qinit is None and int(items["init_row"].max()) >= 0:
+                raise EngineError(what + "init_row outside qpos_init")
             N, B = int(pos.shape[0]), int(pos.shape[1])
-            items = np.ascontiguousarray(items, dtype=_native.WORK_ITEM_DTYPE)
-            slot_col = np.ascontiguousarray(slot_col, dtype=np.int32)
-            if slot_col.shape != (eng.info.nslot,):
-                raise EngineError(f"member {i}: slot_col has the wrong length")
-            qinit = qfin = done = None
-            if state:
-                qinit, qfin = _state_arrays(eng.nq, self.device, items, b.get("qpos_init"), b.get("qpos_final"), int(b.get("n_final", 0) or 0),
-                                            b.get("frames_done"), what)
-                done = b.get("frames_done")
-                if len(items) and qinit is None and int(items["init_row"].max()) >= 0:
-                    raise EngineError(what + "init_row outside qpos_init")
-            elif len(items) and (int(items["init_row"].max()) >= 0 or int(items["final_row"].max()) >= 0 or int(items["burn_row"].max()) >= 0):
-                raise EngineError("group launches take plain per-clip items (no state rows) unless the batch supplies the state arrays")
-            out = iters = None
-            if with_outputs:
-                out, iters = (b.get("out"), b.get("iters")) if state else (None, None)
-                if out is None:
-                    out = torch.full((N, eng.nq), float("nan"), dtype=torch.float64, device=self.device)
-                elif out.shape != (N, eng.nq) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != self.device:
-                    raise EngineError(what + "out must be a contiguous float64 [N, nq] tensor on the engine's device")
-                if iters is None:
-                    iters = torch.zeros(N, dtype=torch.int32, device=self.device)
-                elif iters.shape != (N,) or iters.dtype != torch.int32 or not iters.is_contiguous() or iters.device != self.device:
-                    raise EngineError(what + "iters must be a contiguous int32 [N] tensor on the engine's device")
             outs.append((out, iters, qfin) if state else (out, iters))
             keep += [pos, quat, items, slot_col, qinit]
             if N == 0 or len(items) == 0:
@@ -639,20 +660,11 @@ class EngineGroup:
         base_i + k, base_i = the items of the members before it), or ``"auto"`` -- plan an order when ``Engine``'s probe policy
         says it pays for all members' items together (they share the wavefront slots).  The order only moves work in time."""
         prm = params or IKParams()
-        from .schedule import group_item_bases
         inputs, outs, all_items, keep = self._inputs(batches)
-        total = int(group_item_bases([inputs[i].n_items for i in range(len(batches))])[-1])
-        if isinstance(launch_order, str):
-            if launch_order != "auto":
-                raise EngineError("launch_order must be a tensor, None or 'auto'")
-            pf = self.engines[0]._probe_frames(np.concatenate(all_items)) if total else 0
-            launch_order = self.plan_order(batches, prm, probe_frames=pf) if pf else None
+        launch_order = _launch_order(self.engines[0], launch_order, all_items, lambda pf: self.plan_order(batches, prm, probe_frames=pf))
         if launch_order is None:
             self._check(self._lib.gmr_group_ik_solve(self._g, inputs, C.byref(prm), self._stream()), "gmr_group_ik_solve")
         else:
-            if not isinstance(launch_order, torch.Tensor) or launch_order.dtype != torch.int32 or launch_order.device != self.device \
-                    or not launch_order.is_contiguous() or launch_order.numel() != total:
-                raise EngineError(f"launch_order must be a contiguous int32 [{total}] tensor on the group's device (one entry per work item)")
             self._check(self._lib.gmr_group_ik_solve_ordered(self._g, inputs, C.byref(prm), _ptr(launch_order), self._stream()),
                         "gmr_group_ik_solve_ordered")
         return outs
@@ -703,7 +715,7 @@ class EngineGroup:
 
         ``chunk="auto"``: ``schedule.auto_chunk`` over the clips of ALL members (they share the wavefront slots); ``(0, 0)`` means
         whole clips, through :meth:`ik_solve` with ``launch_order="auto"``.  The choice is kept in ``last_chunk``."""
-        from .schedule import auto_chunk, group_chunk_offsets, make_items, plan_walks
+        from .schedule import auto_chunk, group_chunk_offsets, make_items
         if len(batches) != len(self.engines):
             raise EngineError("one batch (or None) per group member")
         if height_scales is not None and len(height_scales) != len(batches):
@@ -715,40 +727,19 @@ class EngineGroup:
                 raise EngineError("chunk must be an integer or 'auto'")
             chunk, burn_in = auto_chunk(group_chunk_offsets(offs), 8 * torch.cuda.get_device_properties(self.device).multi_processor_count)
         self.last_chunk = (int(chunk), int(burn_in))
-        prm = params or IKParams()
-        prm = IKParams(prm.damping, prm.tol, prm.limit_gain, prm.lm_damping, prm.max_iter, prm.offset_to_ground, eps)
+        prm = _chunk_params(params, eps)
         if chunk <= 0:
             items = [None if b is None else make_items(o, height_scales=h, clip_init=clip_init) for b, o, h in zip(batches, offs, hs)]
             res = self.ik_solve([None if b is None else (b[0], b[1], b[2], it) for b, it in zip(batches, items)], prm, launch_order="auto")
             return [(None, None, None) if b is None else (r[0], r[1], {"chunks": len(it), "passes": 0, "resolved_frames": 0})
                     for b, r, it in zip(batches, res, items)]
-        items = [None if b is None else make_items(o, chunk=chunk, burn_in=burn_in, track=True, height_scales=h, chunk_init=chunk_init,
-                                                   clip_init=clip_init) for b, o, h in zip(batches, offs, hs)]
-        first = self.ik_solve([None if b is None else {"pos": b[0], "quat": b[1], "slot_col": b[2], "items": it, "n_final": 2 * len(it)}
-                               for b, it in zip(batches, items)], prm)
-        second, done = [], []
-        for b, it, o, r in zip(batches, items, offs, first):
-            w = None if b is None or len(it) == 0 else plan_walks(it, o, chunk)
-            if w is None or len(w) == 0:
-                second.append(None)
-                done.append(None)
-                continue
-            d = torch.zeros(len(w), dtype=torch.int32, device=self.device)
-            done.append(d)
-            second.append({"pos": b[0], "quat": b[1], "slot_col": b[2], "items": w, "qpos_init": r[2], "qpos_final": r[2], "out": r[0],
-                           "iters": r[1], "frames_done": d})
-        if any(x is not None for x in second):
-            self.ik_solve(second, prm)
-        res = []
-        for b, it, r, d in zip(batches, items, first, done):
-            if b is None:
-                res.append((None, None, None))
-                continue
-            info = {"chunks": len(it), "passes": 0, "resolved_frames": 0}
-            if d is not None:
-                info["resolved_frames"], info["passes"] = int(d.sum().item()), 1
-            res.append((r[0], r[1], info))
-        return res
+        first = [None if b is None else _chunk_batch(b[0], b[1], b[2], o, chunk, burn_in, h, chunk_init, clip_init)
+                 for b, o, h in zip(batches, offs, hs)]
+        res = self.ik_solve(first, prm)
+        second = [(None, None) if f is None else _walk_batch(f, r, o, chunk) for f, r, o in zip(first, res, offs)]
+        if any(w is not None for w, _ in second):
+            self.ik_solve([w for w, _ in second], prm)
+        return [(None, None, None) if f is None else (r[0], r[1], info()) for f, r, (_, info) in zip(first, res, second)]
 
 
 class Session:
