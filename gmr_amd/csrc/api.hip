@@ -53,6 +53,8 @@ struct gmr_model {
   hipMemPool_t pool = nullptr;        // the library's scratch pool of this device (scratch_pool)
   int fk_pos_parts = 1;               // gmr_fk without rotations: fk_pos_kernel<parts> (GMR_AMD_FK_PARTS=0 falls back to fk_kernel<0>)
   bool force_generic = false;         // GMR_AMD_GENERIC_QP=1: use the dense generic QP even where the structured one applies
+  bool force_generic_shape = false;   // GMR_AMD_GENERIC_SHAPE=1: never a shaped kernel instance (tests, A/B runs)
+  int shape = -1;                     // index into GMR_FOR_EACH_IK_SHAPE of the shape this model matches, -1 = none (ik_shape_of)
 };
 
 // State of a single-sequence session (gmr_session_*): one frame per call, warm start carried on the device.
@@ -173,6 +175,40 @@ int scratch_alloc(gmr_model *m, CallScratch &sc, size_t bytes, hipStream_t st) {
 #define GMR_FOR_EACH_NVP(X) X(32) X(36) X(40) X(48) X(64)
 #endif
 
+// Shaped kernel instances (ik_kernel.hip.h, IkShapeAny): X(struct, NVP).  Each entry costs one more ik_kernel and ik_probe_kernel
+// instance at compile time; a model that matches none runs the generic instance.  The structs are defined beside IkShapeAny.
+#define GMR_FOR_EACH_IK_SHAPE(X) X(IkShapeG1Smplx, 36)
+
+// Does the host copy of a model carry exactly the values the shape SH fixes?  (SH::plain is the launch's side: launch_ik.)
+template <class SH>
+bool ik_shape_matches(const gmr::DevModel &d) {
+#define GMR_X(f, e) if (SH::f >= 0 && SH::f != (e)) return false;
+  GMR_IK_SHAPE_FIELDS(GMR_X)
+#undef GMR_X
+  return true;
+}
+// The shape (index into GMR_FOR_EACH_IK_SHAPE) of a model built for kernel variant nvp with the structured QP, or -1.
+int ik_shape_of(const gmr::DevModel &d, int nvp, bool sq) {
+  int idx = 0;
+#define GMR_X(S, v) if (sq && nvp == v && ik_shape_matches<gmr::S>(d)) return idx; ++idx;
+  GMR_FOR_EACH_IK_SHAPE(GMR_X)
+#undef GMR_X
+  return -1;
+}
+const char *ik_shape_name(int shape) {
+  int idx = 0;
+#define GMR_X(S, v) if (shape == idx++) return #S;
+  GMR_FOR_EACH_IK_SHAPE(GMR_X)
+#undef GMR_X
+  return "generic";
+}
+
+// The instance a launch takes: the model's shape where the launch is what `plain` stands for in a shape (float32 key-points, no
+// offset_to_ground, every item plain), else -1 = the generic instance.
+int ik_launch_shape(int model_shape, bool force_generic_shape, bool plain, bool in_f64, bool offset_to_ground) {
+  return model_shape >= 0 && !force_generic_shape && plain && !in_f64 && !offset_to_ground ? model_shape : -1;
+}
+
 int pick_nvp(int n_act) {
 #define GMR_X(v) if (n_act <= v) return v;
   GMR_FOR_EACH_NVP(GMR_X)
@@ -180,9 +216,28 @@ int pick_nvp(int n_act) {
   return -1;
 }
 
+// plain: every item of the launch is a plain one (no verification walk, no speculative chunk start; ik_run).  A shaped instance runs
+// only where the model matched its shape (m->shape) AND the launch is what the shape's `plain` stands for; it does not re-check.
 template <int NVP>
-void launch_ik(const gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool probe) {
+void launch_ik(const gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool probe, bool plain) {
   const bool sq = m->dm.sq_ok && !m->force_generic;
+  const int shape = sq ? ik_launch_shape(m->shape, m->force_generic_shape, plain, L.in_f64 != 0, L.prm.offset_to_ground != 0) : -1;
+  if (getenv("GMR_DEBUG_PLAN")) fprintf(stderr, "gmr: ik launch: %s instance %s\n", probe ? "probe" : "solve", ik_shape_name(shape));
+  if (shape >= 0) {
+    int idx = 0;
+#define GMR_X(S, v)                                                                                                                      \
+  if constexpr (NVP == v) {                                                                                                              \
+    if (shape == idx) {                                                                                                                  \
+      if (probe) hipLaunchKernelGGL((gmr::ik_probe_kernel<NVP, gmr::S>), dim3(L.n_items), dim3(64), m->lds_bytes, st, m->dm_dev, L, m->lay); \
+      else hipLaunchKernelGGL((gmr::ik_kernel<NVP, gmr::S>), dim3(L.n_items), dim3(64), m->lds_bytes, st, m->dm_dev, L, m->lay);           \
+      return;                                                                                                                            \
+    }                                                                                                                                    \
+  }                                                                                                                                      \
+  ++idx;
+    GMR_FOR_EACH_IK_SHAPE(GMR_X)
+#undef GMR_X
+    (void)idx;
+  }
   if (probe) {
     if (sq) hipLaunchKernelGGL((gmr::ik_probe_kernel<NVP, true>), dim3(L.n_items), dim3(64), m->lds_bytes, st, m->dm_dev, L, m->lay);
 #ifndef GMR_IK_DEV_ONLY36
@@ -198,9 +253,9 @@ void launch_ik(const gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool 
 #endif
 }
 
-int launch_ik_variant(gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool probe = false) {
+int launch_ik_variant(gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool probe = false, bool plain = false) {
   switch (m->nvp) {
-#define GMR_X(v) case v: launch_ik<v>(m, L, st, probe); break;
+#define GMR_X(v) case v: launch_ik<v>(m, L, st, probe, plain); break;
     GMR_FOR_EACH_NVP(GMR_X)
 #undef GMR_X
     default: set_err(m, "internal: no kernel variant for nvp=%d", m->nvp); return GMR_EUNSUPPORTED;
@@ -240,7 +295,8 @@ void launch_ik_session(const gmr_model *m, const gmr::IkGroupEntry *entries, gmr
 #endif
 }
 
-int build_device_model(gmr_model *m) {
+// host_only: stop in front of the first device call (the model's scalars and its shape are then known: gmr_debug_ik_shape)
+int build_device_model(gmr_model *m, bool host_only = false) {
   const gmr_blob_header &h = m->h;
   const auto &B = m->blob;
   const int nb = h.nbody;
@@ -831,6 +887,9 @@ int build_device_model(gmr_model *m) {
     m->lds_bytes_eval = oe * (int)sizeof(double);
   }
 
+  m->shape = ik_shape_of(dm, m->nvp, dm.sq_ok && !m->force_generic);
+  if (host_only) return GMR_OK;
+
   Packer P;
   const size_t o_dm = P.add(std::vector<gmr::DevModel>(1));
   const size_t o_dm_eval = P.add(dm_eval_v);
@@ -898,6 +957,9 @@ int build_device_model(gmr_model *m) {
 #endif
   GMR_FOR_EACH_NVP(GMR_X)
 #undef GMR_X
+#define GMR_X(S, v) GMR_LDS_OPT_IN((gmr::ik_kernel<v, gmr::S>)) GMR_LDS_OPT_IN((gmr::ik_probe_kernel<v, gmr::S>))
+  GMR_FOR_EACH_IK_SHAPE(GMR_X)
+#undef GMR_X
   GMR_LDS_OPT_IN(gmr::eval_kernel)
   GMR_LDS_OPT_IN(gmr::fk_pos_kernel<1>) GMR_LDS_OPT_IN(gmr::fk_pos_kernel<2>)
   GMR_LDS_OPT_IN(gmr::fk_kernel<0>) GMR_LDS_OPT_IN(gmr::fk_kernel<1>)
@@ -951,6 +1013,7 @@ static gmr_model *model_create_impl(const void *blob, size_t blob_bytes, int dev
   m->pool = scratch_pool(device);  // (nullptr: no pool support on this runtime -- per-call scratch then comes from the device's default pool as it is)
   if (const char *e = getenv("GMR_AMD_GENERIC_QP")) m->force_generic = e[0] == '1';
   if (force_generic) m->force_generic = true;
+  if (const char *e = getenv("GMR_AMD_GENERIC_SHAPE")) m->force_generic_shape = e[0] == '1';
   m->min_nvp = min_nvp;
   if (const char *e = getenv("GMR_AMD_FK_PARTS")) m->fk_pos_parts = e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1;
   if (build_device_model(m) != GMR_OK) return fail(m, "model build failed");
@@ -979,6 +1042,35 @@ int gmr_model_info_get(const gmr_model *m, gmr_model_info *out) {
   out->n_active_dof = m->n_act; out->nv_padded = m->nvp; out->lds_bytes = m->lds_bytes; out->device = m->device;
   out->reserved[0] = m->dm.sq_ok && !m->force_generic ? 16 - m->dm.sq_nlimb : 0;  // core size of the structured QP, 0 = generic QP
   return GMR_OK;
+}
+
+// Debug / test hook, host only (no device is touched, so it works on a machine without one; not part of gmr_amd.h): builds the model
+// of a blob as gmr_model_create does up to its first device call and reports which kernel instance a launch of it would take.
+// alter_field >= 0: first add alter_delta to that shape field (in GMR_IK_SHAPE_FIELDS order) of the host model.  launch flags as
+// launch_ik sees them.  fields_out: NULL or room for 16 ints, receives the (altered) shape fields.  name_out receives the instance's
+// name ("generic" or the shape's).  Returns the shape's index, -1 for the generic instance, < -1 on a blob that does not build.
+int gmr_debug_ik_shape(const void *blob, size_t blob_bytes, int force_generic, int alter_field, int alter_delta, int in_f64,
+                       int offset_to_ground, int plain, int *fields_out, char *name_out, size_t name_len) {
+  if (!blob || blob_bytes < sizeof(gmr_blob_header)) return -2;
+  gmr_model m;
+  memcpy(&m.h, blob, sizeof(m.h));
+  if (m.h.magic != GMR_BLOB_MAGIC || m.h.version != GMR_BLOB_VERSION || m.h.total_bytes != blob_bytes) return -2;
+  m.blob.assign(static_cast<const uint8_t *>(blob), static_cast<const uint8_t *>(blob) + blob_bytes);
+  m.force_generic = force_generic != 0;
+  if (build_device_model(&m, true) != GMR_OK) return -3;
+  gmr::DevModel &d = m.dm;
+  int k = 0;
+#define GMR_X(f, e) if (k++ == alter_field) (e) += alter_delta;
+  GMR_IK_SHAPE_FIELDS(GMR_X)
+#undef GMR_X
+  k = 0;
+#define GMR_X(f, e) if (fields_out) fields_out[k++] = (e);
+  GMR_IK_SHAPE_FIELDS(GMR_X)
+#undef GMR_X
+  const bool sq = d.sq_ok && !m.force_generic;
+  const int shape = ik_launch_shape(ik_shape_of(d, m.nvp, sq), false, plain != 0, in_f64 != 0, offset_to_ground != 0);
+  if (name_out && name_len) snprintf(name_out, name_len, "%s", ik_shape_name(shape));
+  return shape;
 }
 
 // Validate one model's batch (`in`: its arguments exactly as gmr_ik_solve takes them), put its scheduling data (length-sorted work
@@ -1144,7 +1236,9 @@ static int ik_run(const gmr_group *g, gmr_model *const *models, const gmr_group_
   }
   if (!g) {
     if (mode == IK_ORDERED) entries[0].L.perm = launch_order;
-    int rc = launch_ik_variant(models[0], entries[0].L, st, mode == IK_PROBE);
+    bool plain = true;  // (the items were validated in prepare_ik_launch)
+    for (const gmr_work_item &w : sorted[0]) plain = plain && w.check_stride == 0 && w.init_row != GMR_INIT_ROOT_TARGET;
+    int rc = launch_ik_variant(models[0], entries[0].L, st, mode == IK_PROBE, plain);
     if (rc != GMR_OK) { err = models[0]->err; return rc; }
   } else {  // the entries and the block -> entry table go into stream-ordered scratch
     const size_t ent_bytes = sizeof(gmr::IkGroupEntry) * (size_t)n, be_off = (ent_bytes + 15) & ~size_t(15);

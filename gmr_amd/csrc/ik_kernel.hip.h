@@ -164,6 +164,43 @@ __device__ __forceinline__ double kc(double c) {
   asm volatile("" : "+s"(c));
   return c;
 }
+// The shape of a (model, call): everything ik_body reads from DevModel / IkLaunch / the work item that is wave-uniform and never
+// changes for a given model and calling mode.  A shape is a struct of static constexpr ints, one per field below, -1 = "read it at
+// run time"; IkShapeAny (all -1) is the generic instance that serves every model, the group kernels and the session kernel.  A
+// shaped instance is only ever launched for a model and a launch the host has matched field by field (api.hip, ik_shape_of): the
+// kernel does not re-check.  X(field, the value in a host DevModel d).
+#define GMR_IK_SHAPE_FIELDS(X)                                                                                                   \
+  X(nlimb, d.sq_nlimb) X(ntask0, d.ntask[0]) X(ntask1, d.ntask[1]) X(use0, d.use_table[0]) X(use1, d.use_table[1])              \
+  X(same_tasks, d.same_tasks) X(ncpass0, d.ncpass[0]) X(ncpass1, d.ncpass[1]) X(npairp, d.npairp) X(nbody, d.nbody)              \
+  X(fkrounds, d.fkrounds) X(n_act, d.n_act) X(nslot, d.nslot) X(nq, d.nq) X(root_slot, d.root_slot)
+// plain (a property of the launch, not of the model): 1 = float32 key-points, no offset_to_ground, no item with a verification walk
+// (check_stride) or a speculative chunk start (GMR_INIT_ROOT_TARGET)
+struct IkShapeAny {
+#define GMR_X(f, e) static constexpr int f = -1;
+  GMR_IK_SHAPE_FIELDS(GMR_X)
+#undef GMR_X
+  static constexpr int plain = -1;
+};
+// unitree_g1 with the smplx config (and whatever else packs to the same counts) in the plain batched call
+struct IkShapeG1Smplx {
+  static constexpr int nlimb = 7, ntask0 = 14, ntask1 = 14, use0 = 1, use1 = 1, same_tasks = 1, ncpass0 = 3, ncpass1 = 3, npairp = 384,
+                       nbody = 32, fkrounds = 4, n_act = 35, nslot = 14, nq = 36, root_slot = 0;
+  // plain stays a run-time matter although the host only sends plain launches here: with the float64 / offset_to_ground / walk paths
+  // compiled out the compiler contracts the target preparation differently and qpos moves by 1e-13 (profiles/r04_shape_fields.md)
+  static constexpr int plain = -1;
+};
+// The shape's value where it fixes one, else the run-time value (whose load is then dead code).
+template <int V>
+__device__ __forceinline__ int shp(int v) {
+  if constexpr (V >= 0) return V;
+  else return v;
+}
+// The same for a per-table value v = table[tab]: fixed only if the shape fixes it for both tables.
+template <int V0, int V1>
+__device__ __forceinline__ int shp2(int tab, int v) {
+  if constexpr (V0 >= 0 && V1 >= 0) return tab ? V1 : V0;
+  else return v;
+}
 // A compile-time lane mask (the same 32-bit pattern in both halves of the wave) materialised from a literal where it is used,
 // not hoisted into scalar registers that then spill to VGPR lanes.
 template <unsigned HALF>
@@ -946,11 +983,12 @@ __device__ __forceinline__ void static_for_down(F &&f) {  // I = N-1 .. I
   }
 }
 
+template <int NL = -1>  // NL >= 0: the number of limb rows per group as a compile-time value (a shaped instance); nl is then unused
 __device__ __forceinline__ int box_qp_struct(int lane, int nl, bool owner, bool pad, const double *Hs, double ci, double lo,
                                              double hi, int &status, double &x_out) {
   const int a = lane & 15;           // local row
   const int gb = lane & 48;          // first lane of my group
-  const bool core_row = a >= nl;
+  const bool core_row = a >= shp<NL>(nl);
   const bool shadow = !owner && !pad;  // copy of a core dof in groups 1..3: mirrors the owner in group 0 (lane a)
   double x = 0.0;
   if (owner) {
@@ -996,7 +1034,7 @@ __device__ __forceinline__ int box_qp_struct(int lane, int nl, bool owner, bool 
     auto elim = [&](auto &&self, auto K) -> void {
       constexpr int k = K;
       if constexpr (k >= 6 && k <= 10) {
-        if (k == launder_uniform(nl)) {  // first core pivot: every copy of the core block / rhs <- sum over the four groups.  Only core rows
+        if (NL >= 0 ? k == NL : k == launder_uniform(nl)) {  // first core pivot: every copy of the core block / rhs <- sum over the four groups.  Only core rows
                                          // (a >= nl) are enabled here, in every group alike; limb columns are already zero in them
           {  // R[k..15] and bb (columns left of the first core pivot are limb columns, zero in the core rows), four or two at a time
             double none = 0.0;
@@ -1114,7 +1152,7 @@ struct IkLive {
   unsigned max_polls, max_frames;
 };
 
-template <int NVP, bool SQ, bool LIVE = false, bool PROBE = false>
+template <int NVP, bool SQ, bool LIVE = false, bool PROBE = false, class SH = IkShapeAny>
 __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLayout lay, const int item, const IkLive live = IkLive{}) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
@@ -1127,10 +1165,10 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   if (lane < kBT) lds[lay.zero + lane] = 0.0;
   {
     uint2 *hp = reinterpret_cast<uint2 *>(lds + lay.hplan);
-    if (!(SQ && m.npairp <= 64 * kHPlanRegsSQ))  // (a plan that fits the registers has no LDS copy)
-      for (int i = lane; i < m.npairp; i += 64) hp[i] = ld_plain(&m.hplan[i]);
+    if (!(SQ && shp<SH::npairp>(m.npairp) <= 64 * kHPlanRegsSQ))  // (a plan that fits the registers has no LDS copy)
+      for (int i = lane; i < shp<SH::npairp>(m.npairp); i += 64) hp[i] = ld_plain(&m.hplan[i]);
     uint4 *cp = reinterpret_cast<uint4 *>(lds + lay.cplan);
-    const int n0 = 4 * m.ncpass[0], n1 = 4 * m.ncpass[1];
+    const int n0 = 4 * shp<SH::ncpass0>(m.ncpass[0]), n1 = 4 * shp<SH::ncpass1>(m.ncpass[1]);
     for (int i = lane; i < n0; i += 64) cp[i] = ld_plain(&m.comp_plan[i]);
     for (int i = lane; i < n1; i += 64) cp[n0 + i] = ld_plain(&m.comp_plan[4 * kMaxCompPass + i]);
   }
@@ -1138,7 +1176,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   constexpr int kHPlanRegs = SQ ? kHPlanRegsSQ : 0, kCompRegs = SQ ? kCompRegsSQ : 0;
   uint2 hreg[kHPlanRegs > 0 ? kHPlanRegs : 1];  // this lane's entries of the first rounds of the H pair plan
 #pragma unroll
-  for (int r = 0; r < kHPlanRegs; ++r) hreg[r] = 64 * r < m.npairp ? ld_plain(&m.hplan[64 * r + lane]) : uint2{0, 0};
+  for (int r = 0; r < kHPlanRegs; ++r) hreg[r] = 64 * r < shp<SH::npairp>(m.npairp) ? ld_plain(&m.hplan[64 * r + lane]) : uint2{0, 0};
   FkJump fkj;  // (lane = body; bodies beyond the tree and finished chains fetch from themselves and do not fold)
   {
     const u64 an = lane < m.nbody ? m.fkanc[lane] : ~0ull;
@@ -1150,7 +1188,10 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
     }
   }
   GMR_STAMP_DECL();
-  const int nq = m.nq, n_act = m.n_act, nslot = m.nslot, root_slot = m.root_slot, npairp = m.npairp, nbody = m.nbody, fkrounds = m.fkrounds;
+  const int nq = shp<SH::nq>(m.nq), n_act = shp<SH::n_act>(m.n_act), nslot = shp<SH::nslot>(m.nslot), root_slot = shp<SH::root_slot>(m.root_slot);
+  const int npairp = shp<SH::npairp>(m.npairp), nbody = shp<SH::nbody>(m.nbody), fkrounds = shp<SH::fkrounds>(m.fkrounds);
+  constexpr bool kPlain = SH::plain > 0;  // the launch is known to be float32 in, no offset_to_ground, no walk and no chunk start
+  const int check_stride = kPlain ? 0 : w.check_stride;
   // active-dof constants of this lane (row of the QP); the rest is re-read where it is used
   const bool real_row = lane < n_act;
   const int arow = real_row ? lane : 0;
@@ -1203,7 +1244,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       if (leave) break;
       live_otg = (live_seq & 1u) != 0;  // bit 0 of the posted word: this frame's offset_to_ground (one PCIe read less than a second field)
     }
-    if (w.check_stride > 0 && left == 0) {
+    if (check_stride > 0 && left == 0) {
       double *B = ik_args(Lk)->qfinal + (size_t)(w.burn_row + kc) * nq;
       // The floating base's quaternion and its negative are one rotation.  The sequential run carries its sign along from qpos0; a
       // speculative chunk took the sign of the target it was started on (key-points from files come in either), so the states are
@@ -1213,7 +1254,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       const double sgn = wave_sum(dq) < 0.0 ? -1.0 : 1.0;
       double d = 0.0;
       for (int i = lane; i < nq; i += 64) d = fmax(d, fabs(q[i] - ((i >= 3 && i < 7) ? sgn * B[i] : B[i])));
-      const int len = min(w.check_stride, nfr - kf);
+      const int len = min(check_stride, nfr - kf);
       if (wave_max(d) < ik_args(Lk)->prm.check_tol) {  // wave-uniform
         const double *Fk = ik_args(Lk)->qfinal + (size_t)(w.final_row + kc) * nq;
         __syncthreads();
@@ -1233,7 +1274,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       left = len;
     }
     const int64_t f = LIVE ? (int64_t)0 : w.frame_begin + kf;  // a live frame always sits in row 0 of the pinned buffers
-    if (w.check_stride == 0 && kf == w.n_burn && w.burn_row >= 0) {  // state the first output frame starts from
+    if (check_stride == 0 && kf == w.n_burn && w.burn_row >= 0) {  // state the first output frame starts from
       double *qfin = ik_args(Lk)->qfinal;
       if (qfin)
         for (int i = lane; i < nq; i += 64) qfin[(size_t)w.burn_row * nq + i] = q[i];
@@ -1244,7 +1285,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       double hp[3] = {0, 0, 0}, hq[4] = {1, 0, 0, 0}, rp[3];
       IkLaunchK *La = ik_args(Lk);
       const int64_t base = f * La->n_cols;
-      if (La->in_f64) {
+      if (!kPlain && La->in_f64) {
         const double *P = (const double *)La->hpos, *Q = (const double *)La->hquat;
 #pragma unroll
         for (int i = 0; i < 3; i++) rp[i] = P[(base + root_col) * 3 + i];
@@ -1283,7 +1324,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
         for (int i = 0; i < 3; i++) p[i] += g[i];
         if (m.sfoot[lane]) pz = p[2];
       }
-      if (LIVE ? live_otg : La->prm.offset_to_ground != 0) {
+      if (LIVE ? live_otg : !kPlain && La->prm.offset_to_ground != 0) {
         const double lowest = wave_min(pz);
         p[2] = p[2] - lowest + 0.1;
       }
@@ -1295,7 +1336,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       }
     }
     __syncthreads();
-    if (kf == 0 && w.init_row == GMR_INIT_ROOT_TARGET && m.root_tslot >= 0) {  // wave-uniform: speculative chunk start (gmr_blob.h)
+    if (!kPlain && kf == 0 && w.init_row == GMR_INIT_ROOT_TARGET && m.root_tslot >= 0) {  // wave-uniform: speculative chunk start (gmr_blob.h)
       const int rts = m.root_tslot;
       if (m.root_planar) {  // a planar base takes the target's place and heading only
         const double tw = tq[4 * rts], tx = tq[4 * rts + 1], ty = tq[4 * rts + 2], tz = tq[4 * rts + 3];
@@ -1324,8 +1365,8 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
     // residual stage 1 ended with -- same poses, same targets -- and only the weighted sum is formed anew.
     double e[6] = {0, 0, 0, 0, 0, 0}, jl_kap = 0.0, jl_bet = 0.0, t_rs[3] = {0, 0, 0}, t_xb[3] = {0, 0, 0}, sum_r2 = 0.0;
     for (int tab = 0; tab < 2; ++tab) {
-      if (!m.use_table[tab]) continue;
-      const int nt = m.ntask[tab];
+      if (!shp2<SH::use0, SH::use1>(tab, m.use_table[tab])) continue;
+      const int nt = shp2<SH::ntask0, SH::ntask1>(tab, m.ntask[tab]);
       // task lanes: up to 16 tasks get a quad each (lanes 4t .. 4t+2 share the task block, task_block_quad); more than 16 one lane
       const bool quad = nt <= 16;
       const int tl = quad ? lane >> 2 : lane, ts = quad ? lane & 3 : 0;
@@ -1336,9 +1377,9 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       const int a_comp = m.acomp[tab * 64 + arow];
       // composite plan of this table: entry of quarter-wave lane >> 4 per pass = four source block offsets + destination
       // (LDS bytes); this lane moves the 16 bytes at el16 of each block.  The first kCompRegs passes are resolved to addresses here.
-      const int np = m.ncpass[tab];
+      const int np = shp2<SH::ncpass0, SH::ncpass1>(tab, m.ncpass[tab]);
       const unsigned el16 = 16u * (lane & 15);
-      const uint4 *cplan_tab = reinterpret_cast<const uint4 *>(lds + lay.cplan) + (tab ? 4 * m.ncpass[0] : 0) + (lane >> 4);
+      const uint4 *cplan_tab = reinterpret_cast<const uint4 *>(lds + lay.cplan) + (tab ? 4 * shp<SH::ncpass0>(m.ncpass[0]) : 0) + (lane >> 4);
       unsigned cadr[kCompRegs > 0 ? kCompRegs : 1][5];
 #pragma unroll
       for (int p = 0; p < kCompRegs; ++p) {
@@ -1364,7 +1405,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
         else { sum_r2 = wave_sum(r2); sum_mu = wave_sum(mu); }
       };
       double sum_mu;
-      if (tab == 1 && m.same_tasks) {  // wave-uniform: e, sum_r2 carried over from stage 1; |W e|^2 with this table's weights
+      if (tab == 1 && shp<SH::same_tasks>(m.same_tasks)) {  // wave-uniform: e, sum_r2 carried over from stage 1; |W e|^2 with this table's weights
         double mu = 0.0, unused;
         if (is_task) mu = t_wp * t_wp * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) + t_wr * t_wr * (e[3] * e[3] + e[4] * e[4] + e[5] * e[5]);
         if (quad) quad_sum2(ts == 2 ? mu : 0.0, unused, sum_mu);
@@ -1527,7 +1568,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
           const double s_lo = fmax(-lgain * (qv - sq_rlo), -1e30), s_hi = fmin(lgain * (sq_rhi - qv), 1e30);
           double xs;
           GMR_DUP_QP_TWICE();
-          qit = box_qp_struct(lane, m.sq_nlimb, sq_own, sq_pad, Hm, s_ci, s_lo, s_hi, sq_status, xs);
+          qit = box_qp_struct<SH::nlimb>(lane, m.sq_nlimb, sq_own, sq_pad, Hm, s_ci, s_lo, s_hi, sq_status, xs);
           const double x_back = __shfl(xs, sq_owner_lane);
           dq = real_row ? x_back : 0.0;
         } else {
@@ -1579,7 +1620,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
         if (lane == 0) itp[f] = solves | (qpflag << 30) | (nonfinite << 31);
       }
       ++out_done;
-      if (w.check_stride > 0 && --left == 0) {  // a chunk solved here: its final state
+      if (check_stride > 0 && --left == 0) {  // a chunk solved here: its final state
         double *Fk = ik_args(Lk)->qfinal + (size_t)(w.final_row + kc) * nq;
         for (int i = lane; i < nq; i += 64) Fk[i] = q[i];
         ++kc;
@@ -1601,7 +1642,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       if (cost && lane == 0) cost[Le->order ? Le->order[item] : item] = cost_acc;
     }
     double *qfin = Le->qfinal;
-    if (w.check_stride == 0 && w.final_row >= 0 && qfin)
+    if (check_stride == 0 && w.final_row >= 0 && qfin)
       for (int i = lane; i < nq; i += 64) qfin[(size_t)w.final_row * nq + i] = q[i];
   }
   GMR_STAMP_FLUSH();
@@ -1618,12 +1659,29 @@ __global__ void __launch_bounds__(64, SQ ? GMR_IK_WAVES_PER_SIMD : 1) ik_kernel(
   ik_body<NVP, SQ>(*(DevModelG *)mp, Lk, lay, item);
 }
 
+// The same launch for a model and a call whose shape SH the host has matched (api.hip): an overload on the kind of the second
+// template argument, so that the generic kernels above keep their symbols.  Structured QP only.
+template <int NVP, class SH>
+__global__ void __launch_bounds__(64, GMR_IK_WAVES_PER_SIMD) ik_kernel(const DevModel *__restrict__ mp, IkLaunch L, LdsLayout lay) {
+  IkLaunchK *Lk = (IkLaunchK *)((const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + 8);
+  const int *perm = Lk->perm;
+  const int item = perm ? __builtin_amdgcn_readfirstlane(perm[blockIdx.x]) : (int)blockIdx.x;
+  if ((unsigned)item >= (unsigned)Lk->n_items) return;
+  ik_body<NVP, true, false, false, SH>(*(DevModelG *)mp, Lk, lay, item);
+}
+
 // The probe in front of an ordered launch (gmr_ik_plan_order): the first frames of every item, solved for their cost only --
 // nothing is written but cost[item], the number of solves they took.
 template <int NVP, bool SQ>
 __global__ void __launch_bounds__(64, SQ ? GMR_IK_WAVES_PER_SIMD : 1) ik_probe_kernel(const DevModel *__restrict__ mp, IkLaunch L, LdsLayout lay) {
   IkLaunchK *Lk = (IkLaunchK *)((const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + 8);
   ik_body<NVP, SQ, false, true>(*(DevModelG *)mp, Lk, lay, (int)blockIdx.x);
+}
+
+template <int NVP, class SH>
+__global__ void __launch_bounds__(64, GMR_IK_WAVES_PER_SIMD) ik_probe_kernel(const DevModel *__restrict__ mp, IkLaunch L, LdsLayout lay) {
+  IkLaunchK *Lk = (IkLaunchK *)((const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + 8);
+  ik_body<NVP, true, false, true, SH>(*(DevModelG *)mp, Lk, lay, (int)blockIdx.x);
 }
 
 // Launch order from the probe: items by predicted cost (probe solves per frame x frames), most expensive first.  One workgroup;

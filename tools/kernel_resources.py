@@ -16,8 +16,9 @@ OUT = "/tmp/gmr_kernel_resources.s"
 def demangle_short(name):
     try:
         return subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt", name], capture_output=True, text=True).stdout.strip().split("(")[0].replace("void ", "")
-    except OSError:
-        return name
+    except OSError:  # no demangler: keep the shaped and the generic instances apart and next to each other in the sorted table
+        m = re.match(r"_ZN3gmr\d+([a-z_]+)ILi(\d+)E(?:Lb([01])|NS_\d+(\w+?))EEE", name)
+        return f"gmr::{m.group(1)}<{m.group(2)}, {m.group(4) or ('true' if m.group(3) == '1' else 'false')}>" if m else name
 
 
 def main():

@@ -1,4 +1,4 @@
-"""SGPR spill traffic of ik_kernel<36, true> by phase (the VALU instructions v_writelane / v_readlane that move spilled scalars).
+"""SGPR spill traffic of ik_kernel<36, true> (the generic instance) and of every shaped instance ik_kernel<36, IkShape...> by phase (the VALU instructions v_writelane / v_readlane that move spilled scalars).
 
     python tools/spill_report.py [extra hipcc flags]
 
@@ -23,7 +23,15 @@ def main():
            "--cuda-device-only", "-o", OUT, f"{ROOT}/gmr_amd/csrc/api.hip"] + sys.argv[1:]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     lines = open(OUT).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN3gmr9ik_kernelILi36ELb1") and ":" in l)
+    # the generic instance, then the shaped ones (second template argument a type: ...ILi36ENS_<len>IkShape...)
+    starts = [i for i, l in enumerate(lines) if re.match(r"_ZN3gmr9ik_kernelILi36E(Lb1|NS_\d+IkShape)\w*:", l)]
+    for start in sorted(starts, key=lambda i: "IkShape" in lines[i]):
+        m = re.search(r"\d+(IkShape[A-Za-z0-9]*?)EEEv", lines[start])
+        print(f"==== ik_kernel<36, {m.group(1) if m else 'true'}>")
+        report(lines, start)
+
+
+def report(lines, start):
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
     body, region, cur = [], [], "pre"
     # a mark closes the phase it names: instructions are attributed to the NEXT mark in layout order
@@ -66,6 +74,7 @@ def main():
             rd[region[i]] += 1
             if 1 <= region[i] <= 9:
                 rel[(m.group(2), int(m.group(3)))] += 1
+    print(f"static instructions: {len(body)}")
     print("spill VGPRs:", sorted(spillv))
     tot_r = tot_w = 0
     for r in sorted(set(region)):
