@@ -28,7 +28,8 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_ik_solve", "gmr_fk", "gmr_fk_shape", "gmr_dof_to_rot", "gmr_rot_to_dof", "gmr_local_rot_to_global", "gmr_fk_min_height", "gmr_bvh_fk", "gmr_bvh_parse_header", "gmr_bvh_parse_motion", "gmr_evaluate", "gmr_smplx_keypoints", "gmr_smplx_keypoints_cols", "gmr_smplx_keypoints_in", "gmr_smplx_body", "gmr_bvh_fk_rows", "gmr_bvh_parse_motion_device",
            "gmr_session_create", "gmr_session_destroy", "gmr_session_reset", "gmr_session_step", "gmr_session_state", "gmr_session_set_persistent", "gmr_ik_plan_order", "gmr_ik_solve_ordered",
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
-           "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue"]
+           "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
+           "gmr_clip_report", "gmr_group_clip_report"]
 
 
 class IKParams(C.Structure):
@@ -73,6 +74,34 @@ class MotionInput(C.Structure):
         ("ground_offset", C.c_double), ("root_pos_out", C.c_void_p), ("root_rot_out", C.c_void_p), ("dof_pos_out", C.c_void_p),
         ("local_body_pos_out", C.c_void_p), ("min_z_out", C.c_void_p),
     ]
+
+
+CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
+CLIP_REPORT_LIMIT_EPS = 1e-3    # GMR_CLIP_REPORT_LIMIT_EPS
+
+
+class ClipReportInput(C.Structure):
+    """``gmr_clip_report_input`` (include/gmr_amd.h): one model's arguments of the clip report."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("human_pos", C.c_void_p), ("human_quat", C.c_void_p),
+        ("in_dtype", C.c_int32), ("n_cols", C.c_int32), ("slot_col", C.c_void_p), ("seq_offsets", C.c_void_p),
+        ("n_seq", C.c_int32), ("reserved", C.c_int32), ("height_scale", C.c_void_p), ("iters", C.c_void_p),
+        ("err_max_out", C.c_void_p), ("err_sum_out", C.c_void_p),
+        ("task_pos_max_out", C.c_void_p), ("task_pos_sum_out", C.c_void_p), ("task_rot_max_out", C.c_void_p), ("task_rot_sum_out", C.c_void_p),
+        ("near_lo_out", C.c_void_p), ("near_hi_out", C.c_void_p),
+        ("dof_step_max_out", C.c_void_p), ("root_step_max_out", C.c_void_p), ("root_turn_max_out", C.c_void_p),
+        ("solves_max_out", C.c_void_p), ("solves_sum_out", C.c_void_p), ("nonfinite_frames_out", C.c_void_p),
+    ]
+
+
+class ClipReportParams(C.Structure):
+    """``gmr_clip_report_params`` (include/gmr_amd.h)."""
+
+    _fields_ = [("limit_eps", C.c_double), ("segment_frames", C.c_int32), ("offset_to_ground", C.c_int32)]
+
+    def __init__(self, limit_eps=CLIP_REPORT_LIMIT_EPS, segment_frames=0, offset_to_ground=0):
+        super().__init__(float(limit_eps), int(segment_frames), int(offset_to_ground))
 
 
 class SmplxBodyClip(C.Structure):
@@ -151,6 +180,10 @@ def load():
     L.gmr_motion_epilogue.argtypes = [vp, C.POINTER(MotionInput), vp]
     L.gmr_group_motion_epilogue.restype = C.c_int
     L.gmr_group_motion_epilogue.argtypes = [vp, C.POINTER(MotionInput), vp]
+    L.gmr_clip_report.restype = C.c_int
+    L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
+    L.gmr_group_clip_report.restype = C.c_int
+    L.gmr_group_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_bvh_parse_header.restype = C.c_int
     L.gmr_bvh_parse_header.argtypes = [vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     L.gmr_evaluate.restype = C.c_int

@@ -26,6 +26,7 @@
 #include "bvh_parse_kernel.hip.h"
 #include "kin_ops_kernel.hip.h"
 #include "motion_kernel.hip.h"
+#include "report_kernel.hip.h"
 #include "bvh_text.h"
 
 using gmr::u64;
@@ -46,6 +47,7 @@ struct gmr_model {
   int lds_bytes_eval = 0;
   gmr::FkTree fk{};
   gmr::KinTables kin{};                    // dof_to_rot / rot_to_dof / local -> global (kin_ops_kernel.hip.h)
+  const double *rep_lo = nullptr, *rep_hi = nullptr;  // device [nq - 7]: hinge limits in qpos order, -inf / +inf where unlimited (gmr_clip_report)
   gmr::LdsLayout lay{};
   int nvp = 0, n_act = 0, lds_bytes = 0, fk_lds_bytes = 0, fk_lds_bytes_min = 0;  // _min: the min-height mode has no output stage
   unsigned long long *dbg = nullptr;  // diagnostic builds (GMR_IK_STAMPS) only
@@ -918,6 +920,11 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   std::stable_sort(k_order.begin(), k_order.end(), [&](uint8_t a, uint8_t b) { return k_depth[a] < k_depth[b]; });
   const size_t o_kdb = P.add(k_dof_body), o_klo = P.add(k_lo), o_khi = P.add(k_hi), o_kdepth = P.add(k_depth),
                o_korder = P.add(k_order);
+  // clip report: float64 limits of every hinge in qpos order, infinite where the hinge is unlimited
+  std::vector<double> rep_lo(ndof_k, -INFINITY), rep_hi(ndof_k, INFINITY);
+  for (int b = 1; b < nb; ++b)
+    if (jtype[b] == GMR_JNT_HINGE && limited[b]) { rep_lo[qadr[b] - 7] = range[2 * b]; rep_hi[qadr[b] - 7] = range[2 * b + 1]; }
+  const size_t o_replo = P.add(rep_lo), o_rephi = P.add(rep_hi);
 
   HIP_TRY(m, hipMalloc(&m->dev, P.buf.size()));
   m->dev_bytes = P.buf.size();
@@ -932,6 +939,7 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   m->kin.dof_body = DP(int, o_kdb); m->kin.lim_lo = DP(float, o_klo); m->kin.lim_hi = DP(float, o_khi);
   m->kin.depth = DP(uint8_t, o_kdepth); m->kin.order = DP(uint8_t, o_korder);
   m->kin.max_depth = k_maxd;
+  m->rep_lo = DP(double, o_replo); m->rep_hi = DP(double, o_rephi);
   fk.dof_in_order = 1;
   for (int b = 0, prev = -1; b < nb; ++b)
     if (dofidx[b] >= 0) { if (dofidx[b] < prev) fk.dof_in_order = 0; prev = dofidx[b]; }
@@ -964,6 +972,7 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   GMR_LDS_OPT_IN(gmr::fk_pos_kernel<1>) GMR_LDS_OPT_IN(gmr::fk_pos_kernel<2>)
   GMR_LDS_OPT_IN(gmr::fk_kernel<0>) GMR_LDS_OPT_IN(gmr::fk_kernel<1>)
   GMR_LDS_OPT_IN(gmr::motion_epilogue_kernel)
+  GMR_LDS_OPT_IN(gmr::clip_report_kernel)
 #undef GMR_LDS_OPT_IN
   (void)hipGetLastError();
   return GMR_OK;
@@ -1824,6 +1833,145 @@ int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void
   if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
   const int rc = motion_run(g->models.data(), inputs, (int)g->models.size(), g->device, static_cast<hipStream_t>(stream), true, g->err);
   return rc;
+}
+
+// ------------------------------------------------------------------ clip report (report_kernel.hip.h)
+// Validate every member with clips, upload the entries, clip offsets and segment prefixes in one block of stream-ordered scratch
+// (which also holds the segments' partial rows), run pass 1 over all members' segments in one grid and pass 2 over all members'
+// clips in a second.  `models[i]` goes with `inputs[i]`; a group call names the member in its messages.  Errors land in `err`.
+static int report_run(gmr_model *const *models, const gmr_clip_report_input *inputs, int n, const gmr_clip_report_params *prm, int device,
+                      hipStream_t st, bool group, std::string &err) {
+  gmr_clip_report_params p{};
+  if (prm) p = *prm; else p.limit_eps = GMR_CLIP_REPORT_LIMIT_EPS;
+  if (p.segment_frames < 0) { err = "negative segment_frames"; return GMR_EINVAL; }
+  if (!(p.limit_eps >= 0.0)) { err = "limit_eps must be >= 0"; return GMR_EINVAL; }
+  const int segment = p.segment_frames ? p.segment_frames : GMR_CLIP_REPORT_SEGMENT;
+  std::vector<gmr::ReportEntry> ent(n);
+  std::vector<std::vector<int>> clip_seg(n);
+  size_t n_offs = 0, n_cols_total = 0, row_words = 0;
+  int64_t segs = 0, clips = 0;
+  int lds = 0;
+  for (int i = 0; i < n; ++i) {
+    const gmr_clip_report_input &in = inputs[i];
+    const gmr_model *m = models[i];
+    const std::string who = group ? "member " + std::to_string(i) + ": " : "";
+    gmr::ReportEntry &e = ent[i];
+    e = gmr::ReportEntry{};
+    e.seg_base = segs; e.clip_base = clips;
+    if (in.n_frames < 0 || in.n_seq < 0) { err = who + "negative size"; return GMR_EINVAL; }
+    if (in.n_seq == 0) {
+      if (in.n_frames != 0) { err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL; }
+      continue;  // no work for this member
+    }
+    if (!in.seq_offsets || in.seq_offsets[0] != 0 || in.seq_offsets[in.n_seq] != in.n_frames) {
+      err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL;
+    }
+    for (int s = 0; s < in.n_seq; ++s)
+      if (in.seq_offsets[s + 1] < in.seq_offsets[s]) { err = who + "seq_offsets must not decrease"; return GMR_EINVAL; }
+    if (in.n_frames > 0 && !in.qpos) { err = who + "null qpos"; return GMR_EINVAL; }
+    const bool want_err = in.err_max_out || in.err_sum_out || in.task_pos_max_out || in.task_pos_sum_out || in.task_rot_max_out || in.task_rot_sum_out;
+    const bool have_kp = in.n_frames > 0 && (in.human_pos || in.human_quat);  // (no frames: nothing is read, every clip reports 0)
+    if (want_err && !have_kp && in.n_frames > 0) { err = who + "the error fields need the human key-points"; return GMR_EINVAL; }
+    if (have_kp) {
+      if (m->h.nslot == 0) { err = who + "model has no IK config"; return GMR_ENOCONFIG; }
+      if (!in.human_pos || !in.human_quat || !in.slot_col || in.n_cols <= 0 || (in.in_dtype != GMR_DTYPE_F32 && in.in_dtype != GMR_DTYPE_F64)) {
+        err = who + "the key-points need both arrays, their dtype and slot_col"; return GMR_EINVAL;
+      }
+      for (int s = 0; s < m->h.nslot; ++s)
+        if (in.slot_col[s] < 0 || in.slot_col[s] >= in.n_cols) {
+          err = who + "slot_col[" + std::to_string(s) + "]=" + std::to_string(in.slot_col[s]) + " outside [0," + std::to_string(in.n_cols) + ")";
+          return GMR_EINVAL;
+        }
+    }
+    std::vector<int> &cs = clip_seg[i];
+    cs.assign((size_t)in.n_seq + 1, 0);
+    int64_t acc = 0;
+    for (int s = 0; s < in.n_seq; ++s) {
+      acc += (in.seq_offsets[s + 1] - in.seq_offsets[s] + segment - 1) / segment;
+      if (acc > 0x7fffffff) { err = who + "too many segments for one launch"; return GMR_EINVAL; }
+      cs[s + 1] = (int)acc;
+    }
+    e.m = m->dm_eval_dev; e.lay = m->lay_eval;
+    e.qpos = in.qpos;
+    if (have_kp) {
+      e.hpos = in.human_pos; e.hquat = in.human_quat;
+      e.in_f64 = in.in_dtype == GMR_DTYPE_F64; e.n_cols = in.n_cols;
+      e.slot_col = reinterpret_cast<const int *>(n_cols_total);  // offsets into the scratch block for now
+      n_cols_total += (size_t)m->h.nslot;
+    }
+    e.hscale = in.height_scale; e.iters = in.iters;
+    e.offs = reinterpret_cast<const int64_t *>(n_offs);
+    e.clip_seg = reinterpret_cast<const int *>(n_offs);
+    n_offs += (size_t)in.n_seq + 1;
+    e.hlo = m->rep_lo; e.hhi = m->rep_hi;
+    e.nh = m->h.nq - 7; e.nt = m->h.ntask[0] + m->h.ntask[1];
+    e.rows = reinterpret_cast<unsigned long long *>(row_words);
+    row_words += (size_t)acc * gmr::report_row_words(e.nt, e.nh);
+    e.err_max = in.err_max_out; e.err_sum = in.err_sum_out;
+    e.task_pos_max = in.task_pos_max_out; e.task_pos_sum = in.task_pos_sum_out;
+    e.task_rot_max = in.task_rot_max_out; e.task_rot_sum = in.task_rot_sum_out;
+    e.dof_step_max = in.dof_step_max_out; e.root_step_max = in.root_step_max_out; e.root_turn_max = in.root_turn_max_out;
+    e.near_lo = in.near_lo_out; e.near_hi = in.near_hi_out; e.solves_max = in.solves_max_out; e.solves_sum = reinterpret_cast<long long *>(in.solves_sum_out);
+    e.nonfinite = in.nonfinite_frames_out;
+    e.limit_eps = p.limit_eps;
+    e.n_seq = in.n_seq; e.offset_to_ground = p.offset_to_ground ? 1 : 0; e.segment = segment;
+    lds = std::max(lds, m->lds_bytes_eval + ((m->h.nq + 1) & ~1) * (int)sizeof(double));
+    segs += acc; clips += in.n_seq;
+  }
+  if (clips == 0) return GMR_OK;
+  if (segs > 0x7fffffff || clips > 0x7fffffff) { err = "too many clips for one launch"; return GMR_EINVAL; }
+  if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
+  // scratch: [entries | int64 offsets | int segment prefixes | int slot columns] uploaded, then the rows
+  const size_t ent_bytes = sizeof(gmr::ReportEntry) * (size_t)n, off_at = (ent_bytes + 15) & ~size_t(15);
+  const size_t seg_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15);
+  const size_t col_at = (seg_at + sizeof(int) * n_offs + 15) & ~size_t(15);
+  const size_t row_at = (col_at + sizeof(int) * n_cols_total + 15) & ~size_t(15);
+  const size_t total = row_at + sizeof(unsigned long long) * std::max<size_t>(row_words, 1);
+  CallScratch sc;
+  gmr_model *m0 = models[0];
+  if (scratch_alloc(m0, sc, total, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
+  uint8_t *ws = static_cast<uint8_t *>(sc.p);
+  std::vector<uint8_t> host(row_at, 0);
+  for (int i = 0; i < n; ++i) {
+    gmr::ReportEntry &e = ent[i];
+    const gmr_clip_report_input &in = inputs[i];
+    if (in.n_seq <= 0) continue;
+    const size_t o = reinterpret_cast<size_t>(e.offs), r = reinterpret_cast<size_t>(e.rows);
+    memcpy(host.data() + off_at + sizeof(int64_t) * o, in.seq_offsets, sizeof(int64_t) * ((size_t)in.n_seq + 1));
+    memcpy(host.data() + seg_at + sizeof(int) * o, clip_seg[i].data(), sizeof(int) * ((size_t)in.n_seq + 1));
+    e.offs = reinterpret_cast<const int64_t *>(ws + off_at) + o;
+    e.clip_seg = reinterpret_cast<const int *>(ws + seg_at) + o;
+    e.rows = reinterpret_cast<unsigned long long *>(ws + row_at) + r;
+    if (e.hpos) {
+      const size_t c = reinterpret_cast<size_t>(e.slot_col);
+      memcpy(host.data() + col_at + sizeof(int) * c, in.slot_col, sizeof(int) * (size_t)models[i]->h.nslot);
+      e.slot_col = reinterpret_cast<const int *>(ws + col_at) + c;
+    }
+  }
+  memcpy(host.data(), ent.data(), ent_bytes);
+  if (hipMemcpyAsync(ws, host.data(), row_at, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
+  const auto *d_ent = reinterpret_cast<const gmr::ReportEntry *>(ws);
+  if (segs > 0) hipLaunchKernelGGL(gmr::clip_report_kernel, dim3((unsigned)segs), dim3(64), (unsigned)lds, st, d_ent, n);
+  hipLaunchKernelGGL(gmr::clip_report_merge_kernel, dim3((unsigned)clips), dim3(gmr::kReportMergeThreads), 0, st, d_ent, n);
+  if (hipGetLastError() != hipSuccess) { err = "kernel launch failed"; return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_clip_report(gmr_model *m, const gmr_clip_report_input *in, const gmr_clip_report_params *prm, void *stream) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  std::string err;
+  const int rc = report_run(&m, in, 1, prm, m->device, static_cast<hipStream_t>(stream), false, err);
+  if (rc != GMR_OK) m->err = err;
+  return rc;
+}
+
+int gmr_group_clip_report(gmr_group *g, const gmr_clip_report_input *inputs, const gmr_clip_report_params *prm, void *stream) {
+  if (!g) return GMR_EINVAL;
+  g->err.clear();
+  if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
+  return report_run(g->models.data(), inputs, (int)g->models.size(), prm, g->device, static_cast<hipStream_t>(stream), true, g->err);
 }
 
 /* Frames per wavefront of the adapter kernels: runs long enough that a wavefront's setup (plan, tables) is amortised and its

@@ -81,16 +81,107 @@ def motions_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_off
 
 def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30,
                    height_adjust: bool = True, root_origin_offset: bool = True, chunk: int = 0, burn_in: int = 0,
-                   human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0") -> List[Dict]:
+                   human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
-    from the reference that spares wound-up clips their slow start)."""
+    from the reference that spares wound-up clips their slow start).  With ``report`` a second value is returned: the
+    ``engine.ClipReport`` of the solved qpos (``GeneralMotionRetargeting.clip_report``, solve counts included), host arrays."""
     tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
     tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
-    qpos = gmr.retarget_batch(tpos.to(gmr.device), tquat.to(gmr.device), body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
-                              human_heights=human_heights, clip_start=clip_start)  # (raises on non-finite qpos / a capped QP)
-    return motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset)
+    tpos, tquat = tpos.to(gmr.device), tquat.to(gmr.device)
+    if not report:
+        qpos = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
+                                  human_heights=human_heights, clip_start=clip_start)  # (raises on non-finite qpos / a capped QP)
+        return motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset)
+    qpos, iters = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
+                                     human_heights=human_heights, clip_start=clip_start, return_iters=True)
+    rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
+    motions = motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset)
+    return motions, rep.numpy()
+
+
+# ------------------------------------------------------------------ the clip report on disk
+def _report_host(report):
+    """The report with host arrays: a ``ClipReport`` holding any device tensor is copied (``ClipReport.numpy``)."""
+    if hasattr(report, "numpy") and any(isinstance(v, torch.Tensor) for v in vars(report).values()):
+        return report.numpy()
+    return report
+
+
+def write_report_csv(path: str, names: Sequence[str], report, append: bool = False) -> None:
+    """One row per clip of an ``engine.ClipReport``: clip name, frames, the scalar fields (both stage errors' max and mean, root
+    step / turn, solves, non-finite frames), then per task ``<task>:pos_max`` / ``<task>:rot_max`` and per hinge
+    ``<hinge>:step_max`` / ``<hinge>:near_lo`` / ``<hinge>:near_hi``.  A field the report does not hold is left out.  ``append``:
+    add the rows to an existing file of the same columns, without a second header (a run's batches, one after the other)."""
+    import csv
+    r = _report_host(report)
+    if len(names) != len(r):
+        raise ValueError("one name per clip")
+    cols = [("clip", list(names)), ("frames", r.frames.tolist())]
+    if r.err_max is not None:
+        mean = r.err_mean
+        for k in (0, 1):
+            cols += [(f"err{k + 1}_max", r.err_max[:, k].tolist()), (f"err{k + 1}_mean", mean[:, k].tolist())]
+    for key in ("root_step_max", "root_turn_max", "solves_max", "solves_sum", "nonfinite_frames"):
+        v = getattr(r, key)
+        if v is not None:
+            cols.append((key, v.tolist()))
+    for field, tag in (("task_pos_max", "pos_max"), ("task_rot_max", "rot_max")):
+        v = getattr(r, field)
+        if v is not None:
+            cols += [(f"{n}:{tag}", v[:, i].tolist()) for i, n in enumerate(r.task_names)]
+    for field, tag in (("dof_step_max", "step_max"), ("near_lo", "near_lo"), ("near_hi", "near_hi")):
+        v = getattr(r, field)
+        if v is not None:
+            cols += [(f"{n}:{tag}", v[:, i].tolist()) for i, n in enumerate(r.hinge_names)]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "a" if append else "w", newline="") as f:
+        w = csv.writer(f)
+        if not append:
+            w.writerow([c for c, _ in cols])
+        for i in range(len(r)):
+            w.writerow([repr(v[i]) if isinstance(v[i], float) else v[i] for _, v in cols])
+
+
+def report_difficulty(report) -> np.ndarray:
+    """[S]: ``err_max`` of the last table the config uses -- the difficulty ``write_hard_list`` records."""
+    r = _report_host(report)
+    if r.err_max is None:
+        raise ValueError("the report holds no stage errors (it was made without key-points)")
+    return np.asarray(r.err_max)[:, r.last_table]
+
+
+def report_hard_mask(report, max_pos_err: Optional[float] = None, max_dof_step: Optional[float] = None) -> np.ndarray:
+    """[S] bool: clips whose largest task position error exceeds ``max_pos_err`` (m) or whose largest joint step between
+    consecutive frames exceeds ``max_dof_step`` (rad); ``None`` switches a test off."""
+    r = _report_host(report)
+    mask = np.zeros(len(r), dtype=bool)
+    if max_pos_err is not None:
+        if r.task_pos_max is None:
+            raise ValueError("the report holds no task errors (it was made without key-points)")
+        mask |= np.asarray(r.task_pos_max).max(axis=1, initial=0.0) > max_pos_err
+    if max_dof_step is not None:
+        mask |= np.asarray(r.dof_step_max).max(axis=1, initial=0.0) > max_dof_step
+    return mask
+
+
+def write_hard_list(path: str, names: Sequence[str], report, mask, append: bool = False) -> int:
+    """The clips of ``mask`` in the reference's hard-motion list format (assets/hard_motions/*.txt, read back by the dataset
+    scripts' ``--hard_motions``): ``Motion: <name>.pkl, Difficulty: <%.2f>`` per line, difficulty = ``report_difficulty``.
+    Returns the number of lines written."""
+    mask = np.asarray(mask, dtype=bool)
+    if len(names) != len(mask):
+        raise ValueError("one name per clip")
+    diff = report_difficulty(report)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    n = 0
+    with open(path, "a" if append else "w") as f:
+        for name, hard, d in zip(names, mask, diff):
+            if hard:
+                f.write(f"Motion: {name}.pkl, Difficulty: {d:.2f}\n")
+                n += 1
+    return n
 
 
 # ------------------------------------------------------------------ writing motion files (row f-3)

@@ -168,6 +168,135 @@ def _motion_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, height_adjust:
     return mi, res, (qpos, offs)
 
 
+CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
+CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
+
+_REPORT_FIELDS = ("err_max", "err_sum", "task_pos_max", "task_pos_sum", "task_rot_max", "task_rot_sum", "near_lo", "near_hi",
+                  "dof_step_max", "root_step_max", "root_turn_max", "solves_max", "solves_sum", "nonfinite_frames")
+_REPORT_SUMS = ("err_sum", "task_pos_sum", "task_rot_sum", "solves_sum")
+
+
+class ClipReport:
+    """Per-clip quality statistics of a retargeted batch (``gmr_clip_report``, include/gmr_amd.h): one row per clip.
+
+    ``err_max`` / ``err_sum`` [S, 2] (stage errors, ``error1()`` / ``error2()``), ``task_pos_max`` / ``task_pos_sum`` [S, nt] (m),
+    ``task_rot_max`` / ``task_rot_sum`` [S, nt] (rad), ``near_lo`` / ``near_hi`` [S, nh] int32, ``dof_step_max`` [S, nh] (rad),
+    ``root_step_max`` (m) / ``root_turn_max`` (rad) [S], ``solves_max`` int32 / ``solves_sum`` int64 [S] (``None`` without
+    ``iters``), ``nonfinite_frames`` [S] int32.  A field that was not computed (no key-points, no ``iters``) is ``None``.
+    ``frames`` [S] holds the clip lengths; ``err_mean``, ``task_pos_mean``, ``task_rot_mean`` and ``solves_mean`` are sum / length,
+    NaN for a clip without frames.  ``task_names`` (``"<table>:<robot body>"``) and ``hinge_names`` label the columns."""
+
+    def __init__(self, frames, task_names, hinge_names, tables_used, **fields):
+        self.frames = np.asarray(frames, dtype=np.int64)
+        self.task_names, self.hinge_names, self.tables_used = list(task_names), list(hinge_names), tuple(tables_used)
+        for k in _REPORT_FIELDS:
+            setattr(self, k, fields.get(k))
+
+    def __len__(self):
+        return int(self.frames.shape[0])
+
+    def _mean(self, total):
+        if total is None:
+            return None
+        n = torch.as_tensor(self.frames, dtype=torch.float64, device=total.device) if isinstance(total, torch.Tensor) \
+            else self.frames.astype(np.float64)
+        n = n.reshape((-1,) + (1,) * (total.dim() - 1 if isinstance(total, torch.Tensor) else total.ndim - 1))
+        if isinstance(total, torch.Tensor):
+            return torch.where(n > 0, total.to(torch.float64) / n.clamp(min=1), torch.full_like(n, float("nan")))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, total.astype(np.float64) / np.maximum(n, 1), np.nan)
+
+    err_mean = property(lambda self: self._mean(self.err_sum))
+    task_pos_mean = property(lambda self: self._mean(self.task_pos_sum))
+    task_rot_mean = property(lambda self: self._mean(self.task_rot_sum))
+    solves_mean = property(lambda self: self._mean(self.solves_sum))
+
+    @property
+    def last_table(self) -> int:
+        """Index (0 / 1) of the last table the config uses: its ``err_max`` is a clip's difficulty."""
+        return 1 if self.tables_used[1] else 0
+
+    def numpy(self) -> "ClipReport":
+        """The same report with host arrays (one synchronisation)."""
+        f = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in ((k, getattr(self, k)) for k in _REPORT_FIELDS)}
+        return ClipReport(self.frames, self.task_names, self.hinge_names, self.tables_used, **f)
+
+
+def _report_names(cm: CompiledModel):
+    """(task names in the row order of ``task_err_out``, hinge names in qpos order, tables in use) of a compiled model."""
+    robot = cm.robot
+    tasks = [f"{k + 1}:{t.frame}" for k, tab in enumerate(cm.tasks or [[], []]) for t in tab]
+    order = sorted((int(robot.qpos_adr[b]), b) for b in range(robot.nbody) if int(robot.jnt_type[b]) == 1)
+    jn = getattr(robot, "jnt_names", None)
+    hinges = [str(jn[b]) if jn is not None and jn[b] else str(robot.body_names[b]) for _, b in order]
+    cfg = cm.config
+    used = (bool(cfg and cfg.use_ik_match_table1 and cm.tasks[0]), bool(cfg and cfg.use_ik_match_table2 and cm.tasks[1]))
+    return tasks, hinges, used
+
+
+def _report_input(eng: "Engine", qpos, pos, quat, slot_col, seq_offsets, height_scale, iters, what: str = ""):
+    """Check one model's clip-report arguments, allocate its outputs and fill its ``ClipReportInput``.  Returns (input, report, keep-alive)."""
+    if not isinstance(qpos, torch.Tensor) or qpos.device != eng.device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or qpos.shape[1] != eng.nq:
+        raise EngineError(what + f"qpos must be a float64 [N, {eng.nq}] tensor on the engine's device")
+    qpos = qpos.contiguous()
+    N = int(qpos.shape[0])
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != N:
+        raise ValueError(what + "seq_offsets must span [0, N]")
+    if (np.diff(offs) < 0).any():
+        raise ValueError(what + "seq_offsets must not decrease")
+    S = len(offs) - 1
+    ri = _native.ClipReportInput()
+    ri.qpos, ri.n_frames, ri.seq_offsets, ri.n_seq = qpos.data_ptr(), N, offs.ctypes.data, S
+    keep = [qpos, offs]
+    have_kp = pos is not None or quat is not None
+    if have_kp:
+        if pos is None or quat is None or slot_col is None:
+            raise EngineError(what + "the error fields need pos, quat and slot_col")
+        if pos.device != eng.device or quat.device != eng.device or pos.dtype != quat.dtype or pos.dtype not in (torch.float32, torch.float64) \
+                or pos.dim() != 3 or quat.dim() != 3 or pos.shape[0] != N or pos.shape[:2] != quat.shape[:2] or pos.shape[2] != 3 or quat.shape[2] != 4:
+            raise EngineError(what + "bad key-point tensors")
+        pos, quat = pos.contiguous(), quat.contiguous()
+        slot_col = np.ascontiguousarray(slot_col, dtype=np.int32)
+        if slot_col.shape != (eng.info.nslot,):
+            raise EngineError(what + "slot_col has the wrong length")
+        ri.human_pos, ri.human_quat, ri.slot_col = pos.data_ptr(), quat.data_ptr(), slot_col.ctypes.data
+        ri.in_dtype = _native.GMR_DTYPE_F64 if pos.dtype == torch.float64 else _native.GMR_DTYPE_F32
+        ri.n_cols = int(pos.shape[1])
+        keep += [pos, quat, slot_col]
+    if height_scale is not None:
+        height_scale = torch.as_tensor(np.asarray(height_scale, dtype=np.float64) if not isinstance(height_scale, torch.Tensor) else height_scale,
+                                       dtype=torch.float64).to(eng.device).contiguous()
+        if tuple(height_scale.shape) != (S,):
+            raise EngineError(what + "height_scale must hold one factor per clip")
+        ri.height_scale = height_scale.data_ptr()
+        keep.append(height_scale)
+    if iters is not None:
+        if not isinstance(iters, torch.Tensor) or iters.device != eng.device or iters.dtype != torch.int32 or tuple(iters.shape) != (N,):
+            raise EngineError(what + "iters must be an int32 [N] tensor on the engine's device")
+        iters = iters.contiguous()
+        ri.iters = iters.data_ptr()
+        keep.append(iters)
+    nt, nh, dev = eng.info.ntask[0] + eng.info.ntask[1], eng.nq - 7, eng.device
+    f64, i32 = torch.float64, torch.int32
+    shapes = {"err_max": ((S, 2), f64), "err_sum": ((S, 2), f64), "task_pos_max": ((S, nt), f64), "task_pos_sum": ((S, nt), f64),
+              "task_rot_max": ((S, nt), f64), "task_rot_sum": ((S, nt), f64), "near_lo": ((S, nh), i32), "near_hi": ((S, nh), i32),
+              "dof_step_max": ((S, nh), f64), "root_step_max": ((S,), f64), "root_turn_max": ((S,), f64),
+              "solves_max": ((S,), i32), "solves_sum": ((S,), torch.int64), "nonfinite_frames": ((S,), i32)}
+    skip = set() if have_kp else {"err_max", "err_sum", "task_pos_max", "task_pos_sum", "task_rot_max", "task_rot_sum"}
+    if iters is None:
+        skip |= {"solves_max", "solves_sum"}
+    fields = {}
+    for k, (sh, dt) in shapes.items():
+        if k in skip:
+            continue
+        fields[k] = torch.zeros(sh, dtype=dt, device=dev)
+        setattr(ri, k + "_out", fields[k].data_ptr())
+    tasks, hinges, used = _report_names(eng.cm)
+    return ri, ClipReport(np.diff(offs), tasks, hinges, used, **fields), keep
+
+
 class Engine:
     def __init__(self, cm: CompiledModel, device: int = 0, _borrowed_handle=None):
         if not torch.cuda.is_available():
@@ -555,6 +684,19 @@ class Engine:
         self._check(self._lib.gmr_motion_epilogue(self._h, C.byref(mi), self._stream()), "gmr_motion_epilogue")
         return res
 
+    def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,
+                    slot_col: Optional[np.ndarray] = None, height_scale=None, iters: Optional[torch.Tensor] = None,
+                    offset_to_ground: bool = False, limit_eps: float = CLIP_REPORT_LIMIT_EPS, segment_frames: int = 0) -> ClipReport:
+        """Per-clip quality statistics of qpos ``[N, nq]`` float64 (engine layout, concatenated clips) in one fused pass
+        (``gmr_clip_report``): see :class:`ClipReport`.  ``pos`` / ``quat`` / ``slot_col`` as in :meth:`evaluate` (without them the
+        error fields are ``None``); ``height_scale [S]``: per-clip factor on the human scale table; ``iters [N]`` int32: the solve
+        counts of ``ik_solve``; ``segment_frames``: frames per wavefront, 0 = ``CLIP_REPORT_SEGMENT`` (maxima and counts do not
+        depend on it, sums to rounding).  Asynchronous on the current stream."""
+        ri, rep, keep = _report_input(self, qpos, pos, quat, slot_col, seq_offsets, height_scale, iters)
+        prm = _native.ClipReportParams(limit_eps, segment_frames, int(bool(offset_to_ground)))
+        self._check(self._lib.gmr_clip_report(self._h, C.byref(ri), C.byref(prm), self._stream()), "gmr_clip_report")
+        return rep
+
 
 class EngineGroup:
     """Several robots' batches in ONE launch (``gmr_group_*``; BASELINE config 4, "heterogeneous trees in one launch").
@@ -704,6 +846,30 @@ class EngineGroup:
             outs.append(res)
             keep.append(k)
         self._check(self._lib.gmr_group_motion_epilogue(self._g, inputs, self._stream()), "gmr_group_motion_epilogue")
+        return outs
+
+    def clip_report(self, batches, offset_to_ground: bool = False, limit_eps: float = CLIP_REPORT_LIMIT_EPS, segment_frames: int = 0):
+        """:meth:`Engine.clip_report` for every member, all members' segments in one grid (``gmr_group_clip_report``).
+        ``batches[i]``: ``None`` (no work) or a dict with ``qpos``, ``seq_offsets`` and optionally ``pos``, ``quat``, ``slot_col``,
+        ``height_scale``, ``iters``.  Returns one :class:`ClipReport` (or ``None``) per member, bit for bit the single calls'."""
+        if len(batches) != len(self.engines):
+            raise EngineError("one batch (or None) per group member")
+        inputs = (_native.ClipReportInput * len(batches))()
+        outs, keep = [], []
+        for i, (eng, b) in enumerate(zip(self.engines, batches)):
+            if b is None:
+                outs.append(None)
+                continue
+            unknown = set(b) - {"qpos", "seq_offsets", "pos", "quat", "slot_col", "height_scale", "iters"}
+            if unknown:
+                raise EngineError(f"member {i}: unknown batch keys {sorted(unknown)}")
+            ri, rep, k = _report_input(eng, b["qpos"], b.get("pos"), b.get("quat"), b.get("slot_col"), b["seq_offsets"],
+                                       b.get("height_scale"), b.get("iters"), f"member {i}: ")
+            inputs[i] = ri
+            outs.append(rep)
+            keep.append(k)
+        prm = _native.ClipReportParams(limit_eps, segment_frames, int(bool(offset_to_ground)))
+        self._check(self._lib.gmr_group_clip_report(self._g, inputs, C.byref(prm), self._stream()), "gmr_group_clip_report")
         return outs
 
     def ik_solve_chunked(self, batches, chunk, burn_in: int, params: Optional[IKParams] = None, eps: float = 1e-7, height_scales=None,

@@ -387,6 +387,34 @@ class GeneralMotionRetargeting:
             iters = iters.cpu().numpy() if iters is not None else None
         return (out, iters) if return_iters else out
 
+    def clip_report(self, qpos, pos, quat, body_names: Sequence[str], seq_offsets=None, human_heights: Optional[Sequence[float]] = None,
+                    iters=None, offset_to_ground: bool = False, limit_eps: Optional[float] = None, segment_frames: int = 0):
+        """Per-clip quality statistics of a retargeted batch, reduced on the GPU (``Engine.clip_report``): ``qpos`` ``[N, nq]`` as
+        ``retarget_batch`` returned it for the key-points ``pos`` / ``quat`` / ``body_names`` (the same column / slot mapping),
+        ``seq_offsets`` and ``human_heights`` as given there, ``iters`` its solve counts (``return_iters``) or ``None``.  numpy or
+        CUDA torch.  Returns an ``engine.ClipReport`` with device tensors (``.numpy()`` for host arrays): stage errors, per-task
+        position / rotation errors, frames near a joint limit, the largest joint and root steps between consecutive frames, solve
+        counts and non-finite frames, one row per clip."""
+        from .engine import CLIP_REPORT_LIMIT_EPS
+        cols = self._columns(list(body_names))
+        as_t = lambda x: torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+        tq = as_t(qpos).to(self.device)
+        if self.model.planar_base and tq.shape[1] == self.model.mj_nq:  # the XML's [x, y, yaw, hinges] -> the engine's layout
+            tq = torch.from_numpy(np.ascontiguousarray(self.model.from_mj_qpos(tq.cpu().numpy()))).to(self.device)
+        tq = tq.to(torch.float64).contiguous()
+        tpos, tquat = as_t(pos).to(self.device), as_t(quat).to(self.device)
+        N = int(tq.shape[0])
+        offs = np.asarray([0, N] if seq_offsets is None else seq_offsets, dtype=np.int64)
+        hs = None
+        if human_heights is not None:
+            hh = np.asarray(human_heights, dtype=np.float64)
+            if hh.shape != (len(offs) - 1,):
+                raise ValueError("human_heights must hold one height per clip")
+            hs = hh / self._cm.config.human_height_assumption / self._cm.ratio
+        it = None if iters is None else as_t(iters).to(self.device).to(torch.int32)
+        return self._engine.clip_report(tq, offs, tpos, tquat, cols, height_scale=hs, iters=it, offset_to_ground=offset_to_ground,
+                                        limit_eps=CLIP_REPORT_LIMIT_EPS if limit_eps is None else limit_eps, segment_frames=segment_frames)
+
     def fk_batch(self, root_pos, root_rot_xyzw, dof_pos, want_rot: bool = False):
         """Batched FK in the ``KinematicsModel.forward_kinematics`` convention (float32, xyzw; kinematics_model.py:213-246) on this
         object's robot: ``root_pos [T,3]``, ``root_rot_xyzw [T,4]``, ``dof_pos [T,ndof]`` -> ``body_pos [T,nbody,3]`` (and

@@ -98,6 +98,36 @@ class MultiRobotRetargeting:
             qpos[r], iters[r] = (q.cpu().numpy(), it.cpu().numpy()) if is_np else (q, it)
         return (qpos, iters) if return_iters else qpos
 
+    def clip_report(self, qpos: Dict[str, torch.Tensor], pos, quat, body_names: Sequence[str], seq_offsets=None,
+                    human_heights: Optional[Sequence[float]] = None, iters: Optional[Dict] = None, offset_to_ground: bool = False,
+                    limit_eps: Optional[float] = None, segment_frames: int = 0):
+        """``GeneralMotionRetargeting.clip_report`` for every robot, all robots' segments in one grid
+        (``EngineGroup.clip_report``): ``qpos[robot]`` / ``iters[robot]`` as :meth:`retarget_batch` returned them for these
+        key-points.  Returns ``{robot: engine.ClipReport}``, bit for bit the single-robot reports."""
+        from .engine import CLIP_REPORT_LIMIT_EPS
+        names = list(body_names)
+        as_t = lambda x: torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+        tpos, tquat = as_t(pos).to(self.device).contiguous(), as_t(quat).to(self.device).contiguous()
+        N = int(tpos.shape[0])
+        offs = np.asarray([0, N] if seq_offsets is None else seq_offsets, dtype=np.int64)
+        hh = None
+        if human_heights is not None:
+            hh = np.asarray(human_heights, dtype=np.float64)
+            if hh.shape != (len(offs) - 1,):
+                raise ValueError("human_heights must hold one height per clip")
+        batches = []
+        for r, model, cm in zip(self.robots, self.models, self._cms):
+            q = as_t(qpos[r]).to(self.device)
+            if model.planar_base and q.shape[1] == model.mj_nq:  # the XML's [x, y, yaw, hinges] -> the engine's layout
+                q = torch.from_numpy(np.ascontiguousarray(model.from_mj_qpos(q.cpu().numpy()))).to(self.device)
+            it = None if iters is None or iters.get(r) is None else as_t(iters[r]).to(self.device).to(torch.int32)
+            batches.append({"qpos": q.to(torch.float64).contiguous(), "seq_offsets": offs, "pos": tpos, "quat": tquat,
+                            "slot_col": cm.slot_columns(names), "iters": it,
+                            "height_scale": None if hh is None else hh / cm.config.human_height_assumption / cm.ratio})
+        reps = self.group.clip_report(batches, offset_to_ground=offset_to_ground, segment_frames=segment_frames,
+                                      limit_eps=CLIP_REPORT_LIMIT_EPS if limit_eps is None else limit_eps)
+        return dict(zip(self.robots, reps))
+
     def _refuse_planar(self):
         planar = [r for r, m in zip(self.robots, self.models) if m.planar_base]
         if planar:
@@ -145,17 +175,23 @@ class MultiRobotRetargeting:
 
     def retarget_clips(self, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30, height_adjust: bool = True,
                        root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
-                       clip_start: str = "qpos0") -> Dict[str, List[Dict]]:
+                       clip_start: str = "qpos0", report: bool = False):
         """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
         solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
-        ``dataset.MotionWriter.submit`` as they are."""
+        ``dataset.MotionWriter.submit`` as they are.  With ``report`` a second value is returned: ``{robot: engine.ClipReport}``
+        of the solved qpos (:meth:`clip_report`, solve counts included), host arrays."""
         self._refuse_planar()
         tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
         tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
-        outs, offs = self._solve(tpos.to(self.device), tquat.to(self.device), body_names, seq_offsets, chunk, burn_in, False, True,
-                                 human_heights, True, clip_start)
-        return self.motions_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, height_adjust=height_adjust,
-                                      root_origin_offset=root_origin_offset)
+        tpos, tquat = tpos.to(self.device), tquat.to(self.device)
+        outs, offs = self._solve(tpos, tquat, body_names, seq_offsets, chunk, burn_in, False, True, human_heights, True, clip_start)
+        reps = None
+        if report:
+            reps = self.clip_report({r: q for r, (q, _) in zip(self.robots, outs)}, tpos, tquat, body_names, offs, human_heights,
+                                    iters={r: it for r, (_, it) in zip(self.robots, outs)})
+        motions = self.motions_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, height_adjust=height_adjust,
+                                         root_origin_offset=root_origin_offset)
+        return (motions, {r: rep.numpy() for r, rep in reps.items()}) if report else motions
 
     def _solve(self, pos, quat, body_names, seq_offsets, chunk, burn_in, offset_to_ground, verify, human_heights, check, clip_start):
         """The solve of :meth:`retarget_batch`: per robot (qpos [N, nq] in the engine's layout, solves per frame) on the device, and

@@ -106,6 +106,24 @@ def group_chunk_offsets(seq_offsets_per_member) -> np.ndarray:
     return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
 
 
+def report_segments(seq_offsets: Sequence[int], segment: int) -> np.ndarray:
+    """The segment table of a clip report launch (``gmr_clip_report``): int64 ``[n_segments, 3]`` rows (clip, first frame, one past
+    the last frame), in launch order -- clip by clip, ascending inside a clip.  A segment is a run of at most ``segment``
+    consecutive frames of one clip; it never crosses a clip boundary and an empty clip has none.  Workgroup k of a member's
+    share of the grid handles row k."""
+    offs = np.asarray(seq_offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1 or np.any(np.diff(offs) < 0):
+        raise ValueError("seq_offsets must be a non-decreasing 1-D array")
+    if segment <= 0:
+        raise ValueError("segment must be positive")
+    a, b = offs[:-1], offs[1:]
+    nseg = (b - a + segment - 1) // segment                                    # segments per clip
+    clip = np.repeat(np.arange(a.size, dtype=np.int64), nseg)
+    k = np.arange(int(nseg.sum()), dtype=np.int64) - np.repeat(np.cumsum(nseg) - nseg, nseg)  # index of the segment inside its clip
+    start = a[clip] + k * segment
+    return np.stack([clip, start, np.minimum(start + segment, b[clip])], axis=1).astype(np.int64).reshape(-1, 3)
+
+
 def plan_walks(items: np.ndarray, seq_offsets: Sequence[int], chunk: int) -> np.ndarray:
     """Verification walks for the tracked chunk items of ``make_items(..., chunk, track=True)``: one item per clip that has
     more than one chunk, running from the clip's second chunk to its end with ``check_stride = chunk`` (gmr_blob.h): it starts

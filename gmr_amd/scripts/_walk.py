@@ -92,7 +92,50 @@ def add_common_flags(ap) -> None:
                     help="qpos0: the reference (every clip starts from the model's rest pose); root_target: start with the floating base on the first root target (not the reference's numbers for the first frames; spares clips that face away from qpos0 their slow start)")
     ap.add_argument("--robots", default=None, type=str,
                     help="comma-separated robots solved together from each batch (MultiRobotRetargeting); robot r's files go to <tgt_folder>/<r>/...")
+    ap.add_argument("--report_csv", default=None, type=str, help="write the per-clip quality report (stage and task errors, joint-limit and step statistics; one row per clip) to this CSV; with --robots one file per robot, <stem>.<robot><ext>; under --shard_by_rank one per rank, <stem>[.<robot>].rank<k><ext>")
+    ap.add_argument("--hard_out", default=None, type=str, help="write the clips that exceed --max_pos_err / --max_dof_step as a hard-motion list (the format --hard_motions reads); with --robots one file per robot, under --shard_by_rank one per rank (named like --report_csv)")
+    ap.add_argument("--max_pos_err", default=None, type=float, help="metres: a clip whose largest task position error exceeds this is not written and is listed in --hard_out")
+    ap.add_argument("--max_dof_step", default=None, type=float, help="radians: a clip whose largest joint step between consecutive frames exceeds this is not written and is listed in --hard_out")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
+
+
+def wants_report(args) -> bool:
+    """Whether any of the report flags is given: only then is the clip report computed at all."""
+    return any(getattr(args, k, None) is not None for k in ("report_csv", "hard_out", "max_pos_err", "max_dof_step"))
+
+
+def report_path(path: str, robot=None, rank=None) -> str:
+    """Where one writer's share of ``--report_csv`` / ``--hard_out`` goes: ``<stem>[.<robot>][.rank<k>]<ext>``.  Every robot of
+    ``--robots`` and, under ``--shard_by_rank``, every rank writes files of its own, so none overwrites another's."""
+    stem, ext = os.path.splitext(path)
+    return stem + (f".{robot}" if robot is not None else "") + (f".rank{rank}" if rank is not None else "") + ext
+
+
+class ReportSink:
+    """One robot's clip reports of a run, batch by batch: the CSV rows and the hard list are on disk as soon as their batch is
+    solved (a run that dies leaves what it had), the withheld clips are counted."""
+
+    def __init__(self, args, robot=None, rank=None):
+        self.args = args
+        self.csv = report_path(args.report_csv, robot, rank) if args.report_csv else None
+        self.hard = report_path(args.hard_out, robot, rank) if args.hard_out else None
+        self.withheld, self._started = 0, False
+
+    def take(self, dataset, targets: Sequence[str], motions: list, report):
+        """One batch: returns the (motions, targets) that are to be written."""
+        names = [os.path.splitext(os.path.basename(t))[0] for t in targets]
+        mask = dataset.report_hard_mask(report, self.args.max_pos_err, self.args.max_dof_step)
+        if self.csv:
+            dataset.write_report_csv(self.csv, names, report, append=self._started)
+        if self.hard:
+            dataset.write_hard_list(self.hard, names, report, mask, append=self._started)
+        self._started = True
+        self.withheld += int(mask.sum())
+        return [m for m, h in zip(motions, mask) if not h], [t for t, h in zip(targets, mask) if not h]
+
+    def close(self):
+        if self.withheld:
+            print(f"{self.withheld} clips withheld (--max_pos_err / --max_dof_step)" + (f", listed in {self.hard}" if self.hard else ""))
 
 
 def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callable, retarget_kw: Callable, workers: int, done: str) -> int:
@@ -102,8 +145,10 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     if args.device is None:
         args.device = int(os.environ.get("LOCAL_RANK", "0"))
+    args.report_rank = None
     if args.shard_by_rank and world > 1:
         pairs = pairs[rank::world]
+        args.report_rank = rank  # every rank writes report files of its own (report_path)
         print(f"rank {rank} of {world}: {len(pairs)} of them")
     if pairs and getattr(args, "robot_list", None):
         return _convert_robots(args, pairs, src_human, batches, retarget_kw, workers, done)
@@ -111,6 +156,7 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         from .. import GeneralMotionRetargeting as GMR, dataset
         g = GMR(src_human=src_human, tgt_robot=args.robot, device=args.device)
         target_of, failed = dict(pairs), 0
+        sink = ReportSink(args, rank=args.report_rank) if wants_report(args) else None
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -118,9 +164,17 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
                     failed += 1
                 if not len(batch):
                     continue
-                motions = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                                 clip_start=args.clip_start, **retarget_kw(batch))
-                writer.submit(motions, [target_of[f] for f in batch.files])
+                targets = [target_of[f] for f in batch.files]
+                if sink is None:
+                    motions = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                                     clip_start=args.clip_start, **retarget_kw(batch))
+                else:
+                    motions, rep = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                                          clip_start=args.clip_start, report=True, **retarget_kw(batch))
+                    motions, targets = sink.take(dataset, targets, motions, rep)
+                writer.submit(motions, targets)
+        if sink is not None:
+            sink.close()
         print(f"{writer.written} files written, {failed} could not be loaded")
     print(done, args.tgt_folder)
     return 0
@@ -132,6 +186,7 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
     from .. import MultiRobotRetargeting, dataset
     mr = MultiRobotRetargeting(src_human, args.robot_list, device=args.device)
     target_of, failed = dict(pairs), 0
+    sinks = {r: ReportSink(args, r, getattr(args, "report_rank", None)) for r in mr.robots} if wants_report(args) else None
     with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
         for batch in batches([s for s, _ in pairs], mr.ik_columns):
             for f, why in batch.skipped:
@@ -139,10 +194,21 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
                 failed += 1
             if not len(batch):
                 continue
-            motions = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                        clip_start=args.clip_start, **retarget_kw(batch))
+            reps = None
+            if sinks is None:
+                motions = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                            clip_start=args.clip_start, **retarget_kw(batch))
+            else:
+                motions, reps = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                                  clip_start=args.clip_start, report=True, **retarget_kw(batch))
             for i, r in enumerate(mr.robots):
-                writer.submit(motions[r], [target_of[f][i] for f in batch.files])
+                ms, ts = motions[r], [target_of[f][i] for f in batch.files]
+                if reps is not None:
+                    ms, ts = sinks[r].take(dataset, ts, ms, reps[r])
+                writer.submit(ms, ts)
+    if sinks is not None:
+        for sink in sinks.values():
+            sink.close()
     print(f"{writer.written} files written, {failed} could not be loaded")
     print(done, args.tgt_folder)
     return 0

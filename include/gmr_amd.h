@@ -207,6 +207,62 @@ typedef struct gmr_motion_input {
 int gmr_motion_epilogue(gmr_model *m, const gmr_motion_input *in, void *stream);
 int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void *stream);
 
+/* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
+ * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
+ * lists -- reduced on the device.  qpos and key-points are read once; the outputs are a few hundred bytes per clip.
+ * Clip s holds the frames [seq_offsets[s], seq_offsets[s+1]).  Outputs are device arrays with n_seq rows, any may be NULL:
+ *   err_max_out, err_sum_out [n_seq][2] f64        max / sum over the clip's frames of gmr_evaluate's err_out (0 for an unused table)
+ *   task_pos_max_out, task_pos_sum_out [n_seq][nt] world distance |x_target - x_body| in metres of every task, target after
+ *                                                  preparation; nt = ntask[0] + ntask[1], rows as in gmr_evaluate's task_err_out
+ *                                                  (rows of an unused table are 0)
+ *   task_rot_max_out, task_rot_sum_out [n_seq][nt] geodesic angle |w| in rad of the same task
+ *   near_lo_out, near_hi_out [n_seq][nh] i32       frames with theta_j - lo_j <= limit_eps / hi_j - theta_j <= limit_eps, nh = nq - 7
+ *                                                  hinges in qpos order; 0 for an unlimited hinge
+ *   dof_step_max_out [n_seq][nh] f64               max |theta_j(t+1) - theta_j(t)| over consecutive frames of the clip
+ *   root_step_max_out, root_turn_max_out [n_seq]   max root displacement (m) and max sign-blind geodesic angle (rad) between the
+ *                                                  root orientations of consecutive frames; a planar base: xy distance and the
+ *                                                  wrapped difference of the headings 2 atan2(qz, qw)
+ *   solves_max_out [n_seq] i32, solves_sum_out [n_seq] i64   max / sum over the clip's frames of the solve counts in the optional
+ *                                                  `iters` input (gmr_ik_solve's iters_out), bits 30 and 31 of every entry -- its
+ *                                                  flags -- masked off (& 0x3FFFFFFF); a non-finite frame (below) is left out;
+ *                                                  both outputs stay untouched when `iters` is NULL
+ *   nonfinite_frames_out [n_seq] i32               frames whose qpos or consumed key-points hold a non-finite value; such a frame
+ *                                                  enters no other statistic, and neither do the steps into and out of it
+ * A clip without frames reports 0 everywhere; steps never cross clips.  The work unit is a segment of at most segment_frames
+ * consecutive frames of one clip, one wavefront each; a second kernel folds a clip's segments in order, without floating-point
+ * atomics: a report is bit-reproducible for a given segment_frames, and its maxima and counts do not depend on it.
+ * The error fields need the key-points (GMR_EINVAL without them); seq_offsets follow gmr_motion_input's rules; a negative
+ * segment_frames is GMR_EINVAL.  params NULL = the defaults.  Asynchronous on `stream`; the handle's device is selected.
+ *   gmr_clip_report        one model
+ *   gmr_group_clip_report  inputs host [group size]: member i's arguments (n_seq = 0: no work), all members' segments in one grid */
+#define GMR_CLIP_REPORT_SEGMENT 32        /* frames per wavefront when segment_frames = 0 */
+#define GMR_CLIP_REPORT_LIMIT_EPS 1e-3    /* rad: limit_eps when params is NULL */
+typedef struct gmr_clip_report_input {
+  const double *qpos;          /* device [n_frames][nq] f64 */
+  int64_t n_frames;
+  const void *human_pos, *human_quat;  /* device [n_frames][n_cols][3] / [4] wxyz, or both NULL (no error fields) */
+  int32_t in_dtype, n_cols;    /* GMR_DTYPE_*, as in gmr_evaluate */
+  const int32_t *slot_col;     /* host [nslot] */
+  const int64_t *seq_offsets;  /* host [n_seq+1], 0 .. n_frames, non-decreasing (empty clips ok) */
+  int32_t n_seq, reserved;
+  const double *height_scale;  /* device [n_seq] f64 or NULL: per-clip factor on the human scale table */
+  const int32_t *iters;        /* device [n_frames] i32 or NULL: gmr_ik_solve's iters_out (solves per frame, flag bits 30 / 31) */
+  double *err_max_out, *err_sum_out;
+  double *task_pos_max_out, *task_pos_sum_out, *task_rot_max_out, *task_rot_sum_out;
+  int32_t *near_lo_out, *near_hi_out;
+  double *dof_step_max_out, *root_step_max_out, *root_turn_max_out;
+  int32_t *solves_max_out;
+  int64_t *solves_sum_out;
+  int32_t *nonfinite_frames_out;
+} gmr_clip_report_input;
+typedef struct gmr_clip_report_params {
+  double limit_eps;            /* rad, >= 0 */
+  int32_t segment_frames;      /* 0 = GMR_CLIP_REPORT_SEGMENT */
+  int32_t offset_to_ground;    /* as gmr_ik_params.offset_to_ground */
+} gmr_clip_report_params;
+int gmr_clip_report(gmr_model *m, const gmr_clip_report_input *in, const gmr_clip_report_params *prm, void *stream);
+int gmr_group_clip_report(gmr_group *g, const gmr_clip_report_input *inputs, const gmr_clip_report_params *prm, void *stream);
+
 /* Single-sequence sessions ("teleop"): one frame per call, warm start carried in the session -- the semantics of calling
  * GeneralMotionRetargeting.retarget once per captured frame (motion_retarget.py:139-185).  Inputs and outputs are HOST
  * pointers: the session owns pinned, device-visible staging that the kernel reads and writes directly (no copy engines on
