@@ -29,7 +29,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_session_create", "gmr_session_destroy", "gmr_session_reset", "gmr_session_step", "gmr_session_state", "gmr_session_set_persistent", "gmr_ik_plan_order", "gmr_ik_solve_ordered",
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
-           "gmr_clip_report", "gmr_group_clip_report"]
+           "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track"]
 
 
 class IKParams(C.Structure):
@@ -74,6 +74,19 @@ class MotionInput(C.Structure):
         ("ground_offset", C.c_double), ("root_pos_out", C.c_void_p), ("root_rot_out", C.c_void_p), ("dof_pos_out", C.c_void_p),
         ("local_body_pos_out", C.c_void_p), ("min_z_out", C.c_void_p),
     ]
+
+
+TRACK_OUTPUTS = ("root_pos", "root_rot", "joint_pos", "root_lin_vel", "root_ang_vel", "joint_vel",
+                 "body_pos_w", "body_quat_w", "body_lin_vel_w", "body_ang_vel_w")  # gmr_track_input's output pointers, in order
+
+
+class TrackInput(C.Structure):
+    """``gmr_track_input`` (include/gmr_amd.h): one model's arguments of the tracking export."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("out_offsets", C.c_void_p), ("ratio", C.c_void_p),
+        ("fps_out", C.c_double), ("n_seq", C.c_int32), ("reserved", C.c_int32),
+    ] + [(k + "_out", C.c_void_p) for k in TRACK_OUTPUTS]
 
 
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
@@ -180,6 +193,10 @@ def load():
     L.gmr_motion_epilogue.argtypes = [vp, C.POINTER(MotionInput), vp]
     L.gmr_group_motion_epilogue.restype = C.c_int
     L.gmr_group_motion_epilogue.argtypes = [vp, C.POINTER(MotionInput), vp]
+    L.gmr_motion_track.restype = C.c_int
+    L.gmr_motion_track.argtypes = [vp, C.POINTER(TrackInput), vp]
+    L.gmr_group_motion_track.restype = C.c_int
+    L.gmr_group_motion_track.argtypes = [vp, C.POINTER(TrackInput), vp]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -26,6 +27,7 @@
 #include "bvh_parse_kernel.hip.h"
 #include "kin_ops_kernel.hip.h"
 #include "motion_kernel.hip.h"
+#include "track_kernel.hip.h"
 #include "report_kernel.hip.h"
 #include "bvh_text.h"
 
@@ -972,6 +974,7 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   GMR_LDS_OPT_IN(gmr::fk_pos_kernel<1>) GMR_LDS_OPT_IN(gmr::fk_pos_kernel<2>)
   GMR_LDS_OPT_IN(gmr::fk_kernel<0>) GMR_LDS_OPT_IN(gmr::fk_kernel<1>)
   GMR_LDS_OPT_IN(gmr::motion_epilogue_kernel)
+  GMR_LDS_OPT_IN(gmr::motion_track_kernel)
   GMR_LDS_OPT_IN(gmr::clip_report_kernel)
 #undef GMR_LDS_OPT_IN
   (void)hipGetLastError();
@@ -1833,6 +1836,106 @@ int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void
   if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
   const int rc = motion_run(g->models.data(), inputs, (int)g->models.size(), g->device, static_cast<hipStream_t>(stream), true, g->err);
   return rc;
+}
+
+// ------------------------------------------------------------------ tracking export (track_kernel.hip.h)
+// Validate every member with work, upload the entries and the members' plans (clip offsets, output offsets, ratios) in one block
+// of stream-ordered scratch, and run all members' tiles in one grid.  `models[i]` goes with `inputs[i]`; a group call names the
+// member in its messages.  Errors land in `err`.
+static int track_run(gmr_model *const *models, const gmr_track_input *inputs, int n, int device, hipStream_t st, bool group, std::string &err) {
+  std::vector<gmr::TrackEntry> ent(n);
+  std::vector<char> work(n, 0);
+  size_t n_offs = 0, n_ratio = 0;
+  int64_t tiles = 0, lds = 0;
+  for (int i = 0; i < n; ++i) {
+    const gmr_track_input &in = inputs[i];
+    const gmr_model *m = models[i];
+    const std::string who = group ? "member " + std::to_string(i) + ": " : "";
+    gmr::TrackEntry &e = ent[i];
+    e = gmr::TrackEntry{};
+    e.tile_base = tiles;
+    if (in.n_frames < 0) { err = who + "negative n_frames"; return GMR_EINVAL; }
+    if (in.n_frames == 0) continue;  // no work for this member
+    if (m->dm.root_planar) { err = who + "the tracking export needs a free-joint root; a planar base is not supported"; return GMR_EUNSUPPORTED; }
+    if (!in.qpos || !in.seq_offsets || !in.out_offsets || !in.ratio) { err = who + "null argument"; return GMR_EINVAL; }
+    if (!(in.fps_out > 0.0) || !std::isfinite(in.fps_out)) { err = who + "fps_out must be positive"; return GMR_EINVAL; }
+    if (in.n_seq < 1 || in.seq_offsets[0] != 0 || in.seq_offsets[in.n_seq] != in.n_frames) {
+      err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL;
+    }
+    if (in.out_offsets[0] != 0) { err = who + "out_offsets must start at 0"; return GMR_EINVAL; }
+    for (int s = 0; s < in.n_seq; ++s) {
+      if (in.seq_offsets[s + 1] < in.seq_offsets[s]) { err = who + "seq_offsets must not decrease"; return GMR_EINVAL; }
+      if (in.out_offsets[s + 1] < in.out_offsets[s]) { err = who + "out_offsets must not decrease"; return GMR_EINVAL; }
+      if (in.out_offsets[s + 1] > in.out_offsets[s] && in.seq_offsets[s + 1] == in.seq_offsets[s]) {
+        err = who + "clip " + std::to_string(s) + " has output frames but no source frames"; return GMR_EINVAL;
+      }
+      if (!(in.ratio[s] > 0.0) || !std::isfinite(in.ratio[s])) { err = who + "ratio (fps_in / fps_out) must be positive"; return GMR_EINVAL; }
+    }
+    const int64_t n_out = in.out_offsets[in.n_seq];
+    if (n_out == 0) continue;
+    const int64_t need = gmr::track_lds_bytes(m->fk.nbody, m->fk.ndof, m->fk.nslots);
+    if (need > 160 * 1024) { err = who + "the tracking tile needs " + std::to_string(need) + " bytes of LDS"; return GMR_EUNSUPPORTED; }
+    lds = std::max(lds, need);
+    e.fk = m->fk;
+    e.qpos = in.qpos;
+    e.root_pos = in.root_pos_out; e.root_rot = in.root_rot_out; e.joint_pos = in.joint_pos_out;
+    e.root_lin_vel = in.root_lin_vel_out; e.root_ang_vel = in.root_ang_vel_out; e.joint_vel = in.joint_vel_out;
+    e.body_pos = in.body_pos_w_out; e.body_quat = in.body_quat_w_out;
+    e.body_lin_vel = in.body_lin_vel_w_out; e.body_ang_vel = in.body_ang_vel_w_out;
+    e.dt = 1.0 / in.fps_out;
+    e.n_out = n_out; e.n_seq = in.n_seq;
+    // the plan arrays: element offsets into the scratch block for now, device pointers once it exists
+    e.seq_offsets = reinterpret_cast<const int64_t *>(n_offs);
+    e.ratio = reinterpret_cast<const double *>(n_ratio);
+    n_offs += 2 * ((size_t)in.n_seq + 1);
+    n_ratio += (size_t)in.n_seq;
+    tiles += (n_out + gmr::kTrackTile - 1) / gmr::kTrackTile;
+    work[i] = 1;
+  }
+  if (tiles == 0) return GMR_OK;
+  if (tiles > 0x7fffffff) { err = "too many frames for one launch"; return GMR_EINVAL; }
+  if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
+  const size_t ent_bytes = sizeof(gmr::TrackEntry) * (size_t)n, off_at = (ent_bytes + 15) & ~size_t(15);
+  const size_t ratio_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15), total = ratio_at + sizeof(double) * n_ratio;
+  CallScratch sc;
+  gmr_model *m0 = models[0];
+  if (scratch_alloc(m0, sc, total, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
+  uint8_t *ws = static_cast<uint8_t *>(sc.p);
+  std::vector<uint8_t> host(total, 0);
+  for (int i = 0; i < n; ++i) {
+    if (!work[i]) continue;
+    gmr::TrackEntry &e = ent[i];
+    const size_t o = reinterpret_cast<size_t>(e.seq_offsets), r = reinterpret_cast<size_t>(e.ratio), ns = (size_t)inputs[i].n_seq;
+    memcpy(host.data() + off_at + sizeof(int64_t) * o, inputs[i].seq_offsets, sizeof(int64_t) * (ns + 1));
+    memcpy(host.data() + off_at + sizeof(int64_t) * (o + ns + 1), inputs[i].out_offsets, sizeof(int64_t) * (ns + 1));
+    memcpy(host.data() + ratio_at + sizeof(double) * r, inputs[i].ratio, sizeof(double) * ns);
+    e.seq_offsets = reinterpret_cast<const int64_t *>(ws + off_at) + o;
+    e.out_offsets = e.seq_offsets + ns + 1;
+    e.ratio = reinterpret_cast<const double *>(ws + ratio_at) + r;
+  }
+  memcpy(host.data(), ent.data(), ent_bytes);
+  if (hipMemcpyAsync(ws, host.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
+  hipLaunchKernelGGL(gmr::motion_track_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, st,
+                     reinterpret_cast<const gmr::TrackEntry *>(ws), n);
+  if (hipGetLastError() != hipSuccess) { err = "kernel launch failed"; return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_track(gmr_model *m, const gmr_track_input *in, void *stream) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  std::string err;
+  const int rc = track_run(&m, in, 1, m->device, static_cast<hipStream_t>(stream), false, err);
+  if (rc != GMR_OK) m->err = err;
+  return rc;
+}
+
+int gmr_group_motion_track(gmr_group *g, const gmr_track_input *inputs, void *stream) {
+  if (!g) return GMR_EINVAL;
+  g->err.clear();
+  if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
+  return track_run(g->models.data(), inputs, (int)g->models.size(), g->device, static_cast<hipStream_t>(stream), true, g->err);
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

@@ -81,24 +81,96 @@ def motions_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_off
 
 def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30,
                    height_adjust: bool = True, root_origin_offset: bool = True, chunk: int = 0, burn_in: int = 0,
-                   human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False):
+                   human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
+                   track_fps: Optional[float] = None):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
     from the reference that spares wound-up clips their slow start).  With ``report`` a second value is returned: the
-    ``engine.ClipReport`` of the solved qpos (``GeneralMotionRetargeting.clip_report``, solve counts included), host arrays."""
+    ``engine.ClipReport`` of the solved qpos (``GeneralMotionRetargeting.clip_report``, solve counts included), host arrays.
+    With ``track_fps`` a last value is added: the clips' tracking dicts at that rate (``tracking_from_qpos`` on the same qpos)."""
     tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
     tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
     tpos, tquat = tpos.to(gmr.device), tquat.to(gmr.device)
     if not report:
         qpos = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
                                   human_heights=human_heights, clip_start=clip_start)  # (raises on non-finite qpos / a capped QP)
-        return motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset)
-    qpos, iters = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
-                                     human_heights=human_heights, clip_start=clip_start, return_iters=True)
-    rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
-    motions = motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset)
-    return motions, rep.numpy()
+        res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset),)
+    else:
+        qpos, iters = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
+                                         human_heights=human_heights, clip_start=clip_start, return_iters=True)
+        rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
+        res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset), rep.numpy())
+    if track_fps is not None:
+        res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps),)
+    return res[0] if len(res) == 1 else res
+
+
+# ------------------------------------------------------------------ the tracking export
+TRACK_ARRAYS = ("joint_pos", "joint_vel", "root_pos", "root_rot", "root_lin_vel", "root_ang_vel",
+                "body_pos_w", "body_quat_w", "body_lin_vel_w", "body_ang_vel_w")
+
+
+def tracks_to_host(tracks, fps_out, body_names, joint_names) -> List[List[Dict]]:
+    """Several ``engine.MotionTrack`` results (one per robot) to the host with every copy in flight before the one
+    synchronisation; per result the list of per-clip dicts of ``tracking_from_qpos``."""
+    hosts = []
+    dev = None
+    for tr in tracks:
+        host = {k: torch.empty(tr[k].shape, dtype=tr[k].dtype, pin_memory=True) for k in TRACK_ARRAYS}
+        for k, h in host.items():
+            h.copy_(tr[k], non_blocking=True)
+            dev = tr[k].device
+        hosts.append({k: h.numpy() for k, h in host.items()})
+    if dev is not None:
+        torch.cuda.current_stream(dev).synchronize()
+    out = []
+    for tr, host, bn, jn in zip(tracks, hosts, body_names, joint_names):
+        offs, bn, jn = tr.out_offsets, list(bn), list(jn)
+        clips = []
+        for s in range(len(offs) - 1):
+            a, b = int(offs[s]), int(offs[s + 1])
+            d = {"fps": fps_out}
+            d.update((k, host[k][a:b]) for k in TRACK_ARRAYS)
+            d.update(body_names=bn, joint_names=jn, quat_order="xyzw")
+            clips.append(d)
+        out.append(clips)
+    return out
+
+
+def tracking_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, fps_out) -> List[Dict]:
+    """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) -> one tracking dict per clip
+    at ``fps_out`` (``Engine.motion_track``, one launch): ``fps``, ``joint_pos``, ``joint_vel``, ``root_pos``, ``root_rot`` (xyzw),
+    ``root_lin_vel``, ``root_ang_vel`` (world frame) in float64, ``body_pos_w``, ``body_quat_w`` (xyzw), ``body_lin_vel_w``,
+    ``body_ang_vel_w`` in float32, ``body_names``, ``joint_names`` (the hinges in qpos order) and ``quat_order = "xyzw"``.
+    The arrays are row slices of batch-sized page-locked host arrays, as ``motions_from_qpos`` hands them out."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("the tracking export assumes a free-joint root; use retarget_batch for a planar-base robot")
+    from .engine import _report_names
+    track = gmr._engine.motion_track(qpos, seq_offsets, fps, fps_out)
+    return tracks_to_host([track], fps_out, [gmr.model.body_names], [_report_names(gmr._cm)[1]])[0]
+
+
+def save_tracking(path: str, track: Dict, override: bool = False) -> bool:
+    """One tracking dict as an uncompressed ``.npz`` (``np.savez``); like ``save_motion``, an existing file is skipped unless
+    ``override``.  Names and ``quat_order`` are stored as unicode arrays, ``fps`` as a float64 scalar."""
+    if os.path.exists(path) and not override:
+        return False
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:  # (a file object: np.savez appends nothing to the name)
+        np.savez(f, fps=np.float64(track["fps"]), body_names=np.asarray(list(track["body_names"]), dtype=np.str_),
+                 joint_names=np.asarray(list(track["joint_names"]), dtype=np.str_), quat_order=np.asarray(track["quat_order"]),
+                 **{k: track[k] for k in TRACK_ARRAYS})
+    return True
+
+
+def load_tracking(path: str) -> Dict:
+    """Read a ``save_tracking`` file back: the same keys, arrays as written, names as lists, ``fps`` a float."""
+    with np.load(path, allow_pickle=False) as z:
+        d = {k: z[k] for k in TRACK_ARRAYS}
+        d.update(fps=float(z["fps"]), body_names=[str(n) for n in z["body_names"]], joint_names=[str(n) for n in z["joint_names"]],
+                 quat_order=str(z["quat_order"]))
+    return d
 
 
 # ------------------------------------------------------------------ the clip report on disk
@@ -245,7 +317,10 @@ def fast_pickle_ok() -> bool:
 
 def save_motion(path: str, motion: Dict, override: bool = False) -> bool:
     """Pickle one motion dict; like the scripts, skip files that already exist unless ``override`` (:219).  The file is
-    what ``pickle.dump(motion, f)`` writes, byte for byte (see ``_MotionPickler``)."""
+    what ``pickle.dump(motion, f)`` writes, byte for byte (see ``_MotionPickler``).  A ``.npz`` path takes a tracking dict
+    (``save_tracking``), so ``MotionWriter`` writes both kinds."""
+    if str(path).endswith(".npz"):  # a tracking dict (tracking_from_qpos)
+        return save_tracking(path, motion, override)
     if os.path.exists(path) and not override:
         return False
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

@@ -168,6 +168,59 @@ def _motion_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, height_adjust:
     return mi, res, (qpos, offs)
 
 
+TRACK_FIELDS = _native.TRACK_OUTPUTS   # the arrays of a tracking export, in gmr_track_input's order
+_TRACK_BODY_FIELDS = ("body_pos_w", "body_quat_w", "body_lin_vel_w", "body_ang_vel_w")
+
+
+class MotionTrack(dict):
+    """Result of ``motion_track``: the device tensors by name (``TRACK_FIELDS``; the four body arrays only with ``bodies``), plus
+    ``out_offsets`` (int64 numpy ``[S + 1]``: clip s owns the rows ``out_offsets[s]:out_offsets[s + 1]``) and ``fps`` as attributes."""
+
+    def __init__(self, tensors, out_offsets, fps):
+        super().__init__(tensors)
+        self.out_offsets = out_offsets
+        self.fps = fps
+
+
+def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out, out, bodies: bool, what: str = ""):
+    """Check one model's tracking arguments, plan the resampling and fill its ``TrackInput``.  Returns (input, MotionTrack,
+    keep-alive)."""
+    from .schedule import track_plan
+    if not isinstance(qpos, torch.Tensor) or qpos.device != eng.device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or qpos.shape[1] != eng.nq:
+        raise EngineError(what + f"qpos must be a float64 [N, {eng.nq}] tensor on the engine's device")
+    qpos = qpos.contiguous()
+    N = int(qpos.shape[0])
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != N:
+        raise ValueError(what + "seq_offsets must span [0, N]")
+    try:
+        out_offs, ratio = track_plan(offs, fps_in, fps_out)
+    except ValueError as e:
+        raise EngineError(what + f"gmr_motion_track: {_ERR[-1]}: {e}") from None
+    M = int(out_offs[-1])
+    nd, nb = eng.nq - 7, eng.nbody
+    shapes = {"root_pos": (M, 3), "root_rot": (M, 4), "joint_pos": (M, nd), "root_lin_vel": (M, 3), "root_ang_vel": (M, 3),
+              "joint_vel": (M, nd), "body_pos_w": (M, nb, 3), "body_quat_w": (M, nb, 4), "body_lin_vel_w": (M, nb, 3),
+              "body_ang_vel_w": (M, nb, 3)}
+    fields = [k for k in TRACK_FIELDS if bodies or k not in _TRACK_BODY_FIELDS]
+    dtype = lambda k: torch.float32 if k in _TRACK_BODY_FIELDS else torch.float64
+    if out is None:
+        res = {k: torch.empty(shapes[k], dtype=dtype(k), device=eng.device) for k in fields}
+    else:
+        res = {k: out[k] for k in fields if k in out}
+        if set(out) - set(fields) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k] or t.dtype != dtype(k)
+                                         or t.device != eng.device or not t.is_contiguous() for k, t in res.items()):
+            raise EngineError(what + "out must map names of TRACK_FIELDS to contiguous tensors of the plan's shapes on the engine's device")
+    ti = _native.TrackInput()
+    ti.qpos, ti.n_frames = qpos.data_ptr(), N
+    ti.seq_offsets, ti.out_offsets, ti.ratio, ti.n_seq = offs.ctypes.data, out_offs.ctypes.data, ratio.ctypes.data, len(offs) - 1
+    ti.fps_out = float(fps_out)
+    for k, t in res.items():
+        setattr(ti, k + "_out", t.data_ptr())
+    return ti, MotionTrack(res, out_offs, fps_out), (qpos, offs, out_offs, ratio)
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -684,6 +737,18 @@ class Engine:
         self._check(self._lib.gmr_motion_epilogue(self._h, C.byref(mi), self._stream()), "gmr_motion_epilogue")
         return res
 
+    def motion_track(self, qpos: torch.Tensor, seq_offsets, fps_in, fps_out, out=None, bodies: bool = True) -> MotionTrack:
+        """The tracking export in one native call (``gmr_motion_track``; the definition is the contract in include/gmr_amd.h):
+        qpos ``[N, nq]`` float64 (free-joint layout, concatenated clips at ``fps_in``: one rate or one per clip) resampled to
+        ``fps_out`` -> a :class:`MotionTrack` of device tensors with ``M = out_offsets[-1]`` rows: root_pos, root_rot (xyzw),
+        joint_pos and their velocities root_lin_vel, root_ang_vel (world frame), joint_vel in float64; with ``bodies`` the world
+        poses body_pos_w, body_quat_w (xyzw) -- bit for bit ``fk`` of the float32 casts of the resampled root and joints -- and
+        their velocities body_lin_vel_w, body_ang_vel_w in float32.  ``out``: caller-owned result tensors by name (a name left
+        out is not computed).  Asynchronous on the current stream."""
+        ti, res, keep = _track_input(self, qpos, seq_offsets, fps_in, fps_out, out, bodies)
+        self._check(self._lib.gmr_motion_track(self._h, C.byref(ti), self._stream()), "gmr_motion_track")
+        return res
+
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,
                     slot_col: Optional[np.ndarray] = None, height_scale=None, iters: Optional[torch.Tensor] = None,
                     offset_to_ground: bool = False, limit_eps: float = CLIP_REPORT_LIMIT_EPS, segment_frames: int = 0) -> ClipReport:
@@ -846,6 +911,26 @@ class EngineGroup:
             outs.append(res)
             keep.append(k)
         self._check(self._lib.gmr_group_motion_epilogue(self._g, inputs, self._stream()), "gmr_group_motion_epilogue")
+        return outs
+
+    def motion_track(self, batches, fps_out, bodies: bool = True):
+        """:meth:`Engine.motion_track` for every member, all members' tiles in one grid (``gmr_group_motion_track``).
+        ``batches[i]``: ``(qpos, seq_offsets, fps_in)`` of member i, or ``None`` (no work).  Returns one :class:`MotionTrack`
+        (or ``None``) per member, bit for bit the single calls'."""
+        if len(batches) != len(self.engines):
+            raise EngineError("one batch (or None) per group member")
+        inputs = (_native.TrackInput * len(batches))()
+        outs, keep = [], []
+        for i, (eng, b) in enumerate(zip(self.engines, batches)):
+            if b is None:
+                outs.append(None)
+                continue
+            qpos, offs, fps_in = b
+            ti, res, k = _track_input(eng, qpos, offs, fps_in, fps_out, None, bodies, f"member {i}: ")
+            inputs[i] = ti
+            outs.append(res)
+            keep.append(k)
+        self._check(self._lib.gmr_group_motion_track(self._g, inputs, self._stream()), "gmr_group_motion_track")
         return outs
 
     def clip_report(self, batches, offset_to_ground: bool = False, limit_eps: float = CLIP_REPORT_LIMIT_EPS, segment_frames: int = 0):

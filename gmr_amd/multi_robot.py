@@ -173,13 +173,34 @@ class MultiRobotRetargeting:
             out[r] = clips
         return out
 
+    def tracking_from_qpos(self, qpos: Dict[str, torch.Tensor], seq_offsets: Sequence[int], fps, fps_out) -> Dict[str, List[Dict]]:
+        """``dataset.tracking_from_qpos`` for every robot in one launch (``EngineGroup.motion_track``): ``qpos[robot]`` ``[N, nq]``
+        float64 on the group's device, the same clips (at ``fps``: one rate or one per clip) for every robot -> ``{robot:
+        [tracking dict per clip]}`` at ``fps_out``, the same keys, dtypes and arrays as the single-robot call."""
+        from . import dataset
+        from .engine import _report_names
+        self._refuse_planar()
+        offs = np.asarray(seq_offsets, dtype=np.int64)
+        missing = [r for r in self.robots if r not in qpos]
+        if missing:
+            raise KeyError(f"no qpos for {missing}")
+        batches = []
+        for r in self.robots:
+            q = qpos[r]
+            q = torch.from_numpy(np.ascontiguousarray(q)).to(self.device) if isinstance(q, np.ndarray) else q
+            batches.append((q, offs, fps))
+        res = self.group.motion_track(batches, fps_out)
+        clips = dataset.tracks_to_host(res, fps_out, [m.body_names for m in self.models], [_report_names(cm)[1] for cm in self._cms])
+        return dict(zip(self.robots, clips))
+
     def retarget_clips(self, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30, height_adjust: bool = True,
                        root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
-                       clip_start: str = "qpos0", report: bool = False):
+                       clip_start: str = "qpos0", report: bool = False, track_fps: Optional[float] = None):
         """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
         solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
         ``dataset.MotionWriter.submit`` as they are.  With ``report`` a second value is returned: ``{robot: engine.ClipReport}``
-        of the solved qpos (:meth:`clip_report`, solve counts included), host arrays."""
+        of the solved qpos (:meth:`clip_report`, solve counts included), host arrays.  With ``track_fps`` a last value is added:
+        ``{robot: [tracking dict per clip]}`` at that rate (:meth:`tracking_from_qpos` on the same qpos)."""
         self._refuse_planar()
         tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
         tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
@@ -191,7 +212,10 @@ class MultiRobotRetargeting:
                                     iters={r: it for r, (_, it) in zip(self.robots, outs)})
         motions = self.motions_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, height_adjust=height_adjust,
                                          root_origin_offset=root_origin_offset)
-        return (motions, {r: rep.numpy() for r, rep in reps.items()}) if report else motions
+        res = (motions, {r: rep.numpy() for r, rep in reps.items()}) if report else (motions,)
+        if track_fps is not None:
+            res += (self.tracking_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, track_fps),)
+        return res[0] if len(res) == 1 else res
 
     def _solve(self, pos, quat, body_names, seq_offsets, chunk, burn_in, offset_to_ground, verify, human_heights, check, clip_start):
         """The solve of :meth:`retarget_batch`: per robot (qpos [N, nq] in the engine's layout, solves per frame) on the device, and

@@ -124,6 +124,28 @@ def report_segments(seq_offsets: Sequence[int], segment: int) -> np.ndarray:
     return np.stack([clip, start, np.minimum(start + segment, b[clip])], axis=1).astype(np.int64).reshape(-1, 3)
 
 
+def track_plan(seq_offsets: Sequence[int], fps_in, fps_out: float):
+    """The resampling plan of the tracking export (``gmr_motion_track``, the contract in include/gmr_amd.h): per clip
+    ``ratio = fps_in / fps_out`` and ``M = floor((T - 1) / ratio + 1e-6) + 1`` output frames (0 for a clip without frames).
+    ``fps_in``: one rate, or one per clip.  Returns (out_offsets int64 ``[S + 1]``, ratio float64 ``[S]``)."""
+    offs = np.asarray(seq_offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1 or np.any(np.diff(offs) < 0):
+        raise ValueError("seq_offsets must be a non-decreasing 1-D array")
+    S = offs.size - 1
+    fin = np.asarray(fps_in, dtype=np.float64)
+    if fin.ndim == 0:
+        fin = np.full(S, float(fin))
+    if fin.shape != (S,):
+        raise ValueError("fps_in must be one rate or one rate per clip")
+    fout = float(fps_out)
+    if not (fout > 0 and np.isfinite(fout)) or not np.all((fin > 0) & np.isfinite(fin)):
+        raise ValueError("frame rates must be positive")
+    ratio = fin / fout
+    T = np.diff(offs)
+    M = np.where(T > 0, np.floor((T - 1).astype(np.float64) / ratio + 1e-6).astype(np.int64) + 1, 0)
+    return np.concatenate([[0], np.cumsum(M)]).astype(np.int64), np.ascontiguousarray(ratio)
+
+
 def plan_walks(items: np.ndarray, seq_offsets: Sequence[int], chunk: int) -> np.ndarray:
     """Verification walks for the tracked chunk items of ``make_items(..., chunk, track=True)``: one item per clip that has
     more than one chunk, running from the clip's second chunk to its end with ``check_stride = chunk`` (gmr_blob.h): it starts

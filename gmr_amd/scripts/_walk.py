@@ -96,7 +96,22 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--hard_out", default=None, type=str, help="write the clips that exceed --max_pos_err / --max_dof_step as a hard-motion list (the format --hard_motions reads); with --robots one file per robot, under --shard_by_rank one per rank (named like --report_csv)")
     ap.add_argument("--max_pos_err", default=None, type=float, help="metres: a clip whose largest task position error exceeds this is not written and is listed in --hard_out")
     ap.add_argument("--max_dof_step", default=None, type=float, help="radians: a clip whose largest joint step between consecutive frames exceeds this is not written and is listed in --hard_out")
+    ap.add_argument("--track_fps", default=None, type=float, help="with --track_folder: also write every clip's tracking export (resampled root, joints and world body poses with their velocities, dataset.tracking_from_qpos) at this rate")
+    ap.add_argument("--track_folder", default=None, type=str, help="with --track_fps: where the tracking exports go, <track_folder>/<relative path>.npz (with --robots <track_folder>/<robot>/...); the pickles are unchanged")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
+
+
+def resolve_track(ap, args) -> None:
+    """``--track_fps`` and ``--track_folder`` come together, and the rate is positive."""
+    if (args.track_fps is None) != (args.track_folder is None):
+        ap.error("--track_fps and --track_folder go together")
+    if args.track_fps is not None and not args.track_fps > 0:
+        ap.error("--track_fps must be positive")
+
+
+def track_path(args, target: str) -> str:
+    """The tracking export beside a clip's pickle: the pickle's path below ``--tgt_folder``, moved below ``--track_folder``, as ``.npz``."""
+    return os.path.join(args.track_folder, os.path.splitext(os.path.relpath(target, args.tgt_folder))[0] + ".npz")
 
 
 def wants_report(args) -> bool:
@@ -157,6 +172,8 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         g = GMR(src_human=src_human, tgt_robot=args.robot, device=args.device)
         target_of, failed = dict(pairs), 0
         sink = ReportSink(args, rank=args.report_rank) if wants_report(args) else None
+        track_fps = getattr(args, "track_fps", None)
+        track_kw = {}if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -165,14 +182,16 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
                 if not len(batch):
                     continue
                 targets = [target_of[f] for f in batch.files]
-                if sink is None:
-                    motions = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                                     clip_start=args.clip_start, **retarget_kw(batch))
-                else:
-                    motions, rep = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                                          clip_start=args.clip_start, report=True, **retarget_kw(batch))
-                    motions, targets = sink.take(dataset, targets, motions, rep)
+                res = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                             clip_start=args.clip_start, report=sink is not None, **retarget_kw(batch), **track_kw)
+                res = res if isinstance(res, tuple) else (res,)
+                motions = res[0]
+                track_of = dict(zip(targets, res[-1])) if track_fps is not None else None
+                if sink is not None:
+                    motions, targets = sink.take(dataset, targets, motions, res[1])
                 writer.submit(motions, targets)
+                if track_of is not None:  # (a withheld clip has no tracking export either)
+                    writer.submit([track_of[t] for t in targets], [track_path(args, t) for t in targets])
         if sink is not None:
             sink.close()
         print(f"{writer.written} files written, {failed} could not be loaded")
@@ -187,6 +206,8 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
     mr = MultiRobotRetargeting(src_human, args.robot_list, device=args.device)
     target_of, failed = dict(pairs), 0
     sinks = {r: ReportSink(args, r, getattr(args, "report_rank", None)) for r in mr.robots} if wants_report(args) else None
+    track_fps = getattr(args, "track_fps", None)
+    track_kw = {} if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
     with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
         for batch in batches([s for s, _ in pairs], mr.ik_columns):
             for f, why in batch.skipped:
@@ -194,18 +215,18 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
                 failed += 1
             if not len(batch):
                 continue
-            reps = None
-            if sinks is None:
-                motions = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                            clip_start=args.clip_start, **retarget_kw(batch))
-            else:
-                motions, reps = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                                  clip_start=args.clip_start, report=True, **retarget_kw(batch))
+            res = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
+                                    clip_start=args.clip_start, report=sinks is not None, **retarget_kw(batch), **track_kw)
+            res = res if isinstance(res, tuple) else (res,)
+            motions, reps = res[0], res[1] if sinks is not None else None
             for i, r in enumerate(mr.robots):
                 ms, ts = motions[r], [target_of[f][i] for f in batch.files]
+                track_of = dict(zip(ts, res[-1][r])) if track_fps is not None else None
                 if reps is not None:
                     ms, ts = sinks[r].take(dataset, ts, ms, reps[r])
                 writer.submit(ms, ts)
+                if track_of is not None:
+                    writer.submit([track_of[t] for t in ts], [track_path(args, t) for t in ts])
     if sinks is not None:
         for sink in sinks.values():
             sink.close()

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import argparse
 
-from ._walk import add_common_flags, convert, plan, resolve_robots
+from ._walk import add_common_flags, convert, plan, resolve_robots, resolve_track
 
 
 def main(argv=None) -> int:
@@ -22,6 +22,7 @@ def main(argv=None) -> int:
     add_common_flags(ap)
     args = ap.parse_args(argv)
     resolve_robots(ap, args)
+    resolve_track(ap, args)
     srcs, tgts, skipped = plan(args, ".bvh", lambda n: n.endswith(".bvh"))
     print(f"{len(srcs)} files to retarget ({skipped} skipped: target exists)")
 

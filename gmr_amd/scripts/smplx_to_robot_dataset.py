@@ -11,7 +11,7 @@ from __future__ import annotations
 import argparse
 import os
 
-from ._walk import add_common_flags, convert, hard_motion_names, plan, resolve_robots
+from ._walk import add_common_flags, convert, hard_motion_names, plan, resolve_robots, resolve_track
 
 EXCLUDE_FILE_CONTENT = ["BMLrub", "EKUT", "crawl", "_lie", "upstairs", "downstairs"]  # smplx_to_robot_dataset.py:218
 
@@ -30,6 +30,7 @@ def main(argv=None) -> int:
     add_common_flags(ap)
     args = ap.parse_args(argv)
     resolve_robots(ap, args)
+    resolve_track(ap, args)
     srcs, tgts, skipped = plan(args, ".npz", lambda n: n.endswith(".npz") and not n.endswith("_stagei.npz"), natural=True)
     print("full args_list:", len(srcs))
     lists = args.hard_motions

@@ -35,6 +35,8 @@
  *   gmr_motion_epilogue, gmr_group_motion_epilogue  the whole post-processing after the retarget loop
  *                      (scripts/smplx_to_robot_dataset.py:93-131): root_rot / dof_pos out of qpos, local_body_pos, the height
  *                      adjust and the root-origin offset -- for one model, or for every member of a group in shared launches
+ *   gmr_motion_track, gmr_group_motion_track  (no counterpart in the reference) what a consumer of the motion files does before it
+ *                      trains a tracking policy: resampling to the controller's rate, world body poses, velocities
  *   gmr_dof_to_rot     KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -206,6 +208,54 @@ typedef struct gmr_motion_input {
 } gmr_motion_input;
 int gmr_motion_epilogue(gmr_model *m, const gmr_motion_input *in, void *stream);
 int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void *stream);
+
+/* The tracking export: solved free-joint qpos (layout [x y z qw qx qy qz hinges], concatenated clips) resampled to one output
+ * rate, with every body's world pose and the velocities a tracking policy is trained on.  All arithmetic below is done as
+ * written, without floating-point contraction.
+ *
+ * Resampling plan (host).  Clip s has T = seq_offsets[s+1] - seq_offsets[s] source frames at fps_in[s] and ratio[s] =
+ * fps_in[s] / fps_out (a double).  It yields M_s = 0 output frames when T = 0, else M_s = floor((T-1) / ratio[s] + 1e-6) + 1;
+ * out_offsets is the prefix sum of M_s.  The plan the caller passes is authoritative (any M_s >= 0, M_s = 0 where T = 0); the
+ * kernel only clamps.  Output frame k of the clip reads the source frames
+ *   u = (double)k * ratio[s],  i0 = min((int64)floor(u), T-1),  i1 = min(i0+1, T-1),  a = u - i0 when i1 > i0, else 0.
+ * Resampled outputs, float64 [M][...], M = out_offsets[n_seq]:
+ *   root_pos_out [M][3], joint_pos_out [M][nq-7]   x0 + a (x1 - x0)
+ *   root_rot_out [M][4] xyzw                       shortest-arc slerp of q0, q1 (as xyzw): d = q0 . q1; d < 0: q1 = -q1, d = -d;
+ *                                                  om = acos(min(d, 1)); (w0, w1) = (1-a, a) when om < 1e-8, else
+ *                                                  (sin((1-a) om), sin(a om)) / sin(om); r = w0 q0 + w1 q1; r / |r|
+ *   a = 0: all three are copies of frame i0, so at fps_out = fps_in they are qpos[:, :3], qpos[:, [4,5,6,3]] and qpos[:, 7:].
+ * World body states, float32: body_pos_w_out [M][nbody][3], body_quat_w_out [M][nbody][4] xyzw: bit for bit what gmr_fk
+ * returns for the float32 casts of root_pos_out, root_rot_out and joint_pos_out.
+ * Velocities, dt = 1 / fps_out, within a clip km = max(k-1, 0), kp = min(k+1, M_s-1), h = (kp - km) dt; every velocity is 0
+ * when h = 0 (a clip of one output frame); no difference crosses a clip:
+ *   root_lin_vel_out [M][3], joint_vel_out [M][nq-7] f64   (x[kp] - x[km]) / h
+ *   root_ang_vel_out [M][3] f64, world frame               rotvec(q[kp] (x) conj(q[km])) / h, where for p (x) conj(q) = (v, w):
+ *                                                          w = pw qw + (pv . qv), v = qw pv - pw qv - pv x qv; negate both
+ *                                                          when w < 0; n = |v|; rotvec = v (2 atan2(n, w) / n) when
+ *                                                          n > 1e-12, else 2 v
+ *   body_lin_vel_w_out, body_ang_vel_w_out [M][nbody][3] f32   the same two formulas on the float32 body_pos_w / body_quat_w,
+ *                                                          promoted to double, the result rounded to float32 once
+ * Any output may be NULL; without any of the four body outputs the FK is skipped.  seq_offsets follow gmr_motion_input's
+ * rules.  GMR_EINVAL: fps_out <= 0, a ratio <= 0 (fps_in <= 0), out_offsets that do not start at 0, decrease, or give output
+ * frames to a clip without source frames.  A planar-base model is refused with GMR_EUNSUPPORTED, a model whose tile does not
+ * fit in LDS too.  Asynchronous on `stream`; the handle's device is selected.
+ *   gmr_motion_track        one model
+ *   gmr_group_motion_track  inputs host [group size]: member i's arguments (n_frames = 0: no work), all members in one grid  */
+typedef struct gmr_track_input {
+  const double *qpos;          /* device [n_frames][nq] f64, free-joint layout                    */
+  int64_t n_frames;
+  const int64_t *seq_offsets;  /* host [n_seq+1], 0 .. n_frames, non-decreasing (empty clips ok)  */
+  const int64_t *out_offsets;  /* host [n_seq+1], the plan: 0 .. M, non-decreasing                */
+  const double *ratio;         /* host [n_seq], fps_in[s] / fps_out                               */
+  double fps_out;
+  int32_t n_seq, reserved;
+  double *root_pos_out, *root_rot_out, *joint_pos_out;          /* device [M][3], [M][4] xyzw, [M][nq-7] f64 */
+  double *root_lin_vel_out, *root_ang_vel_out, *joint_vel_out;  /* device [M][3], [M][3], [M][nq-7] f64      */
+  float *body_pos_w_out, *body_quat_w_out;                      /* device [M][nbody][3], [M][nbody][4] xyzw f32 */
+  float *body_lin_vel_w_out, *body_ang_vel_w_out;               /* device [M][nbody][3] f32 */
+} gmr_track_input;
+int gmr_motion_track(gmr_model *m, const gmr_track_input *in, void *stream);
+int gmr_group_motion_track(gmr_group *g, const gmr_track_input *inputs, void *stream);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
