@@ -257,7 +257,9 @@ __global__ void __launch_bounds__(kFkWave) motion_track_kernel(const TrackEntry 
       q0[i] = quats[row * 8 + ((i + 1) & 3)];
       q1[i] = quats[row * 8 + 4 + ((i + 1) & 3)];
     }
-    if (a == 0.0) {
+    // a = 0 is a copy; so are two identical source rows (a standing robot): the slerp of q with itself would give q / |q|, an ulp
+    // beside the copied rows of the same clip, and a velocity that is not zero
+    if (a == 0.0 || (q0[0] == q1[0] && q0[1] == q1[1] && q0[2] == q1[2] && q0[3] == q1[3])) {
 #pragma unroll
       for (int i = 0; i < 4; i++) qr[i] = q0[i];
     } else {

@@ -224,6 +224,7 @@ int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void
  *                                                  om = acos(min(d, 1)); (w0, w1) = (1-a, a) when om < 1e-8, else
  *                                                  (sin((1-a) om), sin(a om)) / sin(om); r = w0 q0 + w1 q1; r / |r|
  *   a = 0: all three are copies of frame i0, so at fps_out = fps_in they are qpos[:, :3], qpos[:, [4,5,6,3]] and qpos[:, 7:].
+ *   q0 == q1 (all four components): root_rot_out is a copy of q0 for every a -- a standing robot's rows are all the same row.
  * World body states, float32: body_pos_w_out [M][nbody][3], body_quat_w_out [M][nbody][4] xyzw: bit for bit what gmr_fk
  * returns for the float32 casts of root_pos_out, root_rot_out and joint_pos_out.
  * Velocities, dt = 1 / fps_out, within a clip km = max(k-1, 0), kp = min(k+1, M_s-1), h = (kp - km) dt; every velocity is 0
