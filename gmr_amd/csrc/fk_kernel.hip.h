@@ -79,6 +79,25 @@ __device__ __forceinline__ void fk_quat_rotate(const float q[4], const float v[3
   o[2] = v[2] * k + cz * w * 2.0f + q[2] * d * 2.0f;
 }
 
+// The per-clip height minimum (fk_kernel<1>, motion_epilogue_kernel) follows torch.min: NaN when any body height is NaN, else
+// the minimum, with +-inf taking part as values.
+//   fk_min_nan   the running minimum: fminf on ordered operands (bit for bit what it was), NaN once either operand is one
+//   fk_min_key   order-preserving int key of a float (the magnitude bits of negatives flipped); every NaN, of either sign,
+//                takes the one key below -inf's, so it wins atomicMin and the wave reduction
+//   fk_key_min   the float of a key; kFkNanKey decodes to the default quiet NaN
+constexpr int kFkNanKey = (int)0x80000000;  // -inf's key is 0x807fffff
+__device__ __forceinline__ float fk_min_nan(float m, float z) {
+  const float r = fminf(m, z);
+  return __builtin_isunordered(m, z) ? __builtin_nanf("") : r;
+}
+__device__ __forceinline__ int fk_min_key(float z) {
+  const int k = __float_as_int(z);
+  return z != z ? kFkNanKey : k >= 0 ? k : (k ^ 0x7fffffff);
+}
+__device__ __forceinline__ float fk_key_min(int k) {
+  return k == kFkNanKey ? __builtin_nanf("") : __int_as_float(k >= 0 ? k : (k ^ 0x7fffffff));
+}
+
 // MODE 0: write body_pos (and body_rot if non-null).  MODE 1: per-clip min of z (atomics on an ordered-int key).
 // Dynamic LDS (floats): [nslots][7][kFkThreads] branch slots |
 //                       [kFkThreads][kFkPosStride] position stage | [kFkThreads][kFkRotStride] rotation stage (MODE 0)
@@ -249,7 +268,7 @@ __global__ void __launch_bounds__(kFkThreads) fk_kernel(FkTree t, const float *_
     fk_quat_mul(lr, jq, tmp);
     fk_quat_mul(pr, tmp, cr);
     if (MODE == 0) stage(j % kFkGroup);
-    else zmin = fminf(zmin, cp[2]);
+    else zmin = fk_min_nan(zmin, cp[2]);
     const int sv = rec.save_slot;
     if (sv >= 0) {
       float *s = slots + (size_t)sv * 7 * kFkThreads + tid;
@@ -270,9 +289,7 @@ __global__ void __launch_bounds__(kFkThreads) fk_kernel(FkTree t, const float *_
       const int mid = (lo + hi) >> 1;
       if (seq_offsets[mid] <= fc) lo = mid; else hi = mid;
     }
-    // order-preserving int key of a float: flip the magnitude bits of negatives
-    int k = __float_as_int(zmin);
-    k = k >= 0 ? k : (k ^ 0x7fffffff);
+    int k = fk_min_key(zmin);
     // clips are thousands of frames long: almost every wavefront sits inside one clip, so reduce in the wave and issue one
     // atomic instead of 64 contending ones; wavefronts that straddle a boundary fall back to one atomic per lane
     const int lo0 = __builtin_amdgcn_readfirstlane(lo);
@@ -422,11 +439,7 @@ __global__ void fk_minkey_init(int *keys, int n) {
 }
 __global__ void fk_minkey_decode(const int *keys, float *out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    int k = keys[i];
-    k = k >= 0 ? k : (k ^ 0x7fffffff);
-    out[i] = __int_as_float(k);
-  }
+  if (i < n) out[i] = fk_key_min(keys[i]);
 }
 
 }  // namespace gmr

@@ -1853,7 +1853,8 @@ __global__ void __launch_bounds__(64) eval_kernel(const DevModel *__restrict__ m
       const bool is_task = lane < m.ntask[tab];
       const int trow = tab * GMR_MAX_TASKS + (is_task ? lane : 0);
       double e[6], kap, bet;  // (kap, bet: unused here)
-      err = fast_sqrt(wave_sum(is_task ? task_residual(m.tbody[trow], m.tslot[trow], xpos, xquat, tp, tq, e, kap, bet) : 0.0));
+      const double ss = wave_sum(is_task ? task_residual(m.tbody[trow], m.tslot[trow], xpos, xquat, tp, tq, e, kap, bet) : 0.0);
+      err = ss == ss ? fast_sqrt(ss) : ss;  // a NaN stays one: fast_sqrt's `x > 0` select would report the frame as error 0
       if (L.task_err_out && is_task) {
         double *o = L.task_err_out + ((size_t)f * (m.ntask[0] + m.ntask[1]) + (tab ? m.ntask[0] : 0) + lane) * 6;
         for (int i = 0; i < 6; i++) o[i] = e[i];

@@ -258,7 +258,7 @@ __global__ void __launch_bounds__(kFkWave) motion_epilogue_kernel(const MotionEn
 #pragma unroll
       for (int i = 0; i < 3; i++) cpR[i] = ppR[i] + wt[i];
       fk_quat_mul(prR, tmp, crR);
-      zmin = fminf(zmin, cpR[2]);
+      zmin = fk_min_nan(zmin, cpR[2]);
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) img[lane * row + 3 * j + i] = cpI[i];
@@ -279,8 +279,7 @@ __global__ void __launch_bounds__(kFkWave) motion_epilogue_kernel(const MotionEn
   }
   if (want_min) {  // fk_kernel<1>'s reduction: one atomic per wavefront inside one clip, one per lane across a boundary
     int* keys = motion_const(&ep->keys);
-    int k = __float_as_int(zmin);
-    k = k >= 0 ? k : (k ^ 0x7fffffff);
+    int k = fk_min_key(zmin);
     const int s0 = __builtin_amdgcn_readfirstlane(s);
     if (__all(s == s0)) {
 #pragma unroll
@@ -292,7 +291,7 @@ __global__ void __launch_bounds__(kFkWave) motion_epilogue_kernel(const MotionEn
   }
 }
 
-__device__ __forceinline__ float motion_decode(int k) { return __int_as_float(k >= 0 ? k : (k ^ 0x7fffffff)); }
+__device__ __forceinline__ float motion_decode(int k) { return fk_key_min(k); }
 
 // Per member: n_frames height items (members that adjust heights), then n_seq decode items (members that want min_z).
 __global__ void __launch_bounds__(kMotionFinishThreads) motion_finish_kernel(const MotionEntry *__restrict__ entries, int n_entries) {

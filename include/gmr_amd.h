@@ -190,6 +190,12 @@ int gmr_group_ik_solve_ordered(gmr_group *g, const gmr_group_input *inputs, cons
  *                       gmr_fk_min_height gives clip s for ((float)qpos[:, :3], (float)root_rot, (float)dof);
  *                       GMR_MOTION_ROOT_ORIGIN: xy minus the xy of the clip's first frame
  *   min_z_out           low_s per clip (+inf for an empty clip), or NULL
+ * low_s is the minimum of the clip's body heights when all of them are ordered.  It is NaN when any of them is NaN (torch.min's
+ * rule, and the reference script's).  +-inf take part in the minimum as values.
+ * Non-finite input: a non-finite coordinate of qpos makes non-finite exactly the outputs that are arithmetic functions of it, and
+ * changes no other output -- its own element of root_rot / dof_pos / root_pos, the bodies of its frame's local_body_pos below a
+ * poisoned hinge, with GMR_MOTION_ROOT_ORIGIN the xy of its clip when it is the xy of the clip's first frame, and through low_s
+ * (min_z_out[s], and with GMR_MOTION_HEIGHT_ADJUST the z of every frame of the clip) what the rule above says.
  * seq_offsets (host) start at 0, end at n_frames and never decrease (empty clips are allowed).  A planar-base model is refused
  * with GMR_EUNSUPPORTED, a model whose tile does not fit in LDS too.  Asynchronous on `stream`; the handle's device is selected.
  *   gmr_motion_epilogue        one model
@@ -236,6 +242,10 @@ int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void
  *                                                          n > 1e-12, else 2 v
  *   body_lin_vel_w_out, body_ang_vel_w_out [M][nbody][3] f32   the same two formulas on the float32 body_pos_w / body_quat_w,
  *                                                          promoted to double, the result rounded to float32 once
+ * Non-finite input: a non-finite coordinate of qpos makes non-finite exactly the outputs that are arithmetic functions of it, and
+ * changes no other output: the output frames k that read its source frame as i0, or as i1 with a > 0 (a = 0 is a copy of frame
+ * i0), and, in the velocity arrays, their neighbours k-1 and k+1 inside the clip.  The formulas decide which elements: r / |r| of
+ * an r with one infinite component is 0 in the other three, and every comparison with a NaN is false (min(d, 1) of a NaN d is 1).
  * Any output may be NULL; without any of the four body outputs the FK is skipped.  seq_offsets follow gmr_motion_input's
  * rules.  GMR_EINVAL: fps_out <= 0, a ratio <= 0 (fps_in <= 0), out_offsets that do not start at 0, decrease, or give output
  * frames to a clip without source frames.  A planar-base model is refused with GMR_EUNSUPPORTED, a model whose tile does not
@@ -342,14 +352,24 @@ int gmr_session_set_persistent(gmr_session *s, int idle_ms);
  *   height_scale device [n] f64 or NULL: per-frame factor on the human scale table (gmr_work_item.height_scale of the clip)
  *   err_out device [n][2] f64 or NULL;  xpos_out device [n][nbody][3] f64 or NULL;  xquat_out device [n][nbody][4] wxyz or NULL
  *   task_err_out device [n][ntask[0]+ntask[1]][6] f64 or NULL: FrameTask.compute_error of every task of table 1 then table 2
- *              (rows of an unused table are left untouched), Log(T_body^-1 T_target) as [v; w] */
+ *              (rows of an unused table are left untouched), Log(T_body^-1 T_target) as [v; w]
+ * Non-finite input: a non-finite coordinate of qpos makes non-finite exactly the outputs of its own frame that are arithmetic
+ * functions of it (the poses at and below its joint, the errors of the tasks on those bodies, the stage errors), and changes no
+ * other output.  The root quaternion is normalised by a refined reciprocal square root of |q|^2: an infinite component makes all
+ * four components of the root's xquat row NaN (0 x inf), not only itself. */
 int gmr_evaluate(gmr_model *m, const double *qpos, int64_t n_frames, const void *human_pos, const void *human_quat, int in_dtype,
                  int n_cols, const int32_t *slot_col, int offset_to_ground, const double *height_scale, double *err_out,
                  double *task_err_out, double *xpos_out, double *xquat_out, void *stream);
 
 /* Batched FK in the KinematicsModel convention (float32, xyzw).
  *   root_pos device [n][3], root_rot_xyzw device [n][4], dof device [n][nq-7]
- *   body_pos_out device [n][nbody][3]; body_rot_out device [n][nbody][4] or NULL   */
+ *   body_pos_out device [n][nbody][3]; body_rot_out device [n][nbody][4] or NULL
+ * Non-finite input: a non-finite input coordinate makes non-finite exactly the outputs that are arithmetic functions of it, and
+ * changes no other output: a root position coordinate reaches that coordinate of every body of its frame, a root quaternion
+ * component every body but the root's position (and every rotation), a hinge angle the rotation of its body and the poses of the
+ * bodies below it.  The same holds for gmr_fk_shape, gmr_dof_to_rot and gmr_local_rot_to_global; gmr_rot_to_dof keeps the
+ * reference's selects: a quaternion whose |xyz| is not above 1e-5 -- a NaN in xyz included -- gives the angle 0, and the clamp to
+ * the joint's range makes an infinite component a limit or 0.   */
 int gmr_fk(gmr_model *m, const float *root_pos, const float *root_rot_xyzw, const float *dof, int64_t n_frames,
            float *body_pos_out, float *body_rot_out, void *stream);
 
@@ -374,7 +394,10 @@ int gmr_rot_to_dof(gmr_model *m, const float *joint_rot, int64_t n_frames, float
 int gmr_local_rot_to_global(gmr_model *m, const float *local_rot, int64_t n_frames, float *global_rot_out, void *stream);
 
 /* Lowest body z per clip: min over frames [seq_offsets[s], seq_offsets[s+1]) and bodies of FK z.
- *   seq_offsets host [n_seq+1]; min_z_out device [n_seq] float32                    */
+ *   seq_offsets host [n_seq+1]; min_z_out device [n_seq] float32
+ * low_s is the minimum of the clip's body heights when all of them are ordered.  It is NaN when any of them is NaN (torch.min's
+ * rule, and the reference script's).  +-inf take part in the minimum as values.  A non-finite input coordinate changes the
+ * minimum of its own clip only.                    */
 int gmr_fk_min_height(gmr_model *m, const float *root_pos, const float *root_rot_xyzw, const float *dof,
                       const int64_t *seq_offsets, int n_seq, float *min_z_out, void *stream);
 
