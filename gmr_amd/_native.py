@@ -29,7 +29,8 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_session_create", "gmr_session_destroy", "gmr_session_reset", "gmr_session_step", "gmr_session_state", "gmr_session_set_persistent", "gmr_ik_plan_order", "gmr_ik_solve_ordered",
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
-           "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track"]
+           "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
+           "gmr_model_set_step_cap", "gmr_model_get_step_cap"]
 
 
 class IKParams(C.Structure):
@@ -161,6 +162,10 @@ def load():
     L.gmr_last_error.restype = C.c_char_p
     L.gmr_last_error.argtypes = [vp]
     L.gmr_model_info_get.argtypes = [vp, C.POINTER(ModelInfo)]
+    L.gmr_model_set_step_cap.restype = C.c_int
+    L.gmr_model_set_step_cap.argtypes = [vp, vp]
+    L.gmr_model_get_step_cap.restype = C.c_int
+    L.gmr_model_get_step_cap.argtypes = [vp, vp]
     batch = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, C.POINTER(IKParams), vp]  # model .. qpos_init of the three IK calls
     solve = batch + [vp, vp, vp, vp, C.POINTER(IKStats)]                                          # qpos_final .. stats
     L.gmr_ik_solve.argtypes = solve + [vp]

@@ -59,6 +59,10 @@ struct gmr_model {
   bool force_generic = false;         // GMR_AMD_GENERIC_QP=1: use the dense generic QP even where the structured one applies
   bool force_generic_shape = false;   // GMR_AMD_GENERIC_SHAPE=1: never a shaped kernel instance (tests, A/B runs)
   int shape = -1;                     // index into GMR_FOR_EACH_IK_SHAPE of the shape this model matches, -1 = none (ik_shape_of)
+  // per-solve step cap (gmr_model_set_step_cap): the caller's table in dof order, and on the device [64] by active dof
+  std::vector<double> cap_host;       // [nv]; empty = off
+  double *cap_dev = nullptr;          // allocated by the first set, rewritten in place by later ones
+  const double *step_cap() const { return cap_host.empty() ? nullptr : cap_dev; }
 };
 
 // State of a single-sequence session (gmr_session_*): one frame per call, warm start carried on the device.
@@ -208,9 +212,9 @@ const char *ik_shape_name(int shape) {
 }
 
 // The instance a launch takes: the model's shape where the launch is what `plain` stands for in a shape (float32 key-points, no
-// offset_to_ground, every item plain), else -1 = the generic instance.
-int ik_launch_shape(int model_shape, bool force_generic_shape, bool plain, bool in_f64, bool offset_to_ground) {
-  return model_shape >= 0 && !force_generic_shape && plain && !in_f64 && !offset_to_ground ? model_shape : -1;
+// offset_to_ground, every item plain, no step cap), else -1 = the generic instance.
+int ik_launch_shape(int model_shape, bool force_generic_shape, bool plain, bool in_f64, bool offset_to_ground, bool capped) {
+  return model_shape >= 0 && !force_generic_shape && plain && !in_f64 && !offset_to_ground && !capped ? model_shape : -1;
 }
 
 int pick_nvp(int n_act) {
@@ -225,7 +229,7 @@ int pick_nvp(int n_act) {
 template <int NVP>
 void launch_ik(const gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool probe, bool plain) {
   const bool sq = m->dm.sq_ok && !m->force_generic;
-  const int shape = sq ? ik_launch_shape(m->shape, m->force_generic_shape, plain, L.in_f64 != 0, L.prm.offset_to_ground != 0) : -1;
+  const int shape = sq ? ik_launch_shape(m->shape, m->force_generic_shape, plain, L.in_f64 != 0, L.prm.offset_to_ground != 0, L.step_cap != nullptr) : -1;
   if (getenv("GMR_DEBUG_PLAN")) fprintf(stderr, "gmr: ik launch: %s instance %s\n", probe ? "probe" : "solve", ik_shape_name(shape));
   if (shape >= 0) {
     int idx = 0;
@@ -1041,10 +1045,37 @@ void gmr_model_destroy(gmr_model *m) {
   if (m->device >= 0) (void)hipSetDevice(m->device);
   if (m->dev) (void)hipFree(m->dev);
   if (m->dbg) (void)hipFree(m->dbg);
+  if (m->cap_dev) (void)hipFree(m->cap_dev);
   delete m;
 }
 
 const char *gmr_last_error(const gmr_model *m) { return m ? m->err.c_str() : "null model"; }
+
+int gmr_model_set_step_cap(gmr_model *m, const double *cap) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!cap) { m->cap_host.clear(); return GMR_OK; }
+  const int nv = m->h.nv;
+  for (int k = 0; k < nv; ++k) {
+    if (!(cap[k] > 0.0)) { set_err(m, "step cap of dof %d must be > 0 or +inf", k); return GMR_EINVAL; }
+    if (k < 6 && std::isfinite(cap[k])) { set_err(m, "the root's dofs (dof %d) cannot be capped", k); return GMR_EINVAL; }
+  }
+  // by active dof, as the kernel's lanes index it: a hinge row takes its dof's entry (dof = qpos address - 1 behind a free joint);
+  // the root's six rows (null dofs of a planar base among them) and the padding stay +inf
+  double rows[64];
+  for (int a = 0; a < 64; ++a) rows[a] = a < m->n_act && m->dm.akind[a] == 6 ? cap[m->dm.aqadr[a] - 1] : INFINITY;
+  HIP_TRY(m, hipSetDevice(m->device));
+  if (!m->cap_dev) HIP_TRY(m, hipMalloc(reinterpret_cast<void **>(&m->cap_dev), sizeof(rows)));
+  HIP_TRY(m, hipMemcpy(m->cap_dev, rows, sizeof(rows), hipMemcpyHostToDevice));
+  m->cap_host.assign(cap, cap + nv);
+  return GMR_OK;
+}
+
+int gmr_model_get_step_cap(const gmr_model *m, double *cap_out) {
+  if (!m || !cap_out) return GMR_EINVAL;
+  for (int k = 0; k < m->h.nv; ++k) cap_out[k] = m->cap_host.empty() ? INFINITY : m->cap_host[k];
+  return GMR_OK;
+}
 
 int gmr_model_info_get(const gmr_model *m, gmr_model_info *out) {
   if (!m || !out) return GMR_EINVAL;
@@ -1080,7 +1111,7 @@ int gmr_debug_ik_shape(const void *blob, size_t blob_bytes, int force_generic, i
   GMR_IK_SHAPE_FIELDS(GMR_X)
 #undef GMR_X
   const bool sq = d.sq_ok && !m.force_generic;
-  const int shape = ik_launch_shape(ik_shape_of(d, m.nvp, sq), false, plain != 0, in_f64 != 0, offset_to_ground != 0);
+  const int shape = ik_launch_shape(ik_shape_of(d, m.nvp, sq), false, plain != 0, in_f64 != 0, offset_to_ground != 0, false);
   if (name_out && name_len) snprintf(name_out, name_len, "%s", ik_shape_name(shape));
   return shape;
 }
@@ -1154,6 +1185,7 @@ static int prepare_ik_launch(gmr_model *m, const gmr_group_input &in, const gmr_
   if (!m->dbg) { HIP_TRY(m, hipMalloc(&m->dbg, 16 * sizeof(unsigned long long))); HIP_TRY(m, hipMemset(m->dbg, 0, 16 * sizeof(unsigned long long))); }
 #endif
   L.dbg = m->dbg;
+  L.step_cap = m->step_cap();
   return GMR_OK;
 }
 
@@ -1414,7 +1446,9 @@ gmr_session *gmr_session_create(gmr_model *m, int in_dtype, int n_cols, const in
   if ((e = hipHostGetDevicePointer(&host_dev, s->host, 0)) != hipSuccess) return fail("hipHostGetDevicePointer", e);
   const size_t item_off = (nq * 8 + 15) & ~size_t(15), col_off = item_off + sizeof(gmr_work_item);
   const size_t ent_off = (col_off + sizeof(int32_t) * (size_t)m->h.nslot + 15) & ~size_t(15);
-  if ((e = hipMalloc(reinterpret_cast<void **>(&s->dev), ent_off + 2 * sizeof(gmr::IkGroupEntry))) != hipSuccess) return fail("hipMalloc", e);
+  const size_t cap_off = (ent_off + 2 * sizeof(gmr::IkGroupEntry) + 15) & ~size_t(15);  // the model's step cap as it is now: the session keeps its own copy
+  if ((e = hipMalloc(reinterpret_cast<void **>(&s->dev), cap_off + 64 * sizeof(double))) != hipSuccess) return fail("hipMalloc", e);
+  if (m->step_cap() && (e = hipMemcpy(s->dev + cap_off, m->step_cap(), 64 * sizeof(double), hipMemcpyDeviceToDevice)) != hipSuccess) return fail("hipMemcpy", e);
   gmr_work_item w{};
   w.frame_begin = 0; w.n_burn = 0; w.n_out = 1; w.init_row = 0; w.final_row = 0; w.burn_row = -1; w.height_scale = 1.0;
   if ((e = hipMemcpy(s->dev + item_off, &w, sizeof(w), hipMemcpyHostToDevice)) != hipSuccess) return fail("hipMemcpy", e);
@@ -1428,6 +1462,7 @@ gmr_session *gmr_session_create(gmr_model *m, int in_dtype, int n_cols, const in
   L.qout = reinterpret_cast<double *>(hd + s->out_off); L.iters = reinterpret_cast<int *>(hd + s->out_off + nq * 8);
   L.in_f64 = in_dtype == GMR_DTYPE_F64; L.n_cols = n_cols; L.n_items = 1; L.prm = *params;
   L.dbg = nullptr;
+  L.step_cap = m->step_cap() ? reinterpret_cast<const double *>(s->dev + cap_off) : nullptr;
   s->box = reinterpret_cast<gmr::IkSessionBox *>(s->host + box_off);
   s->box_dev = reinterpret_cast<gmr::IkSessionBox *>(hd + box_off);
   s->entries = reinterpret_cast<gmr::IkGroupEntry *>(s->dev + ent_off);

@@ -142,6 +142,9 @@ struct IkLaunch {
   u64 *dbg;  // [16] phase cycle sums, diagnostic builds only
   const int *perm;  // [n_items] or NULL: workgroup b runs item perm[b] (a launch order made on the device, gmr_ik_plan_order)
   int *cost;        // ik_probe_kernel only: [n_items] solves spent on each item, indexed like frames_done
+  // NULL or [64] by active dof (the order of DevModel::abody): the largest |dq| of one solve, +inf = no limit (root and null dofs
+  // always).  A launch that carries one is not plain: it runs on the generic instance (api.hip, ik_launch_shape).
+  const double *step_cap;
 };
 
 // Opaque to the optimiser: values derived from it cannot be hoisted out of the enclosing loop.  Used on indices of
@@ -174,7 +177,7 @@ __device__ __forceinline__ double kc(double c) {
   X(same_tasks, d.same_tasks) X(ncpass0, d.ncpass[0]) X(ncpass1, d.ncpass[1]) X(npairp, d.npairp) X(nbody, d.nbody)              \
   X(fkrounds, d.fkrounds) X(n_act, d.n_act) X(nslot, d.nslot) X(nq, d.nq) X(root_slot, d.root_slot)
 // plain (a property of the launch, not of the model): 1 = float32 key-points, no offset_to_ground, no item with a verification walk
-// (check_stride) or a speculative chunk start (GMR_INIT_ROOT_TARGET)
+// (check_stride) or a speculative chunk start (GMR_INIT_ROOT_TARGET), no step cap (IkLaunch::step_cap)
 struct IkShapeAny {
 #define GMR_X(f, e) static constexpr int f = -1;
   GMR_IK_SHAPE_FIELDS(GMR_X)
@@ -1192,6 +1195,9 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   const int npairp = shp<SH::npairp>(m.npairp), nbody = shp<SH::nbody>(m.nbody), fkrounds = shp<SH::fkrounds>(m.fkrounds);
   constexpr bool kPlain = SH::plain > 0;  // the launch is known to be float32 in, no offset_to_ground, no walk and no chunk start
   const int check_stride = kPlain ? 0 : w.check_stride;
+  // The per-solve step cap (IkLaunch::step_cap) exists in the generic instance alone: the host sends a capped launch nowhere else.
+  // (kPlain does not tell the instances apart -- the shapes leave `plain` to run time, see IkShapeG1Smplx.)
+  constexpr bool kCap = !kPlain && std::is_same_v<SH, IkShapeAny>;
   // active-dof constants of this lane (row of the QP); the rest is re-read where it is used
   const bool real_row = lane < n_act;
   const int arow = real_row ? lane : 0;
@@ -1211,6 +1217,13 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   if (SQ && sq_own) {
     sq_qadr = m.aqadr[sq_g];
     if (m.alimited[sq_g]) { sq_rlo = m.arange[2 * sq_g]; sq_rhi = m.arange[2 * sq_g + 1]; }
+  }
+  // structured layout: the cap on |dq| per solve of the dof this lane owns, once per work item, beside its joint range.  (The dense
+  // layout has no registers to spare -- NVP 64 would spill -- and re-reads its row's cap beside the joint range, once per solve.)
+  double sq_cap = INFINITY;
+  if constexpr (kCap && SQ) {
+    const double *sc = ik_args(Lk)->step_cap;
+    if (sc && sq_own) sq_cap = sc[sq_g];
   }
   int sq_status = 0;
   for (int i = lane; i < nq; i += 64) q[i] = w.init_row >= 0 ? Lk->qinit[(size_t)w.init_row * nq + i] : m.qpos0[i];
@@ -1508,6 +1521,14 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
             lo = -lgain_generic * (qv - m.arange[ar]);
             hi = lgain_generic * (m.arange[ar + 1] - qv);
           }
+          if constexpr (kCap && !SQ) {  // the step cap: the exact intersection of the two boxes, no limit_gain on the cap
+            const double *sc = ik_args(Lk)->step_cap;
+            if (sc) {  // (wave-uniform)
+              const double cap = sc[launder(lane)];
+              lo = fmax(lo, -cap);
+              hi = fmin(hi, cap);
+            }
+          }
         }
         __syncthreads();  // Bc / poses are dead from here: H overwrites them
         GMR_STAMP(6);
@@ -1565,7 +1586,8 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
           // mink ConfigurationLimit, evaluated by the lane that owns the dof in the QP layout: -gain (q - lower) <= dq <= gain (upper - q)
           const double qv = q[sq_qadr];
           const double lgain = ik_args(Lk)->prm.limit_gain;
-          const double s_lo = fmax(-lgain * (qv - sq_rlo), -1e30), s_hi = fmin(lgain * (sq_rhi - qv), 1e30);
+          double s_lo = fmax(-lgain * (qv - sq_rlo), -1e30), s_hi = fmin(lgain * (sq_rhi - qv), 1e30);
+          if constexpr (kCap) { s_lo = fmax(s_lo, -sq_cap); s_hi = fmin(s_hi, sq_cap); }
           double xs;
           GMR_DUP_QP_TWICE();
           qit = box_qp_struct<SH::nlimb>(lane, m.sq_nlimb, sq_own, sq_pad, Hm, s_ci, s_lo, s_hi, sq_status, xs);

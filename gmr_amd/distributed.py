@@ -59,6 +59,25 @@ def broadcast_blob(blob: Optional[bytes], src: int = 0) -> bytes:
     return bytes(buf.cpu().numpy().tobytes())
 
 
+def broadcast_step_cap(cap: Optional[np.ndarray], src: int = 0) -> Optional[np.ndarray]:
+    """Broadcast a model's step cap (``CompiledModel.step_cap``: ``[nv]`` float64 or ``None``) from ``src``.  It travels beside the
+    blob, not inside it: a rank that builds its model from ``broadcast_blob`` hands the result to ``Engine.set_step_cap``
+    (or sets ``CompiledModel.step_cap`` before it builds the engine).  Other ranks may pass ``None``."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return None if cap is None else np.asarray(cap, dtype=np.float64)
+    dev = _comm_device()
+    n = torch.tensor([-1 if cap is None else len(cap)] if dist.get_rank() == src else [0], dtype=torch.int64, device=dev)
+    dist.broadcast(n, src)
+    if int(n.item()) < 0:
+        return None
+    if dist.get_rank() == src:
+        buf = torch.from_numpy(np.array(cap, dtype=np.float64)).to(dev)
+    else:
+        buf = torch.empty(int(n.item()), dtype=torch.float64, device=dev)
+    dist.broadcast(buf, src)
+    return buf.cpu().numpy()
+
+
 def my_clips(lengths: Sequence[int], rank: Optional[int] = None, world: Optional[int] = None) -> List[int]:
     if rank is None:
         rank = dist.get_rank() if dist.is_initialized() else 0

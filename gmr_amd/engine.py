@@ -370,6 +370,27 @@ class Engine:
         self._lib.gmr_model_info_get(self._h, C.byref(info))
         self.info = info
         self.nq, self.nv, self.nbody = info.nq, info.nv, info.nbody
+        if getattr(cm, "step_cap", None) is not None:  # the model's velocity limit (model.step_cap): part of the handle from here on
+            self.set_step_cap(cm.step_cap)
+
+    def set_step_cap(self, cap) -> None:
+        """``gmr_model_set_step_cap``: ``cap [nv]`` (dof order, each > 0 or ``inf``) bounds ``|dq|`` of every QP solve of every
+        later launch of this engine -- batch, ordered, chunked, group member; ``None`` switches it off.  Sessions keep the cap they
+        were created under.  Not while launches of this engine are in flight: synchronise first."""
+        if cap is None:
+            self._check(self._lib.gmr_model_set_step_cap(self._h, None), "gmr_model_set_step_cap")
+            return
+        a = np.ascontiguousarray(cap, dtype=np.float64)
+        if a.shape != (self.nv,):
+            raise ValueError(f"step cap must hold nv = {self.nv} entries, got shape {a.shape}")
+        self._check(self._lib.gmr_model_set_step_cap(self._h, a.ctypes.data), "gmr_model_set_step_cap")
+
+    @property
+    def step_cap(self) -> np.ndarray:
+        """``gmr_model_get_step_cap``: the handle's cap ``[nv]``, all ``inf`` when the limit is off."""
+        out = np.empty(self.nv, dtype=np.float64)
+        self._check(self._lib.gmr_model_get_step_cap(self._h, out.ctypes.data), "gmr_model_get_step_cap")
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

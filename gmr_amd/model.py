@@ -28,6 +28,45 @@ MAX_BODIES = 64
 MAX_TASKS = 32
 MAX_SLOTS = 32
 
+DEFAULT_VELOCITY_LIMIT = 3.0 * np.pi  # rad/s, what ``use_velocity_limit=True`` puts on every limited hinge
+
+
+def resolve_velocity_limits(robot: RobotModel, use_velocity_limit: bool = False, velocity_limits=None) -> Optional[Dict[str, float]]:
+    """The ``{joint name: rad/s}`` table of a retargeter's ``use_velocity_limit`` / ``velocity_limits`` arguments, or ``None`` when
+    neither asks for a limit.  ``use_velocity_limit=True`` alone: every *limited* hinge at ``DEFAULT_VELOCITY_LIMIT`` (mink's
+    ``VelocityLimit`` acts on limited hinges, never on the free joint).  ``velocity_limits`` implies the switch: one number
+    limits every hinge; a dict limits the hinges it names (``KeyError`` for a name the robot has no hinge of) -- on top of the default
+    table where ``use_velocity_limit=True`` is given too, else alone.  Every value must be > 0 (``inf`` = no limit)."""
+    if velocity_limits is None and not use_velocity_limit:
+        return None
+    hinges = [robot.jnt_names[b] for b in robot.hinge_bodies()]
+    limited = [robot.jnt_names[b] for b in robot.hinge_bodies() if robot.jnt_limited[b]]
+    table: Dict[str, float] = {n: DEFAULT_VELOCITY_LIMIT for n in limited} if use_velocity_limit else {}
+    if isinstance(velocity_limits, dict):
+        for n, v in velocity_limits.items():
+            if n not in hinges:
+                raise KeyError(n)
+            table[n] = float(v)
+    elif velocity_limits is not None:
+        table = {n: float(velocity_limits) for n in hinges}
+    for n, v in table.items():
+        if not v > 0.0:
+            raise ValueError(f"velocity limit of {n!r} must be > 0, got {v}")
+    return table
+
+
+def step_cap(robot: RobotModel, velocity_limits: Optional[Dict[str, float]]) -> Optional[np.ndarray]:
+    """``[nv]`` in dof order: the largest ``|dq|`` of one QP solve, ``robot.timestep * vmax`` (mink's ``VelocityLimit`` with
+    ``dt = model.opt.timestep``), ``+inf`` on the root's six dofs and on hinges the table does not name.  ``None`` for ``None``."""
+    if velocity_limits is None:
+        return None
+    cap = np.full(robot.nv, np.inf)
+    for b in robot.hinge_bodies():
+        v = velocity_limits.get(robot.jnt_names[b])
+        if v is not None:
+            cap[robot.dof_adr[b]] = robot.timestep * v
+    return cap
+
 
 @dataclasses.dataclass
 class CompiledModel:
@@ -44,6 +83,8 @@ class CompiledModel:
     slot_pos_off: np.ndarray         # [nslot,3] table-1 pos_offset - ground
     slot_rot_off: np.ndarray         # [nslot,4] table-1 rot_offset, unit wxyz
     blob: bytes
+    velocity_limits: Optional[Dict[str, float]] = None  # resolve_velocity_limits; not part of the blob
+    step_cap: Optional[np.ndarray] = None                # [nv] step_cap(robot, velocity_limits): what an Engine hands to its model handle
 
     @property
     def nslot(self) -> int:
@@ -84,7 +125,8 @@ def _align8(n: int) -> int:
     return (n + 7) & ~7
 
 
-def compile_model(robot: RobotModel, config: Optional[IKConfig], actual_human_height: Optional[float] = None) -> CompiledModel:
+def compile_model(robot: RobotModel, config: Optional[IKConfig], actual_human_height: Optional[float] = None,
+                  velocity_limits: Optional[Dict[str, float]] = None) -> CompiledModel:
     if robot.nbody > MAX_BODIES:
         raise NotImplementedError(f"{robot.name}: {robot.nbody} bodies > {MAX_BODIES} supported by the IK kernel")
     slot_names: List[str] = []
@@ -196,4 +238,5 @@ def compile_model(robot: RobotModel, config: Optional[IKConfig], actual_human_he
         robot=robot, config=config, ratio=ratio, slot_names=slot_names, unoffset_scale_keys=unoffset,
         root_slot=root_slot, tasks=tasks, task_body=task_body, task_slot=task_slot,
         slot_scale=slot_scale, slot_pos_off=slot_pos_off, slot_rot_off=slot_rot_off, blob=blob,
+        velocity_limits=velocity_limits, step_cap=step_cap(robot, velocity_limits),
     )

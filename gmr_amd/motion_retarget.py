@@ -24,7 +24,7 @@ from ._native import IKParams
 from .engine import Engine
 from .ik_config import load_ik_config
 from .mjcf import load_robot
-from .model import compile_model
+from .model import compile_model, resolve_velocity_limits
 from .params import IK_CONFIG_DICT, ROBOT_XML_DICT
 from .schedule import make_items
 
@@ -131,6 +131,8 @@ class GeneralMotionRetargeting:
         verbose: bool = False,
         device: int = 0,
         persistent_session_ms: int = 0,
+        use_velocity_limit: bool = False,
+        velocity_limits=None,
     ) -> None:
         # persistent_session_ms > 0 (not in the reference's signature): retarget() frames go through a resident wavefront that idles
         # out after that many milliseconds (gmr_session_set_persistent) -- for a process whose job is the live loop
@@ -145,7 +147,11 @@ class GeneralMotionRetargeting:
         ik_config = load_ik_config(cfg_path)
         if verbose:
             print("Use IK config: ", cfg_path)
-        self._cm = compile_model(self.model, ik_config, actual_human_height)
+        # use_velocity_limit (the reference's newer releases: a mink.VelocityLimit of 3 pi rad/s in solve_ik) / velocity_limits
+        # ({joint: rad/s} or one number, implies the switch): |dq| <= model.timestep * vmax in every QP solve (model.step_cap)
+        self.velocity_limits = resolve_velocity_limits(self.model, use_velocity_limit, velocity_limits)
+        self.use_velocity_limit = self.velocity_limits is not None
+        self._cm = compile_model(self.model, ik_config, actual_human_height, velocity_limits=self.velocity_limits)
         ratio = self._cm.ratio
 
         self.ik_match_table1 = ik_config.ik_match_table1
@@ -174,6 +180,7 @@ class GeneralMotionRetargeting:
         self.human_body_to_task2 = {t.human_body: t for t in self.tasks2}
 
         self._engine = Engine(self._cm, device)
+        self._cap_key = None if self._cm.step_cap is None else self._cm.step_cap.tobytes()  # a session keeps the cap it was created under
         self.device = self._engine.device
         self.setup_retarget_configuration()
 
@@ -207,7 +214,7 @@ class GeneralMotionRetargeting:
 
     def _session(self, names: Sequence[str]):
         """The live session for this frame layout; the warm start follows the object, not the session."""
-        key = (tuple(names), float(self.damping), int(self.max_iter))
+        key = (tuple(names), float(self.damping), int(self.max_iter), self._cap_key)
         s = self._sessions.get(key)
         if s is None:
             s = self._engine.session(self._columns(names), len(names), self._params(False))

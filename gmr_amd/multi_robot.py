@@ -28,7 +28,7 @@ class MultiRobotRetargeting:
     """
 
     def __init__(self, src_human: str, tgt_robots: Sequence[str], actual_human_height: float = None, damping: float = 5e-1,
-                 device: int = 0, verbose: bool = False) -> None:
+                 device: int = 0, verbose: bool = False, use_velocity_limit: bool = False, velocity_limits=None) -> None:
         robots = list(tgt_robots)
         # every refusal before any device work
         if not robots:
@@ -43,18 +43,23 @@ class MultiRobotRetargeting:
         from .engine import EngineGroup
         from .ik_config import load_ik_config
         from .mjcf import load_robot
-        from .model import compile_model
+        from .model import compile_model, resolve_velocity_limits
         self.src_human = src_human
         self.robots = robots
         self.damping = damping
         self.max_iter = 10
         self.models, self._cms = [], []
+        # use_velocity_limit / velocity_limits as GeneralMotionRetargeting takes them, for every robot; velocity_limits may also be
+        # {robot: number or {joint: rad/s}} -- a robot it does not name then has the switch alone
+        per_robot = isinstance(velocity_limits, dict) and len(velocity_limits) > 0 and all(k in robots for k in velocity_limits)
+        self.velocity_limits: Dict[str, Optional[dict]] = {}
         for r in robots:
             if verbose:
                 print("Use robot model: ", ROBOT_XML_DICT[r], " IK config: ", cfgs[r])
             model = load_robot(str(ROBOT_XML_DICT[r]), name=r)
             self.models.append(model)
-            self._cms.append(compile_model(model, load_ik_config(cfgs[r]), actual_human_height))
+            self.velocity_limits[r] = resolve_velocity_limits(model, use_velocity_limit, velocity_limits.get(r) if per_robot else velocity_limits)
+            self._cms.append(compile_model(model, load_ik_config(cfgs[r]), actual_human_height, velocity_limits=self.velocity_limits[r]))
         self.group = EngineGroup(self._cms, device)
         self.engines = self.group.engines
         self.device = self.group.device

@@ -90,6 +90,8 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--device", default=None, type=int, help="GPU to use (default: LOCAL_RANK under torch.distributed.run, else 0)")
     ap.add_argument("--clip_start", default="qpos0", choices=["qpos0", "root_target"],
                     help="qpos0: the reference (every clip starts from the model's rest pose); root_target: start with the floating base on the first root target (not the reference's numbers for the first frames; spares clips that face away from qpos0 their slow start)")
+    ap.add_argument("--use_velocity_limit", default=False, action="store_true", help="cap every limited hinge at 3 pi rad/s in each IK solve (the reference's use_velocity_limit: |dq| <= model timestep x limit per solve)")
+    ap.add_argument("--velocity_limit", default=None, type=float, metavar="RAD_PER_S", help="cap every hinge at this rate instead (implies --use_velocity_limit)")
     ap.add_argument("--robots", default=None, type=str,
                     help="comma-separated robots solved together from each batch (MultiRobotRetargeting); robot r's files go to <tgt_folder>/<r>/...")
     ap.add_argument("--report_csv", default=None, type=str, help="write the per-clip quality report (stage and task errors, joint-limit and step statistics; one row per clip) to this CSV; with --robots one file per robot, <stem>.<robot><ext>; under --shard_by_rank one per rank, <stem>[.<robot>].rank<k><ext>")
@@ -169,7 +171,7 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         return _convert_robots(args, pairs, src_human, batches, retarget_kw, workers, done)
     if pairs:
         from .. import GeneralMotionRetargeting as GMR, dataset
-        g = GMR(src_human=src_human, tgt_robot=args.robot, device=args.device)
+        g = GMR(src_human=src_human, tgt_robot=args.robot, device=args.device, use_velocity_limit=args.use_velocity_limit, velocity_limits=args.velocity_limit)
         target_of, failed = dict(pairs), 0
         sink = ReportSink(args, rank=args.report_rank) if wants_report(args) else None
         track_fps = getattr(args, "track_fps", None)
@@ -203,7 +205,7 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
     """``convert`` for ``--robots``: each batch is loaded once and solved for every robot (``MultiRobotRetargeting.retarget_clips``);
     a target that exists already is skipped by the writer unless ``--override``."""
     from .. import MultiRobotRetargeting, dataset
-    mr = MultiRobotRetargeting(src_human, args.robot_list, device=args.device)
+    mr = MultiRobotRetargeting(src_human, args.robot_list, device=args.device, use_velocity_limit=args.use_velocity_limit, velocity_limits=args.velocity_limit)
     target_of, failed = dict(pairs), 0
     sinks = {r: ReportSink(args, r, getattr(args, "report_rank", None)) for r in mr.robots} if wants_report(args) else None
     track_fps = getattr(args, "track_fps", None)

@@ -103,6 +103,17 @@ void gmr_model_destroy(gmr_model *m);
 const char *gmr_last_error(const gmr_model *m);
 int gmr_model_info_get(const gmr_model *m, gmr_model_info *out);
 
+/* Per-joint velocity limit (mink.VelocityLimit as a box on the step of one QP solve): |dq_i| <= cap[i] in EVERY solve of every
+ * launch of this model, intersected with the ConfigurationLimit box (no limit_gain on the cap).  cap = timestep * vmax.
+ *   cap: host array of nv doubles in dof order, each > 0 or +inf; NULL switches the limit off (the state after create).
+ *        GMR_EINVAL: an entry that is NaN, zero or negative, or a finite entry on one of the root's six dofs.
+ * Takes effect for launches enqueued after it returns; must not be called while launches of this model are in flight.
+ * gmr_ik_solve, gmr_ik_plan_order, gmr_ik_solve_ordered and the three group solves (each member's own cap) pick it up per call; a
+ * session copies it at gmr_session_create and keeps that copy.  A capped launch runs the generic kernel instance.
+ * gmr_model_get_step_cap returns GMR_OK and fills cap_out[nv] (+inf everywhere when the limit is off). */
+int gmr_model_set_step_cap(gmr_model *m, const double *cap);
+int gmr_model_get_step_cap(const gmr_model *m, double *cap_out);
+
 /* Batched two-stage IK over work items.
  *   human_pos  device, [n_frames][n_cols][3] in_dtype, metres
  *   human_quat device, [n_frames][n_cols][4] in_dtype, wxyz
