@@ -24,6 +24,9 @@ def __getattr__(name):
     if name == "SmplxBodyModel":
         from .smplx_body import SmplxBodyModel
         return SmplxBodyModel
+    if name == "MotionLibrary":
+        from .dataset import MotionLibrary
+        return MotionLibrary
     if name == "load_robot_motion":
         from .dataset import load_robot_motion
         return load_robot_motion

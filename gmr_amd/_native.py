@@ -30,7 +30,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
-           "gmr_model_set_step_cap", "gmr_model_get_step_cap"]
+           "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample"]
 
 
 class IKParams(C.Structure):
@@ -87,6 +87,17 @@ class TrackInput(C.Structure):
     _fields_ = [
         ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("out_offsets", C.c_void_p), ("ratio", C.c_void_p),
         ("fps_out", C.c_double), ("n_seq", C.c_int32), ("reserved", C.c_int32),
+    ] + [(k + "_out", C.c_void_p) for k in TRACK_OUTPUTS]
+
+
+class SampleInput(C.Structure):
+    """``gmr_sample_input`` (include/gmr_amd.h): the arguments of one motion-library query call."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("fps", C.c_void_p),
+        ("n_seq", C.c_int32), ("k_per_id", C.c_int32), ("ids", C.c_void_p), ("times", C.c_void_p),
+        ("time_dtype", C.c_int32), ("out_dtype", C.c_int32), ("n_queries", C.c_int64),
+        ("body_ids", C.c_void_p), ("n_sel", C.c_int32), ("reserved", C.c_int32),
     ] + [(k + "_out", C.c_void_p) for k in TRACK_OUTPUTS]
 
 
@@ -202,6 +213,8 @@ def load():
     L.gmr_motion_track.argtypes = [vp, C.POINTER(TrackInput), vp]
     L.gmr_group_motion_track.restype = C.c_int
     L.gmr_group_motion_track.argtypes = [vp, C.POINTER(TrackInput), vp]
+    L.gmr_motion_sample.restype = C.c_int
+    L.gmr_motion_sample.argtypes = [vp, C.POINTER(SampleInput), vp]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

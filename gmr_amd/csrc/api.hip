@@ -28,6 +28,7 @@
 #include "kin_ops_kernel.hip.h"
 #include "motion_kernel.hip.h"
 #include "track_kernel.hip.h"
+#include "sample_kernel.hip.h"
 #include "report_kernel.hip.h"
 #include "bvh_text.h"
 
@@ -979,6 +980,7 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   GMR_LDS_OPT_IN(gmr::fk_kernel<0>) GMR_LDS_OPT_IN(gmr::fk_kernel<1>)
   GMR_LDS_OPT_IN(gmr::motion_epilogue_kernel)
   GMR_LDS_OPT_IN(gmr::motion_track_kernel)
+  GMR_LDS_OPT_IN(gmr::motion_sample_kernel)
   GMR_LDS_OPT_IN(gmr::clip_report_kernel)
 #undef GMR_LDS_OPT_IN
   (void)hipGetLastError();
@@ -1971,6 +1973,44 @@ int gmr_group_motion_track(gmr_group *g, const gmr_track_input *inputs, void *st
   g->err.clear();
   if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
   return track_run(g->models.data(), inputs, (int)g->models.size(), g->device, static_cast<hipStream_t>(stream), true, g->err);
+}
+
+// ------------------------------------------------------------------ motion library sampling (sample_kernel.hip.h)
+// Validate, fill the kernel argument and launch: one kernel and nothing else -- no scratch, no copy, no synchronisation (the clip
+// table, the ids and the times are device arrays; everything else travels in the argument).
+int gmr_motion_sample(gmr_model *m, const gmr_sample_input *in, void *stream) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->k_per_id < 1) { set_err(m, "k_per_id must be at least 1"); return GMR_EINVAL; }
+  if (in->n_queries < 0 || in->n_frames < 0 || in->n_seq < 0 || in->n_sel < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (in->n_queries % in->k_per_id != 0) { set_err(m, "n_queries must be a multiple of k_per_id"); return GMR_EINVAL; }
+  if (!in->body_ids && in->n_sel != 0) { set_err(m, "n_sel without body_ids"); return GMR_EINVAL; }
+  if ((in->time_dtype != GMR_DTYPE_F32 && in->time_dtype != GMR_DTYPE_F64) || (in->out_dtype != GMR_DTYPE_F32 && in->out_dtype != GMR_DTYPE_F64)) {
+    set_err(m, "unknown element type"); return GMR_EINVAL;
+  }
+  if (m->dm.root_planar) { set_err(m, "the motion library needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int64_t lds = gmr::sample_lds(m->fk.nbody, m->fk.ndof, m->fk.nslots, in->body_ids ? in->n_sel : 0).bytes;
+  if (lds > 160 * 1024) { set_err(m, "the sampling tile needs %lld bytes of LDS", (long long)lds); return GMR_EUNSUPPORTED; }
+  if (in->n_queries == 0) return GMR_OK;
+  if (!in->ids || !in->times || (in->n_seq > 0 && (!in->qpos || !in->seq_offsets || !in->fps))) { set_err(m, "null argument"); return GMR_EINVAL; }
+  const int64_t tiles = (in->n_queries + gmr::kFkWave - 1) / gmr::kFkWave;
+  if (tiles > 0x7fffffff) { set_err(m, "too many queries for one launch"); return GMR_EINVAL; }
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::SampleArgs a{};
+  a.body = m->fk.body; a.save_slot = m->fk.save_slot;
+  a.nbody = m->fk.nbody; a.ndof = m->fk.ndof; a.nslots = m->fk.nslots; a.n_seq = in->n_seq;
+  a.qpos = in->qpos; a.n_frames = in->n_frames; a.seq_offsets = in->seq_offsets; a.fps = in->fps;
+  a.ids = in->ids; a.times = in->times; a.n_queries = in->n_queries;
+  a.body_ids = in->body_ids; a.n_sel = in->n_sel; a.k_per_id = in->k_per_id;
+  a.time_f64 = in->time_dtype == GMR_DTYPE_F64; a.out_f64 = in->out_dtype == GMR_DTYPE_F64;
+  a.root_pos = in->root_pos_out; a.root_rot = in->root_rot_out; a.joint_pos = in->joint_pos_out;
+  a.root_lin_vel = in->root_lin_vel_out; a.root_ang_vel = in->root_ang_vel_out; a.joint_vel = in->joint_vel_out;
+  a.body_pos = in->body_pos_w_out; a.body_quat = in->body_quat_w_out;
+  a.body_lin_vel = in->body_lin_vel_w_out; a.body_ang_vel = in->body_ang_vel_w_out;
+  hipLaunchKernelGGL(gmr::motion_sample_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, static_cast<hipStream_t>(stream), a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

@@ -151,6 +151,104 @@ def tracking_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_of
     return tracks_to_host([track], fps_out, [gmr.model.body_names], [_report_names(gmr._cm)[1]])[0]
 
 
+# ------------------------------------------------------------------ the motion library
+class MotionLibrary:
+    """A set of retargeted clips of one robot kept on the GPU as qpos (288 B per G1 frame) and sampled at arbitrary times: what a
+    tracking / AMP trainer asks at every simulation step, one kernel per call (``Engine.motion_sample``; the definition is the
+    contract of ``gmr_motion_sample`` in include/gmr_amd.h).
+
+    ``qpos`` ``[N, nq]`` float64 (free-joint layout ``[x y z qw qx qy qz hinges]``, concatenated clips) and ``seq_offsets``
+    ``[S + 1]`` as numpy arrays or device tensors; ``fps``: one rate, or one per clip.  Attributes: ``num_clips``, ``num_frames``,
+    ``durations`` (device float64 ``[S]``: ``(T - 1) / fps``, 0 for a clip of one frame or none)."""
+
+    def __init__(self, gmr: GeneralMotionRetargeting, qpos, seq_offsets, fps):
+        if gmr.model.planar_base:
+            raise NotImplementedError("the motion library assumes a free-joint root; a planar-base robot is not supported")
+        from .schedule import clip_durations
+        self.gmr = gmr
+        self._eng = eng = gmr._engine
+        dev = eng.device
+        offs = seq_offsets.detach().cpu().numpy() if isinstance(seq_offsets, torch.Tensor) else seq_offsets
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        q = torch.from_numpy(np.ascontiguousarray(qpos, dtype=np.float64)) if not isinstance(qpos, torch.Tensor) else qpos
+        if q.dim() != 2 or q.shape[1] != eng.nq or q.dtype != torch.float64:
+            raise ValueError(f"qpos must be a float64 [N, {eng.nq}] array")
+        if offs.ndim != 1 or offs.size < 1 or offs[0] != 0 or offs[-1] != q.shape[0]:
+            raise ValueError("seq_offsets must span [0, N]")
+        f = fps.detach().cpu().numpy() if isinstance(fps, torch.Tensor) else fps
+        dur = clip_durations(offs, f)  # (checks the offsets and the rates)
+        S = offs.size - 1
+        f = np.array(np.broadcast_to(np.asarray(f, dtype=np.float64), (S,)))  # (a writable copy)
+        self.qpos = q.to(dev).contiguous()
+        self.seq_offsets = offs
+        self.fps = f
+        self.num_clips, self.num_frames = S, int(offs[-1])
+        self._offs_dev = torch.from_numpy(offs).to(dev)
+        self._fps_dev = torch.from_numpy(f).to(dev)
+        self.durations = torch.from_numpy(dur).to(dev)
+        lens = np.diff(offs)
+        w = dur if dur.sum() > 0 else (lens > 0).astype(np.float64)  # all durations 0: uniform over the clips that have a frame
+        self._weights = torch.from_numpy(np.ascontiguousarray(w)).to(dev) if w.sum() > 0 else None
+        self._bodies = {}
+
+    @classmethod
+    def from_motions(cls, gmr: GeneralMotionRetargeting, motions: Sequence[Dict]) -> "MotionLibrary":
+        """From motion dicts (``retarget_clips`` / the dict of ``load_robot_motion``): ``root_pos``, xyzw ``root_rot``, ``dof_pos``
+        and ``fps`` of every clip, checked with ``validate_motion``."""
+        nq = gmr._engine.nq
+        rows, lens, fps = [], [], []
+        for m in motions:
+            validate_motion(m, nq)
+            rr = np.asarray(m["root_rot"], dtype=np.float64)
+            rows.append(np.concatenate([np.asarray(m["root_pos"], dtype=np.float64), rr[:, [3, 0, 1, 2]],
+                                        np.asarray(m["dof_pos"], dtype=np.float64)], axis=1))
+            lens.append(rows[-1].shape[0])
+            fps.append(float(m["fps"]))
+        qpos = np.concatenate(rows) if rows else np.zeros((0, nq))
+        return cls(gmr, qpos, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(fps, dtype=np.float64))
+
+    def sample_ids(self, n: int, generator=None) -> torch.Tensor:
+        """``n`` clip ids (device int64) drawn in proportion to the durations; a clip without frames is never drawn."""
+        if self._weights is None:
+            raise ValueError("the library holds no frames")
+        return torch.multinomial(self._weights, int(n), replacement=True, generator=generator)
+
+    def sample_times(self, ids: torch.Tensor, generator=None) -> torch.Tensor:
+        """One time per id (device float64), uniform in ``[0, duration]``."""
+        d = self.durations[ids]
+        return torch.rand(d.shape, dtype=torch.float64, device=d.device, generator=generator) * d
+
+    def body_ids(self, bodies: Sequence[str]) -> torch.Tensor:
+        """The device int32 index tensor of a list of body names, resolved once per tuple of names."""
+        key = tuple(bodies)
+        if key not in self._bodies:
+            names = list(self.gmr.model.body_names)
+            missing = [b for b in key if b not in names]
+            if missing:
+                raise KeyError(f"unknown bodies {missing}")
+            self._bodies[key] = torch.tensor([names.index(b) for b in key], dtype=torch.int32, device=self._eng.device)
+        return self._bodies[key]
+
+    def query(self, ids: torch.Tensor, times: torch.Tensor, future: Optional[torch.Tensor] = None, bodies: Optional[Sequence[str]] = None,
+              fields=None, out=None, dtype=torch.float32, check: bool = True):
+        """The reference state of clip ``ids[e]`` at ``times[e]`` seconds (device tensors ``[E]``; or flat ``[Q]`` pairs), as an
+        ``engine.MotionSample`` named as ``TRACK_ARRAYS``.  ``future``: a 1-D device tensor of K offsets in seconds -- every id is
+        then answered at ``times[e] + future[k]``, shapes ``[E, K, ...]``.  ``bodies``: the body names of the four body arrays, in
+        this order (default: all, in model order).  ``fields`` / ``out`` / ``dtype``: as ``Engine.motion_sample``.  Times outside
+        ``[0, duration]`` clamp to the clip's ends.  ``check=True`` validates the id range on the device (one synchronisation)
+        and raises ``ValueError``; ``check=False`` is for training loops: a bad id, an empty clip or a non-finite time gives NaN
+        rows and nothing is read out of range."""
+        if check and ids.numel() > 0 and bool(((ids < 0) | (ids >= self.num_clips)).any()):
+            raise ValueError(f"clip ids must lie in [0, {self.num_clips})")
+        if future is not None:
+            if future.dim() != 1 or times.dim() != 1:
+                raise ValueError("future must be 1-D offsets for 1-D times")
+            times = times[:, None] + future
+        return self._eng.motion_sample(self.qpos, self._offs_dev, self._fps_dev, ids, times,
+                                       k_per_id=int(times.shape[1]) if times.dim() == 2 else 1,
+                                       bodies=None if bodies is None else self.body_ids(bodies), fields=fields, out=out, dtype=dtype)
+
+
 def save_tracking(path: str, track: Dict, override: bool = False) -> bool:
     """One tracking dict as an uncompressed ``.npz`` (``np.savez``); like ``save_motion``, an existing file is skipped unless
     ``override``.  Names and ``quat_order`` are stored as unicode arrays, ``fps`` as a float64 scalar."""

@@ -221,6 +221,68 @@ def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out
     return ti, MotionTrack(res, out_offs, fps_out), (qpos, offs, out_offs, ratio)
 
 
+class MotionSample(dict):
+    """Result of ``motion_sample``: the device tensors by name (``TRACK_FIELDS``), ``[E, K, ...]`` for 2-D times, else ``[Q, ...]``."""
+
+
+def _sample_input(eng: "Engine", qpos, seq_offsets_dev, fps_dev, ids, times, k_per_id, bodies, fields, out, dtype):
+    """Check the arguments of one query call and fill its ``SampleInput``.  Returns (input, MotionSample, keep-alive).  Nothing
+    here touches the device: shapes and dtypes only."""
+    dev = eng.device
+    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or qpos.shape[1] != eng.nq or not qpos.is_contiguous():
+        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
+    for t, dt, what in ((seq_offsets_dev, torch.int64, "seq_offsets_dev"), (fps_dev, torch.float64, "fps_dev"), (ids, torch.int64, "ids")):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+            raise EngineError(f"{what} must be a contiguous 1-D {dt} tensor on the engine's device")
+    n_seq = int(fps_dev.shape[0])
+    if int(seq_offsets_dev.shape[0]) != n_seq + 1:
+        raise EngineError("seq_offsets_dev must hold one entry more than fps_dev")
+    if not isinstance(times, torch.Tensor) or times.device != dev or times.dtype not in (torch.float32, torch.float64) \
+            or times.dim() not in (1, 2) or not times.is_contiguous():
+        raise EngineError("times must be a contiguous float32 / float64 [Q] or [E, K] tensor on the engine's device")
+    if dtype not in (torch.float32, torch.float64):
+        raise EngineError("dtype must be torch.float32 or torch.float64")
+    k_per_id = int(k_per_id)
+    if times.dim() == 2:
+        if k_per_id not in (1, int(times.shape[1])):
+            raise EngineError("k_per_id must equal the second dimension of 2-D times")
+        k_per_id = int(times.shape[1])
+    lead = tuple(times.shape)
+    Q = int(times.numel())
+    if k_per_id < 1 or int(ids.shape[0]) * k_per_id != Q:
+        raise EngineError("ids must hold one entry per k_per_id times")
+    if bodies is not None:
+        if not isinstance(bodies, torch.Tensor) or bodies.device != dev or bodies.dtype != torch.int32 or bodies.dim() != 1 or not bodies.is_contiguous():
+            raise EngineError("bodies must be a contiguous 1-D int32 tensor of body indices on the engine's device")
+    nd, nc = eng.nq - 7, eng.nbody if bodies is None else int(bodies.shape[0])
+    tail = {"root_pos": (3,), "root_rot": (4,), "joint_pos": (nd,), "root_lin_vel": (3,), "root_ang_vel": (3,), "joint_vel": (nd,),
+            "body_pos_w": (nc, 3), "body_quat_w": (nc, 4), "body_lin_vel_w": (nc, 3), "body_ang_vel_w": (nc, 3)}
+    want = list(TRACK_FIELDS) if fields is None else list(fields)
+    if set(want) - set(TRACK_FIELDS):
+        raise EngineError("fields must name arrays of TRACK_FIELDS")
+    dt_of = lambda k: torch.float32 if k in _TRACK_BODY_FIELDS else dtype
+    if out is None:
+        res = {k: torch.empty(lead + tail[k], dtype=dt_of(k), device=dev) for k in TRACK_FIELDS if k in want}
+    else:
+        res = {k: out[k] for k in TRACK_FIELDS if k in out and k in want}
+        if set(out) - set(TRACK_FIELDS) or (fields is not None and set(want) - set(out)) \
+                or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != lead + tail[k] or t.dtype != dt_of(k) or t.device != dev
+                       or not t.is_contiguous() for k, t in res.items()):
+            raise EngineError("out must map names of TRACK_FIELDS to contiguous tensors of the query's shapes on the engine's device")
+    si = _native.SampleInput()
+    si.qpos, si.n_frames = qpos.data_ptr(), int(qpos.shape[0])
+    si.seq_offsets, si.fps, si.n_seq, si.k_per_id = seq_offsets_dev.data_ptr(), fps_dev.data_ptr(), n_seq, k_per_id
+    si.ids, si.times, si.n_queries = ids.data_ptr(), times.data_ptr(), Q
+    si.time_dtype = _native.GMR_DTYPE_F64 if times.dtype == torch.float64 else _native.GMR_DTYPE_F32
+    si.out_dtype = _native.GMR_DTYPE_F64 if dtype == torch.float64 else _native.GMR_DTYPE_F32
+    if bodies is not None:
+        si.body_ids, si.n_sel = bodies.data_ptr(), nc
+    for k, t in res.items():
+        setattr(si, k + "_out", t.data_ptr())
+    return si, MotionSample(res), (qpos, seq_offsets_dev, fps_dev, ids, times, bodies)
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -768,6 +830,23 @@ class Engine:
         out is not computed).  Asynchronous on the current stream."""
         ti, res, keep = _track_input(self, qpos, seq_offsets, fps_in, fps_out, out, bodies)
         self._check(self._lib.gmr_motion_track(self._h, C.byref(ti), self._stream()), "gmr_motion_track")
+        return res
+
+    def motion_sample(self, qpos: torch.Tensor, seq_offsets_dev: torch.Tensor, fps_dev: torch.Tensor, ids: torch.Tensor,
+                      times: torch.Tensor, k_per_id: int = 1, bodies: Optional[torch.Tensor] = None, fields=None, out=None,
+                      dtype=torch.float64) -> MotionSample:
+        """Random access into a library of clips kept as qpos, in one kernel and nothing else (``gmr_motion_sample``; the
+        definition is the contract in include/gmr_amd.h).  qpos ``[N, nq]`` float64 (concatenated clips), the clip table
+        ``seq_offsets_dev`` int64 ``[S + 1]`` and ``fps_dev`` float64 ``[S]`` ON THE DEVICE, ``ids`` int64 and ``times`` (seconds,
+        float32 or float64) ``[Q]``, or ``[E]`` and ``[E, K]`` (``k_per_id = K``: K times per id).  Returns a
+        :class:`MotionSample` named as ``TRACK_FIELDS``, shaped ``[E, K, ...]`` for 2-D times and ``[Q, ...]`` otherwise: the six
+        generalized arrays in ``dtype``, the four body arrays in float32 with one column per entry of ``bodies`` (an int32
+        device tensor of body indices, trusted; ``None``: every body in model order).  ``fields``: the names to compute;
+        ``out``: caller-owned result tensors by name (a name left out is not computed).  A query with an id outside the table,
+        an empty clip or a non-finite time yields NaN in every array.  Asynchronous on the current stream; no allocation
+        with ``out``, no copy, no synchronisation."""
+        si, res, keep = _sample_input(self, qpos, seq_offsets_dev, fps_dev, ids, times, k_per_id, bodies, fields, out, dtype)
+        self._check(self._lib.gmr_motion_sample(self._h, C.byref(si), self._stream()), "gmr_motion_sample")
         return res
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,

@@ -146,6 +146,24 @@ def track_plan(seq_offsets: Sequence[int], fps_in, fps_out: float):
     return np.concatenate([[0], np.cumsum(M)]).astype(np.int64), np.ascontiguousarray(ratio)
 
 
+def clip_durations(seq_offsets: Sequence[int], fps) -> np.ndarray:
+    """Seconds from the first to the last frame of every clip of a motion library: ``(T - 1) / fps``, 0 for a clip of one frame
+    or none (float64 ``[S]``).  ``fps``: one rate, or one per clip.  The sampling weights of ``dataset.MotionLibrary``."""
+    offs = np.asarray(seq_offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1 or np.any(np.diff(offs) < 0):
+        raise ValueError("seq_offsets must be a non-decreasing 1-D array")
+    S = offs.size - 1
+    f = np.asarray(fps, dtype=np.float64)
+    if f.ndim == 0:
+        f = np.full(S, float(f))
+    if f.shape != (S,):
+        raise ValueError("fps must be one rate or one rate per clip")
+    if not np.all((f > 0) & np.isfinite(f)):
+        raise ValueError("frame rates must be positive")
+    T = np.diff(offs)
+    return np.where(T > 1, (T - 1).astype(np.float64) / f, 0.0)
+
+
 def plan_walks(items: np.ndarray, seq_offsets: Sequence[int], chunk: int) -> np.ndarray:
     """Verification walks for the tracked chunk items of ``make_items(..., chunk, track=True)``: one item per clip that has
     more than one chunk, running from the clip's second chunk to its end with ``check_stride = chunk`` (gmr_blob.h): it starts

@@ -37,6 +37,8 @@
  *                      adjust and the root-origin offset -- for one model, or for every member of a group in shared launches
  *   gmr_motion_track, gmr_group_motion_track  (no counterpart in the reference) what a consumer of the motion files does before it
  *                      trains a tracking policy: resampling to the controller's rate, world body poses, velocities
+ *   gmr_motion_sample  (the reference's KinematicsModel in a trainer's loop: interpolation plus a torch loop over bodies per query)
+ *                      the reference state of (clip, time) queries against a library of retargeted clips kept as qpos
  *   gmr_dof_to_rot     KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -278,6 +280,70 @@ typedef struct gmr_track_input {
 } gmr_track_input;
 int gmr_motion_track(gmr_model *m, const gmr_track_input *in, void *stream);
 int gmr_group_motion_track(gmr_group *g, const gmr_track_input *inputs, void *stream);
+
+/* The motion library's random access: Q queries (clip, time) against solved free-joint qpos (layout [x y z qw qx qy qz hinges],
+ * concatenated clips), each answered with the interpolated generalized state, its velocity, and the world poses and twists of
+ * the bodies that are asked for.  All arithmetic below is done as written, without floating-point contraction.  "The export"
+ * is gmr_motion_track above; lerp(x0, x1, a) is its x0 + a (x1 - x0) with a = 0 a copy of x0, slerp its shortest-arc slerp,
+ * angvel(p, q, h) its rotvec(p (x) conj(q)) / h.
+ *
+ * Query j: clip s = ids[j / k_per_id], time t = times[j] in seconds from the clip's first frame (a float32 t is promoted to
+ * double first).  T = seq_offsets[s+1] - seq_offsets[s], f = fps[s].
+ *   u = t f;  i0 = 0 when u <= 0, T-1 when u >= T-1, else floor(u);  i1 = min(i0+1, T-1);
+ *   a = u - i0 when i1 > i0 and 0 < u, else 0.
+ * Pose, the export's formula on the rows i0, i1 and the weight a, under the same conditions:
+ *   root_pos_out [Q][3], joint_pos_out [Q][nq-7]   lerp(x[i0], x[i1], a)
+ *   root_rot_out [Q][4] xyzw                       slerp(q[i0], q[i1], a); a copy of q[i0] when a = 0 or when q[i0] == q[i1]
+ * Generalized velocity, continuous in t, and at an integer frame the export's value at equal rates.  For a source frame i:
+ * km = max(i-1, 0), kp = min(i+1, T-1), h = (double)(kp - km) * (1.0 / f), and
+ *   v_i = (x[kp] - x[km]) / h,  w_i = angvel(q[kp], q[km], h) (q as xyzw),  both 0 when h = 0;
+ *   root_lin_vel_out [Q][3], joint_vel_out [Q][nq-7]   lerp(v_i0, v_i1, a)
+ *   root_ang_vel_out [Q][3], world frame               lerp(w_i0, w_i1, a), componentwise
+ * A query reads at most the four rows i0-1, i0, i1, i1+1, clamped to its clip; nothing crosses a clip.
+ * The six generalized outputs have the element type out_dtype: the float64 value, or its single rounding to float32.
+ * World body states, float32 whatever out_dtype is; column c of a query is body body_ids[c] (body_ids NULL: all bodies in model
+ * order, n_sel = 0, and nbody columns):
+ *   body_pos_w_out [Q][n_sel][3], body_quat_w_out [Q][n_sel][4] xyzw   bit for bit what gmr_fk returns for the float32 casts of
+ *                                                  the float64 root_pos, root_rot and joint_pos of the query
+ *   body_lin_vel_w_out, body_ang_vel_w_out [Q][n_sel][3]   the twist the generalized velocity gives the body at that pose,
+ *       carried down gmr_fk's chain in float32 from the root's v = (float)root_lin_vel, w = (float)root_ang_vel (float64 values).
+ *       For body j with parent p, x and R the chain's own position and rotation (xyzw quaternion r), thetadot = (float)joint_vel:
+ *         d = x_j - x_p (componentwise);  v_j = v_p + (w_p x d),  (w x d)_x = w_y d_z - w_z d_y and cyclic;
+ *         w_j = w_p + (R_j axis_j) thetadot_j componentwise, w_j = w_p for a body without a hinge;  axis_j = (float) of the unit
+ *         axis, R axis = gmr_fk's quat_rotate(r, axis): axis (2 r_w^2 - 1) + (r_v x axis) r_w 2 + r_v (r_v . axis) 2.
+ * Invalid query: id < 0, id >= n_seq, T = 0, a non-finite time (or a NaN u, from a NaN fps).  Every output element of the query
+ * is NaN and no row of qpos is read for it: the only bounds protection for ids that arrive on the device, for any int64 value.
+ * Non-finite qpos rows: rows the query reads make non-finite exactly the outputs that are arithmetic functions of them (the
+ * export's rule: a = 0 is a copy of row i0 and of v_i0, w_i0); no other query is affected.
+ * GMR_EINVAL: k_per_id < 1, n_queries not a multiple of k_per_id, a negative count, n_sel < 0, body_ids NULL with n_sel != 0, an
+ * unknown dtype.  GMR_EUNSUPPORTED: a planar-base model, or one whose per-wavefront LDS exceeds 160 KB.  n_queries = 0 returns
+ * GMR_OK without a launch.  Any output may be NULL; without any of the four body outputs the chain is skipped.  body_ids is
+ * trusted (each 0 <= id < nbody): range checking is the caller's job.
+ * A call enqueues one kernel and nothing else: no allocation, no host-to-device copy, no synchronisation -- the clip table
+ * (seq_offsets, fps), ids and times are device arrays and this struct travels as the kernel's argument.  Asynchronous on
+ * `stream`; the handle's device is selected.
+ * Layout (LP64): sizeof 168; offsets qpos 0, n_frames 8, seq_offsets 16, fps 24, n_seq 32, k_per_id 36, ids 40, times 48,
+ * time_dtype 56, out_dtype 60, n_queries 64, body_ids 72, n_sel 80, reserved 84, root_pos_out 88, root_rot_out 96,
+ * joint_pos_out 104, root_lin_vel_out 112, root_ang_vel_out 120, joint_vel_out 128, body_pos_w_out 136, body_quat_w_out 144,
+ * body_lin_vel_w_out 152, body_ang_vel_w_out 160.  */
+typedef struct gmr_sample_input {
+  const double  *qpos;         /* device [n_frames][nq] f64, free-joint layout, concatenated clips */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;  /* DEVICE [n_seq+1] */
+  const double  *fps;          /* DEVICE [n_seq], > 0 */
+  int32_t        n_seq, k_per_id;       /* k_per_id >= 1: query j uses ids[j / k_per_id] */
+  const int64_t *ids;          /* device [n_queries / k_per_id] */
+  const void    *times;        /* device [n_queries], seconds from the clip's first frame */
+  int32_t        time_dtype, out_dtype; /* GMR_DTYPE_F32 / F64: times; the six generalized outputs */
+  int64_t        n_queries;
+  const int32_t *body_ids;     /* device [n_sel] body indices, or NULL = all bodies in model order */
+  int32_t        n_sel, reserved;
+  void  *root_pos_out, *root_rot_out, *joint_pos_out;           /* [Q][3], [Q][4] xyzw, [Q][nq-7] */
+  void  *root_lin_vel_out, *root_ang_vel_out, *joint_vel_out;   /* [Q][3], [Q][3], [Q][nq-7]      */
+  float *body_pos_w_out, *body_quat_w_out;                      /* [Q][n_sel][3], [Q][n_sel][4] xyzw f32 */
+  float *body_lin_vel_w_out, *body_ang_vel_w_out;               /* [Q][n_sel][3] f32 */
+} gmr_sample_input;
+int gmr_motion_sample(gmr_model *m, const gmr_sample_input *in, void *stream);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
