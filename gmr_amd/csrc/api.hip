@@ -1173,7 +1173,10 @@ static int prepare_ik_launch(gmr_model *m, const gmr_group_input &in, const gmr_
   int rc = scratch_alloc(m, sc, col_off + col_bytes, st);
   if (rc != GMR_OK) return rc;
   uint8_t *ws = static_cast<uint8_t *>(sc.p);
-  // pageable-host copies are staged by the runtime before returning, so the vectors may die after the call
+  // The sources are pageable host memory (vectors that die with the call, the caller's own slot_col).  Observed on ROCm 7 behind a
+  // busy stream (tests/test_gpu_stream_order.py): hipMemcpyAsync takes its copy of the bytes when it is called -- the
+  // sources may be overwritten or freed as soon as it returns -- and up to 512 KiB it does not wait for the stream; at 1 MiB it
+  // returns only when the earlier work on the stream has finished.  Every table copy in this file relies on the first part.
   HIP_TRY(m, hipMemcpyAsync(ws, sorted.data(), items_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(m, hipMemcpyAsync(ws + order_off, order.data(), order_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(m, hipMemcpyAsync(ws + col_off, slot_col, col_bytes, hipMemcpyHostToDevice, st));
