@@ -30,7 +30,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
-           "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample"]
+           "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients"]
 
 
 class IKParams(C.Structure):
@@ -86,7 +86,7 @@ class TrackInput(C.Structure):
 
     _fields_ = [
         ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("out_offsets", C.c_void_p), ("ratio", C.c_void_p),
-        ("fps_out", C.c_double), ("n_seq", C.c_int32), ("reserved", C.c_int32),
+        ("fps_out", C.c_double), ("n_seq", C.c_int32), ("lowpass_hz", C.c_float),
     ] + [(k + "_out", C.c_void_p) for k in TRACK_OUTPUTS]
 
 
@@ -213,6 +213,8 @@ def load():
     L.gmr_motion_track.argtypes = [vp, C.POINTER(TrackInput), vp]
     L.gmr_group_motion_track.restype = C.c_int
     L.gmr_group_motion_track.argtypes = [vp, C.POINTER(TrackInput), vp]
+    L.gmr_lowpass_coefficients.restype = C.c_int
+    L.gmr_lowpass_coefficients.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double)]
     L.gmr_motion_sample.restype = C.c_int
     L.gmr_motion_sample.argtypes = [vp, C.POINTER(SampleInput), vp]
     L.gmr_clip_report.restype = C.c_int

@@ -28,6 +28,7 @@
 #include "kin_ops_kernel.hip.h"
 #include "motion_kernel.hip.h"
 #include "track_kernel.hip.h"
+#include "lowpass_kernel.hip.h"
 #include "sample_kernel.hip.h"
 #include "report_kernel.hip.h"
 #include "bvh_text.h"
@@ -1879,14 +1880,31 @@ int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void
 }
 
 // ------------------------------------------------------------------ tracking export (track_kernel.hip.h)
+int gmr_lowpass_coefficients(double cutoff_hz, double fs, double *c) {
+#pragma clang fp contract(off)
+  if (!c || !std::isfinite(cutoff_hz) || !std::isfinite(fs) || !(cutoff_hz > 0.0) || !(cutoff_hz < fs / 2)) return GMR_EINVAL;
+  const double pi = 3.14159265358979323846, r2 = sqrt(2.0);
+  const double K = tan(pi * cutoff_hz / fs);
+  const double n = 1.0 / (1.0 + r2 * K + K * K);
+  const double b0 = K * K * n;
+  c[0] = b0; c[1] = 2.0 * b0; c[2] = b0;
+  c[3] = 2.0 * (K * K - 1.0) * n;
+  c[4] = (1.0 - r2 * K + K * K) * n;
+  return GMR_OK;
+}
+
 // Validate every member with work, upload the entries and the members' plans (clip offsets, output offsets, ratios) in one block
 // of stream-ordered scratch, and run all members' tiles in one grid.  `models[i]` goes with `inputs[i]`; a group call names the
 // member in its messages.  Errors land in `err`.
+// A member with lowpass_hz > 0 is filtered first (lowpass_kernel.hip.h): its entry of the filter launch and one row of five
+// coefficients per clip ride in the same host block, the filtered qpos goes into a scratch image of its own (n_frames * nq
+// doubles, released behind the launches like the block), and the member's TrackEntry reads that image instead of qpos.
 static int track_run(gmr_model *const *models, const gmr_track_input *inputs, int n, int device, hipStream_t st, bool group, std::string &err) {
   std::vector<gmr::TrackEntry> ent(n);
   std::vector<char> work(n, 0);
-  size_t n_offs = 0, n_ratio = 0;
-  int64_t tiles = 0, lds = 0;
+  std::vector<size_t> coef_at(n, 0);  // filtered members: first coefficient row (in rows of 5 doubles)
+  size_t n_offs = 0, n_ratio = 0, n_coef = 0;
+  int64_t tiles = 0, lds = 0, clips = 0;
   for (int i = 0; i < n; ++i) {
     const gmr_track_input &in = inputs[i];
     const gmr_model *m = models[i];
@@ -1895,6 +1913,7 @@ static int track_run(gmr_model *const *models, const gmr_track_input *inputs, in
     e = gmr::TrackEntry{};
     e.tile_base = tiles;
     if (in.n_frames < 0) { err = who + "negative n_frames"; return GMR_EINVAL; }
+    if (in.lowpass_hz < 0.0f || !std::isfinite(in.lowpass_hz)) { err = who + "lowpass_hz must be finite and >= 0"; return GMR_EINVAL; }
     if (in.n_frames == 0) continue;  // no work for this member
     if (m->dm.root_planar) { err = who + "the tracking export needs a free-joint root; a planar base is not supported"; return GMR_EUNSUPPORTED; }
     if (!in.qpos || !in.seq_offsets || !in.out_offsets || !in.ratio) { err = who + "null argument"; return GMR_EINVAL; }
@@ -1910,6 +1929,16 @@ static int track_run(gmr_model *const *models, const gmr_track_input *inputs, in
         err = who + "clip " + std::to_string(s) + " has output frames but no source frames"; return GMR_EINVAL;
       }
       if (!(in.ratio[s] > 0.0) || !std::isfinite(in.ratio[s])) { err = who + "ratio (fps_in / fps_out) must be positive"; return GMR_EINVAL; }
+      if (in.lowpass_hz != 0.0f && in.seq_offsets[s + 1] > in.seq_offsets[s]) {
+        const double fs = in.ratio[s] * in.fps_out;
+        if (!((double)in.lowpass_hz < fs / 2)) {
+          err = who + "clip " + std::to_string(s) + ": lowpass_hz " + std::to_string(in.lowpass_hz) + " is not below half its frame rate " + std::to_string(fs);
+          return GMR_EINVAL;
+        }
+      }
+    }
+    if (in.lowpass_hz != 0.0f && m->fk.ndof + 7 > gmr::kLowpassMaxNq) {
+      err = who + "the low-pass filter takes at most " + std::to_string(gmr::kLowpassMaxNq) + " qpos columns"; return GMR_EUNSUPPORTED;
     }
     const int64_t n_out = in.out_offsets[in.n_seq];
     if (n_out == 0) continue;
@@ -1931,17 +1960,55 @@ static int track_run(gmr_model *const *models, const gmr_track_input *inputs, in
     n_ratio += (size_t)in.n_seq;
     tiles += (n_out + gmr::kTrackTile - 1) / gmr::kTrackTile;
     work[i] = 1;
+    if (in.lowpass_hz != 0.0f) {
+      work[i] = 2;
+      coef_at[i] = n_coef;
+      n_coef += (size_t)in.n_seq;
+      clips += in.n_seq;
+    }
   }
   if (tiles == 0) return GMR_OK;
-  if (tiles > 0x7fffffff) { err = "too many frames for one launch"; return GMR_EINVAL; }
+  if (tiles > 0x7fffffff || clips > 0x7fffffff) { err = "too many frames for one launch"; return GMR_EINVAL; }
   if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
   const size_t ent_bytes = sizeof(gmr::TrackEntry) * (size_t)n, off_at = (ent_bytes + 15) & ~size_t(15);
-  const size_t ratio_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15), total = ratio_at + sizeof(double) * n_ratio;
+  const size_t ratio_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15);
+  // without a filtered member the block ends behind the ratios, as it always has
+  const size_t lp_at = clips ? (ratio_at + sizeof(double) * n_ratio + 15) & ~size_t(15) : 0;
+  const size_t coef_bytes_at = lp_at + sizeof(gmr::LowpassEntry) * (size_t)n;
+  const size_t total = clips ? coef_bytes_at + sizeof(double) * 5 * n_coef : ratio_at + sizeof(double) * n_ratio;
   CallScratch sc;
+  std::vector<CallScratch> images(clips ? n : 0);  // the filtered members' qpos
   gmr_model *m0 = models[0];
   if (scratch_alloc(m0, sc, total, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
   uint8_t *ws = static_cast<uint8_t *>(sc.p);
   std::vector<uint8_t> host(total, 0);
+  if (clips) {
+    int64_t base = 0;
+    for (int i = 0; i < n; ++i) {
+      gmr::LowpassEntry le{};
+      le.clip_base = base;
+      if (work[i] == 2) {
+        const gmr_track_input &in = inputs[i];
+        const int nq = models[i]->fk.ndof + 7;
+        if (scratch_alloc(m0, images[i], sizeof(double) * (size_t)in.n_frames * (size_t)nq, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
+        double *coef = reinterpret_cast<double *>(host.data() + coef_bytes_at) + 5 * coef_at[i];
+        for (int s = 0; s < in.n_seq; ++s)
+          if (in.seq_offsets[s + 1] > in.seq_offsets[s] &&
+              gmr_lowpass_coefficients((double)in.lowpass_hz, in.ratio[s] * in.fps_out, coef + 5 * s) != GMR_OK) {
+            err = (group ? "member " + std::to_string(i) + ": " : "") + "clip " + std::to_string(s) + ": no low-pass coefficients";  // (refused above)
+            return GMR_EINVAL;
+          }
+        le.src = in.qpos;
+        le.dst = static_cast<double *>(images[i].p);
+        le.seq_offsets = reinterpret_cast<const int64_t *>(ws + off_at) + reinterpret_cast<size_t>(ent[i].seq_offsets);
+        le.coef = reinterpret_cast<const double *>(ws + coef_bytes_at) + 5 * coef_at[i];
+        le.n_seq = in.n_seq; le.nq = nq;
+        ent[i].qpos = le.dst;
+        base += in.n_seq;
+      }
+      memcpy(host.data() + lp_at + sizeof(gmr::LowpassEntry) * (size_t)i, &le, sizeof(le));
+    }
+  }
   for (int i = 0; i < n; ++i) {
     if (!work[i]) continue;
     gmr::TrackEntry &e = ent[i];
@@ -1955,6 +2022,8 @@ static int track_run(gmr_model *const *models, const gmr_track_input *inputs, in
   }
   memcpy(host.data(), ent.data(), ent_bytes);
   if (hipMemcpyAsync(ws, host.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
+  if (clips)
+    hipLaunchKernelGGL(gmr::lowpass_kernel, dim3((unsigned)clips), dim3(gmr::kFkWave), 0, st, reinterpret_cast<const gmr::LowpassEntry *>(ws + lp_at), n);
   hipLaunchKernelGGL(gmr::motion_track_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, st,
                      reinterpret_cast<const gmr::TrackEntry *>(ws), n);
   if (hipGetLastError() != hipSuccess) { err = "kernel launch failed"; return GMR_EDEVICE; }

@@ -82,23 +82,29 @@ def motions_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_off
 def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30,
                    height_adjust: bool = True, root_origin_offset: bool = True, chunk: int = 0, burn_in: int = 0,
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
-                   track_fps: Optional[float] = None):
+                   track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
     from the reference that spares wound-up clips their slow start).  With ``report`` a second value is returned: the
     ``engine.ClipReport`` of the solved qpos (``GeneralMotionRetargeting.clip_report``, solve counts included), host arrays.
-    With ``track_fps`` a last value is added: the clips' tracking dicts at that rate (``tracking_from_qpos`` on the same qpos)."""
+    With ``track_fps`` a last value is added: the clips' tracking dicts at that rate (``tracking_from_qpos`` on the same qpos).
+    With ``lowpass_hz`` the solved qpos is smoothed once (``smooth_qpos`` at ``fps``), and the motions, the report and the tracks
+    are all made from the smoothed qpos."""
     tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
     tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
     tpos, tquat = tpos.to(gmr.device), tquat.to(gmr.device)
     if not report:
         qpos = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
                                   human_heights=human_heights, clip_start=clip_start)  # (raises on non-finite qpos / a capped QP)
+        if lowpass_hz:
+            qpos = smooth_qpos(gmr, qpos, seq_offsets, fps, lowpass_hz)
         res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset),)
     else:
         qpos, iters = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
                                          human_heights=human_heights, clip_start=clip_start, return_iters=True)
+        if lowpass_hz:
+            qpos = smooth_qpos(gmr, qpos, seq_offsets, fps, lowpass_hz)
         rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
         res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset), rep.numpy())
     if track_fps is not None:
@@ -138,17 +144,66 @@ def tracks_to_host(tracks, fps_out, body_names, joint_names) -> List[List[Dict]]
     return out
 
 
-def tracking_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, fps_out) -> List[Dict]:
+def tracking_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, fps_out,
+                       lowpass_hz: Optional[float] = None) -> List[Dict]:
     """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) -> one tracking dict per clip
     at ``fps_out`` (``Engine.motion_track``, one launch): ``fps``, ``joint_pos``, ``joint_vel``, ``root_pos``, ``root_rot`` (xyzw),
     ``root_lin_vel``, ``root_ang_vel`` (world frame) in float64, ``body_pos_w``, ``body_quat_w`` (xyzw), ``body_lin_vel_w``,
     ``body_ang_vel_w`` in float32, ``body_names``, ``joint_names`` (the hinges in qpos order) and ``quat_order = "xyzw"``.
-    The arrays are row slices of batch-sized page-locked host arrays, as ``motions_from_qpos`` hands them out."""
+    The arrays are row slices of batch-sized page-locked host arrays, as ``motions_from_qpos`` hands them out.  ``lowpass_hz``:
+    the cutoff of the zero-phase low-pass applied to qpos first, in the same call (``None``: off)."""
     if gmr.model.planar_base:
         raise NotImplementedError("the tracking export assumes a free-joint root; use retarget_batch for a planar-base robot")
     from .engine import _report_names
-    track = gmr._engine.motion_track(qpos, seq_offsets, fps, fps_out)
+    track = gmr._engine.motion_track(qpos, seq_offsets, fps, fps_out, lowpass_hz=0.0 if lowpass_hz is None else lowpass_hz)
     return tracks_to_host([track], fps_out, [gmr.model.body_names], [_report_names(gmr._cm)[1]])[0]
+
+
+def smooth_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, lowpass_hz) -> torch.Tensor:
+    """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) through the zero-phase
+    2nd-order Butterworth low-pass of the tracking export (the contract above ``gmr_track_input`` in include/gmr_amd.h) ->
+    the filtered qpos ``[N, nq]`` float64 on the device, root quaternion wxyz, sign-continuous and of unit norm.  It runs the
+    export at ``fps_out = fps`` without body outputs, where every output frame is a copy of one filtered row; with per-clip
+    rates that is one call per distinct rate.  ``lowpass_hz`` ``None`` or 0: a copy.  No clamp to the joint ranges: the clip
+    report of the result shows any overshoot."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("the low-pass assumes a free-joint root; a planar-base robot is not supported")
+    return _smooth_qpos(gmr._engine, qpos, seq_offsets, fps, lowpass_hz)
+
+
+def _smooth_qpos(eng, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, lowpass_hz) -> torch.Tensor:
+    """``smooth_qpos`` on an ``Engine`` (a free-joint model)."""
+    from .schedule import lowpass_check
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    S = offs.size - 1
+    f = np.asarray(fps.detach().cpu().numpy() if isinstance(fps, torch.Tensor) else fps, dtype=np.float64)
+    f = np.full(S, float(f)) if f.ndim == 0 else f
+    if f.shape != (S,):
+        raise ValueError("fps must be one rate or one rate per clip")
+    if lowpass_check(offs, f, 1.0, lowpass_hz, ratio=f) == 0.0:  # (ratio 1 in the calls below: fs is the clip's own rate)
+        return qpos.clone()
+    lens = np.diff(offs)
+    res = torch.empty_like(qpos)
+    fields = ("root_pos", "root_rot", "joint_pos")
+    for rate in np.unique(f[lens > 0]):
+        sel = np.flatnonzero((f == rate) & (lens > 0))
+        if sel.size == np.count_nonzero(lens > 0):  # one rate: the batch as it is
+            rows, q, o = None, qpos, offs
+        else:
+            rows = torch.from_numpy(np.concatenate([np.arange(offs[s], offs[s + 1]) for s in sel])).to(qpos.device)
+            q, o = qpos.index_select(0, rows), np.concatenate([[0], np.cumsum(lens[sel])]).astype(np.int64)
+        n = int(q.shape[0])
+        out = {"root_pos": torch.empty((n, 3), dtype=torch.float64, device=q.device),
+               "root_rot": torch.empty((n, 4), dtype=torch.float64, device=q.device),
+               "joint_pos": torch.empty((n, eng.nq - 7), dtype=torch.float64, device=q.device)}
+        tr = eng.motion_track(q, o, float(rate), float(rate), out=out, bodies=False, lowpass_hz=lowpass_hz)
+        assert int(tr.out_offsets[-1]) == n
+        sm = torch.cat([tr["root_pos"], tr["root_rot"][:, [3, 0, 1, 2]], tr["joint_pos"]], dim=1)
+        if rows is None:
+            res = sm
+        else:
+            res.index_copy_(0, rows, sm)
+    return res
 
 
 # ------------------------------------------------------------------ the motion library
@@ -159,9 +214,10 @@ class MotionLibrary:
 
     ``qpos`` ``[N, nq]`` float64 (free-joint layout ``[x y z qw qx qy qz hinges]``, concatenated clips) and ``seq_offsets``
     ``[S + 1]`` as numpy arrays or device tensors; ``fps``: one rate, or one per clip.  Attributes: ``num_clips``, ``num_frames``,
-    ``durations`` (device float64 ``[S]``: ``(T - 1) / fps``, 0 for a clip of one frame or none)."""
+    ``durations`` (device float64 ``[S]``: ``(T - 1) / fps``, 0 for a clip of one frame or none).  ``lowpass_hz``: the clips are
+    filtered once at construction (``smooth_qpos``); ``None``: kept as they are."""
 
-    def __init__(self, gmr: GeneralMotionRetargeting, qpos, seq_offsets, fps):
+    def __init__(self, gmr: GeneralMotionRetargeting, qpos, seq_offsets, fps, lowpass_hz: Optional[float] = None):
         if gmr.model.planar_base:
             raise NotImplementedError("the motion library assumes a free-joint root; a planar-base robot is not supported")
         from .schedule import clip_durations
@@ -180,6 +236,8 @@ class MotionLibrary:
         S = offs.size - 1
         f = np.array(np.broadcast_to(np.asarray(f, dtype=np.float64), (S,)))  # (a writable copy)
         self.qpos = q.to(dev).contiguous()
+        if lowpass_hz:  # filtered once, here: the queries read the smoothed clips
+            self.qpos = smooth_qpos(gmr, self.qpos, offs, f, lowpass_hz)
         self.seq_offsets = offs
         self.fps = f
         self.num_clips, self.num_frames = S, int(offs[-1])
@@ -192,7 +250,7 @@ class MotionLibrary:
         self._bodies = {}
 
     @classmethod
-    def from_motions(cls, gmr: GeneralMotionRetargeting, motions: Sequence[Dict]) -> "MotionLibrary":
+    def from_motions(cls, gmr: GeneralMotionRetargeting, motions: Sequence[Dict], lowpass_hz: Optional[float] = None) -> "MotionLibrary":
         """From motion dicts (``retarget_clips`` / the dict of ``load_robot_motion``): ``root_pos``, xyzw ``root_rot``, ``dof_pos``
         and ``fps`` of every clip, checked with ``validate_motion``."""
         nq = gmr._engine.nq
@@ -205,7 +263,8 @@ class MotionLibrary:
             lens.append(rows[-1].shape[0])
             fps.append(float(m["fps"]))
         qpos = np.concatenate(rows) if rows else np.zeros((0, nq))
-        return cls(gmr, qpos, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(fps, dtype=np.float64))
+        return cls(gmr, qpos, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(fps, dtype=np.float64),
+                   lowpass_hz=lowpass_hz)
 
     def sample_ids(self, n: int, generator=None) -> torch.Tensor:
         """``n`` clip ids (device int64) drawn in proportion to the durations; a clip without frames is never drawn."""

@@ -182,10 +182,11 @@ class MotionTrack(dict):
         self.fps = fps
 
 
-def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out, out, bodies: bool, what: str = ""):
+def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out, out, bodies: bool, what: str = "",
+                 lowpass_hz=0.0):
     """Check one model's tracking arguments, plan the resampling and fill its ``TrackInput``.  Returns (input, MotionTrack,
     keep-alive)."""
-    from .schedule import track_plan
+    from .schedule import lowpass_check, track_plan
     if not isinstance(qpos, torch.Tensor) or qpos.device != eng.device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
             or qpos.shape[1] != eng.nq:
         raise EngineError(what + f"qpos must be a float64 [N, {eng.nq}] tensor on the engine's device")
@@ -196,6 +197,7 @@ def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out
         raise ValueError(what + "seq_offsets must span [0, N]")
     try:
         out_offs, ratio = track_plan(offs, fps_in, fps_out)
+        lowpass_hz = lowpass_check(offs, fps_in, fps_out, lowpass_hz, ratio=ratio)
     except ValueError as e:
         raise EngineError(what + f"gmr_motion_track: {_ERR[-1]}: {e}") from None
     M = int(out_offs[-1])
@@ -216,6 +218,7 @@ def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out
     ti.qpos, ti.n_frames = qpos.data_ptr(), N
     ti.seq_offsets, ti.out_offsets, ti.ratio, ti.n_seq = offs.ctypes.data, out_offs.ctypes.data, ratio.ctypes.data, len(offs) - 1
     ti.fps_out = float(fps_out)
+    ti.lowpass_hz = lowpass_hz
     for k, t in res.items():
         setattr(ti, k + "_out", t.data_ptr())
     return ti, MotionTrack(res, out_offs, fps_out), (qpos, offs, out_offs, ratio)
@@ -820,15 +823,19 @@ class Engine:
         self._check(self._lib.gmr_motion_epilogue(self._h, C.byref(mi), self._stream()), "gmr_motion_epilogue")
         return res
 
-    def motion_track(self, qpos: torch.Tensor, seq_offsets, fps_in, fps_out, out=None, bodies: bool = True) -> MotionTrack:
+    def motion_track(self, qpos: torch.Tensor, seq_offsets, fps_in, fps_out, out=None, bodies: bool = True,
+                     lowpass_hz: float = 0.0) -> MotionTrack:
         """The tracking export in one native call (``gmr_motion_track``; the definition is the contract in include/gmr_amd.h):
         qpos ``[N, nq]`` float64 (free-joint layout, concatenated clips at ``fps_in``: one rate or one per clip) resampled to
         ``fps_out`` -> a :class:`MotionTrack` of device tensors with ``M = out_offsets[-1]`` rows: root_pos, root_rot (xyzw),
         joint_pos and their velocities root_lin_vel, root_ang_vel (world frame), joint_vel in float64; with ``bodies`` the world
         poses body_pos_w, body_quat_w (xyzw) -- bit for bit ``fk`` of the float32 casts of the resampled root and joints -- and
         their velocities body_lin_vel_w, body_ang_vel_w in float32.  ``out``: caller-owned result tensors by name (a name left
-        out is not computed).  Asynchronous on the current stream."""
-        ti, res, keep = _track_input(self, qpos, seq_offsets, fps_in, fps_out, out, bodies)
+        out is not computed).  ``lowpass_hz`` > 0: qpos is first filtered per clip with a zero-phase 2nd-order Butterworth
+        low-pass at that cutoff, on the device (one more kernel; root quaternion sign-continuous and normalised), and every
+        output is what the unfiltered call gives on the filtered qpos; the cutoff must lie below half of every clip's rate.
+        Asynchronous on the current stream."""
+        ti, res, keep = _track_input(self, qpos, seq_offsets, fps_in, fps_out, out, bodies, lowpass_hz=lowpass_hz)
         self._check(self._lib.gmr_motion_track(self._h, C.byref(ti), self._stream()), "gmr_motion_track")
         return res
 
@@ -1013,12 +1020,16 @@ class EngineGroup:
         self._check(self._lib.gmr_group_motion_epilogue(self._g, inputs, self._stream()), "gmr_group_motion_epilogue")
         return outs
 
-    def motion_track(self, batches, fps_out, bodies: bool = True):
+    def motion_track(self, batches, fps_out, bodies: bool = True, lowpass_hz=0.0):
         """:meth:`Engine.motion_track` for every member, all members' tiles in one grid (``gmr_group_motion_track``).
-        ``batches[i]``: ``(qpos, seq_offsets, fps_in)`` of member i, or ``None`` (no work).  Returns one :class:`MotionTrack`
-        (or ``None``) per member, bit for bit the single calls'."""
+        ``batches[i]``: ``(qpos, seq_offsets, fps_in)`` of member i, or ``None`` (no work).  ``lowpass_hz``: one cutoff, or one
+        per member (0: that member is not filtered); the filtered members share one filter launch.  Returns one
+        :class:`MotionTrack` (or ``None``) per member, bit for bit the single calls'."""
         if len(batches) != len(self.engines):
             raise EngineError("one batch (or None) per group member")
+        cut = [lowpass_hz] * len(batches) if lowpass_hz is None or np.ndim(lowpass_hz) == 0 else list(lowpass_hz)
+        if len(cut) != len(batches):
+            raise EngineError("lowpass_hz: one cutoff, or one per group member")
         inputs = (_native.TrackInput * len(batches))()
         outs, keep = [], []
         for i, (eng, b) in enumerate(zip(self.engines, batches)):
@@ -1026,7 +1037,7 @@ class EngineGroup:
                 outs.append(None)
                 continue
             qpos, offs, fps_in = b
-            ti, res, k = _track_input(eng, qpos, offs, fps_in, fps_out, None, bodies, f"member {i}: ")
+            ti, res, k = _track_input(eng, qpos, offs, fps_in, fps_out, None, bodies, f"member {i}: ", lowpass_hz=cut[i])
             inputs[i] = ti
             outs.append(res)
             keep.append(k)

@@ -178,10 +178,12 @@ class MultiRobotRetargeting:
             out[r] = clips
         return out
 
-    def tracking_from_qpos(self, qpos: Dict[str, torch.Tensor], seq_offsets: Sequence[int], fps, fps_out) -> Dict[str, List[Dict]]:
+    def tracking_from_qpos(self, qpos: Dict[str, torch.Tensor], seq_offsets: Sequence[int], fps, fps_out,
+                           lowpass_hz=None) -> Dict[str, List[Dict]]:
         """``dataset.tracking_from_qpos`` for every robot in one launch (``EngineGroup.motion_track``): ``qpos[robot]`` ``[N, nq]``
         float64 on the group's device, the same clips (at ``fps``: one rate or one per clip) for every robot -> ``{robot:
-        [tracking dict per clip]}`` at ``fps_out``, the same keys, dtypes and arrays as the single-robot call."""
+        [tracking dict per clip]}`` at ``fps_out``, the same keys, dtypes and arrays as the single-robot call.  ``lowpass_hz``:
+        the cutoff of the zero-phase low-pass applied to qpos first (``None``: off); one value, or one per robot."""
         from . import dataset
         from .engine import _report_names
         self._refuse_planar()
@@ -194,23 +196,28 @@ class MultiRobotRetargeting:
             q = qpos[r]
             q = torch.from_numpy(np.ascontiguousarray(q)).to(self.device) if isinstance(q, np.ndarray) else q
             batches.append((q, offs, fps))
-        res = self.group.motion_track(batches, fps_out)
+        res = self.group.motion_track(batches, fps_out, lowpass_hz=0.0 if lowpass_hz is None else lowpass_hz)
         clips = dataset.tracks_to_host(res, fps_out, [m.body_names for m in self.models], [_report_names(cm)[1] for cm in self._cms])
         return dict(zip(self.robots, clips))
 
     def retarget_clips(self, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30, height_adjust: bool = True,
                        root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
-                       clip_start: str = "qpos0", report: bool = False, track_fps: Optional[float] = None):
+                       clip_start: str = "qpos0", report: bool = False, track_fps: Optional[float] = None,
+                       lowpass_hz: Optional[float] = None):
         """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
         solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
         ``dataset.MotionWriter.submit`` as they are.  With ``report`` a second value is returned: ``{robot: engine.ClipReport}``
         of the solved qpos (:meth:`clip_report`, solve counts included), host arrays.  With ``track_fps`` a last value is added:
-        ``{robot: [tracking dict per clip]}`` at that rate (:meth:`tracking_from_qpos` on the same qpos)."""
+        ``{robot: [tracking dict per clip]}`` at that rate (:meth:`tracking_from_qpos` on the same qpos).  With ``lowpass_hz``
+        every robot's solved qpos is smoothed once (``dataset.smooth_qpos`` at ``fps``) and everything is made from that."""
         self._refuse_planar()
         tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
         tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
         tpos, tquat = tpos.to(self.device), tquat.to(self.device)
         outs, offs = self._solve(tpos, tquat, body_names, seq_offsets, chunk, burn_in, False, True, human_heights, True, clip_start)
+        if lowpass_hz:
+            from .dataset import _smooth_qpos
+            outs = [(_smooth_qpos(eng, q, offs, fps, lowpass_hz), it) for eng, (q, it) in zip(self.group.engines, outs)]
         reps = None
         if report:
             reps = self.clip_report({r: q for r, (q, _) in zip(self.robots, outs)}, tpos, tquat, body_names, offs, human_heights,

@@ -146,6 +146,35 @@ def track_plan(seq_offsets: Sequence[int], fps_in, fps_out: float):
     return np.concatenate([[0], np.cumsum(M)]).astype(np.int64), np.ascontiguousarray(ratio)
 
 
+def lowpass_check(seq_offsets: Sequence[int], fps_in, fps_out: float, lowpass_hz, ratio=None) -> float:
+    """The host-side check of the tracking export's low-pass (``gmr_track_input.lowpass_hz``, the contract in include/gmr_amd.h):
+    the cutoff, rounded to float32 as the C struct holds it, must be finite and >= 0, and below half the rate
+    ``fs = ratio * fps_out`` (``ratio = fps_in / fps_out``) of every clip that has frames.  ``ratio``: the plan's, where the caller
+    has it already (``track_plan``); else it is taken from ``fps_in``, one rate or one per clip.  Raises ``ValueError`` naming the
+    first clip at or above Nyquist; returns the cutoff as a float (0.0: off).  ``None`` is off."""
+    fc = 0.0 if lowpass_hz is None else float(np.float32(lowpass_hz))
+    if not (fc >= 0.0 and np.isfinite(fc)):
+        raise ValueError(f"lowpass_hz must be finite and >= 0, not {lowpass_hz}")
+    if fc == 0.0:
+        return 0.0
+    T = np.diff(np.asarray(seq_offsets, dtype=np.int64))
+    fout = float(fps_out)
+    if ratio is None:
+        fin = np.asarray(fps_in, dtype=np.float64)
+        fin = np.full(T.size, float(fin)) if fin.ndim == 0 else fin
+        if fin.shape != T.shape:
+            raise ValueError("fps_in must be one rate or one rate per clip")
+        if not (fout > 0 and np.isfinite(fout)) or not np.all((fin > 0) & np.isfinite(fin)):
+            raise ValueError("frame rates must be positive")
+        ratio = fin / fout
+    fs = np.asarray(ratio, dtype=np.float64) * fout
+    bad = np.flatnonzero((T > 0) & ~(fc < fs / 2))
+    if bad.size:
+        s = int(bad[0])
+        raise ValueError(f"clip {s}: lowpass_hz {fc:g} is not below half its frame rate {fs[s]:g}")
+    return fc
+
+
 def clip_durations(seq_offsets: Sequence[int], fps) -> np.ndarray:
     """Seconds from the first to the last frame of every clip of a motion library: ``(T - 1) / fps``, 0 for a clip of one frame
     or none (float64 ``[S]``).  ``fps``: one rate, or one per clip.  The sampling weights of ``dataset.MotionLibrary``."""

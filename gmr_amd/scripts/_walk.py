@@ -100,6 +100,7 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--max_dof_step", default=None, type=float, help="radians: a clip whose largest joint step between consecutive frames exceeds this is not written and is listed in --hard_out")
     ap.add_argument("--track_fps", default=None, type=float, help="with --track_folder: also write every clip's tracking export (resampled root, joints and world body poses with their velocities, dataset.tracking_from_qpos) at this rate")
     ap.add_argument("--track_folder", default=None, type=str, help="with --track_fps: where the tracking exports go, <track_folder>/<relative path>.npz (with --robots <track_folder>/<robot>/...); the pickles are unchanged")
+    ap.add_argument("--lowpass_hz", default=None, type=float, metavar="HZ", help="smooth the solved qpos once with a zero-phase 2nd-order Butterworth low-pass at this cutoff (dataset.smooth_qpos, on the GPU) before the report, the pickles and the tracking exports are made; default: off")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -109,6 +110,8 @@ def resolve_track(ap, args) -> None:
         ap.error("--track_fps and --track_folder go together")
     if args.track_fps is not None and not args.track_fps > 0:
         ap.error("--track_fps must be positive")
+    if getattr(args, "lowpass_hz", None) is not None and not args.lowpass_hz > 0:
+        ap.error("--lowpass_hz must be positive")
 
 
 def track_path(args, target: str) -> str:
@@ -176,6 +179,8 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         sink = ReportSink(args, rank=args.report_rank) if wants_report(args) else None
         track_fps = getattr(args, "track_fps", None)
         track_kw = {}if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
+        if getattr(args, "lowpass_hz", None) is not None:
+            track_kw["lowpass_hz"] = args.lowpass_hz
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -210,6 +215,8 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
     sinks = {r: ReportSink(args, r, getattr(args, "report_rank", None)) for r in mr.robots} if wants_report(args) else None
     track_fps = getattr(args, "track_fps", None)
     track_kw = {} if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
+    if getattr(args, "lowpass_hz", None) is not None:
+        track_kw["lowpass_hz"] = args.lowpass_hz
     with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
         for batch in batches([s for s, _ in pairs], mr.ik_columns):
             for f, why in batch.skipped:

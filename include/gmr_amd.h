@@ -278,7 +278,40 @@ int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void
  * frames to a clip without source frames.  A planar-base model is refused with GMR_EUNSUPPORTED, a model whose tile does not
  * fit in LDS too.  Asynchronous on `stream`; the handle's device is selected.
  *   gmr_motion_track        one model
- *   gmr_group_motion_track  inputs host [group size]: member i's arguments (n_frames = 0: no work), all members in one grid  */
+ *   gmr_group_motion_track  inputs host [group size]: member i's arguments (n_frames = 0: no work), all members in one grid
+ *
+ * The low-pass (lowpass_hz > 0): qpos is first filtered per clip with a zero-phase 2nd-order Butterworth low-pass, forward and
+ * backward (scipy.signal.filtfilt of scipy.signal.butter(2, 2 fc / fs)), on the device.  lowpass_hz = 0 (also -0) leaves the
+ * call exactly as described above.  All arithmetic is done as written, in float64, without contraction.
+ * Coefficients.  For clip s, fs = ratio[s] * fps_out (this product, in double) and fc = (double)lowpass_hz;
+ *   K = tan(pi fc / fs), n = 1 / (1 + sqrt(2) K + K K),
+ *   b0 = K K n, b1 = 2 b0, b2 = b0, a1 = 2 (K K - 1) n, a2 = (1 - sqrt(2) K + K K) n
+ * as gmr_lowpass_coefficients below returns them (the call uses that function for every clip).  Applied forward and backward
+ * the filter is -6 dB at fc, exactly as filtfilt is; no cutoff correction is applied.
+ * One column x[0..T-1] of one clip.  T <= 1: a copy.  Otherwise e = min(9, T - 1) (scipy's padlen = 3 * 3, shortened for the
+ * clips scipy would refuse), and the odd extension is
+ *   ext = [2 x[0] - x[e], ..., 2 x[0] - x[1], x[0..T-1], 2 x[T-1] - x[T-2], ..., 2 x[T-1] - x[T-1-e]].
+ * One pass is the transposed direct form II, y = b0 x + z1; z1 = (b1 x - a1 y) + z2; z2 = b2 x - a2 y, started at
+ * z1 = (1 - b0) u, z2 = (b2 - a2) u with u the first sample of the pass (lfilter_zi times the first sample).  The forward pass
+ * runs over ext, the backward pass over the forward result reversed; the output is the middle T samples.
+ * Columns.  x y z and every hinge are filtered as above.  The root quaternion (columns 3..6, wxyz) is first made
+ * sign-continuous along the clip: q'_0 = q_0, and q'_i = -q_i when q'_{i-1} . q_i < 0, else q_i, the dot product being
+ * ((w w + x x) + y y) + z z.  The four components of q' are filtered like any other column (T = 1: copied), and the result r
+ * leaves as r / sqrt(((rw rw + rx rx) + ry ry) + rz rz).  The filtered quaternion is therefore sign-continuous, and negating
+ * any input rows other than row 0 changes no output bit.  There is no clamp to the joint ranges.
+ * The export.  All ten outputs are, bit for bit, what the same call with lowpass_hz = 0 gives on the filtered qpos.
+ * Non-finite input.  A non-finite coordinate makes non-finite every frame of its own column of its own clip (the backward
+ * pass starts from what the forward pass ended with); in the root quaternion it makes non-finite all four columns of that clip
+ * (a NaN norm).  It changes no other column and no other clip.  The export's own rule applies from there.
+ * Errors.  GMR_EINVAL for a negative or non-finite lowpass_hz and for any clip with source frames and lowpass_hz >= fs / 2
+ * (the message names the clip, and in a group the member); GMR_EUNSUPPORTED when nq > 64 (no registry robot exceeds 50).
+ * Memory.  With the filter on the call takes n_frames * nq * 8 bytes of stream-ordered scratch per filtered member on the
+ * call's stream (the filtered qpos), released behind the launches, and enqueues one more kernel.  */
+
+/* The five coefficients gmr_motion_track uses for a clip sampled at fs with cutoff cutoff_hz: c = {b0, b1, b2, a1, a2}.
+ * GMR_EINVAL unless 0 < cutoff_hz < fs / 2 and both are finite.  Host only: no stream, no device work. */
+int gmr_lowpass_coefficients(double cutoff_hz, double fs, double *c);
+
 typedef struct gmr_track_input {
   const double *qpos;          /* device [n_frames][nq] f64, free-joint layout                    */
   int64_t n_frames;
@@ -286,7 +319,8 @@ typedef struct gmr_track_input {
   const int64_t *out_offsets;  /* host [n_seq+1], the plan: 0 .. M, non-decreasing                */
   const double *ratio;         /* host [n_seq], fps_in[s] / fps_out                               */
   double fps_out;
-  int32_t n_seq, reserved;
+  int32_t n_seq;
+  float lowpass_hz;            /* cutoff of the zero-phase low-pass applied to qpos first; 0 (all-zero bits, or -0): off */
   double *root_pos_out, *root_rot_out, *joint_pos_out;          /* device [M][3], [M][4] xyzw, [M][nq-7] f64 */
   double *root_lin_vel_out, *root_ang_vel_out, *joint_vel_out;  /* device [M][3], [M][3], [M][nq-7] f64      */
   float *body_pos_w_out, *body_quat_w_out;                      /* device [M][nbody][3], [M][nbody][4] xyzw f32 */

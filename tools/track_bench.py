@@ -1,6 +1,6 @@
 """Tracking export: the fused call (Engine.motion_track) against the unfused composition on the same device.
 
-    python tools/track_bench.py [--clips 8192] [--frames 3000] [--batch_clips 512] [--repeats 7] [--warmup 2] [--out FILE]
+    python tools/track_bench.py [--clips 8192] [--frames 3000] [--batch_clips 512] [--repeats 7] [--warmup 2] [--lowpass_hz HZ] [--out FILE]
 
 Workload: unitree_g1, `clips` clips x `frames` frames at 30 fps, resampled to 50 fps and to 30 fps.  Both sides run the workload
 as consecutive batches of `batch_clips` clips into result tensors allocated once (8192 x 3000 frames at 50 fps are 41 M output
@@ -8,6 +8,13 @@ frames x 2.1 KB); every batch reads the same smooth random qpos, which does not 
 what a user of the package writes without the call: a torch lerp and slerp on index tensors, Engine.fk(want_rot=True) on the
 float32 casts, and torch differences; its index tensors (i0, i1, a, km, kp, h) are built outside the timed region.  Timing: HIP
 events around the whole workload, `warmup` untimed runs, the median of `repeats` runs (min and max alongside).  Prints one JSON line.
+
+With --lowpass_hz the fused call is also timed with the low-pass on (`fused_lowpass`: one more kernel per batch, in front of the
+export), and what a user does without it is timed once for one batch (`host_filtfilt_one_batch`): qpos to the host,
+scipy.signal.filtfilt per clip (all columns at once; the root quaternion made sign-continuous first and normalised after), and
+back to the device.  The filter kernel's own duration comes from a kernel trace of its own:
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/track_bench.py --lowpass_hz 6 --trace_only
 """
 from __future__ import annotations
 
@@ -93,6 +100,23 @@ def composition(eng, q, plan, out_pos, out_rot):
     return root_pos, root_rot, joint_pos, root_lin, root_ang, joint_vel, bp, br, body_lin, body_ang
 
 
+def host_filtfilt(q: torch.Tensor, offs, fs: float, fc: float) -> torch.Tensor:
+    """The host route for one batch, copies included: the same filter through scipy, clip by clip."""
+    from scipy import signal
+    b, a = signal.butter(2, 2 * fc / fs)
+    x = q.cpu().numpy()
+    out = np.empty_like(x)
+    for s in range(len(offs) - 1):
+        c = x[offs[s]:offs[s + 1]].copy()
+        w = c[:, 3:7]
+        flip = np.cumprod(np.where(np.sum(w[1:] * w[:-1], axis=1) < 0, -1.0, 1.0))  # (the sign of each row against its corrected predecessor)
+        w[1:] *= flip[:, None]
+        c = signal.filtfilt(b, a, c, axis=0, padlen=min(9, c.shape[0] - 1))
+        c[:, 3:7] /= np.linalg.norm(c[:, 3:7], axis=1, keepdims=True)
+        out[offs[s]:offs[s + 1]] = c
+    return torch.from_numpy(out).to(q.device)
+
+
 def timed(fn, warmup: int, repeats: int):
     for _ in range(warmup):
         fn()
@@ -117,10 +141,15 @@ def main(argv=None) -> int:
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--robot", default="unitree_g1")
+    ap.add_argument("--lowpass_hz", type=float, default=None, help="also time the fused call with the low-pass at this cutoff, and the host route once")
+    ap.add_argument("--trace_only", action="store_true", help="with --lowpass_hz: the filtered fused call over the workload three times at "
+                    "30 -> 50 fps and nothing else (for a rocprofv3 --kernel-trace run)")
     ap.add_argument("--out", default=None, help="also write the JSON result here")
     args = ap.parse_args(argv)
     if args.repeats < 5:
         ap.error("--repeats must be at least 5")
+    if args.trace_only and args.lowpass_hz is None:
+        ap.error("--trace_only needs --lowpass_hz")
     from gmr_amd import GeneralMotionRetargeting
     from gmr_amd.engine import TRACK_FIELDS
     from gmr_amd.schedule import track_plan
@@ -146,6 +175,15 @@ def main(argv=None) -> int:
         def fused():
             for _ in range(n_batches):
                 eng.motion_track(q, offs, 30.0, fps_out, out=out)
+
+        def fused_lowpass():
+            for _ in range(n_batches):
+                eng.motion_track(q, offs, 30.0, fps_out, out=out, lowpass_hz=args.lowpass_hz)
+        if args.trace_only:
+            for _ in range(3):
+                fused_lowpass()
+            torch.cuda.synchronize()
+            return 0
         plan = composition_plan(offs, out_offs, ratio, fps_out, dev)
         bp, br = torch.empty_like(out["body_pos_w"]), torch.empty_like(out["body_quat_w"])
 
@@ -158,13 +196,34 @@ def main(argv=None) -> int:
         worst = max(float((out[k].to(torch.float64) - r.to(torch.float64)).abs().max()) for k, r in zip(TRACK_FIELDS, ref))
         case = {"fps_in": 30.0, "fps_out": fps_out, "output_frames": frames_out, "algorithmic_bytes_per_output_frame": round(bytes_per_frame, 1),
                 "max_abs_difference_fused_vs_composition": worst}
-        for name, fn in (("fused", fused), ("composition", unfused)):
+        sides = [("fused", fused), ("composition", unfused)]
+        if args.lowpass_hz is not None:
+            # the filtered call is the plain call on the filtered qpos, and the host route computes the same filtered qpos
+            import time
+            from gmr_amd import dataset
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            qh = host_filtfilt(q, offs, 30.0, args.lowpass_hz)
+            torch.cuda.synchronize()
+            host_s = time.perf_counter() - t0
+            qs = dataset.smooth_qpos(g, q, offs, 30.0, args.lowpass_hz)
+            case["lowpass_hz"] = args.lowpass_hz
+            case["max_abs_difference_device_vs_host_filtfilt"] = float((qs - qh).abs().max())
+            case["host_filtfilt_one_batch"] = {"s": round(host_s, 3), "clips": bc, "note": "device -> host, scipy.signal.filtfilt per clip, host -> device; once"}
+            fused_lowpass()
+            plain = eng.motion_track(qs, offs, 30.0, fps_out)
+            case["filtered_call_equals_plain_call_on_filtered_qpos"] = all(bool(torch.equal(out[k], plain[k])) for k in TRACK_FIELDS)
+            del qh, qs, plain
+            sides.insert(1, ("fused_lowpass", fused_lowpass))
+        for name, fn in sides:
             med, lo, hi = timed(fn, args.warmup, args.repeats)
             print(f"30 -> {fps_out:g} fps, {name}: {med:.2f} ms (median of {args.repeats})", file=sys.stderr, flush=True)
             fps = frames_out / (med * 1e-3)
             case[name] = {"ms_median": round(med, 3), "ms_min": round(lo, 3), "ms_max": round(hi, 3), "output_frames_per_s": round(fps, 1),
                           "fraction_of_8TBps_hbm": round(fps * bytes_per_frame / HBM_BYTES_PER_S, 4)}
         case["speedup_fused_over_composition"] = round(case["composition"]["ms_median"] / case["fused"]["ms_median"], 2)
+        if args.lowpass_hz is not None:
+            case["lowpass_ms_per_workload"] = round(case["fused_lowpass"]["ms_median"] - case["fused"]["ms_median"], 3)
         res["cases"].append(case)
         del out, bp, br, plan, ref
         torch.cuda.empty_cache()
