@@ -30,7 +30,8 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_group_create", "gmr_group_destroy", "gmr_group_size", "gmr_group_model", "gmr_group_last_error", "gmr_group_ik_solve",
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
-           "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients"]
+           "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
+           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts"]
 
 
 class IKParams(C.Structure):
@@ -180,6 +181,10 @@ def load():
     batch = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int, C.POINTER(IKParams), vp]  # model .. qpos_init of the three IK calls
     solve = batch + [vp, vp, vp, vp, C.POINTER(IKStats)]                                          # qpos_final .. stats
     L.gmr_ik_solve.argtypes = solve + [vp]
+    L.gmr_ik_balance_plan.restype = C.c_int
+    L.gmr_ik_balance_plan.argtypes = [vp, C.c_int, C.c_int]
+    L.gmr_ik_sliced_timeouts.restype = C.c_int
+    L.gmr_ik_sliced_timeouts.argtypes = [vp]
     L.gmr_ik_solve_ordered.argtypes = solve + [vp, vp]
     L.gmr_ik_plan_order.argtypes = batch + [C.c_int, vp, vp]
     L.gmr_group_ik_solve.argtypes = [vp, C.POINTER(GroupInput), C.POINTER(IKParams), vp]

@@ -65,6 +65,9 @@ struct gmr_model {
   std::vector<double> cap_host;       // [nv]; empty = off
   double *cap_dev = nullptr;          // allocated by the first set, rewritten in place by later ones
   const double *step_cap() const { return cap_host.empty() ? nullptr : cap_dev; }
+  // sliced launches (ik_kernel_sliced): the pinned word a wavefront that hit the poll cap sets, and the wavefront slots of the device
+  unsigned *slice_err = nullptr, *slice_err_dev = nullptr;  // allocated with the handle
+  int slots = 0;
 };
 
 // State of a single-sequence session (gmr_session_*): one frame per call, warm start carried on the device.
@@ -266,6 +269,78 @@ void launch_ik(const gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool 
 int launch_ik_variant(gmr_model *m, const gmr::IkLaunch &L, hipStream_t st, bool probe = false, bool plain = false) {
   switch (m->nvp) {
 #define GMR_X(v) case v: launch_ik<v>(m, L, st, probe, plain); break;
+    GMR_FOR_EACH_NVP(GMR_X)
+#undef GMR_X
+    default: set_err(m, "internal: no kernel variant for nvp=%d", m->nvp); return GMR_EUNSUPPORTED;
+  }
+  HIP_TRY(m, hipGetLastError());
+  return GMR_OK;
+}
+
+// The sliced launch of a plain batch (ik_kernel_sliced): `grid` = n_items x rounds one-wavefront workgroups; same choice of instance
+// as launch_ik.
+template <int NVP>
+void launch_ik_sliced(const gmr_model *m, const gmr::IkLaunch &L, const gmr::IkSliceArgs &S, unsigned grid, hipStream_t st, bool plain) {
+  const bool sq = m->dm.sq_ok && !m->force_generic;
+  const int shape = sq ? ik_launch_shape(m->shape, m->force_generic_shape, plain, L.in_f64 != 0, L.prm.offset_to_ground != 0, L.step_cap != nullptr) : -1;
+  if (getenv("GMR_DEBUG_PLAN"))
+    fprintf(stderr, "gmr: ik launch: sliced instance %s, slice %d frames, %u tickets for %d items\n", ik_shape_name(shape), S.slice_len, grid, L.n_items);
+  if (shape >= 0) {
+    int idx = 0;
+#define GMR_X(SH, v)                                                                                                                   \
+  if constexpr (NVP == v) {                                                                                                            \
+    if (shape == idx) {                                                                                                                \
+      hipLaunchKernelGGL((gmr::ik_kernel_sliced<NVP, gmr::SH>), dim3(grid), dim3(64), m->lds_bytes, st, m->dm_dev, L, m->lay, S);          \
+      return;                                                                                                                          \
+    }                                                                                                                                  \
+  }                                                                                                                                    \
+  ++idx;
+    GMR_FOR_EACH_IK_SHAPE(GMR_X)
+#undef GMR_X
+    (void)idx;
+  }
+  if (sq)
+    hipLaunchKernelGGL((gmr::ik_kernel_sliced<NVP, true>), dim3(grid), dim3(64), m->lds_bytes, st, m->dm_dev, L, m->lay, S);
+#ifndef GMR_IK_DEV_ONLY36
+  else
+    hipLaunchKernelGGL((gmr::ik_kernel_sliced<NVP, false>), dim3(grid), dim3(64), m->lds_bytes, st, m->dm_dev, L, m->lay, S);
+#endif
+}
+
+// Slice length in frames.  Swept on the headline batch (8192 x 3000 frames, profiles/sliced_slice_sweep.md): 32 / 64 / 128 / 256 / 512
+// frames take 516.3 / 515.4 / 513.6 / 518.3 / 525.3 ms against 539.0 ms for probe + ordered launch -- shorter slices shorten the
+// last round's tail, longer ones pay the per-slice set-up less often.  256, not 128: with the four-slice rule below a 128-frame
+// slice would also take the batches of 512 .. 1023 frames, for which nothing was measured and which the probe policy serves
+// (Engine.PROBE_*, measured down to 300 frames).
+constexpr int kBalanceSlice = 256;
+constexpr bool kBalanceDefault = true;          // without GMR_AMD_BALANCE: take the sliced path where the plan says it pays
+constexpr double kBalanceMaxLengthSpread = 0.10;  // "equal lengths": the band Engine.PROBE_MAX_LENGTH_SPREAD uses
+constexpr int kBalanceMinSlices = 4;            // mean item length, in slices, from which slicing pays
+// Slice length of a batch, 0 = whole-clip launch: see gmr_ik_balance_plan (gmr_amd.h).
+int balance_plan(const gmr_work_item *items, int n_items, int slots) {
+  if (!items || n_items <= 0) return 0;
+  const char *sw = getenv("GMR_AMD_BALANCE");
+  const int mode = sw && sw[0] == '0' ? 0 : sw && sw[0] == '1' ? 1 : sw && sw[0] == '2' ? 2 : (kBalanceDefault ? 2 : 0);  // 0 off, 1 forced, 2 where it pays
+  if (mode == 0) return 0;
+  int slice = kBalanceSlice;
+  if (const char *e = getenv("GMR_AMD_BALANCE_SLICE")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= INT32_MAX) slice = (int)v; }
+  double sum = 0.0, sum2 = 0.0;
+  for (int i = 0; i < n_items; ++i) {
+    const gmr_work_item &w = items[i];
+    if (w.check_stride != 0 || w.n_burn != 0 || w.init_row == GMR_INIT_ROOT_TARGET || w.n_out < 0) return 0;  // plain items only
+    sum += w.n_out; sum2 += (double)w.n_out * w.n_out;
+  }
+  if (mode == 1) return slice;
+  if (n_items <= slots) return 0;  // everything starts at once: nothing to balance
+  const double mean = sum / n_items, var = std::max(0.0, sum2 / n_items - mean * mean);
+  if (std::sqrt(var) > kBalanceMaxLengthSpread * mean) return 0;  // unequal lengths: round-robin would leave the long clips to finish alone
+  if (mean < (double)kBalanceMinSlices * slice) return 0;
+  return slice;
+}
+
+int launch_ik_sliced_variant(gmr_model *m, const gmr::IkLaunch &L, const gmr::IkSliceArgs &S, unsigned grid, hipStream_t st, bool plain) {
+  switch (m->nvp) {
+#define GMR_X(v) case v: launch_ik_sliced<v>(m, L, S, grid, st, plain); break;
     GMR_FOR_EACH_NVP(GMR_X)
 #undef GMR_X
     default: set_err(m, "internal: no kernel variant for nvp=%d", m->nvp); return GMR_EUNSUPPORTED;
@@ -1029,6 +1104,16 @@ static gmr_model *model_create_impl(const void *blob, size_t blob_bytes, int dev
   m->h = h;
   m->blob.assign(static_cast<const uint8_t *>(blob), static_cast<const uint8_t *>(blob) + blob_bytes);
   if (hipSetDevice(device) != hipSuccess) return fail(m, "hipSetDevice failed");
+  {  // what a sliced launch needs beside its per-call scratch, made here so that gmr_ik_solve allocates nothing outside its stream
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return fail(m, "hipDeviceGetAttribute failed");
+    m->slots = 8 * cus;  // two wavefronts per SIMD
+    void *d = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&m->slice_err), 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return fail(m, "hipHostMalloc failed");
+    memset(m->slice_err, 0, 64);
+    if (hipHostGetDevicePointer(&d, m->slice_err, 0) != hipSuccess) return fail(m, "hipHostGetDevicePointer failed");
+    m->slice_err_dev = static_cast<unsigned *>(d);
+  }
   m->pool = scratch_pool(device);  // (nullptr: no pool support on this runtime -- per-call scratch then comes from the device's default pool as it is)
   if (const char *e = getenv("GMR_AMD_GENERIC_QP")) m->force_generic = e[0] == '1';
   if (force_generic) m->force_generic = true;
@@ -1047,6 +1132,7 @@ void gmr_model_destroy(gmr_model *m) {
   if (!m) return;
   if (m->device >= 0) (void)hipSetDevice(m->device);
   if (m->dev) (void)hipFree(m->dev);
+  if (m->slice_err) (void)hipHostFree(m->slice_err);
   if (m->dbg) (void)hipFree(m->dbg);
   if (m->cap_dev) (void)hipFree(m->cap_dev);
   delete m;
@@ -1216,6 +1302,50 @@ static int probe_batch(gmr_group_input &in, int probe_frames, std::vector<gmr_wo
 
 enum IkMode { IK_PLAIN, IK_PROBE, IK_ORDERED };
 
+// The sliced launch of a model's own plain call, where balance_plan says so (`sliced` tells): ticket counter, `done` words and the
+// hand-over records in stream-ordered scratch, the first two cleared on the stream in front of the launch.  `sorted`: the items as
+// the launch runs them (longest first).
+static int ik_run_sliced(gmr_model *m, const gmr::IkLaunch &L, const std::vector<gmr_work_item> &sorted, hipStream_t st, CallScratch &ss,
+                         bool plain, bool &sliced) {
+  sliced = false;
+  const int n_items = (int)sorted.size();
+  const int slice = balance_plan(sorted.data(), n_items, m->slots);
+  if (slice <= 0) {
+    if (getenv("GMR_DEBUG_PLAN")) fprintf(stderr, "gmr: ik launch: whole clips (balance plan 0)\n");
+    return GMR_OK;
+  }
+  const int longest = sorted[0].n_burn + sorted[0].n_out;
+  const int64_t rounds = std::max<int64_t>(1, ((int64_t)longest + slice - 1) / slice), grid = rounds * n_items;
+  const size_t rec = (size_t)m->dm.nq + 7 * (size_t)m->dm.nbody;  // (the kernel's own tree: DevModel::nbody)
+  const size_t flag_bytes = (sizeof(unsigned) * ((size_t)n_items + 1) + 15) & ~size_t(15);  // [head | done[n_items]], cleared every call
+  const size_t lane_off = flag_bytes, state_off = lane_off + sizeof(int) * 64 * (size_t)n_items;
+  const size_t total = state_off + sizeof(double) * rec * (size_t)n_items;
+  if (grid > INT32_MAX || total > (size_t(1) << 30)) {  // (beyond one grid or 1 GiB of records: whole clips, as before)
+    if (getenv("GMR_DEBUG_PLAN")) fprintf(stderr, "gmr: ik launch: whole clips (sliced launch too large)\n");
+    return GMR_OK;
+  }
+  if (!m->slice_err_dev || m->slots <= 0) { set_err(m, "internal: the handle has no sliced-launch state"); return GMR_EDEVICE; }
+  int rc = scratch_alloc(m, ss, total, st);
+  if (rc != GMR_OK) return rc;
+  uint8_t *ws = static_cast<uint8_t *>(ss.p);
+  HIP_TRY(m, hipMemsetAsync(ws, 0, flag_bytes, st));
+  gmr::IkSliceArgs S{};
+  S.head = reinterpret_cast<unsigned *>(ws);
+  S.done = S.head + 1;
+  S.timeouts = m->slice_err_dev;
+  S.lane_state = reinterpret_cast<int *>(ws + lane_off);
+  S.state = reinterpret_cast<double *>(ws + state_off);
+  S.slice_len = slice;
+  S.rec_doubles = (int)rec;
+  // The poll cap, a guard far beyond the longest wait of a correct run.  With more items than slots a predecessor finished rounds ago; with
+  // fewer, ceil(slots / n_items) slices of one clip are resident at once and the last of them waits for the whole chain before it.  2048
+  // polls (3-4 us each) per frame waited for, against the 0.05-0.2 ms a frame takes.
+  const int64_t chain = std::max<int64_t>(1, std::min<int64_t>(rounds, ((int64_t)m->slots + n_items - 1) / n_items));
+  S.max_polls = (unsigned)std::min<int64_t>((int64_t)UINT32_MAX, ((int64_t)1 << 18) + (int64_t)2048 * slice * chain);
+  sliced = true;
+  return launch_ik_sliced_variant(m, L, S, (unsigned)grid, st, plain);
+}
+
 // Every batched IK call.  `models[i]` goes with `inputs[i]`.  With `g` NULL it is a model's own call (n = 1): ik_kernel / ik_probe_kernel
 // with the launch arguments by value; with a group, one grid of the ik_group_* kernels over all members' items -- a block finds its
 // entry in block_entry[] and its item as its global index - item_base.  Members without work get an empty entry.
@@ -1249,7 +1379,7 @@ static int ik_run(const gmr_group *g, gmr_model *const *models, const gmr_group_
     inputs = pin.data();
   }
   std::vector<CallScratch> scratch(n);
-  CallScratch ms, gs;
+  CallScratch ms, gs, ss;
   std::vector<gmr::IkGroupEntry> entries(n);
   int total = 0, lds_bytes = 0;
   for (int i = 0; i < n; ++i) {
@@ -1288,7 +1418,13 @@ static int ik_run(const gmr_group *g, gmr_model *const *models, const gmr_group_
     if (mode == IK_ORDERED) entries[0].L.perm = launch_order;
     bool plain = true;  // (the items were validated in prepare_ik_launch)
     for (const gmr_work_item &w : sorted[0]) plain = plain && w.check_stride == 0 && w.init_row != GMR_INIT_ROOT_TARGET;
-    int rc = launch_ik_variant(models[0], entries[0].L, st, mode == IK_PROBE, plain);
+    int rc = GMR_OK;
+    bool sliced = false;
+    if (mode == IK_PLAIN) {  // a plain call of equal-length clips runs as slices drawn by ticket (gmr_ik_balance_plan)
+      rc = ik_run_sliced(models[0], entries[0].L, sorted[0], st, ss, plain, sliced);
+      if (rc != GMR_OK) { err = models[0]->err; return rc; }
+    }
+    if (!sliced) rc = launch_ik_variant(models[0], entries[0].L, st, mode == IK_PROBE, plain);
     if (rc != GMR_OK) { err = models[0]->err; return rc; }
   } else {  // the entries and the block -> entry table go into stream-ordered scratch
     const size_t ent_bytes = sizeof(gmr::IkGroupEntry) * (size_t)n, be_off = (ent_bytes + 15) & ~size_t(15);
@@ -1322,6 +1458,19 @@ int gmr_ik_solve(gmr_model *m, const void *human_pos, const void *human_quat, in
   const gmr_group_input in = {human_pos, human_quat, in_dtype, n_cols, slot_col, n_frames, items, n_items, 0,
                               qpos_init, qpos_final, qpos_out, iters_out, frames_done};
   return ik_run(nullptr, &m, &in, 1, params, static_cast<hipStream_t>(stream), IK_PLAIN, 0, nullptr, nullptr, stats, m->err);
+}
+
+// Host only: the slice length gmr_ik_solve would run this batch with on a device of `slots` wavefront slots, 0 = whole clips.
+int gmr_ik_balance_plan(const gmr_work_item *items, int n_items, int slots) { return balance_plan(items, n_items, slots); }
+
+// Host only: 1 if a wavefront of a sliced launch of this handle has hit its poll cap (the item's remaining frames were not
+// written) since the last call, 0 otherwise.  Reads and clears the handle's pinned word; call it after synchronising the stream.
+int gmr_ik_sliced_timeouts(gmr_model *m) {
+  if (!m || !m->slice_err) return 0;
+  volatile unsigned *w = m->slice_err;
+  const unsigned v = *w;
+  if (v) *w = 0;
+  return v != 0;
 }
 
 // ---- launch order by predicted cost.  Items of equal length still differ in cost (solves per frame: 1.15 max / mean on the

@@ -147,6 +147,19 @@ struct IkLaunch {
   const double *step_cap;
 };
 
+// The sliced launch (ik_kernel_sliced): the fourth kernel argument.  Every pointer is per-call scratch, cleared on the stream
+// in front of the launch (head, done) or written before it is read (the records); `timeouts` is the handle's own pinned word.
+struct IkSliceArgs {
+  unsigned *head;      // the ticket counter
+  unsigned *done;      // [n_items] by sorted item: slices finished and published; kSliceGaveUp = a wavefront of the item hit the poll cap
+  unsigned *timeouts;  // host memory: set to 1 by a wavefront that gave up (gmr_ik_sliced_timeouts reads and clears it)
+  double *state;       // [n_items][rec_doubles]: q [nq], xpos [3 nbody], xquat [4 nbody] at the end of the item's last finished slice
+  int *lane_state;     // [n_items][64]: the QP's working set of every lane (sq_status / status)
+  int slice_len, rec_doubles;
+  unsigned max_polls, pad;
+};
+constexpr unsigned kSliceGaveUp = 0xffffffffu;
+
 // Opaque to the optimiser: values derived from it cannot be hoisted out of the enclosing loop.  Used on indices of
 // per-solve table look-ups so that LICM does not turn them into dozens of VGPRs that stay live across the QP.
 __device__ __forceinline__ int launder(int v) {
@@ -1155,8 +1168,55 @@ struct IkLive {
   unsigned max_polls, max_frames;
 };
 
-template <int NVP, bool SQ, bool LIVE = false, bool PROBE = false, class SH = IkShapeAny>
-__device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLayout lay, const int item, const IkLive live = IkLive{}) {
+// A slice of a plain item (ik_kernel_sliced): frames [r slice_len, (r + 1) slice_len) of sorted item `item`.  A slice that is not
+// the first RESUMES: it waits for its predecessor's record and starts from exactly the state that one ended with -- q, the poses
+// of the last stepped FK and the QP's working set of every lane; nothing else outlives a frame (e, jl_*, sum_r2 are rebuilt at
+// stage-1 entry, solves and qpflag are per frame).  The poses are carried, not recomputed: an entry FK normalises the root
+// quaternion a second time and lands up to 1 ulp beside the stepped FK's poses, and the next residual with them.
+using IkSliceK = const IkSliceArgs __attribute__((address_space(4)));
+__device__ __forceinline__ IkSliceK *ik_slice_args(IkSliceK *p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+struct IkSliceRun {
+  IkSliceK *Sk;
+  int item, r;
+};
+// The record travels between workgroups of one launch: every word is stored and loaded at agent scope (write-through stores,
+// loads that bypass this CU's L1), behind a release fence and the `done` word on the one side, an acquire on the other.
+__device__ __forceinline__ double slice_ld(const double *p) {
+  return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const u64 *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+__device__ __forceinline__ void slice_st(double *p, double v) {
+  __hip_atomic_store(reinterpret_cast<u64 *>(p), (u64)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Wait until `r` slices of the item are published.  Tickets are drawn by running wavefronts only, so the slice waited for was
+// drawn earlier by a wavefront that runs or has finished: the wait ends by construction, and max_polls only guards against a
+// broken protocol.  On the cap the item is marked (its later slices then leave at once) and a word in host memory is set.
+__device__ __forceinline__ bool slice_wait(IkSliceK *Sk, int item, int r, int lane) {
+  unsigned *done = ik_slice_args(Sk)->done + item;
+  const unsigned max_polls = ik_slice_args(Sk)->max_polls;
+  unsigned d;
+  for (unsigned polls = 0;;) {
+    d = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    if (d >= (unsigned)r) break;
+    if (++polls >= max_polls) {
+      if (lane == 0) {
+        __hip_atomic_store(done, kSliceGaveUp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ik_slice_args(Sk)->timeouts, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // (a store, as the session's mailbox: no PCIe atomic)
+      }
+      return false;
+    }
+    __builtin_amdgcn_s_sleep(100);
+  }
+  if (d == kSliceGaveUp) return false;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  return true;
+}
+
+template <int NVP, bool SQ, bool LIVE = false, bool PROBE = false, class SH = IkShapeAny, bool SLICED = false>
+__device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLayout lay, const int item, const IkLive live = IkLive{},
+                                        const IkSliceRun sl = IkSliceRun{}) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
   double *q = lds + lay.q, *xpos = lds + lay.xpos, *xquat = lds + lay.xquat, *tp = lds + lay.tp, *tq = lds + lay.tq;
@@ -1226,8 +1286,27 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
     if (sc && sq_own) sq_cap = sc[sq_g];
   }
   int sq_status = 0;
-  for (int i = lane; i < nq; i += 64) q[i] = w.init_row >= 0 ? Lk->qinit[(size_t)w.init_row * nq + i] : m.qpos0[i];
+  int slice_ls = 0;  // SLICED, resumed: this lane's word of the record
+  if constexpr (SLICED) {
+    if (sl.r > 0) {  // wave-uniform: resume from the predecessor's record
+      if (!slice_wait(sl.Sk, sl.item, sl.r, lane)) return;
+      IkSliceK *Sa = ik_slice_args(sl.Sk);
+      const double *rec = Sa->state + (size_t)sl.item * Sa->rec_doubles;
+      for (int i = lane; i < nq; i += 64) q[i] = slice_ld(rec + i);
+      for (int i = lane; i < 3 * nbody; i += 64) xpos[i] = slice_ld(rec + nq + i);
+      for (int i = lane; i < 4 * nbody; i += 64) xquat[i] = slice_ld(rec + nq + 3 * nbody + i);
+      slice_ls = __hip_atomic_load(Sa->lane_state + (size_t)sl.item * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (SQ) sq_status = slice_ls;
+    } else {
+      for (int i = lane; i < nq; i += 64) q[i] = w.init_row >= 0 ? Lk->qinit[(size_t)w.init_row * nq + i] : m.qpos0[i];
+    }
+  } else {
+    for (int i = lane; i < nq; i += 64) q[i] = w.init_row >= 0 ? Lk->qinit[(size_t)w.init_row * nq + i] : m.qpos0[i];
+  }
   int status = real_row ? 0 : 3;
+  if constexpr (SLICED && !SQ) {
+    if (sl.r > 0) status = slice_ls;
+  }
   __syncthreads();
   const double hscale = w.height_scale != 0.0 ? w.height_scale : 1.0;  // per-clip human height factor (gmr_blob.h)
 
@@ -1235,14 +1314,19 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   unsigned live_last = 0, live_seq = 0;
   bool live_otg = false;
   if constexpr (LIVE) live_last = (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(&live.box->ack, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
-  bool poses_valid = false;
+  bool poses_valid = SLICED && sl.r > 0;
+  int kf0 = 0, kend = nfr;  // SLICED: this slice's frames
+  if constexpr (SLICED) {
+    kf0 = sl.r * ik_slice_args(sl.Sk)->slice_len;
+    kend = min(nfr, kf0 + ik_slice_args(sl.Sk)->slice_len);
+  }
   // Verification walk (check_stride > 0, gmr_blob.h): the item runs down a clip whose chunks were already solved
   // speculatively.  At every chunk boundary the state is compared with the state B that chunk started its output from: equal
   // -> the chunk's stored frames are what a sequential run would produce, adopt its stored final state F and skip it;
   // different -> solve the chunk here, from the true state.  kc = chunk index, left = frames left in the chunk being solved.
-  int out_done = 0, kc = 0, left = 0;
+  int out_done = SLICED ? kf0 : 0, kc = 0, left = 0;  // (a sliced item has no burn-in: the frames before this slice are output frames)
   int cost_acc = 0;  // PROBE: solves spent on this item
-  for (int kf = 0; kf < nfr; ++kf) {
+  for (int kf = kf0; kf < kend; ++kf) {
     if constexpr (LIVE) {  // wait for the host's next frame (every value made wave-uniform: the loop must not diverge)
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
       unsigned polls = 0;
@@ -1655,6 +1739,25 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       live_last = live_seq;
     }
   }
+  if constexpr (SLICED) {
+    if (kend < nfr) {  // wave-uniform: not the item's last slice -- hand the state over instead of finishing the item
+      IkSliceK *Sa = ik_slice_args(sl.Sk);
+      double *rec = Sa->state + (size_t)sl.item * Sa->rec_doubles;
+      for (int i = lane; i < nq; i += 64) slice_st(rec + i, q[i]);
+      for (int i = lane; i < 3 * nbody; i += 64) slice_st(rec + nq + i, xpos[i]);
+      for (int i = lane; i < 4 * nbody; i += 64) slice_st(rec + nq + 3 * nbody + i, xquat[i]);
+      __hip_atomic_store(Sa->lane_state + (size_t)sl.item * 64 + lane, SQ ? sq_status : status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // Every store of this wavefront has left before the release, and the release has completed before the word that publishes it.
+      // The two waits are explicit on purpose: the fence's own wait is the compiler's to place, and it has been seen to drop it where
+      // it believes an earlier wait covers the stores; these pin the order record -> write-back -> done word in the instruction stream.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0) __hip_atomic_store(Sa->done + sl.item, (unsigned)sl.r + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      GMR_STAMP_FLUSH();
+      return;
+    }
+  }
   {
     IkLaunchK *Le = ik_args(Lk);
     int *fdone = Le->frames_done;
@@ -1690,6 +1793,37 @@ __global__ void __launch_bounds__(64, GMR_IK_WAVES_PER_SIMD) ik_kernel(const Dev
   const int item = perm ? __builtin_amdgcn_readfirstlane(perm[blockIdx.x]) : (int)blockIdx.x;
   if ((unsigned)item >= (unsigned)Lk->n_items) return;
   ik_body<NVP, true, false, false, SH>(*(DevModelG *)mp, Lk, lay, item);
+}
+
+// The sliced launch: n_items x n_rounds one-wavefront workgroups, each of which draws a ticket h and runs slice h / n_items of
+// sorted item h % n_items (longest first, as ik_kernel runs them): round-robin over the items, so that equal-length items
+// advance at the same pace and finish in the same last round whatever they cost.  The order comes from the ticket, not from
+// blockIdx.x: a ticket is only ever drawn by a running wavefront, so whatever a wavefront waits for (slice_wait) was drawn
+// earlier by one that runs or has finished -- no assumption about the dispatcher's order or the spread over XCDs.  A ticket
+// past its item's end leaves at once.
+constexpr int kSliceArgOff = (8 + (int)sizeof(IkLaunch) + (int)sizeof(LdsLayout) + 7) & ~7;  // IkSliceArgs in the kernarg segment
+static_assert(alignof(IkLaunch) == 8 && sizeof(IkLaunch) % 8 == 0 && alignof(LdsLayout) == 4 && alignof(IkSliceArgs) == 8, "kernarg layout of ik_kernel_sliced");
+template <int NVP, bool SQ, class SH>
+__device__ __forceinline__ void ik_sliced_item(const DevModel *mp, const LdsLayout lay) {
+  const char __attribute__((address_space(4))) *ka = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+  IkLaunchK *Lk = (IkLaunchK *)(ka + 8);
+  IkSliceK *Sk = (IkSliceK *)(ka + kSliceArgOff);
+  unsigned h = 0;
+  if (threadIdx.x == 0) h = __hip_atomic_fetch_add(Sk->head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  h = (unsigned)__builtin_amdgcn_readfirstlane((int)h);
+  const unsigned n = (unsigned)Lk->n_items;
+  const int item = (int)(h % n), r = (int)(h / n);
+  const int nfr = Lk->items[item].n_burn + Lk->items[item].n_out;
+  if (r > 0 && (long long)r * Sk->slice_len >= (long long)nfr) return;  // (slice 0 always runs: an empty item still reports frames_done = 0 and its state)
+  ik_body<NVP, SQ, false, false, SH, true>(*(DevModelG *)mp, Lk, lay, item, IkLive{}, IkSliceRun{Sk, item, r});
+}
+template <int NVP, bool SQ>
+__global__ void __launch_bounds__(64, SQ ? GMR_IK_WAVES_PER_SIMD : 1) ik_kernel_sliced(const DevModel *__restrict__ mp, IkLaunch L, LdsLayout lay, IkSliceArgs S) {
+  ik_sliced_item<NVP, SQ, IkShapeAny>(mp, lay);
+}
+template <int NVP, class SH>
+__global__ void __launch_bounds__(64, GMR_IK_WAVES_PER_SIMD) ik_kernel_sliced(const DevModel *__restrict__ mp, IkLaunch L, LdsLayout lay, IkSliceArgs S) {
+  ik_sliced_item<NVP, true, SH>(mp, lay);
 }
 
 // The probe in front of an ordered launch (gmr_ik_plan_order): the first frames of every item, solved for their cost only --

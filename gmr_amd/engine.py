@@ -88,14 +88,15 @@ def _ik_batch(eng: "Engine", pos: torch.Tensor, quat: torch.Tensor, slot_col, it
     return pos, quat, slot_col, items, out, iters, qpos_init, qfin
 
 
-def _launch_order(eng: "Engine", launch_order, item_arrays, plan):
+def _launch_order(eng: "Engine", launch_order, item_arrays, plan, sliced: bool = False):
     """What an ``ik_solve`` launches by: ``None`` or a checked order tensor.  ``item_arrays``: the work items of the launch (one array per
-    model); ``"auto"`` asks ``eng``'s probe policy about all of them together and has ``plan(probe_frames)`` make the order."""
+    model); ``"auto"`` asks ``eng``'s probe policy about all of them together and has ``plan(probe_frames)`` make the order.  ``sliced``:
+    the launch is a model's own ``gmr_ik_solve``, which may cut the batch into slices instead (a group launch never does)."""
     total = sum(len(it) for it in item_arrays)
     if isinstance(launch_order, str):
         if launch_order != "auto":
             raise EngineError("launch_order must be a tensor, None or 'auto'")
-        pf = eng._probe_frames(np.concatenate(item_arrays))
+        pf = eng._probe_frames(np.concatenate(item_arrays), sliced=sliced)
         launch_order = plan(pf) if pf else None
     if launch_order is not None and (not isinstance(launch_order, torch.Tensor) or launch_order.dtype != torch.int32
                                      or launch_order.device != eng.device or not launch_order.is_contiguous() or launch_order.numel() != total):
@@ -493,6 +494,10 @@ class Engine:
         ``launch_order``: an int32 device tensor from :meth:`plan_order`, ``None`` (array order, longer items first) or ``"auto"``
         -- plan an order when that pays: more plain items than wavefront slots, long enough for the probe to be a small fraction of
         the work (``PROBE_*`` below).  The order only moves work in time; results are identical.
+        A plain batch of equal-length clips may run as slices instead (``gmr_ik_balance_plan``; same results).  A slice that gives up
+        waiting -- a guard that a correct run never reaches -- leaves the rest of its clip unwritten (NaN rows in a fresh ``out``) and
+        sets a word that this method checks, without synchronising, at the START of the next call: it raises for an earlier launch that
+        has already finished that way.  To check one call, synchronise and read :attr:`sliced_timeouts` (1 = it happened; reading clears).
         """
         pos, quat, slot_col, items, out, iters, qpos_init, qfin = _ik_batch(
             self, pos, quat, slot_col, items, out=out, iters=iters, want_iters=want_iters, qpos_init=qpos_init, qpos_final=qpos_final,
@@ -503,8 +508,10 @@ class Engine:
         self.last_stats = stats
         if N == 0 or len(items) == 0:  # nothing to launch (empty tensors have no device pointer)
             return out, iters, qfin
+        if self.sliced_timeouts:  # (a word in host memory: no device call)
+            raise EngineError("an earlier sliced ik_solve launch of this engine gave up waiting for a slice: the rest of that clip was not written")
         launch_order = _launch_order(self, launch_order, [items],
-                                     lambda pf: self.plan_order(pos, quat, slot_col, items, prm, qpos_init, probe_frames=pf))
+                                     lambda pf: self.plan_order(pos, quat, slot_col, items, prm, qpos_init, probe_frames=pf), sliced=True)
         args = (self._h, _ptr(pos), _ptr(quat), _native.GMR_DTYPE_F64 if pos.dtype == torch.float64 else _native.GMR_DTYPE_F32, B,
                 slot_col.ctypes.data_as(C.c_void_p), N, items.ctypes.data_as(C.c_void_p), len(items), C.byref(prm), _ptr(qpos_init), _ptr(qfin),
                 _ptr(out), _ptr(iters), _ptr(frames_done), C.byref(stats))
@@ -531,11 +538,15 @@ class Engine:
     PROBE_MIN_LENGTH_EQUAL = 64      # mean item length from which a probe pays: equal lengths ...
     PROBE_MIN_LENGTH = 1000          # ... and lengths that differ
 
-    def _probe_frames(self, items: np.ndarray) -> int:
-        """Frames of every item to probe before an ``launch_order="auto"`` launch; 0 = launch in length order without a probe."""
+    def _probe_frames(self, items: np.ndarray, sliced: bool = True) -> int:
+        """Frames of every item to probe before an ``launch_order="auto"`` launch; 0 = launch in length order without a probe.
+        ``sliced``: the launch is this engine's own ``gmr_ik_solve`` (``ik_solve``, ``bench.py``), which slices the batches
+        ``gmr_ik_balance_plan`` names and needs no order for them; group launches run whole clips and pass ``False``."""
         if len(items) == 0 or np.any(items["check_stride"] != 0) or np.any(items["n_burn"] > 0):
             return 0  # walks cannot be probed; speculative chunks (burn-in) are short and alike within a clip: 1.84e7 -> 1.69e7 frames/s with a probe
         slots = 8 * torch.cuda.get_device_properties(self.device).multi_processor_count  # two wavefronts per SIMD
+        if sliced and self.balance_plan(items, slots) > 0:
+            return 0  # gmr_ik_solve cuts this batch into slices drawn by ticket: no order to plan, no probe
         if len(items) <= self.PROBE_MIN_ITEMS_PER_SLOT * slots:
             return 0
         ln = (items["n_burn"] + items["n_out"]).astype(np.float64)
@@ -545,6 +556,17 @@ class Engine:
                 return 0
             return self.PROBE_FRAMES if mean >= self.PROBE_SHORT_BELOW else self.PROBE_FRAMES_SHORT
         return self.PROBE_FRAMES if mean >= self.PROBE_MIN_LENGTH else 0
+
+    def balance_plan(self, items: np.ndarray, slots: int) -> int:
+        """``gmr_ik_balance_plan``: the slice length ``gmr_ik_solve`` would run ``items`` with on ``slots`` wavefront slots, 0 = whole clips."""
+        items = np.ascontiguousarray(items, dtype=_native.WORK_ITEM_DTYPE)
+        return int(self._lib.gmr_ik_balance_plan(items.ctypes.data_as(C.c_void_p), len(items), int(slots)))
+
+    @property
+    def sliced_timeouts(self) -> int:
+        """``gmr_ik_sliced_timeouts``: 1 if a sliced launch of this engine gave up waiting since the last look (synchronise first), else 0;
+        reading clears it.  ``ik_solve`` looks at every call and raises for an earlier launch that did."""
+        return int(self._lib.gmr_ik_sliced_timeouts(self._h))
 
     def _order_pays(self, items: np.ndarray) -> bool:
         return self._probe_frames(items) > 0

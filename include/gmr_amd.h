@@ -150,6 +150,24 @@ int gmr_ik_solve(gmr_model *m, const void *human_pos, const void *human_quat, in
                  const gmr_ik_params *params, const double *qpos_init, double *qpos_final, double *qpos_out,
                  int32_t *iters_out, int32_t *frames_done, gmr_ik_stats *stats, void *stream);
 
+/* How gmr_ik_solve launches a batch: whole clips, one wavefront each from start to end, or -- plain clips of (nearly) equal
+ * length, more of them than the device has wavefront slots -- cut into slices of a fixed number of frames that wavefronts draw
+ * round-robin by ticket, the full solver state handed from slice to slice exactly, so that all clips advance at the same pace and
+ * finish in the same last round whatever each costs.  Results are bit-identical either way.
+ * gmr_ik_balance_plan is that choice as a pure host function (no device, no stream): the slice length in frames, or 0 for whole
+ * clips.  Nonzero when every item is plain (no check_stride, no burn-in, no GMR_INIT_ROOT_TARGET start), n_items > slots (wavefront
+ * slots of the device: 8 per compute unit), the standard deviation of the item lengths is at most 10 % of their mean, and the mean
+ * is at least four slices.  Environment: GMR_AMD_BALANCE=0 never slices, GMR_AMD_BALANCE=1 slices every plain batch,
+ * GMR_AMD_BALANCE=2 applies the rule above (the default, where DESIGN.md 8 says so), GMR_AMD_BALANCE_SLICE=<frames> overrides the
+ * slice length.  gmr_ik_solve_ordered and the group calls always run whole clips.
+ * gmr_ik_sliced_timeouts: a waiting slice polls a bounded number of times; the bound only guards against a broken protocol.  A
+ * wavefront that reaches it writes no frame and ends, as do the later slices of its clip (their rows of qpos_out and
+ * frames_done stay as the caller left them), and this function -- host only, call it after synchronising the stream -- returns 1 if
+ * that happened on the handle since its last call (it clears the word), else 0.  The cap grows with the slice length and with
+ * the number of slices of one clip that can be resident at once, so a correct run stays orders of magnitude below it. */
+int gmr_ik_balance_plan(const gmr_work_item *items, int n_items, int slots);
+int gmr_ik_sliced_timeouts(gmr_model *m);
+
 /* Launch order by predicted cost.  Work items start in array order (gmr_ik_solve puts longer items first); items of EQUAL
  * length still differ in cost -- solves per frame -- and with a few items per wavefront slot the start order decides how long the
  * last ones run alone (8192 clips x 3000 frames: 608 ms in array order, 549 ms most-expensive-first).
