@@ -31,7 +31,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
-           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts"]
+           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts"]
 
 
 class IKParams(C.Structure):
@@ -100,6 +100,23 @@ class SampleInput(C.Structure):
         ("time_dtype", C.c_int32), ("out_dtype", C.c_int32), ("n_queries", C.c_int64),
         ("body_ids", C.c_void_p), ("n_sel", C.c_int32), ("reserved", C.c_int32),
     ] + [(k + "_out", C.c_void_p) for k in TRACK_OUTPUTS]
+
+
+CONTACT_GROUND_FIXED, CONTACT_GROUND_CLIP_MIN = 0, 1   # GMR_CONTACT_GROUND_* (include/gmr_amd.h)
+CONTACT_MAX_BODIES = 64
+CONTACT_OUTPUTS = ("contact", "frames", "touchdowns", "slide_sum", "slide_step_max", "depth_max", "airborne_frames", "base")  # gmr_contact_input's output pointers, in order
+
+
+class ContactInput(C.Structure):
+    """``gmr_contact_input`` (include/gmr_amd.h): the whole call of the contact labels, its stream included."""
+
+    _fields_ = [
+        ("body_pos_w", C.c_void_p), ("body_lin_vel_w", C.c_void_p), ("n_rows", C.c_int64), ("out_offsets", C.c_void_p),
+        ("body_ids", C.c_void_p), ("height_offset", C.c_void_p), ("n_seq", C.c_int32), ("n_contact", C.c_int32),
+        ("ground_mode", C.c_int32), ("reserved", C.c_int32), ("ground_z", C.c_double),
+        ("height_on", C.c_double), ("height_off", C.c_double), ("speed_on", C.c_double), ("speed_off", C.c_double),
+        ("stream", C.c_void_p),
+    ] + [(k + "_out", C.c_void_p) for k in CONTACT_OUTPUTS]
 
 
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
@@ -222,6 +239,8 @@ def load():
     L.gmr_lowpass_coefficients.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double)]
     L.gmr_motion_sample.restype = C.c_int
     L.gmr_motion_sample.argtypes = [vp, C.POINTER(SampleInput), vp]
+    L.gmr_motion_contacts.restype = C.c_int
+    L.gmr_motion_contacts.argtypes = [vp, C.POINTER(ContactInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

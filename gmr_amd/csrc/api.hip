@@ -31,6 +31,7 @@
 #include "lowpass_kernel.hip.h"
 #include "sample_kernel.hip.h"
 #include "report_kernel.hip.h"
+#include "contact_kernel.hip.h"
 #include "bvh_text.h"
 
 using gmr::u64;
@@ -2232,6 +2233,45 @@ int gmr_motion_sample(gmr_model *m, const gmr_sample_input *in, void *stream) {
   hipLaunchKernelGGL(gmr::motion_sample_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, static_cast<hipStream_t>(stream), a);
   if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
   return GMR_OK;
+}
+
+// ------------------------------------------------------------------ contact labels (contact_kernel.hip.h)
+// The launch of gmr_motion_contacts: one kernel, one wavefront per clip, and nothing else -- every array is a device array and
+// everything else travels in the kernel's argument.
+static int contact_run(gmr_model *m, const gmr_contact_input &in, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::ContactArgs a{};
+  a.pos = in.body_pos_w; a.vel = in.body_lin_vel_w;
+  a.out_offsets = in.out_offsets; a.body_ids = in.body_ids; a.height_offset = in.height_offset;
+  a.n_rows = in.n_rows;
+  a.nbody = m->fk.nbody; a.n_contact = in.n_contact; a.clip_min = in.ground_mode == GMR_CONTACT_GROUND_CLIP_MIN;
+  a.ground_z = in.ground_z; a.height_on = in.height_on; a.height_off = in.height_off;
+  a.speed_on2 = in.speed_on * in.speed_on; a.speed_off2 = in.speed_off * in.speed_off;
+  a.contact = in.contact_out; a.frames = in.frames_out; a.touchdowns = in.touchdowns_out;
+  a.slide_sum = in.slide_sum_out; a.slide_step_max = in.slide_step_max_out; a.depth_max = in.depth_max_out;
+  a.airborne = in.airborne_frames_out; a.base = in.base_out;
+  hipLaunchKernelGGL(gmr::motion_contacts_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_contacts(gmr_model *m, const gmr_contact_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_rows < 0 || in->n_seq < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (in->n_contact < 1) { set_err(m, "n_contact must be at least 1"); return GMR_EINVAL; }
+  if (in->n_contact > gmr::kContactMaxCols) { set_err(m, "at most %d contact bodies per call", gmr::kContactMaxCols); return GMR_EUNSUPPORTED; }
+  if (in->ground_mode != GMR_CONTACT_GROUND_FIXED && in->ground_mode != GMR_CONTACT_GROUND_CLIP_MIN) { set_err(m, "unknown ground_mode"); return GMR_EINVAL; }
+  if (!std::isfinite(in->height_on) || !std::isfinite(in->height_off) || !std::isfinite(in->speed_on) || !std::isfinite(in->speed_off)) {
+    set_err(m, "the contact thresholds must be finite"); return GMR_EINVAL;
+  }
+  if (in->height_on > in->height_off) { set_err(m, "height_on must not exceed height_off"); return GMR_EINVAL; }
+  if (in->speed_on < 0.0 || in->speed_on > in->speed_off) { set_err(m, "0 <= speed_on <= speed_off is required"); return GMR_EINVAL; }
+  if (in->ground_mode == GMR_CONTACT_GROUND_FIXED && !std::isfinite(in->ground_z)) { set_err(m, "ground_z must be finite"); return GMR_EINVAL; }
+  if (in->n_rows == 0 || in->n_seq == 0) return GMR_OK;
+  if (!in->body_pos_w || !in->body_lin_vel_w || !in->out_offsets || !in->body_ids) { set_err(m, "null argument"); return GMR_EINVAL; }
+  return contact_run(m, *in, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

@@ -82,7 +82,8 @@ def motions_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_off
 def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30,
                    height_adjust: bool = True, root_origin_offset: bool = True, chunk: int = 0, burn_in: int = 0,
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
-                   track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None):
+                   track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
+                   contact_bodies: Optional[Sequence[str]] = None, contact=None):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -90,7 +91,10 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     ``engine.ClipReport`` of the solved qpos (``GeneralMotionRetargeting.clip_report``, solve counts included), host arrays.
     With ``track_fps`` a last value is added: the clips' tracking dicts at that rate (``tracking_from_qpos`` on the same qpos).
     With ``lowpass_hz`` the solved qpos is smoothed once (``smooth_qpos`` at ``fps``), and the motions, the report and the tracks
-    are all made from the smoothed qpos."""
+    are all made from the smoothed qpos.  ``contact_bodies`` / ``contact`` (with ``track_fps``): ``tracking_from_qpos``'s contact
+    labels on the tracking dicts."""
+    if contact_bodies is not None and track_fps is None:
+        raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
     tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
     tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
     tpos, tquat = tpos.to(gmr.device), tquat.to(gmr.device)
@@ -108,7 +112,7 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
         rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
         res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset), rep.numpy())
     if track_fps is not None:
-        res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps),)
+        res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps, contact_bodies=contact_bodies, contact=contact),)
     return res[0] if len(res) == 1 else res
 
 
@@ -117,21 +121,70 @@ TRACK_ARRAYS = ("joint_pos", "joint_vel", "root_pos", "root_rot", "root_lin_vel"
                 "body_pos_w", "body_quat_w", "body_lin_vel_w", "body_ang_vel_w")
 
 
-def tracks_to_host(tracks, fps_out, body_names, joint_names) -> List[List[Dict]]:
+CONTACT_STATS = ("frames", "touchdowns", "slide_sum", "slide_step_max", "depth_max", "base")  # the keys of a clip's contact_stats
+
+
+class ContactParams:
+    """The parameters of the contact labels of ``tracking_from_qpos`` (``Engine.motion_contacts``): a body is in contact from a
+    frame at or below ``height_on`` (m above the ground) and ``speed_on`` (m/s) until one above ``height_off`` or ``speed_off``.
+    ``ground``: ``"clip_min"`` (every clip is measured against the lowest contact-body height it reaches) or the ground height;
+    ``height_offset``: one height per contact body of its origin above its own sole (``None``: zeros).  The default thresholds
+    -- enter at 0.03 m and 0.3 m/s, leave at 0.05 m and 0.6 m/s -- are conventions from common practice, not measured on any
+    robot here."""
+
+    def __init__(self, height_on: Optional[float] = None, height_off: Optional[float] = None, speed_on: Optional[float] = None,
+                 speed_off: Optional[float] = None, ground="clip_min", height_offset=None):
+        from .engine import CONTACT_DEFAULTS as d   # (None: the engine's default)
+        given = {"height_on": height_on, "height_off": height_off, "speed_on": speed_on, "speed_off": speed_off}
+        self.height_on, self.height_off, self.speed_on, self.speed_off = (float(d[k] if v is None else v) for k, v in given.items())
+        self.ground, self.height_offset = ground, height_offset
+
+    def kwargs(self) -> Dict:
+        return {"height_on": self.height_on, "height_off": self.height_off, "speed_on": self.speed_on, "speed_off": self.speed_off,
+                "ground": self.ground, "height_offset": self.height_offset}
+
+
+def contact_body_ids(model_body_names, contact_bodies: Sequence[str]) -> List[int]:
+    """The body indices of a list of body names; an unknown name raises ``KeyError`` listing the model's names."""
+    names = list(model_body_names)
+    missing = [b for b in contact_bodies if b not in names]
+    if missing:
+        raise KeyError(f"unknown contact bodies {missing}; the model's bodies are {names}")
+    return [names.index(b) for b in contact_bodies]
+
+
+def _track_contacts(eng, track, model_body_names, contact_bodies, contact: Optional[ContactParams]):
+    """One contacts launch on a ``MotionTrack``: (``engine.MotionContacts``, the names)."""
+    ids = contact_body_ids(model_body_names, contact_bodies)
+    prm = contact if contact is not None else ContactParams()
+    return eng.motion_contacts(track, track.out_offsets, ids, **prm.kwargs()), list(contact_bodies)
+
+
+def tracks_to_host(tracks, fps_out, body_names, joint_names, contacts=None) -> List[List[Dict]]:
     """Several ``engine.MotionTrack`` results (one per robot) to the host with every copy in flight before the one
-    synchronisation; per result the list of per-clip dicts of ``tracking_from_qpos``."""
-    hosts = []
+    synchronisation; per result the list of per-clip dicts of ``tracking_from_qpos``.  ``contacts``: per result ``None`` or
+    (``engine.MotionContacts``, contact body names) -- its copies ride in the same synchronisation and every clip's dict also
+    gets ``contact``, ``contact_body_names``, ``contact_stats`` and ``airborne_frames``."""
+    hosts, chosts = [], []
     dev = None
-    for tr in tracks:
+    contacts = [None] * len(tracks) if contacts is None else list(contacts)
+    for tr, ct in zip(tracks, contacts):
         host = {k: torch.empty(tr[k].shape, dtype=tr[k].dtype, pin_memory=True) for k in TRACK_ARRAYS}
         for k, h in host.items():
             h.copy_(tr[k], non_blocking=True)
             dev = tr[k].device
         hosts.append({k: h.numpy() for k, h in host.items()})
+        if ct is None:
+            chosts.append(None)
+            continue
+        chost = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in ct[0].items()}
+        for k, h in chost.items():
+            h.copy_(ct[0][k], non_blocking=True)
+        chosts.append({k: h.numpy() for k, h in chost.items()})
     if dev is not None:
         torch.cuda.current_stream(dev).synchronize()
     out = []
-    for tr, host, bn, jn in zip(tracks, hosts, body_names, joint_names):
+    for tr, host, bn, jn, ct, chost in zip(tracks, hosts, body_names, joint_names, contacts, chosts):
         offs, bn, jn = tr.out_offsets, list(bn), list(jn)
         clips = []
         for s in range(len(offs) - 1):
@@ -139,24 +192,39 @@ def tracks_to_host(tracks, fps_out, body_names, joint_names) -> List[List[Dict]]
             d = {"fps": fps_out}
             d.update((k, host[k][a:b]) for k in TRACK_ARRAYS)
             d.update(body_names=bn, joint_names=jn, quat_order="xyzw")
+            if ct is not None:
+                stats = {k: chost[k][s] for k in CONTACT_STATS}
+                d.update(contact=chost["contact"][a:b], contact_body_names=list(ct[1]), contact_stats=stats,
+                         airborne_frames=int(chost["airborne_frames"][s]))
             clips.append(d)
         out.append(clips)
     return out
 
 
 def tracking_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, fps_out,
-                       lowpass_hz: Optional[float] = None) -> List[Dict]:
+                       lowpass_hz: Optional[float] = None, contact_bodies: Optional[Sequence[str]] = None,
+                       contact: Optional[ContactParams] = None) -> List[Dict]:
     """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) -> one tracking dict per clip
     at ``fps_out`` (``Engine.motion_track``, one launch): ``fps``, ``joint_pos``, ``joint_vel``, ``root_pos``, ``root_rot`` (xyzw),
     ``root_lin_vel``, ``root_ang_vel`` (world frame) in float64, ``body_pos_w``, ``body_quat_w`` (xyzw), ``body_lin_vel_w``,
     ``body_ang_vel_w`` in float32, ``body_names``, ``joint_names`` (the hinges in qpos order) and ``quat_order = "xyzw"``.
     The arrays are row slices of batch-sized page-locked host arrays, as ``motions_from_qpos`` hands them out.  ``lowpass_hz``:
-    the cutoff of the zero-phase low-pass applied to qpos first, in the same call (``None``: off)."""
+    the cutoff of the zero-phase low-pass applied to qpos first, in the same call (``None``: off).
+    ``contact_bodies``: body names (the feet) whose contact with the ground is labelled on the export, one more kernel
+    (``Engine.motion_contacts``); every clip's dict then also holds ``contact`` (uint8 ``[M_s, C]``, 1 = on the ground),
+    ``contact_body_names``, ``contact_stats`` -- ``frames``, ``touchdowns`` (int32 ``[C]``), ``slide_sum``, ``slide_step_max``,
+    ``depth_max`` (float64 ``[C]``, metres: how far a planted body slides in all and in one frame, how deep it goes below the
+    ground) and ``base`` (float64: the ground height the clip was measured against) -- and ``airborne_frames`` (frames with no
+    body in contact).  ``contact``: a :class:`ContactParams` (thresholds, ground, height offsets); the defaults are conventions
+    from common practice, not measured on any robot.  An unknown body name raises ``KeyError`` listing the model's names."""
     if gmr.model.planar_base:
         raise NotImplementedError("the tracking export assumes a free-joint root; use retarget_batch for a planar-base robot")
     from .engine import _report_names
+    if contact_bodies is not None:
+        contact_body_ids(gmr.model.body_names, contact_bodies)  # (an unknown name: before any launch)
     track = gmr._engine.motion_track(qpos, seq_offsets, fps, fps_out, lowpass_hz=0.0 if lowpass_hz is None else lowpass_hz)
-    return tracks_to_host([track], fps_out, [gmr.model.body_names], [_report_names(gmr._cm)[1]])[0]
+    contacts = None if contact_bodies is None else [_track_contacts(gmr._engine, track, gmr.model.body_names, contact_bodies, contact)]
+    return tracks_to_host([track], fps_out, [gmr.model.body_names], [_report_names(gmr._cm)[1]], contacts=contacts)[0]
 
 
 def smooth_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, lowpass_hz) -> torch.Tensor:
@@ -310,23 +378,37 @@ class MotionLibrary:
 
 def save_tracking(path: str, track: Dict, override: bool = False) -> bool:
     """One tracking dict as an uncompressed ``.npz`` (``np.savez``); like ``save_motion``, an existing file is skipped unless
-    ``override``.  Names and ``quat_order`` are stored as unicode arrays, ``fps`` as a float64 scalar."""
+    ``override``.  Names and ``quat_order`` are stored as unicode arrays, ``fps`` as a float64 scalar.  A dict with contact
+    labels (``tracking_from_qpos(..., contact_bodies=...)``) also stores ``contact``, ``contact_body_names``, one array
+    ``contact_stats_<key>`` per statistic and ``airborne_frames``, behind the other arrays; without them the file is what it
+    always was."""
     if os.path.exists(path) and not override:
         return False
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    extra = {}
+    if "contact" in track:
+        extra = {"contact": track["contact"], "contact_body_names": np.asarray(list(track["contact_body_names"]), dtype=np.str_),
+                 "airborne_frames": np.int32(track["airborne_frames"])}
+        extra.update(("contact_stats_" + k, np.asarray(track["contact_stats"][k])) for k in CONTACT_STATS)
     with open(path, "wb") as f:  # (a file object: np.savez appends nothing to the name)
         np.savez(f, fps=np.float64(track["fps"]), body_names=np.asarray(list(track["body_names"]), dtype=np.str_),
                  joint_names=np.asarray(list(track["joint_names"]), dtype=np.str_), quat_order=np.asarray(track["quat_order"]),
-                 **{k: track[k] for k in TRACK_ARRAYS})
+                 **{k: track[k] for k in TRACK_ARRAYS}, **extra)
     return True
 
 
 def load_tracking(path: str) -> Dict:
-    """Read a ``save_tracking`` file back: the same keys, arrays as written, names as lists, ``fps`` a float."""
+    """Read a ``save_tracking`` file back: the same keys, arrays as written, names as lists, ``fps`` a float; the contact keys
+    when the file holds them (``airborne_frames`` an int, ``base`` of ``contact_stats`` a float64 scalar)."""
     with np.load(path, allow_pickle=False) as z:
         d = {k: z[k] for k in TRACK_ARRAYS}
         d.update(fps=float(z["fps"]), body_names=[str(n) for n in z["body_names"]], joint_names=[str(n) for n in z["joint_names"]],
                  quat_order=str(z["quat_order"]))
+        if "contact" in z.files:
+            stats = {k: z["contact_stats_" + k] for k in CONTACT_STATS}
+            stats["base"] = np.float64(stats["base"])
+            d.update(contact=z["contact"], contact_body_names=[str(n) for n in z["contact_body_names"]], contact_stats=stats,
+                     airborne_frames=int(z["airborne_frames"]))
     return d
 
 

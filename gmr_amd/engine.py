@@ -287,6 +287,94 @@ def _sample_input(eng: "Engine", qpos, seq_offsets_dev, fps_dev, ids, times, k_p
     return si, MotionSample(res), (qpos, seq_offsets_dev, fps_dev, ids, times, bodies)
 
 
+CONTACT_FIELDS = _native.CONTACT_OUTPUTS   # the arrays of the contact labels, in gmr_contact_input's order
+# Thresholds of the contact labels when none are given: conventions from common practice (enter at 3 cm and 0.3 m/s, leave at
+# 5 cm and 0.6 m/s), not measured on any robot here.
+CONTACT_DEFAULTS = {"height_on": 0.03, "height_off": 0.05, "speed_on": 0.3, "speed_off": 0.6}
+
+
+class MotionContacts(dict):
+    """Result of ``motion_contacts``: the device tensors by name (``CONTACT_FIELDS``): ``contact`` uint8 ``[M, C]``, ``frames`` and
+    ``touchdowns`` int32 ``[S, C]``, ``slide_sum`` (m), ``slide_step_max`` (m) and ``depth_max`` (m) float64 ``[S, C]``,
+    ``airborne_frames`` int32 ``[S]``, ``base`` float64 ``[S]`` (the ground height the clip was measured against)."""
+
+
+def _contact_input(eng: "Engine", track_or_arrays, out_offsets, body_ids, height_offset, ground, height_on, height_off,
+                   speed_on, speed_off, out):
+    """Check the arguments of one contacts call and fill its ``ContactInput`` (all but the stream).  Returns (input,
+    MotionContacts, keep-alive)."""
+    dev = eng.device
+    if isinstance(track_or_arrays, dict):
+        pos, vel = track_or_arrays.get("body_pos_w"), track_or_arrays.get("body_lin_vel_w")
+        if out_offsets is None:
+            out_offsets = getattr(track_or_arrays, "out_offsets", None)
+    else:
+        pos, vel = track_or_arrays
+    for t in (pos, vel):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.dim() != 3 \
+                or tuple(t.shape[1:]) != (eng.nbody, 3) or not t.is_contiguous():
+            raise EngineError(f"body_pos_w and body_lin_vel_w must be contiguous float32 [M, {eng.nbody}, 3] tensors on the engine's device")
+    M = int(pos.shape[0])
+    if int(vel.shape[0]) != M:
+        raise EngineError("body_pos_w and body_lin_vel_w must hold the same rows")
+    if out_offsets is None:
+        raise EngineError("out_offsets is needed with plain arrays")
+    if isinstance(out_offsets, torch.Tensor):
+        offs = out_offsets
+        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
+            raise EngineError("out_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
+    else:
+        o = np.ascontiguousarray(out_offsets, dtype=np.int64)
+        if o.ndim != 1 or o.size < 1:
+            raise ValueError("out_offsets must hold n_seq + 1 entries")
+        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    S = int(offs.shape[0]) - 1
+    if isinstance(body_ids, torch.Tensor):
+        ids = body_ids
+        if ids.device != dev or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+            raise EngineError("body_ids must be a contiguous 1-D int32 tensor of body indices on the engine's device (or a host sequence)")
+    else:
+        b = np.ascontiguousarray(body_ids, dtype=np.int32)
+        if b.ndim != 1 or (b.size and (b.min() < 0 or b.max() >= eng.nbody)):
+            raise ValueError(f"body_ids must be body indices in [0, {eng.nbody})")
+        ids = torch.from_numpy(b).to(dev)
+    Cn = int(ids.shape[0])
+    keep = [pos, vel, offs, ids]
+    ci = _native.ContactInput()
+    if height_offset is not None:
+        ho = height_offset if isinstance(height_offset, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(height_offset, dtype=np.float64))
+        ho = ho.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(ho.shape) != (Cn,):
+            raise EngineError("height_offset must hold one height per contact body")
+        ci.height_offset = ho.data_ptr()
+        keep.append(ho)
+    if isinstance(ground, str):
+        if ground != "clip_min":
+            raise ValueError("ground must be 'clip_min' or the ground height")
+        ci.ground_mode, ci.ground_z = _native.CONTACT_GROUND_CLIP_MIN, 0.0
+    else:
+        ci.ground_mode, ci.ground_z = _native.CONTACT_GROUND_FIXED, float(ground)
+    f64, i32 = torch.float64, torch.int32
+    shapes = {"contact": ((M, Cn), torch.uint8), "frames": ((S, Cn), i32), "touchdowns": ((S, Cn), i32), "slide_sum": ((S, Cn), f64),
+              "slide_step_max": ((S, Cn), f64), "depth_max": ((S, Cn), f64), "airborne_frames": ((S,), i32), "base": ((S,), f64)}
+    if out is None:
+        # zeros: rows outside every clip are not written, and a call without rows launches nothing (every clip is empty then)
+        res = {k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}
+        if M == 0 and S > 0:
+            res["base"].fill_(float("nan") if isinstance(ground, str) else float(ground))
+    else:
+        res = {k: out[k] for k in CONTACT_FIELDS if k in out}
+        if set(out) - set(CONTACT_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                                 or t.device != dev or not t.is_contiguous() for k, t in res.items()):
+            raise EngineError("out must map names of CONTACT_FIELDS to contiguous tensors of the call's shapes on the engine's device")
+    ci.body_pos_w, ci.body_lin_vel_w, ci.n_rows = pos.data_ptr(), vel.data_ptr(), M
+    ci.out_offsets, ci.body_ids, ci.n_seq, ci.n_contact = offs.data_ptr(), ids.data_ptr(), S, Cn
+    ci.height_on, ci.height_off, ci.speed_on, ci.speed_off = float(height_on), float(height_off), float(speed_on), float(speed_off)
+    for k, t in res.items():
+        setattr(ci, k + "_out", t.data_ptr())
+    return ci, MotionContacts(res), keep
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -876,6 +964,27 @@ class Engine:
         with ``out``, no copy, no synchronisation."""
         si, res, keep = _sample_input(self, qpos, seq_offsets_dev, fps_dev, ids, times, k_per_id, bodies, fields, out, dtype)
         self._check(self._lib.gmr_motion_sample(self._h, C.byref(si), self._stream()), "gmr_motion_sample")
+        return res
+
+    def motion_contacts(self, track_or_arrays, out_offsets=None, body_ids=(), height_offset=None, ground="clip_min",
+                        height_on: float = CONTACT_DEFAULTS["height_on"], height_off: float = CONTACT_DEFAULTS["height_off"],
+                        speed_on: float = CONTACT_DEFAULTS["speed_on"], speed_off: float = CONTACT_DEFAULTS["speed_off"],
+                        out=None) -> MotionContacts:
+        """Foot-contact labels and slide statistics of a tracking export in one kernel (``gmr_motion_contacts``; the definition
+        is the contract in include/gmr_amd.h).  ``track_or_arrays``: a :class:`MotionTrack` (or any dict with ``body_pos_w`` and
+        ``body_lin_vel_w``), or the pair ``(body_pos_w, body_lin_vel_w)`` of float32 ``[M, nbody, 3]`` device tensors.
+        ``out_offsets`` ``[S + 1]``: the clips' rows, a host sequence (uploaded once) or a device int64 tensor; ``None`` takes a
+        MotionTrack's own.  ``body_ids``: the C <= 64 contact bodies, a host sequence of body indices (range-checked here) or a
+        device int32 tensor (trusted).  ``height_offset`` ``[C]``: height of each body origin above its own sole (``None``:
+        zeros).  ``ground``: ``"clip_min"`` measures every clip against the lowest contact-body height it reaches, a number is
+        the ground height.  A body is in contact from a frame at or below ``height_on`` and ``speed_on`` until one above
+        ``height_off`` or ``speed_off``; the defaults (3 cm and 0.3 m/s, 5 cm and 0.6 m/s) are conventions from common practice,
+        not measured on any robot.  Returns a :class:`MotionContacts` of device tensors; ``out``: caller-owned result tensors by
+        name (a name left out is not computed).  Asynchronous on the current stream."""
+        ci, res, keep = _contact_input(self, track_or_arrays, out_offsets, body_ids, height_offset, ground, height_on, height_off,
+                                       speed_on, speed_off, out)
+        ci.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.gmr_motion_contacts(self._h, C.byref(ci)), "gmr_motion_contacts")
         return res
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,

@@ -179,11 +179,15 @@ class MultiRobotRetargeting:
         return out
 
     def tracking_from_qpos(self, qpos: Dict[str, torch.Tensor], seq_offsets: Sequence[int], fps, fps_out,
-                           lowpass_hz=None) -> Dict[str, List[Dict]]:
+                           lowpass_hz=None, contact_bodies: Optional[Dict[str, Sequence[str]]] = None,
+                           contact=None) -> Dict[str, List[Dict]]:
         """``dataset.tracking_from_qpos`` for every robot in one launch (``EngineGroup.motion_track``): ``qpos[robot]`` ``[N, nq]``
         float64 on the group's device, the same clips (at ``fps``: one rate or one per clip) for every robot -> ``{robot:
         [tracking dict per clip]}`` at ``fps_out``, the same keys, dtypes and arrays as the single-robot call.  ``lowpass_hz``:
-        the cutoff of the zero-phase low-pass applied to qpos first (``None``: off); one value, or one per robot."""
+        the cutoff of the zero-phase low-pass applied to qpos first (``None``: off); one value, or one per robot.
+        ``contact_bodies``: ``{robot: [body names]}`` -- the contact labels of ``dataset.tracking_from_qpos`` for the robots it
+        names, one ``Engine.motion_contacts`` launch per robot behind the shared export (there is no group entry); ``contact``:
+        one ``dataset.ContactParams`` for all, or ``{robot: ContactParams}``."""
         from . import dataset
         from .engine import _report_names
         self._refuse_planar()
@@ -191,26 +195,41 @@ class MultiRobotRetargeting:
         missing = [r for r in self.robots if r not in qpos]
         if missing:
             raise KeyError(f"no qpos for {missing}")
+        contacts = None
+        if contact_bodies is not None:
+            unknown = [r for r in contact_bodies if r not in self.robots]
+            if unknown:
+                raise KeyError(f"contact_bodies names robots that are not solved here: {unknown}")
+            for r, m in zip(self.robots, self.models):
+                if r in contact_bodies:
+                    dataset.contact_body_ids(m.body_names, contact_bodies[r])  # (an unknown name: before any launch)
         batches = []
         for r in self.robots:
             q = qpos[r]
             q = torch.from_numpy(np.ascontiguousarray(q)).to(self.device) if isinstance(q, np.ndarray) else q
             batches.append((q, offs, fps))
         res = self.group.motion_track(batches, fps_out, lowpass_hz=0.0 if lowpass_hz is None else lowpass_hz)
-        clips = dataset.tracks_to_host(res, fps_out, [m.body_names for m in self.models], [_report_names(cm)[1] for cm in self._cms])
+        if contact_bodies is not None:
+            contacts = [dataset._track_contacts(eng, tr, m.body_names, contact_bodies[r], contact.get(r) if isinstance(contact, dict) else contact)
+                        if r in contact_bodies else None for r, eng, m, tr in zip(self.robots, self.group.engines, self.models, res)]
+        clips = dataset.tracks_to_host(res, fps_out, [m.body_names for m in self.models], [_report_names(cm)[1] for cm in self._cms],
+                                       contacts=contacts)
         return dict(zip(self.robots, clips))
 
     def retarget_clips(self, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30, height_adjust: bool = True,
                        root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
                        clip_start: str = "qpos0", report: bool = False, track_fps: Optional[float] = None,
-                       lowpass_hz: Optional[float] = None):
+                       lowpass_hz: Optional[float] = None, contact_bodies: Optional[Dict[str, Sequence[str]]] = None, contact=None):
         """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
         solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
         ``dataset.MotionWriter.submit`` as they are.  With ``report`` a second value is returned: ``{robot: engine.ClipReport}``
         of the solved qpos (:meth:`clip_report`, solve counts included), host arrays.  With ``track_fps`` a last value is added:
         ``{robot: [tracking dict per clip]}`` at that rate (:meth:`tracking_from_qpos` on the same qpos).  With ``lowpass_hz``
-        every robot's solved qpos is smoothed once (``dataset.smooth_qpos`` at ``fps``) and everything is made from that."""
+        every robot's solved qpos is smoothed once (``dataset.smooth_qpos`` at ``fps``) and everything is made from that.
+        ``contact_bodies`` / ``contact`` (with ``track_fps``): :meth:`tracking_from_qpos`'s contact labels."""
         self._refuse_planar()
+        if contact_bodies is not None and track_fps is None:
+            raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
         tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
         tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
         tpos, tquat = tpos.to(self.device), tquat.to(self.device)
@@ -226,7 +245,8 @@ class MultiRobotRetargeting:
                                          root_origin_offset=root_origin_offset)
         res = (motions, {r: rep.numpy() for r, rep in reps.items()}) if report else (motions,)
         if track_fps is not None:
-            res += (self.tracking_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, track_fps),)
+            res += (self.tracking_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, track_fps,
+                                            contact_bodies=contact_bodies, contact=contact),)
         return res[0] if len(res) == 1 else res
 
     def _solve(self, pos, quat, body_names, seq_offsets, chunk, burn_in, offset_to_ground, verify, human_heights, check, clip_start):

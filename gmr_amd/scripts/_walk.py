@@ -101,6 +101,11 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--track_fps", default=None, type=float, help="with --track_folder: also write every clip's tracking export (resampled root, joints and world body poses with their velocities, dataset.tracking_from_qpos) at this rate")
     ap.add_argument("--track_folder", default=None, type=str, help="with --track_fps: where the tracking exports go, <track_folder>/<relative path>.npz (with --robots <track_folder>/<robot>/...); the pickles are unchanged")
     ap.add_argument("--lowpass_hz", default=None, type=float, metavar="HZ", help="smooth the solved qpos once with a zero-phase 2nd-order Butterworth low-pass at this cutoff (dataset.smooth_qpos, on the GPU) before the report, the pickles and the tracking exports are made; default: off")
+    ap.add_argument("--contact_bodies", default=None, type=str, metavar="A,B", help="with --track_fps: label these bodies' contact with the ground on every tracking export (contact, contact_stats, airborne_frames in the .npz; dataset.tracking_from_qpos); with --robots: robot:a,b;robot2:c,d")
+    ap.add_argument("--contact_height_on", default=None, type=float, metavar="M", help="a body enters contact at or below this height above the clip's lowest contact height (default 0.03, a convention, not measured on any robot)")
+    ap.add_argument("--contact_height_off", default=None, type=float, metavar="M", help="... and leaves it above this height (default 0.05)")
+    ap.add_argument("--contact_speed_on", default=None, type=float, metavar="M_PER_S", help="a body enters contact at or below this speed (default 0.3)")
+    ap.add_argument("--contact_speed_off", default=None, type=float, metavar="M_PER_S", help="... and leaves it above this speed (default 0.6)")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -112,6 +117,47 @@ def resolve_track(ap, args) -> None:
         ap.error("--track_fps must be positive")
     if getattr(args, "lowpass_hz", None) is not None and not args.lowpass_hz > 0:
         ap.error("--lowpass_hz must be positive")
+    resolve_contact(ap, args)
+
+
+_CONTACT_THRESHOLDS = ("height_on", "height_off", "speed_on", "speed_off")
+
+
+def resolve_contact(ap, args) -> None:
+    """``--contact_bodies`` needs ``--track_fps``; sets ``args.contact_kw``: the ``contact_bodies`` / ``contact`` arguments of
+    ``retarget_clips`` (empty without the flag: nothing changes then).  One robot: ``a,b``; ``--robots``: ``robot:a,b;robot2:c,d``."""
+    args.contact_kw = {}
+    given = [k for k in _CONTACT_THRESHOLDS if getattr(args, "contact_" + k, None) is not None]
+    spec = getattr(args, "contact_bodies", None)
+    if spec is None:
+        if given:
+            ap.error("--contact_" + given[0] + " needs --contact_bodies")
+        return
+    if args.track_fps is None:
+        ap.error("--contact_bodies is only valid with --track_fps")
+    names = lambda text: [n.strip() for n in text.split(",") if n.strip()]
+    robots = getattr(args, "robot_list", None)
+    if robots is None:
+        if ":" in spec or ";" in spec:
+            ap.error("--contact_bodies takes a,b for one robot (robot:a,b;robot2:c,d goes with --robots)")
+        bodies = names(spec)
+        if not bodies:
+            ap.error("--contact_bodies needs at least one body name")
+    else:
+        bodies = {}
+        for part in (p for p in spec.split(";") if p.strip()):
+            robot, sep, rest = part.partition(":")
+            robot = robot.strip()
+            if not sep or robot not in robots or robot in bodies or not names(rest):
+                ap.error("--contact_bodies with --robots takes robot:a,b;robot2:c,d, each robot one of --robots and named once")
+            bodies[robot] = names(rest)
+        if not bodies:
+            ap.error("--contact_bodies needs at least one robot:a,b group")
+    from ..dataset import ContactParams
+    prm = ContactParams(**{k: getattr(args, "contact_" + k) for k in given})
+    if not (prm.height_on <= prm.height_off and 0 <= prm.speed_on <= prm.speed_off):
+        ap.error("--contact_height_on <= --contact_height_off and 0 <= --contact_speed_on <= --contact_speed_off are required")
+    args.contact_kw = {"contact_bodies": bodies, "contact": prm}
 
 
 def track_path(args, target: str) -> str:
@@ -181,6 +227,7 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         track_kw = {}if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
         if getattr(args, "lowpass_hz", None) is not None:
             track_kw["lowpass_hz"] = args.lowpass_hz
+        track_kw.update(getattr(args, "contact_kw", {}))
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -217,6 +264,7 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
     track_kw = {} if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
     if getattr(args, "lowpass_hz", None) is not None:
         track_kw["lowpass_hz"] = args.lowpass_hz
+    track_kw.update(getattr(args, "contact_kw", {}))
     with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
         for batch in batches([s for s, _ in pairs], mr.ik_columns):
             for f, why in batch.skipped:

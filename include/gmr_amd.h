@@ -53,6 +53,8 @@
  *                      trains a tracking policy: resampling to the controller's rate, world body poses, velocities
  *   gmr_motion_sample  (the reference's KinematicsModel in a trainer's loop: interpolation plus a torch loop over bodies per query)
  *                      the reference state of (clip, time) queries against a library of retargeted clips kept as qpos
+ *   gmr_motion_contacts  (no counterpart in the reference) the per-frame foot-contact labels a tracking / AMP pipeline computes
+ *                      from the export in a host loop, and the foot-slide and ground-penetration figures of a retargeted clip
  *   gmr_dof_to_rot     KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -410,6 +412,69 @@ typedef struct gmr_sample_input {
   float *body_lin_vel_w_out, *body_ang_vel_w_out;               /* [Q][n_sel][3] f32 */
 } gmr_sample_input;
 int gmr_motion_sample(gmr_model *m, const gmr_sample_input *in, void *stream);
+
+/* Foot-contact labels and slide statistics of a tracking export: which of C chosen bodies are on the ground in which frame --
+ * near the ground, slow, with hysteresis -- and per clip how far a planted body slides and how deep it goes below the ground.
+ * All arithmetic below is done as written, in float64, without floating-point contraction.
+ *
+ * Inputs, all device arrays; the call enqueues one kernel and nothing else: no allocation, no copy, no synchronisation.  The
+ * whole call is this struct, its stream included (in->stream: the call's stream, in the sense of the stream-order paragraph at
+ * the top of this file); the struct is read completely before the call returns.
+ *   body_pos_w, body_lin_vel_w  float32 [n_rows][nbody][3]: what gmr_motion_track wrote, or any arrays of that shape (M = n_rows)
+ *   out_offsets                 int64 [n_seq+1]: clip s owns the rows a = clamp(out_offsets[s], 0, M) to
+ *                               b = clamp(out_offsets[s+1], a, M), M_s = b - a.  The kernel only clamps.
+ *   body_ids                    int32 [C], C = n_contact, 1 <= C <= 64.  Trusted, as in gmr_motion_sample.
+ *   height_offset               float64 [C], or NULL for all zeros: the height of the body origin above its own sole
+ *   ground_mode, ground_z       GMR_CONTACT_GROUND_FIXED or GMR_CONTACT_GROUND_CLIP_MIN; the ground height of the fixed mode
+ *   height_on, height_off, speed_on, speed_off   the thresholds, metres and metres per second
+ * Per clip s, frame k = 0 .. M_s-1 (row g = a + k), contact column c (body j = body_ids[c]):
+ *   hc = (double)body_pos_w[g][j][2] - height_offset[c]
+ *   base_s = ground_z in the fixed mode.  In the CLIP_MIN mode the minimum of hc over all k and all c of the clip: NaN when
+ *            any hc is NaN (torch.min's rule, the one gmr_fk_min_height follows); +-inf take part as values.
+ *   h = hc - base_s;  s2 = (vx vx + vy vy) + vz vz of the promoted body_lin_vel_w[g][j]
+ *   enter = h <= height_on && s2 <= speed_on * speed_on;  stay = h <= height_off && s2 <= speed_off * speed_off
+ *   the label starts at c_{-1} = 0; then c_k = 1 when enter, 0 when !stay, and c_{k-1} otherwise.
+ * Every comparison with a NaN is false: a non-finite frame is off, and a clip with a NaN base_s is off everywhere.
+ * Outputs, any may be NULL; d_k = sqrt(dx dx + dy dy) with dx = (double)x_k - (double)x_{k-1} and dy likewise:
+ *   contact_out [n_rows][C] u8           c_k, 0 or 1
+ *   frames_out [n_seq][C] i32            sum of c_k over the clip
+ *   touchdowns_out [n_seq][C] i32        number of k with c_k = 1 and c_{k-1} = 0
+ *   slide_sum_out [n_seq][C] f64         sum of d_k over k >= 1 with c_k = c_{k-1} = 1
+ *   slide_step_max_out [n_seq][C] f64    sqrt of the maximum of (dx dx + dy dy) over the same k; 0 when there is none
+ *   depth_max_out [n_seq][C] f64         running r = 0; r = (base_s - hc_k) > r ? (base_s - hc_k) : r
+ *   airborne_frames_out [n_seq] i32      number of k with c_k = 0 in every column
+ *   base_out [n_seq] f64                 base_s; for M_s = 0 in the CLIP_MIN mode it is NaN
+ * A clip without frames reports 0 everywhere else.  Nothing crosses a clip.  A non-finite element changes no output of another
+ * clip; within its own clip in the fixed mode it changes only its own column, plus airborne_frames.  Rows outside every clip
+ * are not written.  slide_sum is reduced in a fixed order (64-frame tiles, added tile by tile): a report is bit-reproducible.
+ * GMR_EINVAL: a threshold that is not finite, height_on > height_off, speed_on < 0, speed_on > speed_off, C < 1, an unknown
+ * mode, a non-finite ground_z in the fixed mode, NULL inputs with M > 0, negative counts.  GMR_EUNSUPPORTED: C > 64.  M = 0 or
+ * n_seq = 0 returns GMR_OK without a launch.  Asynchronous on in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 176; offsets body_pos_w 0, body_lin_vel_w 8, n_rows 16, out_offsets 24, body_ids 32, height_offset 40,
+ * n_seq 48, n_contact 52, ground_mode 56, reserved 60, ground_z 64, height_on 72, height_off 80, speed_on 88, speed_off 96,
+ * stream 104, contact_out 112, frames_out 120, touchdowns_out 128, slide_sum_out 136, slide_step_max_out 144,
+ * depth_max_out 152, airborne_frames_out 160, base_out 168.  */
+#define GMR_CONTACT_GROUND_FIXED 0
+#define GMR_CONTACT_GROUND_CLIP_MIN 1
+typedef struct gmr_contact_input {
+  const float   *body_pos_w;      /* device [n_rows][nbody][3] f32 */
+  const float   *body_lin_vel_w;  /* device [n_rows][nbody][3] f32 */
+  int64_t        n_rows;
+  const int64_t *out_offsets;     /* DEVICE [n_seq+1] */
+  const int32_t *body_ids;        /* device [n_contact] body indices */
+  const double  *height_offset;   /* device [n_contact], or NULL = zeros */
+  int32_t        n_seq, n_contact;
+  int32_t        ground_mode, reserved;
+  double         ground_z;
+  double         height_on, height_off, speed_on, speed_off;
+  void          *stream;          /* the call's stream */
+  uint8_t       *contact_out;
+  int32_t       *frames_out, *touchdowns_out;
+  double        *slide_sum_out, *slide_step_max_out, *depth_max_out;
+  int32_t       *airborne_frames_out;
+  double        *base_out;
+} gmr_contact_input;
+int gmr_motion_contacts(gmr_model *m, const gmr_contact_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
