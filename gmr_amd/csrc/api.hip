@@ -33,6 +33,7 @@
 #include "report_kernel.hip.h"
 #include "contact_kernel.hip.h"
 #include "bvh_text.h"
+#include "call_block.h"
 
 using gmr::u64;
 
@@ -129,18 +130,6 @@ bool range_ok(const gmr_blob_header &h, uint32_t off, size_t bytes) {
   return off >= sizeof(gmr_blob_header) && (off & 7u) == 0 && (size_t)off + bytes <= h.total_bytes;
 }
 
-// Packs host arrays into one device image, remembering where each one went.
-struct Packer {
-  std::vector<uint8_t> buf;
-  template <class T>
-  size_t add(const std::vector<T> &v) {
-    size_t off = (buf.size() + 15) & ~size_t(15);
-    buf.resize(off + std::max<size_t>(v.size(), 1) * sizeof(T));
-    if (!v.empty()) memcpy(buf.data() + off, v.data(), v.size() * sizeof(T));
-    return off;
-  }
-};
-
 // Per-call scheduling data (work items, slot columns, clip offsets) lives in stream-ordered memory: allocated on the call's
 // stream and released on it right behind the launch that reads it.  Calls on the same handle from different streams or host
 // threads therefore never share (or pull away) each other's launch metadata; the pool keeps released blocks for reuse
@@ -180,6 +169,50 @@ int scratch_alloc(const gmr_model *m, CallScratch &sc, size_t bytes, hipStream_t
   return GMR_OK;
 }
 int scratch_alloc(gmr_model *m, CallScratch &sc, size_t bytes, hipStream_t st) { return scratch_alloc(m, sc, bytes, st, m->err); }
+
+// The members of a member-wise call (motion_run, track_run, report_run): a group's models, or one model as a group of one.
+// Errors land in `err`; a group call names the member in its messages.
+struct Members {
+  gmr_model *const *models;
+  int n, device;
+  bool group;
+  std::string &err;
+  std::string who(int i) const { return group ? "member " + std::to_string(i) + ": " : ""; }
+};
+
+// The single form (m) and the group form (g) of a member-wise entry: `run` takes the Members.
+template <class In, class Run>
+int member_call(gmr_model *m, gmr_group *g, const In *inputs, Run run) {
+  if (!m && !g) return GMR_EINVAL;
+  std::string &err = g ? g->err : m->err;
+  err.clear();
+  if (!inputs) { err = g ? "null inputs" : "null input"; return GMR_EINVAL; }
+  if (g) return run(Members{g->models.data(), (int)g->models.size(), g->device, true, err});
+  return run(Members{&m, 1, m->device, false, err});
+}
+
+// The HIP half of a call block (call_block.h): one stream-ordered allocation (from the first member's pool), then `fill`, which
+// writes into the host image what needs the block's device address, then one copy of the uploaded prefix.
+template <class Fill>
+int send_call_block(const Members &g, gmr::CallBlock &blk, CallScratch &sc, hipStream_t st, Fill fill) {
+  gmr_model *m0 = g.models[0];
+  if (scratch_alloc(m0, sc, blk.total_bytes(), st) != GMR_OK) { g.err = m0->err; return GMR_EDEVICE; }
+  const int rc = fill(blk.on(sc.p));
+  if (rc != GMR_OK) return rc;
+  if (hipMemcpyAsync(sc.p, blk.image(), blk.uploaded_bytes(), hipMemcpyHostToDevice, st) != hipSuccess) { g.err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+// The rules of a clip-offset table [n_seq + 1] over n_frames rows, NULL or what is wrong: the table's ends, clip s, all of it.
+const char *seq_ends_error(const int64_t *offs, int n_seq, int64_t n_frames) {
+  return !offs || n_seq < 1 || offs[0] != 0 || offs[n_seq] != n_frames ? "seq_offsets must run from 0 to n_frames" : nullptr;
+}
+const char *seq_clip_error(const int64_t *offs, int s) { return offs[s + 1] < offs[s] ? "seq_offsets must not decrease" : nullptr; }
+const char *seq_offsets_error(const int64_t *offs, int n_seq, int64_t n_frames) {
+  const char *why = seq_ends_error(offs, n_seq, n_frames);
+  for (int s = 0; !why && s < n_seq; ++s) why = seq_clip_error(offs, s);
+  return why;
+}
 
 // Kernel variants by padded system size.  GMR_IK_DEV_ONLY36 (experiments only, never the shipped library) builds just
 // ik_kernel<36, true> to cut compile time.
@@ -976,12 +1009,14 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   m->shape = ik_shape_of(dm, m->nvp, dm.sq_ok && !m->force_generic);
   if (host_only) return GMR_OK;
 
-  Packer P;
-  const size_t o_dm = P.add(std::vector<gmr::DevModel>(1));
-  const size_t o_dm_eval = P.add(dm_eval_v);
-  const size_t o_parent = P.add(v_parent);
-  const size_t o_dofidx = P.add(dofidx), o_src = P.add(src_slot), o_save = P.add(save_slot);
-  const size_t o_lpos = P.add(lpos), o_lrot = P.add(lrot), o_jaxis = P.add(jaxis), o_jaxis64 = P.add(jaxis64);
+  // the model image: every array holds at least one element, so that no two tables share an address
+  gmr::CallBlock P;
+  const auto o_dm = P.uploaded<gmr::DevModel>(1);
+  const auto o_dm_eval = P.put(dm_eval_v, 1);
+  const auto o_parent = P.put(v_parent, 1);
+  const auto o_dofidx = P.put(dofidx, 1), o_src = P.put(src_slot, 1), o_save = P.put(save_slot, 1);
+  const auto o_lpos = P.put(lpos, 1), o_lrot = P.put(lrot, 1), o_jaxis = P.put(jaxis, 1);
+  const auto o_jaxis64 = P.put(jaxis64, 1);
   std::vector<gmr::FkBody> fkbody(nb);
   for (int b = 0; b < nb; ++b) {
     gmr::FkBody &r = fkbody[b];
@@ -990,7 +1025,7 @@ int build_device_model(gmr_model *m, bool host_only = false) {
     for (int i = 0; i < 3; ++i) { r.lpos[i] = lpos[3 * b + i]; r.axis[i] = jaxis64[3 * b + i]; }
     for (int i = 0; i < 4; ++i) r.lrot[i] = lrot[4 * b + i];
   }
-  const size_t o_fkbody = P.add(fkbody);
+  const auto o_fkbody = P.put(fkbody, 1);
   // kin_ops tables: hinge -> body, float32 limits, tree level of every body, bodies by level
   const int ndof_k = nq - 7;
   std::vector<int> k_dof_body(ndof_k, 0);
@@ -1002,34 +1037,33 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   for (int b = 1; b < nb; ++b) { k_depth[b] = (uint8_t)(k_depth[parent[b]] + 1); k_maxd = std::max<int>(k_maxd, k_depth[b]); }
   std::iota(k_order.begin(), k_order.end(), (uint8_t)0);
   std::stable_sort(k_order.begin(), k_order.end(), [&](uint8_t a, uint8_t b) { return k_depth[a] < k_depth[b]; });
-  const size_t o_kdb = P.add(k_dof_body), o_klo = P.add(k_lo), o_khi = P.add(k_hi), o_kdepth = P.add(k_depth),
-               o_korder = P.add(k_order);
+  const auto o_kdb = P.put(k_dof_body, 1);
+  const auto o_klo = P.put(k_lo, 1), o_khi = P.put(k_hi, 1);
+  const auto o_kdepth = P.put(k_depth, 1), o_korder = P.put(k_order, 1);
   // clip report: float64 limits of every hinge in qpos order, infinite where the hinge is unlimited
   std::vector<double> rep_lo(ndof_k, -INFINITY), rep_hi(ndof_k, INFINITY);
   for (int b = 1; b < nb; ++b)
     if (jtype[b] == GMR_JNT_HINGE && limited[b]) { rep_lo[qadr[b] - 7] = range[2 * b]; rep_hi[qadr[b] - 7] = range[2 * b + 1]; }
-  const size_t o_replo = P.add(rep_lo), o_rephi = P.add(rep_hi);
+  const auto o_replo = P.put(rep_lo, 1), o_rephi = P.put(rep_hi, 1);
 
-  HIP_TRY(m, hipMalloc(&m->dev, P.buf.size()));
-  m->dev_bytes = P.buf.size();
-  const uint8_t *D = static_cast<const uint8_t *>(m->dev);
-#define DP(T, off) reinterpret_cast<const T *>(D + (off))
-  m->dm_dev = DP(gmr::DevModel, o_dm);
-  m->dm_eval_dev = DP(gmr::DevModel, o_dm_eval);
+  HIP_TRY(m, hipMalloc(&m->dev, P.total_bytes()));
+  m->dev_bytes = P.total_bytes();
+  const gmr::CallBlock::Device D = P.on(m->dev);
+  m->dm_dev = D(o_dm);
+  m->dm_eval_dev = D(o_dm_eval);
   gmr::FkTree &fk = m->fk;
-  fk.parent = DP(int, o_parent); fk.dofidx = DP(int, o_dofidx); fk.src_slot = DP(int, o_src); fk.save_slot = DP(int, o_save);
-  fk.lpos = DP(float, o_lpos); fk.lrot = DP(float, o_lrot); fk.jaxis = DP(float, o_jaxis); fk.jaxis64 = DP(double, o_jaxis64); fk.body = DP(gmr::FkBody, o_fkbody);
+  fk.parent = D(o_parent); fk.dofidx = D(o_dofidx); fk.src_slot = D(o_src); fk.save_slot = D(o_save);
+  fk.lpos = D(o_lpos); fk.lrot = D(o_lrot); fk.jaxis = D(o_jaxis); fk.jaxis64 = D(o_jaxis64); fk.body = D(o_fkbody);
   fk.nbody = nb; fk.ndof = nq - 7; fk.nslots = nslots;
-  m->kin.dof_body = DP(int, o_kdb); m->kin.lim_lo = DP(float, o_klo); m->kin.lim_hi = DP(float, o_khi);
-  m->kin.depth = DP(uint8_t, o_kdepth); m->kin.order = DP(uint8_t, o_korder);
+  m->kin.dof_body = D(o_kdb); m->kin.lim_lo = D(o_klo); m->kin.lim_hi = D(o_khi);
+  m->kin.depth = D(o_kdepth); m->kin.order = D(o_korder);
   m->kin.max_depth = k_maxd;
-  m->rep_lo = DP(double, o_replo); m->rep_hi = DP(double, o_rephi);
+  m->rep_lo = D(o_replo); m->rep_hi = D(o_rephi);
   fk.dof_in_order = 1;
   for (int b = 0, prev = -1; b < nb; ++b)
     if (dofidx[b] >= 0) { if (dofidx[b] < prev) fk.dof_in_order = 0; prev = dofidx[b]; }
-#undef DP
-  memcpy(P.buf.data() + o_dm, &dm, sizeof(dm));
-  HIP_TRY(m, hipMemcpy(m->dev, P.buf.data(), P.buf.size(), hipMemcpyHostToDevice));
+  *P[o_dm] = dm;
+  HIP_TRY(m, hipMemcpy(m->dev, P.image(), P.uploaded_bytes(), hipMemcpyHostToDevice));
   // branch slots + dof tile + position / rotation stages (fk_kernel.hip.h)
   m->fk_lds_bytes = (std::max(1, nslots) * 7 + gmr::kFkPosStride + gmr::kFkRotStride) * gmr::kFkThreads * (int)sizeof(float);
   m->fk_lds_bytes_min = std::max(1, nslots) * 7 * gmr::kFkThreads * (int)sizeof(float);
@@ -1921,21 +1955,26 @@ int gmr_fk_min_height(gmr_model *m, const float *root_pos, const float *root_rot
 }
 
 // ------------------------------------------------------------------ dataset epilogue (motion_kernel.hip.h)
-// Validate every member with work, upload the entries, clip offsets and minimum keys in one block of stream-ordered scratch,
-// and run pass 1 over all members' tiles in one grid, pass 2 (height adjust, decoded minima) in a second when any member needs it.
-// `models[i]` goes with `inputs[i]`; a group call names the member in its messages.  Errors land in `err`.
-static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, int n, int device, hipStream_t st, bool group, std::string &err) {
+// Validate every member with work, send the entries, clip offsets and minimum keys in one call block ("the call
+// block"), and run pass 1 over all members' tiles in one grid, pass 2 (height adjust, decoded minima) in a second when any
+// member needs it.
+static int motion_run(const Members &g, const gmr_motion_input *inputs, hipStream_t st) {
+  struct Member { bool work = false; gmr::CallBlock::Uploaded<int64_t> offs; size_t key0 = 0; };  // key0: its first key
+  const int n = g.n;
+  std::string &err = g.err;
+  gmr::CallBlock blk;
+  const auto h_ent = blk.uploaded<gmr::MotionEntry>((size_t)n);
   std::vector<gmr::MotionEntry> ent(n);
-  size_t n_offs = 0, n_keys = 0;
+  std::vector<Member> mem(n);
+  size_t n_keys = 0;
   int64_t tiles = 0, finish = 0, lds = 0;
   bool any = false, any_finish = false;
   std::vector<int> empty_min;  // members without frames that want min_z
   for (int i = 0; i < n; ++i) {
     const gmr_motion_input &in = inputs[i];
-    const gmr_model *m = models[i];
-    const std::string who = group ? "member " + std::to_string(i) + ": " : "";
+    const gmr_model *m = g.models[i];
+    const std::string who = g.who(i);
     gmr::MotionEntry &e = ent[i];
-    e = gmr::MotionEntry{};
     e.tile_base = tiles; e.finish_base = finish;
     if (in.n_frames < 0) { err = who + "negative n_frames"; return GMR_EINVAL; }
     if (in.n_frames == 0) {  // no work for this member; its clips (all empty) still report fk_min_height's +inf
@@ -1948,11 +1987,7 @@ static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, 
       err = who + "null argument"; return GMR_EINVAL;
     }
     if (in.flags & ~(GMR_MOTION_HEIGHT_ADJUST | GMR_MOTION_ROOT_ORIGIN)) { err = who + "unknown flags"; return GMR_EINVAL; }
-    if (in.n_seq < 1 || in.seq_offsets[0] != 0 || in.seq_offsets[in.n_seq] != in.n_frames) {
-      err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL;
-    }
-    for (int s = 0; s < in.n_seq; ++s)
-      if (in.seq_offsets[s + 1] < in.seq_offsets[s]) { err = who + "seq_offsets must not decrease"; return GMR_EINVAL; }
+    if (const char *why = seq_offsets_error(in.seq_offsets, in.n_seq, in.n_frames)) { err = who + why; return GMR_EINVAL; }
     const int64_t need = gmr::motion_lds_bytes(m->fk.nbody, ndof, m->fk.nslots);
     if (need > 160 * 1024) { err = who + "the epilogue tile needs " + std::to_string(need) + " bytes of LDS"; return GMR_EUNSUPPORTED; }
     lds = std::max(lds, need);
@@ -1963,10 +1998,9 @@ static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, 
     e.ground_offset = in.ground_offset;
     e.n_frames = in.n_frames; e.n_seq = in.n_seq;
     e.flags = in.flags | (in.min_z_out ? gmr::kMotionWantMin : 0);
-    // offsets and keys: byte offsets into the scratch block for now, device pointers once it exists
-    e.seq_offsets = reinterpret_cast<const int64_t *>(n_offs);
-    e.keys = reinterpret_cast<int *>(n_keys);
-    n_offs += (size_t)in.n_seq + 1;
+    mem[i].work = true;
+    mem[i].offs = blk.put(in.seq_offsets, (size_t)in.n_seq + 1);
+    mem[i].key0 = n_keys;
     n_keys += (size_t)in.n_seq;
     tiles += (in.n_frames + gmr::kFkWave - 1) / gmr::kFkWave;
     const int64_t items = ((e.flags & gmr::kMotionHeight) ? in.n_frames : 0) + ((e.flags & gmr::kMotionWantMin) ? in.n_seq : 0);
@@ -1975,7 +2009,7 @@ static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, 
     any_finish = any_finish || items > 0;
   }
   if (!empty_min.empty()) {
-    if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
+    if (hipSetDevice(g.device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
     for (int i : empty_min)
       if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(inputs[i].min_z_out), 0x7f800000, (size_t)inputs[i].n_seq, st) != hipSuccess) {
         err = "hipMemsetD32Async failed"; return GMR_EDEVICE;
@@ -1983,50 +2017,35 @@ static int motion_run(gmr_model *const *models, const gmr_motion_input *inputs, 
   }
   if (!any) return GMR_OK;
   if (tiles > 0x7fffffff || finish > 0x7fffffff || n_keys > 0x7fffffff) { err = "too many frames for one launch"; return GMR_EINVAL; }
-  if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
-  const size_t ent_bytes = sizeof(gmr::MotionEntry) * (size_t)n, off_at = (ent_bytes + 15) & ~size_t(15);
-  const size_t key_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15), total = key_at + sizeof(int) * std::max<size_t>(n_keys, 1);
+  if (hipSetDevice(g.device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
+  const auto h_keys = blk.device_only<int>(std::max<size_t>(n_keys, 1));  // all members' keys in a row: one launch sets them
   CallScratch sc;
-  gmr_model *m0 = models[0];
-  if (scratch_alloc(m0, sc, total, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
-  uint8_t *ws = static_cast<uint8_t *>(sc.p);
-  std::vector<uint8_t> host(key_at, 0);
-  for (int i = 0; i < n; ++i) {
-    gmr::MotionEntry &e = ent[i];
-    if (inputs[i].n_frames <= 0) continue;
-    const size_t o = reinterpret_cast<size_t>(e.seq_offsets), k = reinterpret_cast<size_t>(e.keys);
-    memcpy(host.data() + off_at + sizeof(int64_t) * o, inputs[i].seq_offsets, sizeof(int64_t) * ((size_t)inputs[i].n_seq + 1));
-    e.seq_offsets = reinterpret_cast<const int64_t *>(ws + off_at) + o;
-    e.keys = reinterpret_cast<int *>(ws + key_at) + k;
-  }
-  memcpy(host.data(), ent.data(), ent_bytes);
-  if (hipMemcpyAsync(ws, host.data(), key_at, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
-  const auto *d_ent = reinterpret_cast<const gmr::MotionEntry *>(ws);
+  const int rc = send_call_block(g, blk, sc, st, [&](const gmr::CallBlock::Device &dev) {
+    for (int i = 0; i < n; ++i) {
+      if (!mem[i].work) continue;
+      ent[i].seq_offsets = dev(mem[i].offs);
+      ent[i].keys = dev(h_keys) + mem[i].key0;
+    }
+    std::copy(ent.begin(), ent.end(), blk[h_ent]);
+    return GMR_OK;
+  });
+  if (rc != GMR_OK) return rc;
+  const gmr::CallBlock::Device dev = blk.on(sc.p);
   if (n_keys > 0)
-    hipLaunchKernelGGL(gmr::fk_minkey_init, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, st, reinterpret_cast<int *>(ws + key_at), (int)n_keys);
-  hipLaunchKernelGGL(gmr::motion_epilogue_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, st, d_ent, n);
+    hipLaunchKernelGGL(gmr::fk_minkey_init, dim3((unsigned)((n_keys + 255) / 256)), dim3(256), 0, st, dev(h_keys), (int)n_keys);
+  hipLaunchKernelGGL(gmr::motion_epilogue_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, st, dev(h_ent), n);
   if (any_finish)
-    hipLaunchKernelGGL(gmr::motion_finish_kernel, dim3((unsigned)finish), dim3(gmr::kMotionFinishThreads), 0, st, d_ent, n);
+    hipLaunchKernelGGL(gmr::motion_finish_kernel, dim3((unsigned)finish), dim3(gmr::kMotionFinishThreads), 0, st, dev(h_ent), n);
   if (hipGetLastError() != hipSuccess) { err = "kernel launch failed"; return GMR_EDEVICE; }
   return GMR_OK;
 }
 
 int gmr_motion_epilogue(gmr_model *m, const gmr_motion_input *in, void *stream) {
-  if (!m) return GMR_EINVAL;
-  m->err.clear();
-  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
-  std::string err;
-  const int rc = motion_run(&m, in, 1, m->device, static_cast<hipStream_t>(stream), false, err);
-  if (rc != GMR_OK) m->err = err;
-  return rc;
+  return member_call(m, nullptr, in, [&](const Members &g) { return motion_run(g, in, static_cast<hipStream_t>(stream)); });
 }
 
 int gmr_group_motion_epilogue(gmr_group *g, const gmr_motion_input *inputs, void *stream) {
-  if (!g) return GMR_EINVAL;
-  g->err.clear();
-  if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
-  const int rc = motion_run(g->models.data(), inputs, (int)g->models.size(), g->device, static_cast<hipStream_t>(stream), true, g->err);
-  return rc;
+  return member_call(nullptr, g, inputs, [&](const Members &ms) { return motion_run(ms, inputs, static_cast<hipStream_t>(stream)); });
 }
 
 // ------------------------------------------------------------------ tracking export (track_kernel.hip.h)
@@ -2043,24 +2062,29 @@ int gmr_lowpass_coefficients(double cutoff_hz, double fs, double *c) {
   return GMR_OK;
 }
 
-// Validate every member with work, upload the entries and the members' plans (clip offsets, output offsets, ratios) in one block
-// of stream-ordered scratch, and run all members' tiles in one grid.  `models[i]` goes with `inputs[i]`; a group call names the
-// member in its messages.  Errors land in `err`.
-// A member with lowpass_hz > 0 is filtered first (lowpass_kernel.hip.h): its entry of the filter launch and one row of five
-// coefficients per clip ride in the same host block, the filtered qpos goes into a scratch image of its own (n_frames * nq
-// doubles, released behind the launches like the block), and the member's TrackEntry reads that image instead of qpos.
-static int track_run(gmr_model *const *models, const gmr_track_input *inputs, int n, int device, hipStream_t st, bool group, std::string &err) {
+// Validate every member with work, send the entries and the members' plans (clip offsets, output offsets, ratios) in one call
+// block ("the call block"), and run all members' tiles in one grid.
+// A member with lowpass_hz > 0 is filtered first (lowpass_kernel.hip.h): the entries of the filter launch and the member's five
+// coefficients per clip ride in the same block, the filtered qpos goes into a scratch image of its own (n_frames * nq doubles,
+// released behind the launches like the block), and the member's TrackEntry reads that image instead of qpos.
+static int track_run(const Members &g, const gmr_track_input *inputs, hipStream_t st) {
+  struct Member {
+    bool work = false, filtered = false;
+    gmr::CallBlock::Uploaded<int64_t> offs, outs;
+    gmr::CallBlock::Uploaded<double> ratio, coef;  // coef: [n_seq][5], filtered members only
+  };
+  const int n = g.n;
+  std::string &err = g.err;
+  gmr::CallBlock blk;
+  const auto h_ent = blk.uploaded<gmr::TrackEntry>((size_t)n);
   std::vector<gmr::TrackEntry> ent(n);
-  std::vector<char> work(n, 0);
-  std::vector<size_t> coef_at(n, 0);  // filtered members: first coefficient row (in rows of 5 doubles)
-  size_t n_offs = 0, n_ratio = 0, n_coef = 0;
+  std::vector<Member> mem(n);
   int64_t tiles = 0, lds = 0, clips = 0;
   for (int i = 0; i < n; ++i) {
     const gmr_track_input &in = inputs[i];
-    const gmr_model *m = models[i];
-    const std::string who = group ? "member " + std::to_string(i) + ": " : "";
+    const gmr_model *m = g.models[i];
+    const std::string who = g.who(i);
     gmr::TrackEntry &e = ent[i];
-    e = gmr::TrackEntry{};
     e.tile_base = tiles;
     if (in.n_frames < 0) { err = who + "negative n_frames"; return GMR_EINVAL; }
     if (in.lowpass_hz < 0.0f || !std::isfinite(in.lowpass_hz)) { err = who + "lowpass_hz must be finite and >= 0"; return GMR_EINVAL; }
@@ -2068,12 +2092,11 @@ static int track_run(gmr_model *const *models, const gmr_track_input *inputs, in
     if (m->dm.root_planar) { err = who + "the tracking export needs a free-joint root; a planar base is not supported"; return GMR_EUNSUPPORTED; }
     if (!in.qpos || !in.seq_offsets || !in.out_offsets || !in.ratio) { err = who + "null argument"; return GMR_EINVAL; }
     if (!(in.fps_out > 0.0) || !std::isfinite(in.fps_out)) { err = who + "fps_out must be positive"; return GMR_EINVAL; }
-    if (in.n_seq < 1 || in.seq_offsets[0] != 0 || in.seq_offsets[in.n_seq] != in.n_frames) {
-      err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL;
-    }
+    // the rules of seq_offsets_error, with those of the output plan between them in the order they have always been reported in
+    if (const char *why = seq_ends_error(in.seq_offsets, in.n_seq, in.n_frames)) { err = who + why; return GMR_EINVAL; }
     if (in.out_offsets[0] != 0) { err = who + "out_offsets must start at 0"; return GMR_EINVAL; }
     for (int s = 0; s < in.n_seq; ++s) {
-      if (in.seq_offsets[s + 1] < in.seq_offsets[s]) { err = who + "seq_offsets must not decrease"; return GMR_EINVAL; }
+      if (const char *why = seq_clip_error(in.seq_offsets, s)) { err = who + why; return GMR_EINVAL; }
       if (in.out_offsets[s + 1] < in.out_offsets[s]) { err = who + "out_offsets must not decrease"; return GMR_EINVAL; }
       if (in.out_offsets[s + 1] > in.out_offsets[s] && in.seq_offsets[s + 1] == in.seq_offsets[s]) {
         err = who + "clip " + std::to_string(s) + " has output frames but no source frames"; return GMR_EINVAL;
@@ -2103,98 +2126,71 @@ static int track_run(gmr_model *const *models, const gmr_track_input *inputs, in
     e.body_lin_vel = in.body_lin_vel_w_out; e.body_ang_vel = in.body_ang_vel_w_out;
     e.dt = 1.0 / in.fps_out;
     e.n_out = n_out; e.n_seq = in.n_seq;
-    // the plan arrays: element offsets into the scratch block for now, device pointers once it exists
-    e.seq_offsets = reinterpret_cast<const int64_t *>(n_offs);
-    e.ratio = reinterpret_cast<const double *>(n_ratio);
-    n_offs += 2 * ((size_t)in.n_seq + 1);
-    n_ratio += (size_t)in.n_seq;
+    Member &mb = mem[i];
+    mb.work = true;
+    mb.offs = blk.put(in.seq_offsets, (size_t)in.n_seq + 1);
+    mb.outs = blk.put(in.out_offsets, (size_t)in.n_seq + 1);
+    mb.ratio = blk.put(in.ratio, (size_t)in.n_seq);
     tiles += (n_out + gmr::kTrackTile - 1) / gmr::kTrackTile;
-    work[i] = 1;
     if (in.lowpass_hz != 0.0f) {
-      work[i] = 2;
-      coef_at[i] = n_coef;
-      n_coef += (size_t)in.n_seq;
+      mb.filtered = true;
+      mb.coef = blk.uploaded<double>(5 * (size_t)in.n_seq);
       clips += in.n_seq;
     }
   }
   if (tiles == 0) return GMR_OK;
   if (tiles > 0x7fffffff || clips > 0x7fffffff) { err = "too many frames for one launch"; return GMR_EINVAL; }
-  if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
-  const size_t ent_bytes = sizeof(gmr::TrackEntry) * (size_t)n, off_at = (ent_bytes + 15) & ~size_t(15);
-  const size_t ratio_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15);
-  // without a filtered member the block ends behind the ratios, as it always has
-  const size_t lp_at = clips ? (ratio_at + sizeof(double) * n_ratio + 15) & ~size_t(15) : 0;
-  const size_t coef_bytes_at = lp_at + sizeof(gmr::LowpassEntry) * (size_t)n;
-  const size_t total = clips ? coef_bytes_at + sizeof(double) * 5 * n_coef : ratio_at + sizeof(double) * n_ratio;
+  if (hipSetDevice(g.device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
+  // without a filtered member the block holds nothing of the filter launch
+  const auto h_lp = blk.uploaded<gmr::LowpassEntry>(clips ? (size_t)n : 0);
   CallScratch sc;
   std::vector<CallScratch> images(clips ? n : 0);  // the filtered members' qpos
-  gmr_model *m0 = models[0];
-  if (scratch_alloc(m0, sc, total, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
-  uint8_t *ws = static_cast<uint8_t *>(sc.p);
-  std::vector<uint8_t> host(total, 0);
-  if (clips) {
+  const int rc = send_call_block(g, blk, sc, st, [&](const gmr::CallBlock::Device &dev) {
     int64_t base = 0;
     for (int i = 0; i < n; ++i) {
-      gmr::LowpassEntry le{};
+      const Member &mb = mem[i];
+      const gmr_track_input &in = inputs[i];
+      gmr::TrackEntry &e = ent[i];
+      if (mb.work) { e.seq_offsets = dev(mb.offs); e.out_offsets = dev(mb.outs); e.ratio = dev(mb.ratio); }
+      if (!clips) continue;
+      gmr::LowpassEntry &le = blk[h_lp][i];  // (zero so far)
       le.clip_base = base;
-      if (work[i] == 2) {
-        const gmr_track_input &in = inputs[i];
-        const int nq = models[i]->fk.ndof + 7;
-        if (scratch_alloc(m0, images[i], sizeof(double) * (size_t)in.n_frames * (size_t)nq, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
-        double *coef = reinterpret_cast<double *>(host.data() + coef_bytes_at) + 5 * coef_at[i];
-        for (int s = 0; s < in.n_seq; ++s)
-          if (in.seq_offsets[s + 1] > in.seq_offsets[s] &&
-              gmr_lowpass_coefficients((double)in.lowpass_hz, in.ratio[s] * in.fps_out, coef + 5 * s) != GMR_OK) {
-            err = (group ? "member " + std::to_string(i) + ": " : "") + "clip " + std::to_string(s) + ": no low-pass coefficients";  // (refused above)
-            return GMR_EINVAL;
-          }
-        le.src = in.qpos;
-        le.dst = static_cast<double *>(images[i].p);
-        le.seq_offsets = reinterpret_cast<const int64_t *>(ws + off_at) + reinterpret_cast<size_t>(ent[i].seq_offsets);
-        le.coef = reinterpret_cast<const double *>(ws + coef_bytes_at) + 5 * coef_at[i];
-        le.n_seq = in.n_seq; le.nq = nq;
-        ent[i].qpos = le.dst;
-        base += in.n_seq;
-      }
-      memcpy(host.data() + lp_at + sizeof(gmr::LowpassEntry) * (size_t)i, &le, sizeof(le));
+      if (!mb.filtered) continue;
+      const int nq = g.models[i]->fk.ndof + 7;
+      gmr_model *m0 = g.models[0];
+      if (scratch_alloc(m0, images[i], sizeof(double) * (size_t)in.n_frames * (size_t)nq, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
+      for (int s = 0; s < in.n_seq; ++s)
+        if (in.seq_offsets[s + 1] > in.seq_offsets[s] &&
+            gmr_lowpass_coefficients((double)in.lowpass_hz, in.ratio[s] * in.fps_out, blk[mb.coef] + 5 * s) != GMR_OK) {
+          err = g.who(i) + "clip " + std::to_string(s) + ": no low-pass coefficients";  // (refused above)
+          return GMR_EINVAL;
+        }
+      le.src = in.qpos;
+      le.dst = static_cast<double *>(images[i].p);
+      le.seq_offsets = dev(mb.offs);
+      le.coef = dev(mb.coef);
+      le.n_seq = in.n_seq; le.nq = nq;
+      e.qpos = le.dst;
+      base += in.n_seq;
     }
-  }
-  for (int i = 0; i < n; ++i) {
-    if (!work[i]) continue;
-    gmr::TrackEntry &e = ent[i];
-    const size_t o = reinterpret_cast<size_t>(e.seq_offsets), r = reinterpret_cast<size_t>(e.ratio), ns = (size_t)inputs[i].n_seq;
-    memcpy(host.data() + off_at + sizeof(int64_t) * o, inputs[i].seq_offsets, sizeof(int64_t) * (ns + 1));
-    memcpy(host.data() + off_at + sizeof(int64_t) * (o + ns + 1), inputs[i].out_offsets, sizeof(int64_t) * (ns + 1));
-    memcpy(host.data() + ratio_at + sizeof(double) * r, inputs[i].ratio, sizeof(double) * ns);
-    e.seq_offsets = reinterpret_cast<const int64_t *>(ws + off_at) + o;
-    e.out_offsets = e.seq_offsets + ns + 1;
-    e.ratio = reinterpret_cast<const double *>(ws + ratio_at) + r;
-  }
-  memcpy(host.data(), ent.data(), ent_bytes);
-  if (hipMemcpyAsync(ws, host.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
+    std::copy(ent.begin(), ent.end(), blk[h_ent]);
+    return GMR_OK;
+  });
+  if (rc != GMR_OK) return rc;
+  const gmr::CallBlock::Device dev = blk.on(sc.p);
   if (clips)
-    hipLaunchKernelGGL(gmr::lowpass_kernel, dim3((unsigned)clips), dim3(gmr::kFkWave), 0, st, reinterpret_cast<const gmr::LowpassEntry *>(ws + lp_at), n);
-  hipLaunchKernelGGL(gmr::motion_track_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, st,
-                     reinterpret_cast<const gmr::TrackEntry *>(ws), n);
+    hipLaunchKernelGGL(gmr::lowpass_kernel, dim3((unsigned)clips), dim3(gmr::kFkWave), 0, st, dev(h_lp), n);
+  hipLaunchKernelGGL(gmr::motion_track_kernel, dim3((unsigned)tiles), dim3(gmr::kFkWave), (unsigned)lds, st, dev(h_ent), n);
   if (hipGetLastError() != hipSuccess) { err = "kernel launch failed"; return GMR_EDEVICE; }
   return GMR_OK;
 }
 
 int gmr_motion_track(gmr_model *m, const gmr_track_input *in, void *stream) {
-  if (!m) return GMR_EINVAL;
-  m->err.clear();
-  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
-  std::string err;
-  const int rc = track_run(&m, in, 1, m->device, static_cast<hipStream_t>(stream), false, err);
-  if (rc != GMR_OK) m->err = err;
-  return rc;
+  return member_call(m, nullptr, in, [&](const Members &g) { return track_run(g, in, static_cast<hipStream_t>(stream)); });
 }
 
 int gmr_group_motion_track(gmr_group *g, const gmr_track_input *inputs, void *stream) {
-  if (!g) return GMR_EINVAL;
-  g->err.clear();
-  if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
-  return track_run(g->models.data(), inputs, (int)g->models.size(), g->device, static_cast<hipStream_t>(stream), true, g->err);
+  return member_call(nullptr, g, inputs, [&](const Members &ms) { return track_run(ms, inputs, static_cast<hipStream_t>(stream)); });
 }
 
 // ------------------------------------------------------------------ motion library sampling (sample_kernel.hip.h)
@@ -2275,38 +2271,38 @@ int gmr_motion_contacts(gmr_model *m, const gmr_contact_input *in) {
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)
-// Validate every member with clips, upload the entries, clip offsets and segment prefixes in one block of stream-ordered scratch
-// (which also holds the segments' partial rows), run pass 1 over all members' segments in one grid and pass 2 over all members'
-// clips in a second.  `models[i]` goes with `inputs[i]`; a group call names the member in its messages.  Errors land in `err`.
-static int report_run(gmr_model *const *models, const gmr_clip_report_input *inputs, int n, const gmr_clip_report_params *prm, int device,
-                      hipStream_t st, bool group, std::string &err) {
+// Validate every member with clips, send the entries, clip offsets, segment prefixes and slot columns in one call block
+// ("the call block"; the segments' partial rows are its device-only tail), run pass 1 over all members' segments in
+// one grid and pass 2 over all members' clips in a second.
+static int report_run(const Members &g, const gmr_clip_report_input *inputs, const gmr_clip_report_params *prm, hipStream_t st) {
+  struct Member {
+    bool work = false, kp = false;
+    gmr::CallBlock::Uploaded<int64_t> offs;
+    gmr::CallBlock::Uploaded<int> clip_seg, slot_col;  // slot_col: members with key-points only
+    gmr::CallBlock::DeviceOnly<unsigned long long> rows;
+  };
+  const int n = g.n;
+  std::string &err = g.err;
   gmr_clip_report_params p{};
   if (prm) p = *prm; else p.limit_eps = GMR_CLIP_REPORT_LIMIT_EPS;
   if (p.segment_frames < 0) { err = "negative segment_frames"; return GMR_EINVAL; }
   if (!(p.limit_eps >= 0.0)) { err = "limit_eps must be >= 0"; return GMR_EINVAL; }
   const int segment = p.segment_frames ? p.segment_frames : GMR_CLIP_REPORT_SEGMENT;
+  gmr::CallBlock blk;
+  const auto h_ent = blk.uploaded<gmr::ReportEntry>((size_t)n);
   std::vector<gmr::ReportEntry> ent(n);
-  std::vector<std::vector<int>> clip_seg(n);
-  size_t n_offs = 0, n_cols_total = 0, row_words = 0;
+  std::vector<Member> mem(n);
   int64_t segs = 0, clips = 0;
   int lds = 0;
   for (int i = 0; i < n; ++i) {
     const gmr_clip_report_input &in = inputs[i];
-    const gmr_model *m = models[i];
-    const std::string who = group ? "member " + std::to_string(i) + ": " : "";
+    const gmr_model *m = g.models[i];
+    const std::string who = g.who(i);
     gmr::ReportEntry &e = ent[i];
-    e = gmr::ReportEntry{};
     e.seg_base = segs; e.clip_base = clips;
     if (in.n_frames < 0 || in.n_seq < 0) { err = who + "negative size"; return GMR_EINVAL; }
-    if (in.n_seq == 0) {
-      if (in.n_frames != 0) { err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL; }
-      continue;  // no work for this member
-    }
-    if (!in.seq_offsets || in.seq_offsets[0] != 0 || in.seq_offsets[in.n_seq] != in.n_frames) {
-      err = who + "seq_offsets must run from 0 to n_frames"; return GMR_EINVAL;
-    }
-    for (int s = 0; s < in.n_seq; ++s)
-      if (in.seq_offsets[s + 1] < in.seq_offsets[s]) { err = who + "seq_offsets must not decrease"; return GMR_EINVAL; }
+    if (in.n_seq == 0 && in.n_frames == 0) continue;  // no work for this member
+    if (const char *why = seq_offsets_error(in.seq_offsets, in.n_seq, in.n_frames)) { err = who + why; return GMR_EINVAL; }
     if (in.n_frames > 0 && !in.qpos) { err = who + "null qpos"; return GMR_EINVAL; }
     const bool want_err = in.err_max_out || in.err_sum_out || in.task_pos_max_out || in.task_pos_sum_out || in.task_rot_max_out || in.task_rot_sum_out;
     const bool have_kp = in.n_frames > 0 && (in.human_pos || in.human_quat);  // (no frames: nothing is read, every clip reports 0)
@@ -2322,30 +2318,29 @@ static int report_run(gmr_model *const *models, const gmr_clip_report_input *inp
           return GMR_EINVAL;
         }
     }
-    std::vector<int> &cs = clip_seg[i];
-    cs.assign((size_t)in.n_seq + 1, 0);
+    Member &mb = mem[i];
+    mb.clip_seg = blk.uploaded<int>((size_t)in.n_seq + 1);
+    int *cs = blk[mb.clip_seg];  // (filled before the next reservation moves the image)
     int64_t acc = 0;
     for (int s = 0; s < in.n_seq; ++s) {
       acc += (in.seq_offsets[s + 1] - in.seq_offsets[s] + segment - 1) / segment;
       if (acc > 0x7fffffff) { err = who + "too many segments for one launch"; return GMR_EINVAL; }
       cs[s + 1] = (int)acc;
     }
+    mb.work = true;
+    mb.offs = blk.put(in.seq_offsets, (size_t)in.n_seq + 1);
     e.m = m->dm_eval_dev; e.lay = m->lay_eval;
     e.qpos = in.qpos;
     if (have_kp) {
       e.hpos = in.human_pos; e.hquat = in.human_quat;
       e.in_f64 = in.in_dtype == GMR_DTYPE_F64; e.n_cols = in.n_cols;
-      e.slot_col = reinterpret_cast<const int *>(n_cols_total);  // offsets into the scratch block for now
-      n_cols_total += (size_t)m->h.nslot;
+      mb.kp = true;
+      mb.slot_col = blk.put(in.slot_col, (size_t)m->h.nslot);
     }
     e.hscale = in.height_scale; e.iters = in.iters;
-    e.offs = reinterpret_cast<const int64_t *>(n_offs);
-    e.clip_seg = reinterpret_cast<const int *>(n_offs);
-    n_offs += (size_t)in.n_seq + 1;
     e.hlo = m->rep_lo; e.hhi = m->rep_hi;
     e.nh = m->h.nq - 7; e.nt = m->h.ntask[0] + m->h.ntask[1];
-    e.rows = reinterpret_cast<unsigned long long *>(row_words);
-    row_words += (size_t)acc * gmr::report_row_words(e.nt, e.nh);
+    mb.rows = blk.device_only<unsigned long long>((size_t)acc * gmr::report_row_words(e.nt, e.nh));
     e.err_max = in.err_max_out; e.err_sum = in.err_sum_out;
     e.task_pos_max = in.task_pos_max_out; e.task_pos_sum = in.task_pos_sum_out;
     e.task_rot_max = in.task_rot_max_out; e.task_rot_sum = in.task_rot_sum_out;
@@ -2359,37 +2354,21 @@ static int report_run(gmr_model *const *models, const gmr_clip_report_input *inp
   }
   if (clips == 0) return GMR_OK;
   if (segs > 0x7fffffff || clips > 0x7fffffff) { err = "too many clips for one launch"; return GMR_EINVAL; }
-  if (hipSetDevice(device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
-  // scratch: [entries | int64 offsets | int segment prefixes | int slot columns] uploaded, then the rows
-  const size_t ent_bytes = sizeof(gmr::ReportEntry) * (size_t)n, off_at = (ent_bytes + 15) & ~size_t(15);
-  const size_t seg_at = (off_at + sizeof(int64_t) * n_offs + 15) & ~size_t(15);
-  const size_t col_at = (seg_at + sizeof(int) * n_offs + 15) & ~size_t(15);
-  const size_t row_at = (col_at + sizeof(int) * n_cols_total + 15) & ~size_t(15);
-  const size_t total = row_at + sizeof(unsigned long long) * std::max<size_t>(row_words, 1);
+  if (hipSetDevice(g.device) != hipSuccess) { err = "hipSetDevice failed"; return GMR_EDEVICE; }
   CallScratch sc;
-  gmr_model *m0 = models[0];
-  if (scratch_alloc(m0, sc, total, st) != GMR_OK) { err = m0->err; return GMR_EDEVICE; }
-  uint8_t *ws = static_cast<uint8_t *>(sc.p);
-  std::vector<uint8_t> host(row_at, 0);
-  for (int i = 0; i < n; ++i) {
-    gmr::ReportEntry &e = ent[i];
-    const gmr_clip_report_input &in = inputs[i];
-    if (in.n_seq <= 0) continue;
-    const size_t o = reinterpret_cast<size_t>(e.offs), r = reinterpret_cast<size_t>(e.rows);
-    memcpy(host.data() + off_at + sizeof(int64_t) * o, in.seq_offsets, sizeof(int64_t) * ((size_t)in.n_seq + 1));
-    memcpy(host.data() + seg_at + sizeof(int) * o, clip_seg[i].data(), sizeof(int) * ((size_t)in.n_seq + 1));
-    e.offs = reinterpret_cast<const int64_t *>(ws + off_at) + o;
-    e.clip_seg = reinterpret_cast<const int *>(ws + seg_at) + o;
-    e.rows = reinterpret_cast<unsigned long long *>(ws + row_at) + r;
-    if (e.hpos) {
-      const size_t c = reinterpret_cast<size_t>(e.slot_col);
-      memcpy(host.data() + col_at + sizeof(int) * c, in.slot_col, sizeof(int) * (size_t)models[i]->h.nslot);
-      e.slot_col = reinterpret_cast<const int *>(ws + col_at) + c;
+  const int rc = send_call_block(g, blk, sc, st, [&](const gmr::CallBlock::Device &dev) {
+    for (int i = 0; i < n; ++i) {
+      const Member &mb = mem[i];
+      if (!mb.work) continue;
+      gmr::ReportEntry &e = ent[i];
+      e.offs = dev(mb.offs); e.clip_seg = dev(mb.clip_seg); e.rows = dev(mb.rows);
+      if (mb.kp) e.slot_col = dev(mb.slot_col);
     }
-  }
-  memcpy(host.data(), ent.data(), ent_bytes);
-  if (hipMemcpyAsync(ws, host.data(), row_at, hipMemcpyHostToDevice, st) != hipSuccess) { err = "hipMemcpyAsync failed"; return GMR_EDEVICE; }
-  const auto *d_ent = reinterpret_cast<const gmr::ReportEntry *>(ws);
+    std::copy(ent.begin(), ent.end(), blk[h_ent]);
+    return GMR_OK;
+  });
+  if (rc != GMR_OK) return rc;
+  const gmr::ReportEntry *d_ent = blk.on(sc.p)(h_ent);
   if (segs > 0) hipLaunchKernelGGL(gmr::clip_report_kernel, dim3((unsigned)segs), dim3(64), (unsigned)lds, st, d_ent, n);
   hipLaunchKernelGGL(gmr::clip_report_merge_kernel, dim3((unsigned)clips), dim3(gmr::kReportMergeThreads), 0, st, d_ent, n);
   if (hipGetLastError() != hipSuccess) { err = "kernel launch failed"; return GMR_EDEVICE; }
@@ -2397,20 +2376,11 @@ static int report_run(gmr_model *const *models, const gmr_clip_report_input *inp
 }
 
 int gmr_clip_report(gmr_model *m, const gmr_clip_report_input *in, const gmr_clip_report_params *prm, void *stream) {
-  if (!m) return GMR_EINVAL;
-  m->err.clear();
-  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
-  std::string err;
-  const int rc = report_run(&m, in, 1, prm, m->device, static_cast<hipStream_t>(stream), false, err);
-  if (rc != GMR_OK) m->err = err;
-  return rc;
+  return member_call(m, nullptr, in, [&](const Members &g) { return report_run(g, in, prm, static_cast<hipStream_t>(stream)); });
 }
 
 int gmr_group_clip_report(gmr_group *g, const gmr_clip_report_input *inputs, const gmr_clip_report_params *prm, void *stream) {
-  if (!g) return GMR_EINVAL;
-  g->err.clear();
-  if (!inputs) { g->err = "null inputs"; return GMR_EINVAL; }
-  return report_run(g->models.data(), inputs, (int)g->models.size(), prm, g->device, static_cast<hipStream_t>(stream), true, g->err);
+  return member_call(nullptr, g, inputs, [&](const Members &ms) { return report_run(ms, inputs, prm, static_cast<hipStream_t>(stream)); });
 }
 
 /* Frames per wavefront of the adapter kernels: runs long enough that a wavefront's setup (plan, tables) is amortised and its

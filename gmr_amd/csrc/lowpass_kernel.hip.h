@@ -28,7 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "motion_kernel.hip.h"
+#include "fk_kernel.hip.h"  // kFkWave
+#include "member_launch.hip.h"
 
 namespace gmr {
 
@@ -45,16 +46,6 @@ struct LowpassEntry {
   int64_t clip_base;           // first workgroup of this member
   int n_seq, nq;               // n_seq = 0: this member is not filtered
 };
-
-// member of workgroup `blk`: the last entry whose base is <= blk (entries in member order, bases non-decreasing)
-__device__ __forceinline__ int lowpass_member(const LowpassEntry *entries, int n_entries, int64_t blk) {
-  int e = 0;
-  while (e + 1 < n_entries) {
-    if (blk < motion_const(&entries[e + 1].clip_base)) break;
-    ++e;
-  }
-  return e;
-}
 
 // lane L's value in every lane
 template <int L>
@@ -90,7 +81,7 @@ __global__ void __launch_bounds__(kFkWave) lowpass_kernel(const LowpassEntry *en
 #pragma clang fp contract(off)  // the contract's arithmetic exactly
   constexpr int B = kLowpassBatch, P = kLowpassPad;
   const int lane = threadIdx.x;
-  const int ei = lowpass_member(entries, n_entries, (int64_t)blockIdx.x);
+  const int ei = launch_member<LowpassEntry, &LowpassEntry::clip_base>(entries, n_entries, (int64_t)blockIdx.x);
   const LowpassEntry *ep = entries + ei;
   const int nq = motion_const(&ep->nq);
   const int s = (int)((int64_t)blockIdx.x - motion_const(&ep->clip_base));

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "fk_kernel.hip.h"
+#include "member_launch.hip.h"
 
 namespace gmr {
 
@@ -47,27 +48,6 @@ struct MotionEntry {
   int64_t finish_base;  // first pass-2 workgroup of this member
   int n_seq, flags;
 };
-
-template <class T>
-__device__ __forceinline__ T motion_const(const T *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return *reinterpret_cast<const T __attribute__((address_space(4))) *>(reinterpret_cast<uintptr_t>(p));
-#else
-  return *p;
-#endif
-}
-
-// member of workgroup `blk`: the last entry whose base is <= blk (entries in member order, bases non-decreasing)
-template <bool FINISH>
-__device__ __forceinline__ int motion_member(const MotionEntry *entries, int n_entries, int64_t blk) {
-  int e = 0;
-  while (e + 1 < n_entries) {
-    const int64_t b = FINISH ? motion_const(&entries[e + 1].finish_base) : motion_const(&entries[e + 1].tile_base);
-    if (blk < b) break;
-    ++e;
-  }
-  return e;
-}
 
 // clip of frame f: the last s with seq_offsets[s] <= f (empty clips share their offset with the next one and are skipped)
 __device__ __forceinline__ int motion_clip(const int64_t *offs, int n_seq, int64_t f) {
@@ -98,7 +78,7 @@ __global__ void __launch_bounds__(kFkWave) motion_epilogue_kernel(const MotionEn
 #pragma clang fp contract(off)  // fk_pos_kernel's and fk_kernel<1>'s arithmetic exactly
   extern __shared__ float fk_lds[];
   const int lane = threadIdx.x;
-  const int ei = motion_member<false>(entries, n_entries, (int64_t)blockIdx.x);
+  const int ei = launch_member<MotionEntry, &MotionEntry::tile_base>(entries, n_entries, (int64_t)blockIdx.x);
   const MotionEntry *ep = entries + ei;
   FkTree t{};  // the fields the chain reads (fk_body, fk_const)
   t.body = motion_const(&ep->fk.body);
@@ -296,7 +276,7 @@ __device__ __forceinline__ float motion_decode(int k) { return fk_key_min(k); }
 // Per member: n_frames height items (members that adjust heights), then n_seq decode items (members that want min_z).
 __global__ void __launch_bounds__(kMotionFinishThreads) motion_finish_kernel(const MotionEntry *__restrict__ entries, int n_entries) {
 #pragma clang fp contract(off)
-  const int ei = motion_member<true>(entries, n_entries, (int64_t)blockIdx.x);
+  const int ei = launch_member<MotionEntry, &MotionEntry::finish_base>(entries, n_entries, (int64_t)blockIdx.x);
   const MotionEntry *ep = entries + ei;
   const int flags = motion_const(&ep->flags);
   const int n_seq = motion_const(&ep->n_seq);

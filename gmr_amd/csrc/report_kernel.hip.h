@@ -38,7 +38,7 @@
 #include <stdint.h>
 
 #include "ik_kernel.hip.h"
-#include "motion_kernel.hip.h"
+#include "member_launch.hip.h"
 
 namespace gmr {
 
@@ -72,23 +72,12 @@ struct ReportEntry {
   int n_seq, in_f64, n_cols, offset_to_ground, segment, nh, nt, pad;
 };
 
-template <bool MERGE>
-__device__ __forceinline__ int report_member(const ReportEntry *entries, int n_entries, int64_t blk) {
-  int e = 0;
-  while (e + 1 < n_entries) {
-    const int64_t b = MERGE ? motion_const(&entries[e + 1].clip_base) : motion_const(&entries[e + 1].seg_base);
-    if (blk < b) break;
-    ++e;
-  }
-  return e;
-}
-
 __device__ __forceinline__ bool report_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN and inf
 
 __global__ void __launch_bounds__(64, 3) clip_report_kernel(const ReportEntry *__restrict__ entries, int n_entries) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
-  const int ei = report_member<false>(entries, n_entries, (int64_t)blockIdx.x);
+  const int ei = launch_member<ReportEntry, &ReportEntry::seg_base>(entries, n_entries, (int64_t)blockIdx.x);
   const ReportEntry *ep = entries + ei;
   DevModelG &m = *(DevModelG *)motion_const(&ep->m);
   const int o_q = motion_const(&ep->lay.q), o_tp = motion_const(&ep->lay.tp), o_tq = motion_const(&ep->lay.tq);
@@ -295,7 +284,7 @@ __global__ void __launch_bounds__(64, 3) clip_report_kernel(const ReportEntry *_
 
 // One workgroup per clip: word w of the clip's rows folded in segment order by lane w (+ 64 k), then stored in its output's type.
 __global__ void __launch_bounds__(kReportMergeThreads) clip_report_merge_kernel(const ReportEntry *__restrict__ entries, int n_entries) {
-  const int ei = report_member<true>(entries, n_entries, (int64_t)blockIdx.x);
+  const int ei = launch_member<ReportEntry, &ReportEntry::clip_base>(entries, n_entries, (int64_t)blockIdx.x);
   const ReportEntry *ep = entries + ei;
   const int s = (int)((int64_t)blockIdx.x - motion_const(&ep->clip_base));
   const int nh = motion_const(&ep->nh), nt = motion_const(&ep->nt), W = report_row_words(nt, nh);

@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "member_launch.hip.h"
 #include "motion_kernel.hip.h"
 
 namespace gmr {
@@ -72,16 +73,6 @@ __host__ __device__ inline TrackLds track_lds(int nbody, int ndof, int nslots) {
   return l;
 }
 __host__ __device__ inline int64_t track_lds_bytes(int nbody, int ndof, int nslots) { return track_lds(nbody, ndof, nslots).bytes; }
-
-// member of workgroup `blk`: the last entry whose base is <= blk (entries in member order, bases non-decreasing)
-__device__ __forceinline__ int track_member(const TrackEntry *entries, int n_entries, int64_t blk) {
-  int e = 0;
-  while (e + 1 < n_entries) {
-    if (blk < motion_const(&entries[e + 1].tile_base)) break;
-    ++e;
-  }
-  return e;
-}
 
 __device__ __forceinline__ double track_lerp(double x0, double x1, double a) {
 #pragma clang fp contract(off)
@@ -154,7 +145,7 @@ __global__ void __launch_bounds__(kFkWave) motion_track_kernel(const TrackEntry 
 #pragma clang fp contract(off)  // gmr_fk's arithmetic exactly; the float64 part as the contract writes it
   extern __shared__ __attribute__((aligned(16))) unsigned char track_smem[];
   const int lane = threadIdx.x;
-  const int ei = track_member(entries, n_entries, (int64_t)blockIdx.x);
+  const int ei = launch_member<TrackEntry, &TrackEntry::tile_base>(entries, n_entries, (int64_t)blockIdx.x);
   const TrackEntry *ep = entries + ei;
   FkTree t{};  // the fields the chain reads (fk_body, fk_const)
   t.body = motion_const(&ep->fk.body);
