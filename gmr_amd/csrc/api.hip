@@ -242,6 +242,14 @@ int ik_shape_of(const gmr::DevModel &d, int nvp, bool sq) {
 #undef GMR_X
   return -1;
 }
+// Is `plain` compiled into the shape (its instances take only plain launches and prepare targets in blocks)?
+bool ik_shape_is_plain(int shape) {
+  int idx = 0;
+#define GMR_X(S, v) if (shape == idx++) return gmr::S::plain > 0;
+  GMR_FOR_EACH_IK_SHAPE(GMR_X)
+#undef GMR_X
+  return false;
+}
 const char *ik_shape_name(int shape) {
   int idx = 0;
 #define GMR_X(S, v) if (shape == idx++) return #S;
@@ -251,7 +259,8 @@ const char *ik_shape_name(int shape) {
 }
 
 // The instance a launch takes: the model's shape where the launch is what `plain` stands for in a shape (float32 key-points, no
-// offset_to_ground, every item plain, no step cap), else -1 = the generic instance.
+// offset_to_ground, every item plain, no step cap), else -1 = the generic instance.  This is the only guard: a shape with `plain`
+// compiled in (IkShapeG1Smplx) has no code for float64 input, offset_to_ground, the verification walk or the chunk start.
 int ik_launch_shape(int model_shape, bool force_generic_shape, bool plain, bool in_f64, bool offset_to_ground, bool capped) {
   return model_shape >= 0 && !force_generic_shape && plain && !in_f64 && !offset_to_ground && !capped ? model_shape : -1;
 }
@@ -1007,6 +1016,15 @@ int build_device_model(gmr_model *m, bool host_only = false) {
   }
 
   m->shape = ik_shape_of(dm, m->nvp, dm.sq_ok && !m->force_generic);
+  // A model that matches a plain shape gets the ring of target images its instances prepare four frames at a time (target_blocks.h):
+  // kTargetBlockFrames x [tp | tq] behind everything else.  G1 / smplx: 16 176 + 3 136 = 19 312 bytes, still eight wavefronts per CU.
+  m->lay.tring = -1;
+  if (ik_shape_is_plain(m->shape) && ns <= gmr::kTargetBlockLanes) {
+    m->lay.tring = m->lay.total_doubles;
+    m->lay.total_doubles += gmr::kTargetBlockFrames * (m->lay.tq - m->lay.tp + 4 * ns);
+    m->lds_bytes = m->lay.total_doubles * (int)sizeof(double);
+    if (m->lds_bytes > 65535) { set_err(m, "model needs %d bytes of LDS per wavefront (plan offsets are 16 bit)", m->lds_bytes); return GMR_EUNSUPPORTED; }
+  }
   if (host_only) return GMR_OK;
 
   // the model image: every array holds at least one element, so that no two tables share an address

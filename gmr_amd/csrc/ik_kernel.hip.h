@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "../../include/gmr_amd.h"
+#include "target_blocks.h"
 
 namespace gmr {
 
@@ -60,6 +61,9 @@ typedef unsigned long long u64;
 #endif
 #ifndef GMR_IK_STAGE_TREE
 #define GMR_IK_STAGE_TREE 1  // joint tree staged in LDS per wavefront; 0 = re-read from L2 (saves 3.3 KB LDS for G1)
+#endif
+#ifndef GMR_IK_TARGET_BLOCKS
+#define GMR_IK_TARGET_BLOCKS 1  // plain instances prepare the targets of four frames per pass (target_blocks.h); 0 = one frame per pass
 #endif
 #ifndef GMR_IK_WAVES_PER_SIMD
 #define GMR_IK_WAVES_PER_SIMD 2  // the structured variants (every registry robot): 2 wavefronts per SIMD at <= 256 registers.  The
@@ -126,6 +130,8 @@ struct LdsLayout {
   // offsets in doubles.  zero: block of zeros; hplan / cplan: the staged H-pair and composite plans; Lb (generic QP broadcast
   // rows) aliases S; Bc aliases the poses; H aliases [B | poses / Bc] (all dead during the QP)
   int zero, hplan, cplan, q, tp, tq, S, F, Lb, bodyc, xpos, xquat, B, Bc, H, total_doubles;
+  // tring: the ring of kTargetBlockFrames target images [tp | tq] of a model that matches a plain shape (target_blocks.h), else -1
+  int tring;
 };
 
 struct IkLaunch {
@@ -201,9 +207,9 @@ struct IkShapeAny {
 struct IkShapeG1Smplx {
   static constexpr int nlimb = 7, ntask0 = 14, ntask1 = 14, use0 = 1, use1 = 1, same_tasks = 1, ncpass0 = 3, ncpass1 = 3, npairp = 384,
                        nbody = 32, fkrounds = 4, n_act = 35, nslot = 14, nq = 36, root_slot = 0;
-  // plain stays a run-time matter although the host only sends plain launches here: with the float64 / offset_to_ground / walk paths
-  // compiled out the compiler contracts the target preparation differently and qpos moves by 1e-13 (profiles/r04_shape_fields.md)
-  static constexpr int plain = -1;
+  // plain is compiled in: the host only sends plain launches here (api.hip, ik_launch_shape), and the target preparation -- the one
+  // block whose contraction used to depend on the float64 / offset_to_ground / walk paths around it -- is pinned (target_prep_slot)
+  static constexpr int plain = 1;
 };
 // The shape's value where it fixes one, else the run-time value (whose load is then dead code).
 template <int V>
@@ -443,6 +449,55 @@ constexpr int kBodyC = 11;  // doubles per body in the LDS-staged joint tree: po
 // `restrict` kernel argument as clobberable -- either way every wave-uniform branch, mask and scalar constant derived from the
 // model would be a VMEM load into VGPRs instead of a scalar load.
 using DevModelG = const DevModel __attribute__((address_space(4)));
+// ------------------------------------------------------------------ target preparation of one slot (update_targets)
+// scale_human_data + offset_human_data for one (frame, slot): p = scaled position + R(qo) poff, qo = normalised(hq) * roff
+// renormalised, pz = p.z of a foot slot (+inf otherwise).  Every instance of ik_body calls this one function, and its bits do not
+// depend on the code around the call: contraction is off, and each fused multiply-add is written out.  Which products are fused is
+// the pattern the compiler had chosen for this block while it was still free to (gfx950 ISA of ik_kernel<36, true>, between the
+// v_cvt_f64_f32 of the key-points and the ds_write of tp / tq); it is now part of the result's definition.  The helpers (the
+// rsqrt Newton step, quaternion product, renormalisation, rotation matrix, matrix x vector) are this function's own copies, spelled
+// inline: fast_rsqrt / qmul / qrenorm / q2mat / mv above stay the FK and residual phases', whose contraction is still the compiler's.
+__device__ __forceinline__ void target_prep_slot(const double hp[3], const double hq[4], const double rp[3], bool is_root, double hscale,
+                                                 double sscale_slot, double sscale_root, const double poff[3], const double roff[4],
+                                                 bool foot, double p[3], double qo[4], double &pz) {
+#pragma clang fp contract(off)
+  const double s_scale = hscale * sscale_slot, root_scale = hscale * sscale_root;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const double rs = rp[i] * root_scale;
+    p[i] = is_root ? rs : __builtin_fma(hp[i] - rp[i], s_scale, rs);
+  }
+  // qnormalize: one third-order Newton step on the v_rsq_f64 seed (fast_rsqrt)
+  const double n = __builtin_fma(hq[3], hq[3], __builtin_fma(hq[2], hq[2], __builtin_fma(hq[0], hq[0], hq[1] * hq[1])));
+  double r = __builtin_amdgcn_rsq(n);
+  const double e = __builtin_fma(r * -n, r, 1.0);
+  r = __builtin_fma(r, e * __builtin_fma(e, 0.375, 0.5), r);
+  const double a0 = hq[0] * r, a1 = hq[1] * r, a2 = hq[2] * r, a3 = hq[3] * r;
+  // qmul(a, roff)
+  const double b0 = roff[0], b1 = roff[1], b2 = roff[2], b3 = roff[3];
+  const double w = __builtin_fma(-a3, b3, __builtin_fma(-a2, b2, __builtin_fma(a0, b0, -(a1 * b1))));
+  const double x = __builtin_fma(-a3, b2, __builtin_fma(a2, b3, __builtin_fma(a1, b0, a0 * b1)));
+  const double y = __builtin_fma(a3, b1, __builtin_fma(a2, b0, __builtin_fma(a0, b2, -(a1 * b3))));
+  const double z = __builtin_fma(a3, b0, __builtin_fma(-a2, b1, __builtin_fma(a1, b2, a0 * b3)));
+  // qrenorm: one Newton step from r = 1
+  const double rn = __builtin_fma(-0.5, __builtin_fma(z, z, __builtin_fma(y, y, __builtin_fma(w, w, x * x))), 1.5);
+  const double q0 = w * rn, q1 = x * rn, q2 = y * rn, q3 = z * rn;
+  qo[0] = q0; qo[1] = q1; qo[2] = q2; qo[3] = q3;
+  // q2mat
+  const double x2 = q1 + q1, y2 = q2 + q2, z2 = q3 + q3;
+  const double wx = q0 * x2, wy = q0 * y2, wz = q0 * z2;
+  const double dyy = __builtin_fma(-q2, y2, 1.0), dxx = __builtin_fma(-q1, x2, 1.0);  // 1 - yy, 1 - xx
+  const double R0 = __builtin_fma(-q3, z2, dyy), R4 = __builtin_fma(-q3, z2, dxx), R8 = __builtin_fma(-q2, y2, dxx);
+  const double R1 = __builtin_fma(x2, q2, -wz), R3 = __builtin_fma(x2, q2, wz);
+  const double R2 = __builtin_fma(x2, q3, wy), R6 = __builtin_fma(x2, q3, -wy);
+  const double R5 = __builtin_fma(y2, q3, -wx), R7 = __builtin_fma(y2, q3, wx);
+  // p += R poff
+  p[0] = p[0] + __builtin_fma(poff[2], R2, __builtin_fma(poff[1], R1, poff[0] * R0));
+  p[1] = p[1] + __builtin_fma(poff[2], R5, __builtin_fma(poff[0], R3, poff[1] * R4));
+  p[2] = p[2] + __builtin_fma(poff[2], R8, __builtin_fma(poff[0], R6, poff[1] * R7));
+  pz = foot ? p[2] : INFINITY;
+}
+
 // HIP's vector classes cannot be copied out of a qualified address space: read those members through a plain pointer (per-lane data).
 template <class T>
 __device__ __forceinline__ T ld_plain(const T __attribute__((address_space(4))) *p) { return *(const T *)(uintptr_t)p; }
@@ -1254,9 +1309,12 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   const int nq = shp<SH::nq>(m.nq), n_act = shp<SH::n_act>(m.n_act), nslot = shp<SH::nslot>(m.nslot), root_slot = shp<SH::root_slot>(m.root_slot);
   const int npairp = shp<SH::npairp>(m.npairp), nbody = shp<SH::nbody>(m.nbody), fkrounds = shp<SH::fkrounds>(m.fkrounds);
   constexpr bool kPlain = SH::plain > 0;  // the launch is known to be float32 in, no offset_to_ground, no walk and no chunk start
+  // Plain instances prepare targets in blocks of four frames (target_blocks.h): needs the ring (lay.tring, api.hip reserves it for a
+  // model that matches a plain shape) and a compile-time nslot that fits 16 lanes.  Every other instance: one frame per pass.
+  constexpr bool kBlocks = GMR_IK_TARGET_BLOCKS != 0 && kPlain && !LIVE && SH::nslot >= 1 && SH::nslot <= kTargetBlockLanes;
+  const int tstride = lay.tq - lay.tp + 4 * nslot;  // doubles per ring image [tp | tq]
   const int check_stride = kPlain ? 0 : w.check_stride;
   // The per-solve step cap (IkLaunch::step_cap) exists in the generic instance alone: the host sends a capped launch nowhere else.
-  // (kPlain does not tell the instances apart -- the shapes leave `plain` to run time, see IkShapeG1Smplx.)
   constexpr bool kCap = !kPlain && std::is_same_v<SH, IkShapeAny>;
   // active-dof constants of this lane (row of the QP); the rest is re-read where it is used
   const bool real_row = lane < n_act;
@@ -1378,7 +1436,42 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
     }
     GMR_STAMP(10);
     // ---- target preparation (update_targets: scale_human_data + offset_human_data, table-1 offsets) ----
-    {
+    if constexpr (kBlocks) {
+      // Target blocks (target_blocks.h): every fourth frame of the run the wavefront prepares four frames at once, lane 16 j + s the
+      // slot s of frame kf + j, into image j of the ring; a frame then reads its image.  Nothing of a block stays in registers.
+      if (target_block_starts(kf0, kf)) {  // wave-uniform
+        const TargetBlockLane tb = target_block_lane(launder(lane), nslot, kf, kend);
+        if (tb.on) {
+          IkLaunchK *La = ik_args(Lk);
+          const int64_t base = (w.frame_begin + tb.frame) * (int64_t)La->n_cols;
+          const float *P = (const float *)La->hpos, *Q = (const float *)La->hquat;
+          const int col = La->slot_col[tb.slot];
+          double hp[3], hq[4], rp[3], p[3], qo[4], pz;
+#pragma unroll
+          for (int i = 0; i < 3; i++) rp[i] = (double)P[(base + root_col) * 3 + i];
+#pragma unroll
+          for (int i = 0; i < 3; i++) hp[i] = (double)P[(base + col) * 3 + i];
+#pragma unroll
+          for (int i = 0; i < 4; i++) hq[i] = (double)Q[(base + col) * 4 + i];
+          const int s = tb.slot;
+          const double s_poff[3] = {m.spoff[3 * s], m.spoff[3 * s + 1], m.spoff[3 * s + 2]};
+          const double s_roff[4] = {m.sroff[4 * s], m.sroff[4 * s + 1], m.sroff[4 * s + 2], m.sroff[4 * s + 3]};
+          target_prep_slot(hp, hq, rp, s == root_slot, hscale, m.sscale[s], m.sscale[root_slot], s_poff, s_roff, false, p, qo, pz);
+          double *rtp = lds + lay.tring + tb.image * tstride, *rtq = rtp + (lay.tq - lay.tp);
+#pragma unroll
+          for (int i = 0; i < 3; i++) rtp[3 * s + i] = p[i];
+#pragma unroll
+          for (int i = 0; i < 4; i++) rtq[4 * s + i] = qo[i];
+        }
+      }
+      // This frame's image becomes tp / tq: one 16-byte move per lane (every offset here is even: api.hip).  The solve keeps reading
+      // the two fixed arrays, so everything behind this point is the code of the per-frame instances, statement for statement.
+      {
+        const double2 *img = reinterpret_cast<const double2 *>(lds + lay.tring + target_block_image(kf0, kf) * tstride);
+        double2 *cur = reinterpret_cast<double2 *>(tp);
+        for (int i = lane; 2 * i < tstride; i += 64) cur[i] = img[i];
+      }
+    } else {
       double hp[3] = {0, 0, 0}, hq[4] = {1, 0, 0, 0}, rp[3];
       IkLaunchK *La = ik_args(Lk);
       const int64_t base = f * La->n_cols;
@@ -1404,22 +1497,12 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
         }
       }
       double pz = INFINITY;
-      double p[3] = {0, 0, 0}, qo[4] = {1, 0, 0, 0}, R[9], g[3];
+      double p[3] = {0, 0, 0}, qo[4] = {1, 0, 0, 0};
       if (is_slot) {
-        const double s_scale = hscale * m.sscale[lane], root_scale = hscale * m.sscale[root_slot];
         const double s_poff[3] = {m.spoff[3 * lane], m.spoff[3 * lane + 1], m.spoff[3 * lane + 2]};
         const double s_roff[4] = {m.sroff[4 * lane], m.sroff[4 * lane + 1], m.sroff[4 * lane + 2], m.sroff[4 * lane + 3]};
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-          p[i] = (lane == root_slot) ? root_scale * rp[i] : (hp[i] - rp[i]) * s_scale + root_scale * rp[i];
-        qnormalize(hq);
-        qmul(hq, s_roff, qo);
-        qrenorm(qo);
-        q2mat(qo, R);
-        mv(R, s_poff, g);
-#pragma unroll
-        for (int i = 0; i < 3; i++) p[i] += g[i];
-        if (m.sfoot[lane]) pz = p[2];
+        target_prep_slot(hp, hq, rp, lane == root_slot, hscale, m.sscale[lane], m.sscale[root_slot], s_poff, s_roff, m.sfoot[lane] != 0,
+                         p, qo, pz);
       }
       if (LIVE ? live_otg : !kPlain && La->prm.offset_to_ground != 0) {
         const double lowest = wave_min(pz);
