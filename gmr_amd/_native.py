@@ -31,7 +31,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
-           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts"]
+           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock"]
 
 
 class IKParams(C.Structure):
@@ -117,6 +117,22 @@ class ContactInput(C.Structure):
         ("height_on", C.c_double), ("height_off", C.c_double), ("speed_on", C.c_double), ("speed_off", C.c_double),
         ("stream", C.c_void_p),
     ] + [(k + "_out", C.c_void_p) for k in CONTACT_OUTPUTS]
+
+
+FOOTLOCK_MAX_BODIES, FOOTLOCK_MAX_ITERATIONS = 8, 32   # contact columns and iterations of one gmr_motion_footlock call
+FOOTLOCK_OUTPUTS = ("qpos", "pos", "shift", "runs", "locked_frames", "shift_max", "residual_max", "limit_frames")  # gmr_footlock_input's output pointers, in order
+
+
+class FootlockInput(C.Structure):
+    """``gmr_footlock_input`` (include/gmr_amd.h): the whole call of the foot locking, its stream included.  ``body_ids`` is a
+    HOST array."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("contact", C.c_void_p), ("body_ids", C.c_void_p),
+        ("n_seq", C.c_int32), ("n_contact", C.c_int32), ("blend_frames", C.c_int32), ("min_run", C.c_int32),
+        ("iterations", C.c_int32), ("reserved", C.c_int32), ("damping", C.c_double), ("step_cap", C.c_double),
+        ("stream", C.c_void_p),
+    ] + [(k + "_out", C.c_void_p) for k in FOOTLOCK_OUTPUTS]
 
 
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
@@ -241,6 +257,8 @@ def load():
     L.gmr_motion_sample.argtypes = [vp, C.POINTER(SampleInput), vp]
     L.gmr_motion_contacts.restype = C.c_int
     L.gmr_motion_contacts.argtypes = [vp, C.POINTER(ContactInput)]
+    L.gmr_motion_footlock.restype = C.c_int
+    L.gmr_motion_footlock.argtypes = [vp, C.POINTER(FootlockInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

@@ -32,6 +32,7 @@
 #include "sample_kernel.hip.h"
 #include "report_kernel.hip.h"
 #include "contact_kernel.hip.h"
+#include "footlock_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
 
@@ -2286,6 +2287,100 @@ int gmr_motion_contacts(gmr_model *m, const gmr_contact_input *in) {
   if (in->n_rows == 0 || in->n_seq == 0) return GMR_OK;
   if (!in->body_pos_w || !in->body_lin_vel_w || !in->out_offsets || !in->body_ids) { set_err(m, "null argument"); return GMR_EINVAL; }
   return contact_run(m, *in, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ foot locking (footlock_kernel.hip.h)
+// The chains of gmr_motion_footlock, derived on the host from the blob's tree and the caller's body ids: per column the path from
+// the root's child down to the contact body, and of its hinges those that lie on no other column's path.  Everything travels in
+// the kernels' argument.
+static int footlock_plan(gmr_model *m, const gmr_footlock_input &in, gmr::FootlockArgs &a, int &lds_doubles) {
+  const int nb = m->h.nbody, C = in.n_contact;
+  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent), *jtype = blob_ptr<int32_t>(m->blob, m->h.off_jnt_type);
+  std::vector<int> on_paths(nb, 0);
+  for (int c = 0; c < C; ++c) {
+    const int id = in.body_ids[c];
+    if (id < 0 || id >= nb) { set_err(m, "body_ids[%d] = %d is not a body of the model (%d bodies)", c, id, nb); return GMR_EINVAL; }
+    for (int d = 0; d < c; ++d)
+      if (in.body_ids[d] == id) { set_err(m, "body %d is named by two contact columns", id); return GMR_EINVAL; }
+  }
+  lds_doubles = 0;
+  for (int c = 0; c < C; ++c) {
+    std::vector<int> path;  // the contact body first
+    for (int j = in.body_ids[c]; j >= 0 && jtype[j] != GMR_JNT_FREE; j = parent[j]) path.push_back(j);
+    if ((int)path.size() > gmr::kFootlockMaxPath) {
+      set_err(m, "contact body %d lies %d bodies below the root; at most %d are supported", in.body_ids[c], (int)path.size(), gmr::kFootlockMaxPath);
+      return GMR_EUNSUPPORTED;
+    }
+    a.path_len[c] = (uint8_t)path.size();
+    for (size_t i = 0; i < path.size(); ++i) {
+      a.path[c][i] = (uint8_t)path[path.size() - 1 - i];
+      on_paths[path[i]] += 1;
+    }
+  }
+  for (int c = 0; c < C; ++c) {
+    int n = 0;
+    uint32_t mask = 0;
+    for (int i = 0; i < a.path_len[c]; ++i) {
+      const int j = a.path[c][i];
+      if (jtype[j] == GMR_JNT_HINGE && on_paths[j] == 1) { mask |= 1u << i; ++n; }
+    }
+    if (n < 3) { set_err(m, "the chain of contact body %d holds %d hinges of its own; at least 3 are needed", in.body_ids[c], n); return GMR_EINVAL; }
+    if (n > gmr::kFootlockMaxChain) {
+      set_err(m, "the chain of contact body %d holds %d hinges; at most %d are supported", in.body_ids[c], n, gmr::kFootlockMaxChain);
+      return GMR_EUNSUPPORTED;
+    }
+    a.chain_mask[c] = mask;
+    a.n_chain[c] = (uint8_t)n;
+    lds_doubles = std::max(lds_doubles, gmr::footlock_solve_doubles(a.path_len[c], n));
+  }
+  return GMR_OK;
+}
+
+// The three launches of gmr_motion_footlock, and nothing else: no allocation, no copy, no synchronisation.
+static int footlock_run(gmr_model *m, const gmr_footlock_input &in, gmr::FootlockArgs &a, int lds_doubles, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  const int nq = m->fk.ndof + 7;
+  a.dm = m->dm_eval_dev; a.lo = m->rep_lo; a.hi = m->rep_hi;
+  a.qpos = in.qpos; a.seq_offsets = in.seq_offsets; a.contact = in.contact; a.n_frames = in.n_frames;
+  a.n_seq = in.n_seq; a.C = in.n_contact; a.nq = nq; a.blend = in.blend_frames; a.min_run = in.min_run; a.iters = in.iterations;
+  a.damping = in.damping; a.step_cap = in.step_cap;
+  a.qpos_out = in.qpos_out; a.pos = in.pos_out; a.shift = in.shift_out;
+  a.runs = in.runs_out; a.locked = in.locked_frames_out; a.shift_max = in.shift_max_out; a.resid_max = in.residual_max_out;
+  a.limit_frames = in.limit_frames_out;
+  // tiles of one clip in flight: four times the mean clip's, so that long clips stride and short ones launch few idle wavefronts
+  const int64_t tiles = (in.n_frames + gmr::kFkWave - 1) / gmr::kFkWave;
+  const unsigned ty = (unsigned)std::min<int64_t>(std::min<int64_t>(tiles, 4 * ((tiles + in.n_seq - 1) / in.n_seq)), 65535);
+  const unsigned lds_a = (unsigned)(gmr::motion_qpitch(nq) * gmr::kFkWave * sizeof(double));
+  const unsigned lds_c = (unsigned)(lds_doubles * gmr::kFkWave * sizeof(double));
+  hipLaunchKernelGGL(gmr::footlock_pos_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), lds_a, st, a);
+  hipLaunchKernelGGL(gmr::footlock_runs_kernel, dim3((unsigned)in.n_seq, (unsigned)in.n_contact), dim3(gmr::kFkWave), 0, st, a);
+  hipLaunchKernelGGL(gmr::footlock_solve_kernel, dim3((unsigned)in.n_seq, ty, (unsigned)in.n_contact), dim3(gmr::kFkWave), lds_c, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_footlock(gmr_model *m, const gmr_footlock_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (in->n_contact < 1 || in->n_contact > gmr::kFootlockMaxCols) { set_err(m, "n_contact must be 1 .. %d", gmr::kFootlockMaxCols); return GMR_EINVAL; }
+  if (in->blend_frames < 0) { set_err(m, "blend_frames must be >= 0"); return GMR_EINVAL; }
+  if (in->min_run < 1) { set_err(m, "min_run must be >= 1"); return GMR_EINVAL; }
+  if (in->iterations < 1 || in->iterations > gmr::kFootlockMaxIters) { set_err(m, "iterations must be 1 .. %d", gmr::kFootlockMaxIters); return GMR_EINVAL; }
+  if (!(in->damping > 0.0) || !std::isfinite(in->damping)) { set_err(m, "damping must be finite and > 0"); return GMR_EINVAL; }
+  if (!(in->step_cap > 0.0) || !std::isfinite(in->step_cap)) { set_err(m, "step_cap must be finite and > 0"); return GMR_EINVAL; }
+  if (!in->body_ids) { set_err(m, "null body_ids"); return GMR_EINVAL; }
+  if (in->qpos_out && in->qpos_out == in->qpos) { set_err(m, "qpos_out must not alias qpos"); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "foot locking needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  gmr::FootlockArgs a{};
+  int lds_doubles = 0;
+  const int rc = footlock_plan(m, *in, a, lds_doubles);
+  if (rc != GMR_OK) return rc;
+  if (in->n_frames == 0 || in->n_seq == 0) return GMR_OK;
+  if (!in->qpos || !in->seq_offsets || !in->contact || !in->qpos_out || !in->pos_out || !in->shift_out) { set_err(m, "null argument"); return GMR_EINVAL; }
+  if ((int64_t)gmr::motion_qpitch(m->fk.ndof + 7) * gmr::kFkWave * 8 > 64 * 1024) { set_err(m, "the row tile needs more than 64 KiB of LDS"); return GMR_EUNSUPPORTED; }
+  return footlock_run(m, *in, a, lds_doubles, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

@@ -83,7 +83,7 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                    height_adjust: bool = True, root_origin_offset: bool = True, chunk: int = 0, burn_in: int = 0,
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
                    track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
-                   contact_bodies: Optional[Sequence[str]] = None, contact=None):
+                   contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -92,9 +92,12 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     With ``track_fps`` a last value is added: the clips' tracking dicts at that rate (``tracking_from_qpos`` on the same qpos).
     With ``lowpass_hz`` the solved qpos is smoothed once (``smooth_qpos`` at ``fps``), and the motions, the report and the tracks
     are all made from the smoothed qpos.  ``contact_bodies`` / ``contact`` (with ``track_fps``): ``tracking_from_qpos``'s contact
-    labels on the tracking dicts."""
+    labels on the tracking dicts; ``lock_feet``: ``tracking_from_qpos``'s foot locking of those bodies (the tracking dicts only: the
+    motions and the report are made from the qpos as solved)."""
     if contact_bodies is not None and track_fps is None:
         raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
+    if lock_feet and contact_bodies is None:
+        raise ValueError("lock_feet needs contact_bodies: the bodies to lock")
     tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
     tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
     tpos, tquat = tpos.to(gmr.device), tquat.to(gmr.device)
@@ -112,7 +115,8 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
         rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
         res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset), rep.numpy())
     if track_fps is not None:
-        res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps, contact_bodies=contact_bodies, contact=contact),)
+        lock_kw = {"lock_feet": lock_feet} if lock_feet else {}  # (absent without the flag: nothing changes then)
+        res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps, contact_bodies=contact_bodies, contact=contact, **lock_kw),)
     return res[0] if len(res) == 1 else res
 
 
@@ -160,14 +164,82 @@ def _track_contacts(eng, track, model_body_names, contact_bodies, contact: Optio
     return eng.motion_contacts(track, track.out_offsets, ids, **prm.kwargs()), list(contact_bodies)
 
 
-def tracks_to_host(tracks, fps_out, body_names, joint_names, contacts=None) -> List[List[Dict]]:
+FOOTLOCK_STATS = ("runs", "locked_frames", "shift_max", "residual_max", "limit_frames")  # the keys of a clip's footlock_stats
+
+
+def lock_feet(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, contact_bodies: Sequence[str],
+              contact: Optional[ContactParams] = None, **footlock_kwargs):
+    """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) with the foot slide of the
+    planted ``contact_bodies`` removed (``Engine.motion_footlock``; the definition is the contract above ``gmr_footlock_input`` in
+    include/gmr_amd.h) -> ``(qpos_locked, stats)``: the cleaned qpos ``[N, nq]`` on the device and ``stats``, the device tensors
+    ``runs``, ``locked_frames``, ``limit_frames`` (int32 ``[S, C]``), ``shift_max`` and ``residual_max`` (float64 ``[S, C]``,
+    metres).  The labels are the tracking export's own: ``Engine.motion_track`` at ``fps_out = fps`` (every output frame is one
+    qpos row), then ``Engine.motion_contacts`` with ``contact`` (a :class:`ContactParams`); with per-clip rates that is one pass
+    per distinct rate.  ``footlock_kwargs``: ``blend_frames``, ``min_run``, ``iterations``, ``damping``, ``step_cap`` of
+    ``Engine.motion_footlock``; its defaults are conventions, not measured on any robot.  Only the hinges between a contact body
+    and the first joint it shares with another one move; everything else is copied bit for bit."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("foot locking assumes a free-joint root; a planar-base robot is not supported")
+    return _lock_feet(gmr._engine, gmr.model.body_names, qpos, seq_offsets, fps, contact_bodies, contact, footlock_kwargs)
+
+
+def _lock_feet(eng, model_body_names, qpos, seq_offsets, fps, contact_bodies, contact, footlock_kwargs):
+    """``lock_feet`` on an ``Engine`` (a free-joint model)."""
+    ids = contact_body_ids(model_body_names, contact_bodies)
+    prm = contact if contact is not None else ContactParams()
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    S, Cn = offs.size - 1, len(ids)
+    f = np.asarray(fps.detach().cpu().numpy() if isinstance(fps, torch.Tensor) else fps, dtype=np.float64)
+    f = np.full(S, float(f)) if f.ndim == 0 else f
+    if f.shape != (S,):
+        raise ValueError("fps must be one rate or one rate per clip")
+    lens = np.diff(offs)
+    res = qpos.clone()
+    stats = {k: torch.zeros((S, Cn), dtype=torch.int32 if k in ("runs", "locked_frames", "limit_frames") else torch.float64,
+                            device=qpos.device) for k in FOOTLOCK_STATS}
+    for rate in np.unique(f[lens > 0]):
+        sel = np.flatnonzero((f == rate) & (lens > 0))
+        whole = sel.size == np.count_nonzero(lens > 0)  # one rate: the batch as it is
+        if whole:
+            rows, q, o = None, qpos.contiguous(), offs
+        else:
+            rows = torch.from_numpy(np.concatenate([np.arange(offs[s], offs[s + 1]) for s in sel])).to(qpos.device)
+            q, o = qpos.index_select(0, rows), np.concatenate([[0], np.cumsum(lens[sel])]).astype(np.int64)
+        track = eng.motion_track(q, o, float(rate), float(rate))
+        assert np.array_equal(track.out_offsets, o)   # fps_out = fps: one output frame per row
+        labels = eng.motion_contacts(track, track.out_offsets, ids, out={"contact": torch.zeros((int(q.shape[0]), Cn), dtype=torch.uint8,
+                                                                                                 device=q.device)}, **prm.kwargs())
+        got = eng.motion_footlock(q, o, labels["contact"], ids, **footlock_kwargs)
+        if whole:
+            res = got["qpos"]
+            stats = {k: got[k] for k in FOOTLOCK_STATS}
+        else:
+            res.index_copy_(0, rows, got["qpos"])
+            clips = torch.from_numpy(sel).to(qpos.device)
+            for k in FOOTLOCK_STATS:
+                stats[k].index_copy_(0, clips, got[k])
+    return res, stats
+
+
+def tracks_to_host(tracks, fps_out, body_names, joint_names, contacts=None, locks=None) -> List[List[Dict]]:
     """Several ``engine.MotionTrack`` results (one per robot) to the host with every copy in flight before the one
     synchronisation; per result the list of per-clip dicts of ``tracking_from_qpos``.  ``contacts``: per result ``None`` or
     (``engine.MotionContacts``, contact body names) -- its copies ride in the same synchronisation and every clip's dict also
-    gets ``contact``, ``contact_body_names``, ``contact_stats`` and ``airborne_frames``."""
+    gets ``contact``, ``contact_body_names``, ``contact_stats`` and ``airborne_frames``.  ``locks``: per result ``None`` or the
+    ``stats`` of ``lock_feet``; every clip's dict then also gets ``footlock_stats``."""
     hosts, chosts = [], []
     dev = None
     contacts = [None] * len(tracks) if contacts is None else list(contacts)
+    locks = [None] * len(tracks) if locks is None else list(locks)
+    lhosts = []
+    for lk in locks:
+        if lk is None:
+            lhosts.append(None)
+            continue
+        lhost = {k: torch.empty(lk[k].shape, dtype=lk[k].dtype, pin_memory=True) for k in FOOTLOCK_STATS}
+        for k, h in lhost.items():
+            h.copy_(lk[k], non_blocking=True)
+        lhosts.append({k: h.numpy() for k, h in lhost.items()})
     for tr, ct in zip(tracks, contacts):
         host = {k: torch.empty(tr[k].shape, dtype=tr[k].dtype, pin_memory=True) for k in TRACK_ARRAYS}
         for k, h in host.items():
@@ -184,7 +256,7 @@ def tracks_to_host(tracks, fps_out, body_names, joint_names, contacts=None) -> L
     if dev is not None:
         torch.cuda.current_stream(dev).synchronize()
     out = []
-    for tr, host, bn, jn, ct, chost in zip(tracks, hosts, body_names, joint_names, contacts, chosts):
+    for tr, host, bn, jn, ct, chost, lhost in zip(tracks, hosts, body_names, joint_names, contacts, chosts, lhosts):
         offs, bn, jn = tr.out_offsets, list(bn), list(jn)
         clips = []
         for s in range(len(offs) - 1):
@@ -196,6 +268,8 @@ def tracks_to_host(tracks, fps_out, body_names, joint_names, contacts=None) -> L
                 stats = {k: chost[k][s] for k in CONTACT_STATS}
                 d.update(contact=chost["contact"][a:b], contact_body_names=list(ct[1]), contact_stats=stats,
                          airborne_frames=int(chost["airborne_frames"][s]))
+            if lhost is not None:
+                d["footlock_stats"] = {k: lhost[k][s] for k in FOOTLOCK_STATS}
             clips.append(d)
         out.append(clips)
     return out
@@ -203,7 +277,7 @@ def tracks_to_host(tracks, fps_out, body_names, joint_names, contacts=None) -> L
 
 def tracking_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, fps_out,
                        lowpass_hz: Optional[float] = None, contact_bodies: Optional[Sequence[str]] = None,
-                       contact: Optional[ContactParams] = None) -> List[Dict]:
+                       contact: Optional[ContactParams] = None, lock_feet=False) -> List[Dict]:
     """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) -> one tracking dict per clip
     at ``fps_out`` (``Engine.motion_track``, one launch): ``fps``, ``joint_pos``, ``joint_vel``, ``root_pos``, ``root_rot`` (xyzw),
     ``root_lin_vel``, ``root_ang_vel`` (world frame) in float64, ``body_pos_w``, ``body_quat_w`` (xyzw), ``body_lin_vel_w``,
@@ -216,15 +290,36 @@ def tracking_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_of
     ``depth_max`` (float64 ``[C]``, metres: how far a planted body slides in all and in one frame, how deep it goes below the
     ground) and ``base`` (float64: the ground height the clip was measured against) -- and ``airborne_frames`` (frames with no
     body in contact).  ``contact``: a :class:`ContactParams` (thresholds, ground, height offsets); the defaults are conventions
-    from common practice, not measured on any robot.  An unknown body name raises ``KeyError`` listing the model's names."""
+    from common practice, not measured on any robot.  An unknown body name raises ``KeyError`` listing the model's names.
+    ``lock_feet`` (only with ``contact_bodies``): the foot slide of the contact bodies is removed from qpos (:func:`lock_feet`, behind
+    the low-pass) before the export, and every clip's dict also holds ``footlock_stats`` -- ``runs``, ``locked_frames``,
+    ``limit_frames`` (int32 ``[C]``), ``shift_max``, ``residual_max`` (float64 ``[C]``, metres); ``True`` or a dict of
+    ``Engine.motion_footlock``'s parameters."""
     if gmr.model.planar_base:
         raise NotImplementedError("the tracking export assumes a free-joint root; use retarget_batch for a planar-base robot")
     from .engine import _report_names
+    if lock_feet and contact_bodies is None:
+        raise ValueError("lock_feet needs contact_bodies: the bodies to lock")
     if contact_bodies is not None:
         contact_body_ids(gmr.model.body_names, contact_bodies)  # (an unknown name: before any launch)
+    locks = None
+    if lock_feet:
+        qpos, stats, lowpass_hz = _smooth_and_lock(gmr._engine, gmr.model.body_names, qpos, seq_offsets, fps, lowpass_hz, contact_bodies,
+                                                   contact, lock_feet)
+        locks = [stats]
     track = gmr._engine.motion_track(qpos, seq_offsets, fps, fps_out, lowpass_hz=0.0 if lowpass_hz is None else lowpass_hz)
     contacts = None if contact_bodies is None else [_track_contacts(gmr._engine, track, gmr.model.body_names, contact_bodies, contact)]
-    return tracks_to_host([track], fps_out, [gmr.model.body_names], [_report_names(gmr._cm)[1]], contacts=contacts)[0]
+    return tracks_to_host([track], fps_out, [gmr.model.body_names], [_report_names(gmr._cm)[1]], contacts=contacts, locks=locks)[0]
+
+
+def _smooth_and_lock(eng, model_body_names, qpos, seq_offsets, fps, lowpass_hz, contact_bodies, contact, lock_feet):
+    """The front of ``tracking_from_qpos(lock_feet=...)`` on an ``Engine``: the low-pass, then the foot locking.  Returns (qpos,
+    stats, the low-pass left for the export: none)."""
+    if lowpass_hz:
+        qpos = _smooth_qpos(eng, qpos, seq_offsets, fps, lowpass_hz)
+    kw = dict(lock_feet) if isinstance(lock_feet, dict) else {}
+    qpos, stats = _lock_feet(eng, model_body_names, qpos, seq_offsets, fps, contact_bodies, contact, kw)
+    return qpos, stats, None
 
 
 def smooth_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, lowpass_hz) -> torch.Tensor:
@@ -390,6 +485,8 @@ def save_tracking(path: str, track: Dict, override: bool = False) -> bool:
         extra = {"contact": track["contact"], "contact_body_names": np.asarray(list(track["contact_body_names"]), dtype=np.str_),
                  "airborne_frames": np.int32(track["airborne_frames"])}
         extra.update(("contact_stats_" + k, np.asarray(track["contact_stats"][k])) for k in CONTACT_STATS)
+    if "footlock_stats" in track:  # (tracking_from_qpos(..., lock_feet=...): one array footlock_stats_<key> per statistic)
+        extra.update(("footlock_stats_" + k, np.asarray(track["footlock_stats"][k])) for k in FOOTLOCK_STATS)
     with open(path, "wb") as f:  # (a file object: np.savez appends nothing to the name)
         np.savez(f, fps=np.float64(track["fps"]), body_names=np.asarray(list(track["body_names"]), dtype=np.str_),
                  joint_names=np.asarray(list(track["joint_names"]), dtype=np.str_), quat_order=np.asarray(track["quat_order"]),
@@ -409,6 +506,8 @@ def load_tracking(path: str) -> Dict:
             stats["base"] = np.float64(stats["base"])
             d.update(contact=z["contact"], contact_body_names=[str(n) for n in z["contact_body_names"]], contact_stats=stats,
                      airborne_frames=int(z["airborne_frames"]))
+        if "footlock_stats_runs" in z.files:
+            d["footlock_stats"] = {k: z["footlock_stats_" + k] for k in FOOTLOCK_STATS}
     return d
 
 

@@ -375,6 +375,74 @@ def _contact_input(eng: "Engine", track_or_arrays, out_offsets, body_ids, height
     return ci, MotionContacts(res), keep
 
 
+FOOTLOCK_FIELDS = _native.FOOTLOCK_OUTPUTS   # the arrays of the foot locking, in gmr_footlock_input's order
+# Parameters of the foot locking when none are given: conventions (a five-frame ramp, runs of two frames, eight damped iterations
+# with lambda^2 = 1e-6 m^2 and steps of at most 0.2 rad), not measured on any robot here.
+FOOTLOCK_DEFAULTS = {"blend_frames": 5, "min_run": 2, "iterations": 8, "damping": 1e-6, "step_cap": 0.2}
+
+
+class MotionFootlock(dict):
+    """Result of ``motion_footlock``: the device tensors by name (``FOOTLOCK_FIELDS``): ``qpos`` float64 ``[N, nq]`` (the cleaned
+    rows), ``pos`` and ``shift`` float64 ``[N, C, 3]`` (the contact bodies' origins before, and how far each is moved), ``runs``,
+    ``locked_frames`` and ``limit_frames`` int32 ``[S, C]``, ``shift_max`` and ``residual_max`` (m) float64 ``[S, C]``."""
+
+
+def _footlock_input(eng: "Engine", qpos, seq_offsets, contact, body_ids, blend_frames, min_run, iterations, damping, step_cap, out):
+    """Check the arguments of one foot-locking call and fill its ``FootlockInput`` (all but the stream).  Returns (input,
+    MotionFootlock, keep-alive)."""
+    dev = eng.device
+    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or int(qpos.shape[1]) != eng.nq or not qpos.is_contiguous():
+        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
+    N = int(qpos.shape[0])
+    if isinstance(seq_offsets, torch.Tensor):
+        offs = seq_offsets
+        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
+            raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
+    else:
+        o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+        if o.ndim != 1 or o.size < 1:
+            raise ValueError("seq_offsets must hold n_seq + 1 entries")
+        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    S = int(offs.shape[0]) - 1
+    ids = np.ascontiguousarray(body_ids, dtype=np.int32)   # a host array: the library reads it before it returns
+    if ids.ndim != 1 or not 1 <= ids.size <= _native.FOOTLOCK_MAX_BODIES:
+        raise ValueError(f"body_ids must name 1 .. {_native.FOOTLOCK_MAX_BODIES} contact bodies")
+    if ids.min() < 0 or ids.max() >= eng.nbody or len(set(ids.tolist())) != ids.size:
+        raise ValueError(f"body_ids must be distinct body indices in [0, {eng.nbody})")
+    Cn = int(ids.size)
+    if not isinstance(contact, torch.Tensor) or contact.device != dev or contact.dtype != torch.uint8 or tuple(contact.shape) != (N, Cn) \
+            or not contact.is_contiguous():
+        raise EngineError(f"contact must be a contiguous uint8 [{N}, {Cn}] tensor on the engine's device")
+    if int(blend_frames) < 0 or int(min_run) < 1 or not 1 <= int(iterations) <= _native.FOOTLOCK_MAX_ITERATIONS:
+        raise ValueError(f"blend_frames >= 0, min_run >= 1 and 1 <= iterations <= {_native.FOOTLOCK_MAX_ITERATIONS} are required")
+    if not (np.isfinite(damping) and damping > 0.0 and np.isfinite(step_cap) and step_cap > 0.0):
+        raise ValueError("damping and step_cap must be finite and > 0")
+    f64, i32 = torch.float64, torch.int32
+    shapes = {"qpos": ((N, eng.nq), f64), "pos": ((N, Cn, 3), f64), "shift": ((N, Cn, 3), f64), "runs": ((S, Cn), i32),
+              "locked_frames": ((S, Cn), i32), "shift_max": ((S, Cn), f64), "residual_max": ((S, Cn), f64), "limit_frames": ((S, Cn), i32)}
+    if out is None:
+        # rows outside every clip are not written, and a call without rows launches nothing: zeros, and qpos starts as a copy
+        res = {k: (qpos.clone() if k == "qpos" else torch.zeros(sh, dtype=dt, device=dev)) for k, (sh, dt) in shapes.items()}
+    else:
+        res = {k: out[k] for k in FOOTLOCK_FIELDS if k in out}
+        if set(out) - set(FOOTLOCK_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                                  or t.device != dev or not t.is_contiguous() for k, t in res.items()):
+            raise EngineError("out must map names of FOOTLOCK_FIELDS to contiguous tensors of the call's shapes on the engine's device")
+        if not {"qpos", "pos", "shift"} <= set(res):
+            raise EngineError("out must hold qpos, pos and shift: the three are required")
+    if res["qpos"].data_ptr() == qpos.data_ptr() and N > 0:
+        raise EngineError("out['qpos'] must not alias qpos")
+    fi = _native.FootlockInput()
+    fi.qpos, fi.n_frames, fi.seq_offsets, fi.contact = qpos.data_ptr(), N, offs.data_ptr(), contact.data_ptr()
+    fi.body_ids, fi.n_seq, fi.n_contact = ids.ctypes.data, S, Cn
+    fi.blend_frames, fi.min_run, fi.iterations = int(blend_frames), int(min_run), int(iterations)
+    fi.damping, fi.step_cap = float(damping), float(step_cap)
+    for k, t in res.items():
+        setattr(fi, k + "_out", t.data_ptr())
+    return fi, MotionFootlock(res), [qpos, offs, contact, ids]
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -985,6 +1053,24 @@ class Engine:
                                        speed_on, speed_off, out)
         ci.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self._lib.gmr_motion_contacts(self._h, C.byref(ci)), "gmr_motion_contacts")
+        return res
+
+    def motion_footlock(self, qpos: torch.Tensor, seq_offsets, contact: torch.Tensor, body_ids,
+                        blend_frames: int = FOOTLOCK_DEFAULTS["blend_frames"], min_run: int = FOOTLOCK_DEFAULTS["min_run"],
+                        iterations: int = FOOTLOCK_DEFAULTS["iterations"], damping: float = FOOTLOCK_DEFAULTS["damping"],
+                        step_cap: float = FOOTLOCK_DEFAULTS["step_cap"], out=None) -> MotionFootlock:
+        """Remove the horizontal slide of planted feet from qpos ``[N, nq]`` float64 (engine layout, concatenated clips) in three
+        kernels (``gmr_motion_footlock``; the definition is the contract in include/gmr_amd.h).  ``seq_offsets`` ``[S + 1]``: the
+        clips' rows, a host sequence (uploaded once) or a device int64 tensor.  ``contact`` uint8 ``[N, C]``: non-zero = planted,
+        labels at qpos's own frames.  ``body_ids``: the 1 <= C <= 8 contact bodies, a host sequence of distinct body indices.  Over
+        every run of at least ``min_run`` planted frames a body is pinned to the mean of its own xy; the shift fades over
+        ``blend_frames`` frames on both sides; ``iterations`` damped least-squares steps (``damping`` = lambda^2 in m^2, steps of at
+        most ``step_cap`` rad) over the hinges only that body hangs on move it there.  The defaults are conventions, not measured
+        on any robot.  Returns a :class:`MotionFootlock` of device tensors; ``out``: caller-owned result tensors by name (``qpos``,
+        ``pos`` and ``shift`` are required, a statistic left out is not computed).  Asynchronous on the current stream."""
+        fi, res, keep = _footlock_input(self, qpos, seq_offsets, contact, body_ids, blend_frames, min_run, iterations, damping, step_cap, out)
+        fi.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.gmr_motion_footlock(self._h, C.byref(fi)), "gmr_motion_footlock")
         return res
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,

@@ -180,14 +180,16 @@ class MultiRobotRetargeting:
 
     def tracking_from_qpos(self, qpos: Dict[str, torch.Tensor], seq_offsets: Sequence[int], fps, fps_out,
                            lowpass_hz=None, contact_bodies: Optional[Dict[str, Sequence[str]]] = None,
-                           contact=None) -> Dict[str, List[Dict]]:
+                           contact=None, lock_feet=False) -> Dict[str, List[Dict]]:
         """``dataset.tracking_from_qpos`` for every robot in one launch (``EngineGroup.motion_track``): ``qpos[robot]`` ``[N, nq]``
         float64 on the group's device, the same clips (at ``fps``: one rate or one per clip) for every robot -> ``{robot:
         [tracking dict per clip]}`` at ``fps_out``, the same keys, dtypes and arrays as the single-robot call.  ``lowpass_hz``:
         the cutoff of the zero-phase low-pass applied to qpos first (``None``: off); one value, or one per robot.
         ``contact_bodies``: ``{robot: [body names]}`` -- the contact labels of ``dataset.tracking_from_qpos`` for the robots it
         names, one ``Engine.motion_contacts`` launch per robot behind the shared export (there is no group entry); ``contact``:
-        one ``dataset.ContactParams`` for all, or ``{robot: ContactParams}``."""
+        one ``dataset.ContactParams`` for all, or ``{robot: ContactParams}``.  ``lock_feet`` (only with ``contact_bodies``): the
+        foot locking of ``dataset.tracking_from_qpos`` for the robots ``contact_bodies`` names, robot after robot in front of the
+        shared export (there is no group entry); the low-pass of those robots then runs in front of it, per robot too."""
         from . import dataset
         from .engine import _report_names
         self._refuse_planar()
@@ -195,7 +197,9 @@ class MultiRobotRetargeting:
         missing = [r for r in self.robots if r not in qpos]
         if missing:
             raise KeyError(f"no qpos for {missing}")
-        contacts = None
+        contacts = locks = None
+        if lock_feet and contact_bodies is None:
+            raise ValueError("lock_feet needs contact_bodies: the bodies to lock")
         if contact_bodies is not None:
             unknown = [r for r in contact_bodies if r not in self.robots]
             if unknown:
@@ -208,28 +212,46 @@ class MultiRobotRetargeting:
             q = qpos[r]
             q = torch.from_numpy(np.ascontiguousarray(q)).to(self.device) if isinstance(q, np.ndarray) else q
             batches.append((q, offs, fps))
+        if lock_feet:
+            hz = list(lowpass_hz) if isinstance(lowpass_hz, (list, tuple, np.ndarray)) else [lowpass_hz] * len(self.robots)
+            locks, left = [], []
+            for i, (r, eng, m) in enumerate(zip(self.robots, self.group.engines, self.models)):
+                if r not in contact_bodies:
+                    locks.append(None)
+                    left.append(0.0 if hz[i] is None else hz[i])
+                    continue
+                q, st, _ = dataset._smooth_and_lock(eng, m.body_names, batches[i][0], offs, fps, hz[i], contact_bodies[r],
+                                                    contact.get(r) if isinstance(contact, dict) else contact, lock_feet)
+                batches[i] = (q, offs, fps)
+                locks.append(st)
+                left.append(0.0)   # (filtered already)
+            lowpass_hz = left
         res = self.group.motion_track(batches, fps_out, lowpass_hz=0.0 if lowpass_hz is None else lowpass_hz)
         if contact_bodies is not None:
             contacts = [dataset._track_contacts(eng, tr, m.body_names, contact_bodies[r], contact.get(r) if isinstance(contact, dict) else contact)
                         if r in contact_bodies else None for r, eng, m, tr in zip(self.robots, self.group.engines, self.models, res)]
         clips = dataset.tracks_to_host(res, fps_out, [m.body_names for m in self.models], [_report_names(cm)[1] for cm in self._cms],
-                                       contacts=contacts)
+                                       contacts=contacts, locks=locks)
         return dict(zip(self.robots, clips))
 
     def retarget_clips(self, pos, quat, body_names: Sequence[str], seq_offsets: Sequence[int], fps=30, height_adjust: bool = True,
                        root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
                        clip_start: str = "qpos0", report: bool = False, track_fps: Optional[float] = None,
-                       lowpass_hz: Optional[float] = None, contact_bodies: Optional[Dict[str, Sequence[str]]] = None, contact=None):
+                       lowpass_hz: Optional[float] = None, contact_bodies: Optional[Dict[str, Sequence[str]]] = None, contact=None,
+                       lock_feet=False):
         """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
         solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
         ``dataset.MotionWriter.submit`` as they are.  With ``report`` a second value is returned: ``{robot: engine.ClipReport}``
         of the solved qpos (:meth:`clip_report`, solve counts included), host arrays.  With ``track_fps`` a last value is added:
         ``{robot: [tracking dict per clip]}`` at that rate (:meth:`tracking_from_qpos` on the same qpos).  With ``lowpass_hz``
         every robot's solved qpos is smoothed once (``dataset.smooth_qpos`` at ``fps``) and everything is made from that.
-        ``contact_bodies`` / ``contact`` (with ``track_fps``): :meth:`tracking_from_qpos`'s contact labels."""
+        ``contact_bodies`` / ``contact`` (with ``track_fps``): :meth:`tracking_from_qpos`'s contact labels; ``lock_feet``: its foot
+        locking (the tracking dicts only)."""
         self._refuse_planar()
         if contact_bodies is not None and track_fps is None:
             raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
+        if lock_feet and contact_bodies is None:
+            raise ValueError("lock_feet needs contact_bodies: the bodies to lock")
         tpos = torch.from_numpy(np.ascontiguousarray(pos)) if isinstance(pos, np.ndarray) else pos
         tquat = torch.from_numpy(np.ascontiguousarray(quat)) if isinstance(quat, np.ndarray) else quat
         tpos, tquat = tpos.to(self.device), tquat.to(self.device)
@@ -246,7 +268,7 @@ class MultiRobotRetargeting:
         res = (motions, {r: rep.numpy() for r, rep in reps.items()}) if report else (motions,)
         if track_fps is not None:
             res += (self.tracking_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, track_fps,
-                                            contact_bodies=contact_bodies, contact=contact),)
+                                            contact_bodies=contact_bodies, contact=contact, **({"lock_feet": lock_feet} if lock_feet else {})),)
         return res[0] if len(res) == 1 else res
 
     def _solve(self, pos, quat, body_names, seq_offsets, chunk, burn_in, offset_to_ground, verify, human_heights, check, clip_start):

@@ -106,6 +106,7 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--contact_height_off", default=None, type=float, metavar="M", help="... and leaves it above this height (default 0.05)")
     ap.add_argument("--contact_speed_on", default=None, type=float, metavar="M_PER_S", help="a body enters contact at or below this speed (default 0.3)")
     ap.add_argument("--contact_speed_off", default=None, type=float, metavar="M_PER_S", help="... and leaves it above this speed (default 0.6)")
+    ap.add_argument("--lock_feet", default=False, action="store_true", help="with --contact_bodies: remove the foot slide of those bodies from qpos before the tracking exports are made (dataset.lock_feet, on the GPU; the .npz gain footlock_stats_*); the pickles are unchanged; default: off")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -132,6 +133,8 @@ def resolve_contact(ap, args) -> None:
     if spec is None:
         if given:
             ap.error("--contact_" + given[0] + " needs --contact_bodies")
+        if getattr(args, "lock_feet", False):
+            ap.error("--lock_feet needs --contact_bodies")
         return
     if args.track_fps is None:
         ap.error("--contact_bodies is only valid with --track_fps")
@@ -158,6 +161,8 @@ def resolve_contact(ap, args) -> None:
     if not (prm.height_on <= prm.height_off and 0 <= prm.speed_on <= prm.speed_off):
         ap.error("--contact_height_on <= --contact_height_off and 0 <= --contact_speed_on <= --contact_speed_off are required")
     args.contact_kw = {"contact_bodies": bodies, "contact": prm}
+    if getattr(args, "lock_feet", False):  # (absent without the flag: nothing changes then)
+        args.contact_kw["lock_feet"] = True
 
 
 def track_path(args, target: str) -> str:

@@ -55,6 +55,8 @@
  *                      the reference state of (clip, time) queries against a library of retargeted clips kept as qpos
  *   gmr_motion_contacts  (no counterpart in the reference) the per-frame foot-contact labels a tracking / AMP pipeline computes
  *                      from the export in a host loop, and the foot-slide and ground-penetration figures of a retargeted clip
+ *   gmr_motion_footlock  (no counterpart in the reference) the foot-slide clean-up such a pipeline runs on the host: a loop over
+ *                      contact phases with a small leg IK per frame, here a post-pass from qpos to qpos
  *   gmr_dof_to_rot     KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -475,6 +477,89 @@ typedef struct gmr_contact_input {
   double        *base_out;
 } gmr_contact_input;
 int gmr_motion_contacts(gmr_model *m, const gmr_contact_input *in);
+
+/* Foot locking: remove the horizontal slide of planted feet from retargeted qpos.  Per contact column the body is pinned, over
+ * every planted run, to the mean of its own xy; the shift is blended out over W frames on both sides of a run; a damped
+ * least-squares iteration over the column's own hinges moves the body there.  Heights and orientations stay: this removes slide,
+ * not penetration.  All arithmetic below is done as written, in float64, without floating-point contraction; a - b - c means
+ * (a - b) - c.
+ *
+ * The whole call is this struct, its stream included (in->stream, in the sense of the stream-order paragraph at the top of this
+ * file); the struct and body_ids are read completely before the call returns.  The call enqueues three kernels on in->stream and
+ * nothing else: no allocation, no copy, no synchronisation.  pos_out and shift_out are also the kernels' exchange.
+ *   qpos          device f64 [n_frames][nq], free-joint layout (x y z, qw qx qy qz, hinges), concatenated clips (N = n_frames)
+ *   seq_offsets   DEVICE int64 [n_seq+1]: clip s owns the rows a = clamp(seq_offsets[s], 0, N) to b = clamp(seq_offsets[s+1], a, N).
+ *                 The kernels only clamp; clips that overlap race with each other.
+ *   contact       device u8 [n_frames][C]: non-zero = planted; labels at qpos's own frames
+ *   body_ids      HOST int32 [C], C = n_contact, 1 <= C <= 8, read and validated before the call returns
+ *   blend_frames  W >= 0;  min_run >= 1;  iterations I, 1 .. 32;  damping = lambda^2 > 0 (m^2);  step_cap > 0 (rad)
+ * Chains.  The path of column c is the bodies from body_ids[c] up to, not including, the root, taken root side first; its chain is
+ * the hinges on that path that lie on no other column's path (a shared waist joint is never moved, nor is the root).
+ * FK of column c at the angles th (MuJoCo's convention, what gmr_evaluate reports as xpos): x = qpos[0..2], r = qpos[3..6] / n with
+ * n = sqrt(qw qw + qx qx + qy qy + qz qz); then per path body j: x = x + rot(r, pos_j), r = r (x) quat_j, and for a hinge
+ * r = r (x) [cos(th_j / 2), sin(th_j / 2) axis_j].  (a (x) b).w = a.w b.w - a.x b.x - a.y b.y - a.z b.z, .x = a.w b.x + a.x b.w +
+ * a.y b.z - a.z b.y, .y = a.w b.y - a.x b.z + a.y b.w + a.z b.x, .z = a.w b.z + a.x b.y - a.y b.x + a.z b.w.  rot(q, v) = v + q.w t +
+ * (q.xyz x t) with t = 2 (q.xyz x v), every cross product as (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x).
+ * Per clip s, frame k = 0 .. M_s-1 (row g = a + k), column c:
+ *   valid[k]  all nq entries of the row are finite
+ *   L[k]      contact[g][c] != 0 && valid[k]
+ *   p[k]      the FK above at the row's own angles
+ *   runs      maximal intervals of L = 1 inside the clip; a run shorter than min_run counts as L = 0.  Nothing crosses a clip.
+ *   anchor    A = (sx / n, sy / n) over the run's n frames.  sx: per 64-frame tile of the clip (frames 64 t .. 64 t + 63 counted
+ *             from the clip's first) the run's p.x at their positions in the tile and zeros elsewhere, summed by the balanced binary
+ *             tree (neighbours first); the tiles the run touches are added to 0.0 in ascending order.  sy likewise.
+ *   inside a run   d[k] = (A.x - p.x, A.y - p.y, 0)
+ *   outside, valid frames   e = the last frame of the nearest run before k, f = the first frame of the nearest run after k (same clip
+ *             and column).  w- = S(1 - (k - e) / (W + 1)) when e exists and k - e <= W, else 0; w+ = S(1 - (f - k) / (W + 1)) when
+ *             f exists and f - k <= W, else 0; S(t) = t t (3 - 2 t).  d[k] = (w- d[e] + w+ d[f]) / max(1, w- + w+), a side
+ *             without weight adding 0.0; no shift when both are 0.
+ *   solve     every valid frame inside a run or with a weight.  t = (p.x + d.x, p.y + d.y, p.z); q = the row's own chain angles q0;
+ *             exactly I times, no early exit:  e = t - p(q);  J_i = w_i x (p(q) - o_i) for the chain's hinges, root side first, w_i
+ *             = rot(r_i, axis_i) and o_i = x_i the hinge body's world pose;  G = J J^T (each entry summed over i in that order from
+ *             0.0) + lambda^2 on the diagonal;  Cholesky l00 = sqrt(g00), l10 = g10 / l00, l20 = g20 / l00, l11 = sqrt(g11 - l10
+ *             l10), l21 = (g21 - l20 l10) / l11, l22 = sqrt(g22 - l20 l20 - l21 l21);  z0 = e0 / l00, z1 = (e1 - l10 z0) / l11,
+ *             z2 = (e2 - l20 z0 - l21 z1) / l22;  y2 = z2 / l22, y1 = (z1 - l21 y2) / l11, y0 = (z0 - l10 y1 - l20 y2) / l00;
+ *             dq_i = J_i0 y0 + J_i1 y1 + J_i2 y2;  m = max |dq_i|, scale = m > step_cap ? step_cap / m : 1;
+ *             q_i = clamp(q_i + scale dq_i, min(lo_i, q0_i), max(hi_i, q0_i)) for a limited hinge, unclamped otherwise.
+ * Outputs, device arrays:
+ *   qpos_out [n_frames][nq] f64          the rows with the solved chain angles.  Every other entry -- the root's seven, hinges outside
+ *                                        the chains, frames that are not solved, invalid frames -- is copied bit for bit.  Must not
+ *                                        alias qpos
+ *   pos_out [n_frames][C][3] f64         p; NaN in an invalid frame.  Required
+ *   shift_out [n_frames][C][3] f64       d, zero where there is none.  Required
+ *   runs_out [n_seq][C] i32              runs of at least min_run frames; may be NULL
+ *   locked_frames_out [n_seq][C] i32     frames inside them; may be NULL
+ *   shift_max_out [n_seq][C] f64         sqrt of the maximum of d.x d.x + d.y d.y over the solved frames; may be NULL
+ *   residual_max_out [n_seq][C] f64      maximum of sqrt(ex ex + ey ey + ez ez), e = t - p(q) after the last iteration; may be NULL
+ *   limit_frames_out [n_seq][C] i32      solved frames in which a limited chain hinge ends on its widened bound; may be NULL
+ * A clip without frames reports 0.  Rows outside every clip are not written.  A non-finite row changes no output byte of another
+ * clip; within its own clip it is copied through and only splits runs.  Two calls give identical bytes.
+ * GMR_EINVAL: a body id out of range or named twice, a chain of fewer than 3 hinges, C outside 1 .. 8, W < 0, min_run < 1, I outside
+ * 1 .. 32, damping or step_cap not finite and > 0, qpos_out == qpos, NULL arrays with work to do, negative counts.
+ * GMR_EUNSUPPORTED: a planar-base model, a chain of more than 16 hinges, a contact body more than 32 bodies below the root.  These
+ * are checked before anything is enqueued.  n_frames = 0 or n_seq = 0 returns GMR_OK without a launch.  Asynchronous on
+ * in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 152; offsets qpos 0, n_frames 8, seq_offsets 16, contact 24, body_ids 32, n_seq 40, n_contact 44,
+ * blend_frames 48, min_run 52, iterations 56, reserved 60, damping 64, step_cap 72, stream 80, qpos_out 88, pos_out 96,
+ * shift_out 104, runs_out 112, locked_frames_out 120, shift_max_out 128, residual_max_out 136, limit_frames_out 144.  */
+typedef struct gmr_footlock_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  const uint8_t *contact;         /* device [n_frames][n_contact] u8 */
+  const int32_t *body_ids;        /* HOST [n_contact] body indices */
+  int32_t        n_seq, n_contact;
+  int32_t        blend_frames, min_run;
+  int32_t        iterations, reserved;
+  double         damping, step_cap;
+  void          *stream;          /* the call's stream */
+  double        *qpos_out;
+  double        *pos_out, *shift_out;
+  int32_t       *runs_out, *locked_frames_out;
+  double        *shift_max_out, *residual_max_out;
+  int32_t       *limit_frames_out;
+} gmr_footlock_input;
+int gmr_motion_footlock(gmr_model *m, const gmr_footlock_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
