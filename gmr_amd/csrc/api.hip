@@ -1,9 +1,10 @@
 // api.hip -- C ABI of libgmr_amd.so (include/gmr_amd.h): model handle, scheduling, kernel launches.
 //
-// Host side is plain C++: blob validation, the derived index structures the kernels want (tree depth
-// levels, active-dof list, ancestor masks, composite nodes of the task tree, FK branch-slot plan), one
-// device allocation per model, a grow-only scheduling workspace, and shape checks in front of every
-// launch.  No torch, no CPU fallback: every failure is reported, nothing is silently computed elsewhere.
+// Host side is plain C++: one device allocation per model for the image that model_plan.h plans from the
+// blob (validation, active-dof list, ancestor masks, composite nodes of the task tree, LDS layout, FK
+// branch-slot plan: host-only code, tested without a device), stream-ordered scheduling scratch, and shape
+// checks in front of every launch.  No torch, no CPU fallback: every failure is reported, nothing is
+// silently computed elsewhere.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,11 +36,11 @@
 #include "footlock_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
+#include "model_plan.h"
 
 using gmr::u64;
 
 struct gmr_model {
-  int hplan_extra_cycles = 0;  // modelled LDS bank-conflict cycles of the H pair plan, per solve (after ordering)
   int device = -1;
   gmr_blob_header h{};
   std::vector<uint8_t> blob;
@@ -127,10 +128,6 @@ const T *blob_ptr(const std::vector<uint8_t> &b, uint32_t off) {
   return reinterpret_cast<const T *>(b.data() + off);
 }
 
-bool range_ok(const gmr_blob_header &h, uint32_t off, size_t bytes) {
-  return off >= sizeof(gmr_blob_header) && (off & 7u) == 0 && (size_t)off + bytes <= h.total_bytes;
-}
-
 // Per-call scheduling data (work items, slot columns, clip offsets) lives in stream-ordered memory: allocated on the call's
 // stream and released on it right behind the launch that reads it.  Calls on the same handle from different streams or host
 // threads therefore never share (or pull away) each other's launch metadata; the pool keeps released blocks for reuse
@@ -215,62 +212,16 @@ const char *seq_offsets_error(const int64_t *offs, int n_seq, int64_t n_frames) 
   return why;
 }
 
-// Kernel variants by padded system size.  GMR_IK_DEV_ONLY36 (experiments only, never the shipped library) builds just
-// ik_kernel<36, true> to cut compile time.
-#ifdef GMR_IK_DEV_ONLY36
-#define GMR_FOR_EACH_NVP(X) X(36)
-#else
-#define GMR_FOR_EACH_NVP(X) X(32) X(36) X(40) X(48) X(64)
-#endif
-
-// Shaped kernel instances (ik_kernel.hip.h, IkShapeAny): X(struct, NVP).  Each entry costs one more ik_kernel and ik_probe_kernel
-// instance at compile time; a model that matches none runs the generic instance.  The structs are defined beside IkShapeAny.
-#define GMR_FOR_EACH_IK_SHAPE(X) X(IkShapeG1Smplx, 36)
-
-// Does the host copy of a model carry exactly the values the shape SH fixes?  (SH::plain is the launch's side: launch_ik.)
-template <class SH>
-bool ik_shape_matches(const gmr::DevModel &d) {
-#define GMR_X(f, e) if (SH::f >= 0 && SH::f != (e)) return false;
-  GMR_IK_SHAPE_FIELDS(GMR_X)
-#undef GMR_X
-  return true;
-}
-// The shape (index into GMR_FOR_EACH_IK_SHAPE) of a model built for kernel variant nvp with the structured QP, or -1.
-int ik_shape_of(const gmr::DevModel &d, int nvp, bool sq) {
-  int idx = 0;
-#define GMR_X(S, v) if (sq && nvp == v && ik_shape_matches<gmr::S>(d)) return idx; ++idx;
-  GMR_FOR_EACH_IK_SHAPE(GMR_X)
-#undef GMR_X
-  return -1;
-}
-// Is `plain` compiled into the shape (its instances take only plain launches and prepare targets in blocks)?
-bool ik_shape_is_plain(int shape) {
-  int idx = 0;
-#define GMR_X(S, v) if (shape == idx++) return gmr::S::plain > 0;
-  GMR_FOR_EACH_IK_SHAPE(GMR_X)
-#undef GMR_X
-  return false;
-}
-const char *ik_shape_name(int shape) {
-  int idx = 0;
-#define GMR_X(S, v) if (shape == idx++) return #S;
-  GMR_FOR_EACH_IK_SHAPE(GMR_X)
-#undef GMR_X
-  return "generic";
-}
+// The kernel variants (GMR_FOR_EACH_NVP), the shaped instances (GMR_FOR_EACH_IK_SHAPE) and the match of a model against them live in
+// model_plan.h: planning a model needs them.
+using gmr::ik_shape_name;
+using gmr::ik_shape_of;
 
 // The instance a launch takes: the model's shape where the launch is what `plain` stands for in a shape (float32 key-points, no
 // offset_to_ground, every item plain, no step cap), else -1 = the generic instance.  This is the only guard: a shape with `plain`
 // compiled in (IkShapeG1Smplx) has no code for float64 input, offset_to_ground, the verification walk or the chunk start.
 int ik_launch_shape(int model_shape, bool force_generic_shape, bool plain, bool in_f64, bool offset_to_ground, bool capped) {
   return model_shape >= 0 && !force_generic_shape && plain && !in_f64 && !offset_to_ground && !capped ? model_shape : -1;
-}
-
-int pick_nvp(int n_act) {
-#define GMR_X(v) if (n_act <= v) return v;
-  GMR_FOR_EACH_NVP(GMR_X)
-#undef GMR_X
-  return -1;
 }
 
 // plain: every item of the launch is a plain one (no verification walk, no speculative chunk start; ik_run).  A shaped instance runs
@@ -424,668 +375,37 @@ void launch_ik_session(const gmr_model *m, const gmr::IkGroupEntry *entries, gmr
 #endif
 }
 
-// host_only: stop in front of the first device call (the model's scalars and its shape are then known: gmr_debug_ik_shape)
-int build_device_model(gmr_model *m, bool host_only = false) {
-  const gmr_blob_header &h = m->h;
-  const auto &B = m->blob;
-  const int nb = h.nbody;
-  const int32_t *parent = blob_ptr<int32_t>(B, h.off_parent), *jtype = blob_ptr<int32_t>(B, h.off_jnt_type);
-  const int32_t *qadr = blob_ptr<int32_t>(B, h.off_qpos_adr), *dadr = blob_ptr<int32_t>(B, h.off_dof_adr);
-  const int32_t *limited = blob_ptr<int32_t>(B, h.off_jnt_limited);
-  const double *bpos = blob_ptr<double>(B, h.off_body_pos), *bquat = blob_ptr<double>(B, h.off_body_quat);
-  const double *bquat_raw = blob_ptr<double>(B, h.off_body_quat_raw), *axis = blob_ptr<double>(B, h.off_jnt_axis);
-  const double *range = blob_ptr<double>(B, h.off_jnt_range), *qpos0 = blob_ptr<double>(B, h.off_qpos0);
+// The host's copy of what a plan (model_plan.h) says of a model; no device pointer yet.
+void adopt_plan(gmr_model *m, const gmr::ModelPlan &p) {
+  m->dm = p.dm;
+  m->lay = p.lay; m->lay_eval = p.lay_eval;
+  m->lds_bytes = p.lds_bytes; m->lds_bytes_eval = p.lds_bytes_eval;
+  m->nvp = p.nvp; m->n_act = p.n_act; m->shape = p.shape;
+  m->fk_lds_bytes = p.fk_lds_bytes; m->fk_lds_bytes_min = p.fk_lds_bytes_min;
+}
 
-  // ---- tree sanity: depth-first order, free root, hinges elsewhere ----
-  if (parent[0] != -1 || jtype[0] != GMR_JNT_FREE || qadr[0] != 0 || dadr[0] != 0) {
-    set_err(m, "body 0 must be the free-joint root");
-    return GMR_EINVAL;
-  }
-  std::vector<int> depth(nb, 0);
-  int maxdepth = 0, nq = 7, nv = 6;
-  for (int b = 1; b < nb; ++b) {
-    if (parent[b] < 0 || parent[b] >= b) { set_err(m, "bodies are not in depth-first order"); return GMR_EINVAL; }
-    depth[b] = depth[parent[b]] + 1;
-    maxdepth = std::max(maxdepth, depth[b]);
-    if (jtype[b] == GMR_JNT_HINGE) {
-      if (qadr[b] != nq || dadr[b] != nv) { set_err(m, "joint addresses out of order at body %d", b); return GMR_EINVAL; }
-      ++nq; ++nv;
-    } else if (jtype[b] != GMR_JNT_NONE) { set_err(m, "unsupported joint type at body %d", b); return GMR_EUNSUPPORTED; }
-  }
-  if (nq != h.nq || nv != h.nv) { set_err(m, "nq/nv do not match the joint list"); return GMR_EINVAL; }
-
-  // ---- tasks ----
-  std::vector<int> tbody(2 * GMR_MAX_TASKS, 0), tslot(2 * GMR_MAX_TASKS, 0);
-  std::vector<double> twp(2 * GMR_MAX_TASKS, 0.0), twr(2 * GMR_MAX_TASKS, 0.0);
-  for (int k = 0; k < 2; ++k) {
-    const int32_t *tb = blob_ptr<int32_t>(B, h.off_task_body[k]), *ts = blob_ptr<int32_t>(B, h.off_task_slot[k]);
-    const double *wp = blob_ptr<double>(B, h.off_task_wp[k]), *wr = blob_ptr<double>(B, h.off_task_wr[k]);
-    for (int t = 0; t < h.ntask[k]; ++t) {
-      if (tb[t] < 0 || tb[t] >= nb || ts[t] < 0 || ts[t] >= h.nslot) { set_err(m, "task %d of table %d out of range", t, k + 1); return GMR_EINVAL; }
-      tbody[k * GMR_MAX_TASKS + t] = tb[t]; tslot[k * GMR_MAX_TASKS + t] = ts[t];
-      twp[k * GMR_MAX_TASKS + t] = wp[t]; twr[k * GMR_MAX_TASKS + t] = wr[t];
-    }
-  }
-  // body a is an ancestor-or-self of body b ?
-  auto above = [&](int a, int b) {
-    while (b > a) b = parent[b];
-    return b == a;
-  };
-  // ---- bodies the IK needs: the task bodies and their ancestors.  Everything else (the 14 finger links of
-  //      unitree_g1_with_hands, head / hand cosmetics) never enters a residual or a screw, so the IK kernel works on this
-  //      pruned tree (fewer lanes, less LDS per wavefront); gmr_evaluate keeps the full tree for configuration.data.xpos. ----
-  std::vector<int> keep, bmap(nb, -1);
-  {
-    std::vector<char> needed(nb, 0);
-    needed[0] = 1;
-    for (int k = 0; k < 2; ++k)
-      for (int t = 0; t < h.ntask[k]; ++t)
-        for (int b = tbody[k * GMR_MAX_TASKS + t]; b >= 0 && !needed[b]; b = parent[b]) needed[b] = 1;
-    for (int b = 0; b < nb; ++b)
-      if (needed[b]) { bmap[b] = (int)keep.size(); keep.push_back(b); }
-  }
-  const int nb_ik = (int)keep.size();
-  // ---- active dofs: root 6 + hinges with at least one task (either table) at or below them ----
-  std::vector<int> abody, akind, aqadr, alim;
-  std::vector<double> arange;
-  // the root's six rows.  A planar base (gmr_blob.h root_dof_mask 0x23) keeps all six in the QP, with z / roll / pitch as *null*
-  // dofs (kind 7): the kernel's hinge path gives them the root body's hinge axis -- zero -- hence a zero screw, a zero gradient,
-  // a diagonal of damping alone and dq = 0 exactly: the reference's 27-dof problem solved inside the 30-row one, with no
-  // branch added to the kernel (rows 3, 4, 5 stay the root's rotation step: 0, 0, yaw).  They keep their place in the
-  // elimination order but are left out of the ancestor relation (no H pairs) and of the structured QP's core.
-  const int root_mask = h.root_dof_mask ? h.root_dof_mask : 0x3F;
-  if (root_mask != 0x3F && root_mask != 0x23) { set_err(m, "root_dof_mask 0x%x: only a free joint (0x3f) or a planar base (0x23) is supported", root_mask); return GMR_EUNSUPPORTED; }
-  if (axis[0] != 0.0 || axis[1] != 0.0 || axis[2] != 0.0) { set_err(m, "the root body must not carry a hinge axis"); return GMR_EINVAL; }
-  for (int k = 0; k < 6; ++k) {
-    abody.push_back(0); akind.push_back(((root_mask >> k) & 1) ? k : 7); aqadr.push_back(k < 3 ? k : 3); alim.push_back(0); arange.push_back(0); arange.push_back(0);
-  }
-  const int n_root = 6;
-  for (int b = 1; b < nb; ++b) {
-    if (jtype[b] != GMR_JNT_HINGE) continue;
-    bool used = false;
-    for (int k = 0; k < 2 && !used; ++k)
-      for (int t = 0; t < h.ntask[k] && !used; ++t) used = above(b, tbody[k * GMR_MAX_TASKS + t]);
-    if (!used) continue;
-    abody.push_back(b); akind.push_back(6); aqadr.push_back(qadr[b]); alim.push_back(limited[b] ? 1 : 0);
-    arange.push_back(range[2 * b]); arange.push_back(range[2 * b + 1]);
-  }
-  const int n_act = (int)abody.size();
-  const int nvp = pick_nvp(std::max(n_act, m->min_nvp));
-  if (nvp < 0) { set_err(m, "%d active dofs exceed the kernel limit of 64", n_act); return GMR_EUNSUPPORTED; }
-  // ancestor relation among active dofs in depth-first order (j above i implies j < i)
-  auto dfs_anc = [&](int j, int i) {
-    if (j >= i) return false;
-    if (akind[i] != 6) return true;      // root dofs (null ones included) form a chain 0 <- 1 <- ... <- 5
-    if (akind[j] != 6) return true;      // every hinge hangs below the root's six dofs
-    return abody[j] != abody[i] && above(abody[j], abody[i]);
-  };
-  // ---- elimination order of the QP: sort dofs by height (longest chain of dofs below), tallest first.  Dofs of equal
-  //      height are never above one another, so a kinematic tree eliminates leaves-first without fill-in and all dofs of
-  //      one height can be eliminated in the same step (level-scheduled sparse U D U' in ik_kernel's box_qp). ----
-  std::vector<int> height(n_act, 0), perm(n_act);
-  for (int i = n_act - 1; i >= 0; --i)
-    for (int j = 0; j < i; ++j)
-      if (dfs_anc(j, i)) height[j] = std::max(height[j], height[i] + 1);
-  std::vector<u64> anc_dfs(n_act, 0);  // relation in depth-first indices, taken before the arrays are permuted
-  for (int i = 0; i < n_act; ++i)
-    for (int j = 0; j < i; ++j)
-      if (dfs_anc(j, i) && akind[i] != 7 && akind[j] != 7) anc_dfs[i] |= 1ull << j;  // a null dof keeps its place in the order but couples with nothing
-  std::iota(perm.begin(), perm.end(), 0);
-  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return height[a] > height[b]; });
-  for (int k = 0; k < n_root; ++k)
-    if (perm[k] != k) { set_err(m, "internal: root dofs must lead the elimination order"); return GMR_EINVAL; }
-  {
-    std::vector<int> b2(n_act), k2(n_act), q2(n_act), l2(n_act), h2(n_act);
-    std::vector<double> r2(2 * n_act);
-    for (int a = 0; a < n_act; ++a) {
-      const int o = perm[a];
-      b2[a] = abody[o]; k2[a] = akind[o]; q2[a] = aqadr[o]; l2[a] = alim[o]; h2[a] = height[o];
-      r2[2 * a] = arange[2 * o]; r2[2 * a + 1] = arange[2 * o + 1];
-    }
-    abody = b2; akind = k2; aqadr = q2; alim = l2; arange = r2; height = h2;
-  }
-  std::vector<u64> aanc(64, 0);
-  for (int a = 0; a < n_act; ++a)
-    for (int b = 0; b < n_act; ++b)
-      if ((anc_dfs[perm[a]] >> perm[b]) & 1ull) {
-        if (b >= a) { set_err(m, "internal: elimination order breaks ancestor-first indexing"); return GMR_EINVAL; }
-        aanc[a] |= 1ull << b;
-      }
-  // ---- FK pointer-jumping plan: ancestor folded in each round, one byte per round (for the pruned IK tree and the full tree) ----
-  auto fk_plan = [&](const std::vector<int> &par, std::vector<u64> &plan, int &rounds) -> bool {
-    const int n = (int)par.size();
-    int maxd = 0;
-    std::vector<int> dep(n, 0);
-    for (int b2 = 1; b2 < n; ++b2) { dep[b2] = dep[par[b2]] + 1; maxd = std::max(maxd, dep[b2]); }
-    rounds = 0;
-    while ((1 << rounds) <= maxd) ++rounds;
-    if (rounds > 8) return false;
-    plan.assign(n, ~0ull);
-    std::vector<int> anc(par);
-    for (int r = 0; r < rounds; ++r) {
-      std::vector<int> nxt(n, -1);
-      for (int b2 = 0; b2 < n; ++b2) {
-        const u64 byte = anc[b2] < 0 ? 0xffull : (u64)anc[b2];
-        plan[b2] = (plan[b2] & ~(0xffull << (8 * r))) | (byte << (8 * r));
-        nxt[b2] = anc[b2] < 0 ? -1 : anc[anc[b2]];
-      }
-      anc = nxt;
-    }
-    for (int b2 = 0; b2 < n; ++b2) if (anc[b2] >= 0) return false;
-    return true;
-  };
-  std::vector<int> par_full(parent, parent + nb), par_ik(nb_ik);
-  for (int i = 0; i < nb_ik; ++i) par_ik[i] = keep[i] == 0 ? -1 : bmap[parent[keep[i]]];
-  std::vector<u64> fkanc, fkanc_full;
-  int fkrounds = 0, fkrounds_full = 0;
-  if (!fk_plan(par_ik, fkanc, fkrounds) || !fk_plan(par_full, fkanc_full, fkrounds_full)) { set_err(m, "tree too deep"); return GMR_EUNSUPPORTED; }
-  (void)maxdepth;
-  // ---- structurally non-zero off-diagonal pairs of H: (i, j) with dof j strictly above dof i ----
-  std::vector<unsigned short> hpair;
-  for (int i = 0; i < n_act; ++i)
-    for (int j = 0; j < i; ++j)
-      if ((aanc[i] >> j) & 1ull) hpair.push_back((unsigned short)((i << 8) | j));
-  // ---- structured QP layout ("core + limbs"): the active dofs are split into an upward-closed core C (root + trunk) and the
-  //      connected pieces left when C is removed (limbs), which never couple with one another.  Four 16-lane groups each hold
-  //      one bin of limbs (rows 0 .. 15-|C|) and a copy of the core (rows 16-|C| .. 15); see box_qp_struct in ik_kernel.hip.h.
-  std::vector<signed char> sq_gdof(64, -1), sq_owner(64, 0);
-  std::vector<int> sq_lane_of_dof(64, 0), sq_diag(64, 0);
-  std::vector<unsigned> sq_dst;
-  int sq_ok = 0, sq_nlimb = 0;
-  {
-    std::vector<int> dparent(n_act, -1), nanc(n_act, 0);
-    for (int i = 0; i < n_act; ++i) nanc[i] = __builtin_popcountll(aanc[i]);
-    for (int i = 0; i < n_act; ++i)
-      for (int j = 0; j < i; ++j)
-        if (((aanc[i] >> j) & 1ull) && (dparent[i] < 0 || nanc[j] > nanc[dparent[i]])) dparent[i] = j;
-    std::vector<char> in_core(n_act, 0);
-    for (int k = 0; k < n_root; ++k) in_core[k] = akind[k] != 7;  // null dofs are one-row "limbs": they need no core column
-    std::vector<std::vector<int>> bins;
-    for (int guard = 0; guard < 64 && !sq_ok; ++guard) {
-      const int nc = (int)std::count(in_core.begin(), in_core.end(), (char)1);
-      if (nc > 10) break;
-      // components of the non-core dofs (dofs are indexed ancestors-first, so a parent is labelled before its children)
-      std::vector<int> comp(n_act, -1), csize, ctop;
-      for (int i = 0; i < n_act; ++i) {
-        if (in_core[i]) continue;
-        if (dparent[i] < 0 || in_core[dparent[i]]) { comp[i] = (int)csize.size(); csize.push_back(1); ctop.push_back(i); }
-        else { comp[i] = comp[dparent[i]]; csize[comp[i]]++; }
-      }
-      const int cap = 16 - nc;
-      int worst = -1;
-      for (size_t c = 0; c < csize.size(); ++c)
-        if (csize[c] > cap && (worst < 0 || csize[c] > csize[worst])) worst = (int)c;
-      bool packed = worst < 0;
-      if (packed) {  // first-fit decreasing into <= 4 bins
-        std::vector<int> order(csize.size());
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return csize[a] > csize[b]; });
-        bins.assign(4, {});
-        std::vector<int> fill(4, 0);
-        for (int c : order) {
-          int g = 0;
-          while (g < 4 && fill[g] + csize[c] > cap) ++g;
-          if (g == 4) { packed = false; break; }
-          fill[g] += csize[c];
-          for (int i = 0; i < n_act; ++i) if (comp[i] == c) bins[g].push_back(i);
-        }
-        if (!packed) for (size_t c = 0; c < csize.size(); ++c) if (worst < 0 || csize[c] > csize[worst]) worst = (int)c;
-      }
-      if (packed) { sq_ok = 1; sq_nlimb = cap; break; }
-      in_core[ctop[worst]] = 1;  // grow the core by the top dof of the largest piece and try again
-    }
-    if (sq_ok) {
-      const int nl = sq_nlimb;
-      std::vector<int> core;
-      for (int i = 0; i < n_act; ++i) if (in_core[i]) core.push_back(i);
-      std::vector<int> grp(n_act, 0), loc(n_act, 0);
-      for (int g = 0; g < 4; ++g) {
-        std::sort(bins[g].begin(), bins[g].end());
-        for (size_t a = 0; a < bins[g].size(); ++a) {
-          const int i = bins[g][a], L = 16 * g + (int)a;
-          grp[i] = g; loc[i] = (int)a; sq_gdof[L] = (signed char)i; sq_owner[L] = 1; sq_lane_of_dof[i] = L;
-        }
-        for (size_t c = 0; c < core.size(); ++c) {
-          const int L = 16 * g + nl + (int)c;
-          sq_gdof[L] = (signed char)core[c]; sq_owner[L] = g == 0;
-          if (g == 0) { sq_lane_of_dof[core[c]] = L; loc[core[c]] = nl + (int)c; grp[core[c]] = 0; }
-        }
-      }
-      for (int i = 0; i < n_act; ++i) sq_diag[i] = loc[i] * 64 + sq_lane_of_dof[i];
-      auto hs = [](int lane, int col) { return (unsigned)(col * 64 + lane); };
-      for (unsigned short pr : hpair) {
-        const int i = pr >> 8, j = pr & 0xff;  // j above i
-        unsigned a, b;
-        if (in_core[i]) { a = hs(sq_lane_of_dof[i], loc[j]); b = hs(sq_lane_of_dof[j], loc[i]); }  // both core: group 0
-        else {
-          const int g = grp[i], Li = sq_lane_of_dof[i];
-          const int Lj = in_core[j] ? 16 * g + loc[j] : sq_lane_of_dof[j];  // the copy of the core dof inside i's group
-          if (!in_core[j] && grp[j] != g) { set_err(m, "internal: structured QP partition"); return GMR_EINVAL; }
-          a = hs(Li, loc[j]); b = hs(Lj, loc[i]);
-        }
-        sq_dst.push_back(a | (b << 16));
-      }
-    }
-  }
-  // ---- composites per table: dofs sharing the same set of tasks below them share one 6x6 block ----
-  std::vector<int> acomp(2 * 64, 0);
-  std::vector<unsigned> compmask(2 * 2 * GMR_MAX_TASKS, 0u), comp_own(64, 0u), comp_kids(64, 0u);
-  int ncomp[2] = {0, 0};
-  for (int k = 0; k < 2; ++k) {
-    std::map<unsigned, int> ids;
-    for (int i = 0; i < n_act; ++i) {
-      unsigned mk = 0;
-      for (int t = 0; t < h.ntask[k]; ++t)
-        if (akind[i] != 6 || above(abody[i], tbody[k * GMR_MAX_TASKS + t])) mk |= 1u << t;
-      auto it = ids.find(mk);
-      if (it == ids.end()) {
-        it = ids.emplace(mk, ncomp[k]).first;
-        compmask[k * 2 * GMR_MAX_TASKS + ncomp[k]] = mk;
-        ++ncomp[k];
-      }
-      acomp[k * 64 + i] = it->second;
-    }
-    if (ncomp[k] > 2 * GMR_MAX_TASKS) { set_err(m, "too many composite nodes"); return GMR_EUNSUPPORTED; }
-    // renumber the composites so that a composite's children (maximal strict subsets) always have lower ids, and split
-    // each into "own tasks" + "child composites": Bc[c] = sum_{t in own} Bt[t] + sum_{d in kids} Bc[d]  (any number of either:
-    // the pass plan below splits a long sum into entries of four sources)
-    const int nc = ncomp[k];
-    if (nc > 32) { set_err(m, "more than 32 composite nodes"); return GMR_EUNSUPPORTED; }
-    std::vector<int> order(nc), newid(nc);
-    std::iota(order.begin(), order.end(), 0);
-    auto mask_of = [&](int c) { return compmask[k * 2 * GMR_MAX_TASKS + c]; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return __builtin_popcount(mask_of(a)) < __builtin_popcount(mask_of(b)); });
-    std::vector<unsigned> sorted_mask(nc);
-    for (int o = 0; o < nc; ++o) { newid[order[o]] = o; sorted_mask[o] = mask_of(order[o]); }
-    for (int i = 0; i < n_act; ++i) acomp[k * 64 + i] = newid[acomp[k * 64 + i]];
-    for (int o = 0; o < nc; ++o) {
-      compmask[k * 2 * GMR_MAX_TASKS + o] = sorted_mask[o];
-      unsigned own = sorted_mask[o], kids = 0, covered = 0;
-      for (int d = o - 1; d >= 0; --d) {
-        const unsigned md = sorted_mask[d];
-        if (md == 0 || md == sorted_mask[o] || (md & ~sorted_mask[o]) != 0 || (md & covered) != 0) continue;
-        kids |= 1u << d; covered |= md;
-      }
-      own &= ~covered;
-      comp_own[k * 32 + o] = own; comp_kids[k * 32 + o] = kids;
-    }
-  }
-  const int ns = h.nslot;
-  // ---- LDS layout of the IK kernel (doubles).  Lifetimes inside one solve:
-  //   poses (FK .. screws) | Bt (task blocks .. composites) | Bc (composites .. F)   -> Bc overwrites the dead poses
-  //   S, F (screws / F .. H assembly)                                                 -> the factorisation's broadcast rows Lb overwrite S
-  //   H (H assembly .. QP) overwrites [Bt | poses/Bc]
-  const int ntmax = std::max(h.ntask[0], h.ntask[1]), ncmax = std::max(ncomp[0], ncomp[1]);
-  const bool sq = sq_ok && !m->force_generic;
-  gmr::LdsLayout &L = m->lay;  // (named L here; the composite plan below needs the byte offsets)
-  auto even = [](int x) { return (x + 1) & ~1; };
-  int o = 0;
-  L.zero = o; o += gmr::kBT;  // a block of zeros: the absent sources of the composite plan (never aliased)
-  const int npairp_host = ((int)hpair.size() + 127) / 128 * 128;
-  // H pair plan, 8 bytes per entry, staged once per wavefront -- unless the structured kernel keeps all of it in registers
-  const bool hplan_in_regs = sq && npairp_host <= 64 * gmr::kHPlanRegsSQ;
-  L.hplan = o; o += hplan_in_regs ? 0 : npairp_host;
-  L.q = o; o += even(nq);
-  L.tp = o; o += even(3 * ns);
-  L.tq = o; o += 4 * ns;
-  L.bodyc = GMR_IK_STAGE_TREE ? o : -1; o += GMR_IK_STAGE_TREE ? even(gmr::kBodyC * nb_ik) : 0;
-  L.S = o; L.Lb = o; o += std::max(6 * nvp, sq ? 128 : 2 * (nvp + 2));
-  L.F = o; o += 6 * nvp;
-  L.B = o; L.H = o;
-  const int bt = even(gmr::kBT * ntmax), px = std::max(even(7 * nb_ik), even(gmr::kBT * ncmax));
-  L.xpos = o + bt; L.xquat = L.xpos + even(3 * nb_ik); L.Bc = o + bt;
-  o += std::max(bt + px, (sq ? 1024 : nvp * nvp) + 2);  // + a dummy slot for the unused lanes of the pair rounds
-  L.cplan = o;  // composite plan, 16 bytes per (table, pass, quarter-wave); sized once the passes are scheduled (below)
-  L.total_doubles = o;
-  m->lds_bytes = o * (int)sizeof(double);
-  m->nvp = nvp;
-  m->n_act = n_act;
-  // ---- composite plan: passes of <= 4 entries, an entry = one composite summed from <= 4 blocks, children before parents ----
-  if (m->lds_bytes > 65535) { set_err(m, "model needs %d bytes of LDS per wavefront (plan offsets are 16 bit)", m->lds_bytes); return GMR_EUNSUPPORTED; }
-  std::vector<uint32_t> comp_plan((size_t)2 * gmr::kMaxCompPass * 4 * 4, 0u);
-  int ncpass[2] = {0, 0};
-  for (int k = 0; k < 2; ++k) {
-    struct Entry { int dst; std::vector<int> src; std::vector<int> deps; int done_pass = -1; int height = 0; };
-    // src / dst are block ids: task t -> t, composite c -> 64 + c;  deps: entries that must have run in an earlier pass
-    std::vector<Entry> ent;
-    std::vector<int> last_entry_of_comp(ncomp[k], -1);
-    // Shallow plan: a composite of ONE task is that task's block (no entry, the dof lanes read the task block itself); a
-    // composite of up to four tasks is summed from the task blocks directly (no dependency on its children); only larger ones
-    // build on child composites.  G1: 3 dependent passes instead of 5.
-    std::vector<int> alias_task(ncomp[k], -1);
-    for (int c = 0; c < ncomp[k]; ++c) {
-      const unsigned mk = compmask[k * 2 * GMR_MAX_TASKS + c];
-      if (__builtin_popcount(mk) == 1) alias_task[c] = __builtin_ctz(mk);
-    }
-    for (int i = 0; i < n_act; ++i) {
-      const int c = acomp[k * 64 + i];
-      acomp[k * 64 + i] = alias_task[c] >= 0 ? alias_task[c] : ntmax + c;  // block index from Bt on (Bc = Bt + kBT ntmax)
-    }
-    for (int c = 0; c < ncomp[k]; ++c) {
-      if (alias_task[c] >= 0) continue;
-      const unsigned mk = compmask[k * 2 * GMR_MAX_TASKS + c];
-      std::vector<int> srcs;
-      if (__builtin_popcount(mk) <= 4) {
-        for (unsigned t = mk; t; t &= t - 1) srcs.push_back(__builtin_ctz(t));
-      } else {
-        for (unsigned own = comp_own[k * 32 + c]; own; own &= own - 1) srcs.push_back(__builtin_ctz(own));
-        for (unsigned kids = comp_kids[k * 32 + c]; kids; kids &= kids - 1) {
-          const int d = __builtin_ctz(kids);
-          srcs.push_back(alias_task[d] >= 0 ? alias_task[d] : 64 + d);
-        }
-      }
-      // child composites first: the entries that wait for them should be few
-      std::stable_sort(srcs.begin(), srcs.end(), [](int a, int b) { return (a >= 64) > (b >= 64); });
-      size_t i = 0;
-      bool first = true;
-      while (i < srcs.size() || first) {
-        Entry e;
-        e.dst = 64 + c;
-        if (!first) { e.src.push_back(64 + c); e.deps.push_back(last_entry_of_comp[c]); }
-        while (i < srcs.size() && e.src.size() < 4) {
-          const int sidx = srcs[i++];
-          e.src.push_back(sidx);
-          if (sidx >= 64) e.deps.push_back(last_entry_of_comp[sidx - 64]);
-        }
-        last_entry_of_comp[c] = (int)ent.size();
-        ent.push_back(std::move(e));
-        first = false;
-      }
-    }
-    const int ne = (int)ent.size();
-    // height = longest chain of dependants above an entry (critical-path priority)
-    for (int i = ne - 1; i >= 0; --i)
-      for (int d : ent[i].deps) ent[d].height = std::max(ent[d].height, ent[i].height + 1);
-    int done = 0, pass = 0;
-    const int boff = m->lay.B * 8, coff = m->lay.Bc * 8, zoff = m->lay.zero * 8, scratch = m->lay.F * 8;  // F is dead during this phase
-    auto block_off = [&](int id) { return id >= 64 ? coff + gmr::kBT * 8 * (id - 64) : boff + gmr::kBT * 8 * id; };
-    while (done < ne) {
-      if (pass >= gmr::kMaxCompPass) { set_err(m, "composite plan of table %d needs more than %d passes", k + 1, gmr::kMaxCompPass); return GMR_EUNSUPPORTED; }
-      int pick[4] = {-1, -1, -1, -1};
-      for (int slot = 0; slot < 4; ++slot) {
-        int best = -1;
-        for (int i = 0; i < ne; ++i) {
-          if (ent[i].done_pass >= 0 || i == pick[0] || i == pick[1] || i == pick[2]) continue;
-          bool ready = true;
-          for (int d : ent[i].deps) ready = ready && ent[d].done_pass >= 0 && ent[d].done_pass < pass;
-          if (ready && (best < 0 || ent[i].height > ent[best].height)) best = i;
-        }
-        pick[slot] = best;
-      }
-      if (pick[0] < 0) { set_err(m, "internal: composite plan stalled"); return GMR_EINVAL; }
-      for (int quarter = 0; quarter < 4; ++quarter) {
-        uint32_t *row = comp_plan.data() + ((size_t)(k * gmr::kMaxCompPass + pass) * 4 + quarter) * 4;
-        const int ei = pick[quarter];
-        uint32_t so[4] = {(uint32_t)zoff, (uint32_t)zoff, (uint32_t)zoff, (uint32_t)zoff}, dst = (uint32_t)scratch;
-        if (ei >= 0) {
-          for (size_t j = 0; j < ent[ei].src.size(); ++j) so[j] = (uint32_t)block_off(ent[ei].src[j]);
-          dst = (uint32_t)block_off(ent[ei].dst);
-        }
-        row[0] = so[0] | (so[1] << 16); row[1] = so[2] | (so[3] << 16); row[2] = dst; row[3] = 0;
-      }
-      for (int slot = 0; slot < 4; ++slot)
-        if (pick[slot] >= 0) { ent[pick[slot]].done_pass = pass; ++done; }
-      ++pass;
-    }
-    ncpass[k] = pass;
-  }
-  if (getenv("GMR_DEBUG_PLAN")) fprintf(stderr, "gmr: composite plan: %d / %d composites, %d / %d passes\n", ncomp[0], ncomp[1], ncpass[0], ncpass[1]);
-  m->lay.total_doubles += 8 * (ncpass[0] + ncpass[1]);
-  m->lds_bytes = m->lay.total_doubles * (int)sizeof(double);
-  if (m->lds_bytes > 65535) { set_err(m, "model needs %d bytes of LDS per wavefront (plan offsets are 16 bit)", m->lds_bytes); return GMR_EUNSUPPORTED; }
-  // ---- H assembly plan: per pair the LDS byte offsets of S_j, F_i and of the two entries of H it fills ----
-  std::vector<uint32_t> hplan;
-  {
-    const gmr::LdsLayout &Ly = m->lay;
-    const int hsize = sq ? 1024 : nvp * nvp;  // the two doubles after H are the dummy slots of the padding entries
-    for (size_t p = 0; p < hpair.size(); ++p) {
-      const int i = hpair[p] >> 8, j = hpair[p] & 0xff;
-      const unsigned d0 = sq ? (sq_dst[p] & 0xffffu) : (unsigned)(j * nvp + i), d1 = sq ? (sq_dst[p] >> 16) : (unsigned)(i * nvp + j);
-      hplan.push_back((uint32_t)((Ly.S + 6 * j) * 8) | ((uint32_t)((Ly.F + 6 * i) * 8) << 16));
-      hplan.push_back((uint32_t)((Ly.H + (int)d0) * 8) | ((uint32_t)((Ly.H + (int)d1) * 8) << 16));
-    }
-    while ((hplan.size() / 2) % 128 != 0) {
-      hplan.push_back((uint32_t)(Ly.S * 8) | ((uint32_t)(Ly.F * 8) << 16));
-      hplan.push_back((uint32_t)((Ly.H + hsize) * 8) | ((uint32_t)((Ly.H + hsize + 1) * 8) << 16));
-    }
-    // Order of the entries = (round, lane) that executes them.  The gathers of S_j / F_i are ds_read_b128 (serviced in four
-    // fixed 16-lane groups, a lane occupying the 16-byte slot (addr / 16) mod 16; equal addresses broadcast) and the two
-    // scatters are ds_write_b64 (16 contiguous lanes per group, unit (addr / 8) mod 16): entries are swapped between positions
-    // while that lowers the number of extra LDS cycles (hill climbing with a fixed seed -- the plan is a pure function of the
-    // model).  Measured on G1: SQ_LDS_BANK_CONFLICT of the H phase (profiles/experiment_log_r01_r02.md, v11).
-    {
-      const int ne = (int)hplan.size() / 2, nr = ne / 64;
-      static const int rgroup[64] = {0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1,
-                                     2, 2, 2, 2, 3, 3, 3, 3, 3, 3, 3, 3, 2, 2, 2, 2, 3, 3, 3, 3, 2, 2, 2, 2, 2, 2, 2, 2, 3, 3, 3, 3};
-      std::vector<int> at(ne);  // position -> entry
-      for (int i = 0; i < ne; ++i) at[i] = i;
-      // extra cycles of one 16-lane group: max over slots of the number of distinct addresses on it, minus one
-      auto extra = [&](const int *pos, int shift, int word, int half) {
-        unsigned addr[16]; int slot[16];
-        for (int l = 0; l < 16; ++l) {
-          const uint32_t wv = hplan[2 * at[pos[l]] + word];
-          addr[l] = half ? (wv >> 16) : (wv & 0xffffu);
-          slot[l] = (int)(addr[l] >> shift) & 15;
-        }
-        int worst = 1;
-        for (int sl = 0; sl < 16; ++sl) {
-          int nd = 0; unsigned seen[16];
-          for (int l = 0; l < 16; ++l) {
-            if (slot[l] != sl) continue;
-            bool dup = false;
-            for (int t = 0; t < nd; ++t) dup = dup || seen[t] == addr[l];
-            if (!dup) seen[nd++] = addr[l];
-          }
-          worst = std::max(worst, nd);
-        }
-        return worst - 1;
-      };
-      auto round_cost = [&](int r) {
-        int c = 0;
-        for (int g = 0; g < 4; ++g) {
-          int rp[16], wp[16], n = 0;
-          for (int l = 0; l < 64; ++l) if (rgroup[l] == g) rp[n++] = 64 * r + l;
-          for (int l = 0; l < 16; ++l) wp[l] = 64 * r + 16 * g + l;
-          c += 3 * (extra(rp, 4, 0, 0) + extra(rp, 4, 0, 1));  // three b128 reads each of S_j and F_i
-          c += extra(wp, 3, 1, 0) + extra(wp, 3, 1, 1);
-        }
-        return c;
-      };
-      std::vector<int> rc(nr);
-      for (int r = 0; r < nr; ++r) rc[r] = round_cost(r);
-      int total0 = 0;
-      for (int r = 0; r < nr; ++r) total0 += rc[r];
-      uint64_t rng = 0x9E3779B97F4A7C15ull;
-      auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (uint32_t)(rng >> 32); };
-      for (int iter = 0; iter < 40000 && nr > 0; ++iter) {
-        const int a = (int)(next() % (uint32_t)ne), b = (int)(next() % (uint32_t)ne);
-        if (a == b) continue;
-        const int ra = a / 64, rb = b / 64;
-        std::swap(at[a], at[b]);
-        const int na = round_cost(ra), nb2 = ra == rb ? na : round_cost(rb);
-        const int before = rc[ra] + (ra == rb ? 0 : rc[rb]), after = na + (ra == rb ? 0 : nb2);
-        if (after <= before) { rc[ra] = na; rc[rb] = nb2; }
-        else std::swap(at[a], at[b]);
-      }
-      std::vector<uint32_t> ordered(hplan.size());
-      for (int i = 0; i < ne; ++i) { ordered[2 * i] = hplan[2 * at[i]]; ordered[2 * i + 1] = hplan[2 * at[i] + 1]; }
-      int total = 0;
-      for (int r = 0; r < nr; ++r) total += rc[r];
-      m->hplan_extra_cycles = total;
-      if (getenv("GMR_DEBUG_PLAN")) fprintf(stderr, "gmr: H pair plan %d entries, modelled conflict cycles per solve %d -> %d\n", ne, total0, total);
-      hplan.swap(ordered);
-    }
-  }
-  // ---- FK (KinematicsModel convention) tables and branch-slot plan ----
-  std::vector<int> dofidx(nb, -1), src_slot(nb, -1), save_slot(nb, -1), last_child(nb, -1), nchild_other(nb, 0);
-  std::vector<float> lpos(3 * nb), lrot(4 * nb), jaxis(3 * nb);
-  std::vector<double> jaxis64(3 * nb);
-  for (int b = 0; b < nb; ++b) {
-    if (jtype[b] == GMR_JNT_HINGE) dofidx[b] = qadr[b] - 7;
-    for (int i = 0; i < 3; ++i) { lpos[3 * b + i] = (float)bpos[3 * b + i]; jaxis[3 * b + i] = (float)axis[3 * b + i]; jaxis64[3 * b + i] = axis[3 * b + i]; }
-    lrot[4 * b + 0] = (float)bquat_raw[4 * b + 1]; lrot[4 * b + 1] = (float)bquat_raw[4 * b + 2];
-    lrot[4 * b + 2] = (float)bquat_raw[4 * b + 3]; lrot[4 * b + 3] = (float)bquat_raw[4 * b + 0];
-    if (b > 0) { last_child[parent[b]] = b; if (parent[b] != b - 1) nchild_other[parent[b]]++; }
-  }
-  std::vector<int> free_slots;
-  int nslots = 0;
-  for (int b = 0; b < nb; ++b) {
-    if (b > 0 && parent[b] != b - 1) {
-      src_slot[b] = save_slot[parent[b]];
-      if (src_slot[b] < 0) { set_err(m, "internal: FK slot plan"); return GMR_EINVAL; }
-    }
-    if (b > 0 && last_child[parent[b]] == b && save_slot[parent[b]] >= 0) free_slots.push_back(save_slot[parent[b]]);
-    if (nchild_other[b] > 0) {
-      if (!free_slots.empty()) { save_slot[b] = free_slots.back(); free_slots.pop_back(); }
-      else save_slot[b] = nslots++;
-    }
-  }
-  if (nslots > gmr::kFkMaxSlots) { set_err(m, "tree too bushy for the FK kernel (%d branch slots)", nslots); return GMR_EUNSUPPORTED; }
-
-  // ---- pack + upload ----
-  std::vector<int> v_parent(parent, parent + nb), v_jtype(jtype, jtype + nb), v_qadr(qadr, qadr + nb);
-  std::vector<double> v_bpos(bpos, bpos + 3 * nb), v_bquat(bquat, bquat + 4 * nb), v_axis(axis, axis + 3 * nb), v_qpos0(qpos0, qpos0 + nq);
-  std::vector<int> p_jtype(nb_ik), p_qadr(nb_ik);
-  std::vector<double> p_bpos(3 * nb_ik), p_bquat(4 * nb_ik), p_axis(3 * nb_ik);
-  for (int i = 0; i < nb_ik; ++i) {
-    const int b = keep[i];
-    p_jtype[i] = jtype[b]; p_qadr[i] = qadr[b];
-    for (int c = 0; c < 3; ++c) { p_bpos[3 * i + c] = bpos[3 * b + c]; p_axis[3 * i + c] = axis[3 * b + c]; }
-    for (int c = 0; c < 4; ++c) p_bquat[4 * i + c] = bquat[4 * b + c];
-  }
-  std::vector<int> tbody_ik(tbody), abody_ik(abody);
-  for (int &b : tbody_ik) b = bmap[b] < 0 ? 0 : bmap[b];
-  for (int &b : abody_ik) b = bmap[b];
-  std::vector<double> v_sscale(blob_ptr<double>(B, h.off_slot_scale), blob_ptr<double>(B, h.off_slot_scale) + ns);
-  std::vector<double> v_spoff(blob_ptr<double>(B, h.off_slot_pos_off), blob_ptr<double>(B, h.off_slot_pos_off) + 3 * ns);
-  std::vector<double> v_sroff(blob_ptr<double>(B, h.off_slot_rot_off), blob_ptr<double>(B, h.off_slot_rot_off) + 4 * ns);
-  std::vector<int> v_sfoot(blob_ptr<int32_t>(B, h.off_slot_is_foot), blob_ptr<int32_t>(B, h.off_slot_is_foot) + ns);
-  abody_ik.resize(64, 0); abody.resize(64, 0); akind.resize(64, 0); aqadr.resize(64, 0); alim.resize(64, 0); arange.resize(128, 0.0);
-
-  gmr::DevModel &dm = m->dm;
-  dm = gmr::DevModel{};
-  dm.nbody = nb_ik; dm.nq = nq; dm.nv = nv; dm.nslot = ns; dm.root_slot = h.root_slot; dm.n_act = n_act;
-  {  // both tables used and task t of either table ties the same robot body to the same human slot: stage 2 inherits the residual
-    bool same = h.use_table[0] && h.use_table[1] && h.ntask[0] == h.ntask[1] && h.ntask[0] > 0;
-    for (int t = 0; same && t < h.ntask[0]; ++t)
-      same = tbody_ik[t] == tbody_ik[GMR_MAX_TASKS + t] && tslot[t] == tslot[GMR_MAX_TASKS + t];
-    dm.same_tasks = same ? 1 : 0;
-  }
-  dm.root_planar = root_mask == 0x23;
-  dm.root_tslot = -1;  // GMR_INIT_ROOT_TARGET: the slot whose prepared target the floating base (body 0) is asked to track
-  for (int k = 0; k < 2 && dm.root_tslot < 0; ++k)
-    for (int t = 0; h.use_table[k] && t < h.ntask[k] && dm.root_tslot < 0; ++t)
-      if (tbody[k * GMR_MAX_TASKS + t] == 0) dm.root_tslot = tslot[k * GMR_MAX_TASKS + t];
-  for (int k = 0; k < 2; ++k) { dm.ntask[k] = h.ntask[k]; dm.use_table[k] = h.use_table[k] && h.ntask[k] > 0; dm.ncomp[k] = ncomp[k]; dm.ncpass[k] = ncpass[k]; }
-  dm.npairp = (int)hplan.size() / 2; dm.fkrounds = fkrounds; dm.sq_ok = sq_ok; dm.sq_nlimb = sq_nlimb;
-  bool fits = true;
-  auto put = [&](auto &dst, const auto &src) {  // vector -> fixed-capacity array of the device struct
-    using D = std::remove_reference_t<decltype(dst[0])>;
-    static_assert(sizeof(D) % sizeof(src[0]) == 0, "element size mismatch");
-    if (src.size() * sizeof(src[0]) > sizeof(dst)) { fits = false; return; }
-    if (!src.empty()) memcpy(&dst[0], src.data(), src.size() * sizeof(src[0]));
-  };
-  put(dm.jtype, p_jtype); put(dm.qadr, p_qadr);
-  put(dm.bpos, p_bpos); put(dm.bquat, p_bquat); put(dm.axis, p_axis); put(dm.qpos0, v_qpos0);
-  put(dm.sscale, v_sscale); put(dm.spoff, v_spoff); put(dm.sroff, v_sroff); put(dm.sfoot, v_sfoot);
-  put(dm.tbody, tbody_ik); put(dm.tslot, tslot); put(dm.twp, twp); put(dm.twr, twr);
-  put(dm.abody, abody_ik); put(dm.akind, akind); put(dm.aqadr, aqadr); put(dm.alimited, alim);
-  put(dm.arange, arange); put(dm.acomp, acomp);
-  put(dm.hplan, hplan); put(dm.fkanc, fkanc); put(dm.comp_plan, comp_plan);
-  put(dm.sq_gdof, sq_gdof); put(dm.sq_owner, sq_owner); put(dm.sq_lane_of_dof, sq_lane_of_dof); put(dm.sq_diag, sq_diag);
-  // the evaluation model: same tables, full body tree (gmr_evaluate returns xpos / xquat of every body)
-  std::vector<gmr::DevModel> dm_eval_v(1, dm);
-  {
-    gmr::DevModel &de = dm_eval_v[0];
-    de.nbody = nb; de.fkrounds = fkrounds_full;
-    put(de.jtype, v_jtype); put(de.qadr, v_qadr);
-    put(de.bpos, v_bpos); put(de.bquat, v_bquat); put(de.axis, v_axis);
-    put(de.tbody, tbody); put(de.abody, abody); put(de.fkanc, fkanc_full);
-  }
-  if (!fits) { set_err(m, "internal: a model table exceeds its fixed capacity"); return GMR_EUNSUPPORTED; }
-  {  // LDS layout of eval_kernel: state, targets, poses of the full tree
-    gmr::LdsLayout &E = m->lay_eval;
-    E = gmr::LdsLayout{};
-    int oe = 0;
-    E.q = oe; oe += even(nq);
-    E.tp = oe; oe += even(3 * ns);
-    E.tq = oe; oe += 4 * ns;
-    E.xpos = oe; oe += even(3 * nb);
-    E.xquat = oe; oe += 4 * nb;
-    E.total_doubles = oe;
-    m->lds_bytes_eval = oe * (int)sizeof(double);
-  }
-
-  m->shape = ik_shape_of(dm, m->nvp, dm.sq_ok && !m->force_generic);
-  // A model that matches a plain shape gets the ring of target images its instances prepare four frames at a time (target_blocks.h):
-  // kTargetBlockFrames x [tp | tq] behind everything else.  G1 / smplx: 16 176 + 3 136 = 19 312 bytes, still eight wavefronts per CU.
-  m->lay.tring = -1;
-  if (ik_shape_is_plain(m->shape) && ns <= gmr::kTargetBlockLanes) {
-    m->lay.tring = m->lay.total_doubles;
-    m->lay.total_doubles += gmr::kTargetBlockFrames * (m->lay.tq - m->lay.tp + 4 * ns);
-    m->lds_bytes = m->lay.total_doubles * (int)sizeof(double);
-    if (m->lds_bytes > 65535) { set_err(m, "model needs %d bytes of LDS per wavefront (plan offsets are 16 bit)", m->lds_bytes); return GMR_EUNSUPPORTED; }
-  }
-  if (host_only) return GMR_OK;
-
-  // the model image: every array holds at least one element, so that no two tables share an address
-  gmr::CallBlock P;
-  const auto o_dm = P.uploaded<gmr::DevModel>(1);
-  const auto o_dm_eval = P.put(dm_eval_v, 1);
-  const auto o_parent = P.put(v_parent, 1);
-  const auto o_dofidx = P.put(dofidx, 1), o_src = P.put(src_slot, 1), o_save = P.put(save_slot, 1);
-  const auto o_lpos = P.put(lpos, 1), o_lrot = P.put(lrot, 1), o_jaxis = P.put(jaxis, 1);
-  const auto o_jaxis64 = P.put(jaxis64, 1);
-  std::vector<gmr::FkBody> fkbody(nb);
-  for (int b = 0; b < nb; ++b) {
-    gmr::FkBody &r = fkbody[b];
-    r = gmr::FkBody{};
-    r.src_slot = src_slot[b]; r.dofidx = dofidx[b]; r.save_slot = save_slot[b];
-    for (int i = 0; i < 3; ++i) { r.lpos[i] = lpos[3 * b + i]; r.axis[i] = jaxis64[3 * b + i]; }
-    for (int i = 0; i < 4; ++i) r.lrot[i] = lrot[4 * b + i];
-  }
-  const auto o_fkbody = P.put(fkbody, 1);
-  // kin_ops tables: hinge -> body, float32 limits, tree level of every body, bodies by level
-  const int ndof_k = nq - 7;
-  std::vector<int> k_dof_body(ndof_k, 0);
-  std::vector<float> k_lo(ndof_k, 0.f), k_hi(ndof_k, 0.f);
-  for (int b = 0; b < nb; ++b)
-    if (dofidx[b] >= 0 && dofidx[b] < ndof_k) { k_dof_body[dofidx[b]] = b; k_lo[dofidx[b]] = (float)range[2 * b]; k_hi[dofidx[b]] = (float)range[2 * b + 1]; }
-  std::vector<uint8_t> k_depth(nb, 0), k_order(nb, 0);
-  int k_maxd = 0;
-  for (int b = 1; b < nb; ++b) { k_depth[b] = (uint8_t)(k_depth[parent[b]] + 1); k_maxd = std::max<int>(k_maxd, k_depth[b]); }
-  std::iota(k_order.begin(), k_order.end(), (uint8_t)0);
-  std::stable_sort(k_order.begin(), k_order.end(), [&](uint8_t a, uint8_t b) { return k_depth[a] < k_depth[b]; });
-  const auto o_kdb = P.put(k_dof_body, 1);
-  const auto o_klo = P.put(k_lo, 1), o_khi = P.put(k_hi, 1);
-  const auto o_kdepth = P.put(k_depth, 1), o_korder = P.put(k_order, 1);
-  // clip report: float64 limits of every hinge in qpos order, infinite where the hinge is unlimited
-  std::vector<double> rep_lo(ndof_k, -INFINITY), rep_hi(ndof_k, INFINITY);
-  for (int b = 1; b < nb; ++b)
-    if (jtype[b] == GMR_JNT_HINGE && limited[b]) { rep_lo[qadr[b] - 7] = range[2 * b]; rep_hi[qadr[b] - 7] = range[2 * b + 1]; }
-  const auto o_replo = P.put(rep_lo, 1), o_rephi = P.put(rep_hi, 1);
-
-  HIP_TRY(m, hipMalloc(&m->dev, P.total_bytes()));
-  m->dev_bytes = P.total_bytes();
-  const gmr::CallBlock::Device D = P.on(m->dev);
-  m->dm_dev = D(o_dm);
-  m->dm_eval_dev = D(o_dm_eval);
+// Plan the model on the host (model_plan.h), then: one device allocation, the image's handles resolved into the handle's tables, one
+// copy, and the opt-in to more than 64 KiB of dynamic LDS.
+int build_device_model(gmr_model *m) {
+  gmr::ModelPlan plan;
+  const int rc = gmr::plan_model(m->blob.data(), m->blob.size(), m->min_nvp, m->force_generic, plan, m->err);
+  if (rc != GMR_OK) return rc;
+  adopt_plan(m, plan);
+  gmr::ModelImage &I = plan.image;
+  HIP_TRY(m, hipMalloc(&m->dev, I.block.total_bytes()));
+  m->dev_bytes = I.block.total_bytes();
+  const gmr::CallBlock::Device D = I.block.on(m->dev);
+  m->dm_dev = D(I.dm);
+  m->dm_eval_dev = D(I.dm_eval);
   gmr::FkTree &fk = m->fk;
-  fk.parent = D(o_parent); fk.dofidx = D(o_dofidx); fk.src_slot = D(o_src); fk.save_slot = D(o_save);
-  fk.lpos = D(o_lpos); fk.lrot = D(o_lrot); fk.jaxis = D(o_jaxis); fk.jaxis64 = D(o_jaxis64); fk.body = D(o_fkbody);
-  fk.nbody = nb; fk.ndof = nq - 7; fk.nslots = nslots;
-  m->kin.dof_body = D(o_kdb); m->kin.lim_lo = D(o_klo); m->kin.lim_hi = D(o_khi);
-  m->kin.depth = D(o_kdepth); m->kin.order = D(o_korder);
-  m->kin.max_depth = k_maxd;
-  m->rep_lo = D(o_replo); m->rep_hi = D(o_rephi);
-  fk.dof_in_order = 1;
-  for (int b = 0, prev = -1; b < nb; ++b)
-    if (dofidx[b] >= 0) { if (dofidx[b] < prev) fk.dof_in_order = 0; prev = dofidx[b]; }
-  *P[o_dm] = dm;
-  HIP_TRY(m, hipMemcpy(m->dev, P.image(), P.uploaded_bytes(), hipMemcpyHostToDevice));
-  // branch slots + dof tile + position / rotation stages (fk_kernel.hip.h)
-  m->fk_lds_bytes = (std::max(1, nslots) * 7 + gmr::kFkPosStride + gmr::kFkRotStride) * gmr::kFkThreads * (int)sizeof(float);
-  m->fk_lds_bytes_min = std::max(1, nslots) * 7 * gmr::kFkThreads * (int)sizeof(float);
+  fk.parent = D(I.parent); fk.dofidx = D(I.dofidx); fk.src_slot = D(I.src_slot); fk.save_slot = D(I.save_slot);
+  fk.lpos = D(I.lpos); fk.lrot = D(I.lrot); fk.jaxis = D(I.jaxis); fk.jaxis64 = D(I.jaxis64); fk.body = D(I.fkbody);
+  fk.nbody = m->h.nbody; fk.ndof = m->h.nq - 7; fk.nslots = plan.nslots; fk.dof_in_order = plan.dof_in_order;
+  m->kin.dof_body = D(I.k_dof_body); m->kin.lim_lo = D(I.k_lo); m->kin.lim_hi = D(I.k_hi);
+  m->kin.depth = D(I.k_depth); m->kin.order = D(I.k_order);
+  m->kin.max_depth = plan.k_maxd;
+  m->rep_lo = D(I.rep_lo); m->rep_hi = D(I.rep_hi);
+  HIP_TRY(m, hipMemcpy(m->dev, I.block.image(), I.block.uploaded_bytes(), hipMemcpyHostToDevice));
 
   if (m->lds_bytes > 160 * 1024) { set_err(m, "model needs %d bytes of LDS per wavefront", m->lds_bytes); return GMR_EUNSUPPORTED; }
   // opt in to > 64 KiB of dynamic LDS where a variant needs it
@@ -1129,26 +449,9 @@ static gmr_model *model_create_impl(const void *blob, size_t blob_bytes, int dev
     if (m) gmr_model_destroy(m);
     return nullptr;
   };
-  if (!blob || blob_bytes < sizeof(gmr_blob_header)) return fail(nullptr, "blob too small");
   gmr_blob_header h;
-  memcpy(&h, blob, sizeof(h));
-  if (h.magic != GMR_BLOB_MAGIC || h.version != GMR_BLOB_VERSION) return fail(nullptr, "bad blob magic/version");
-  if (h.total_bytes != blob_bytes) return fail(nullptr, "blob size mismatch");
-  if (h.nbody < 1 || h.nbody > GMR_MAX_BODIES) return fail(nullptr, "nbody outside [1, 64]");
-  if (h.nq != h.nv + 1 || h.nv < 6) return fail(nullptr, "bad nq/nv");
-  if (h.nslot < 0 || h.nslot > GMR_MAX_SLOTS || h.ntask[0] < 0 || h.ntask[0] > GMR_MAX_TASKS || h.ntask[1] < 0 || h.ntask[1] > GMR_MAX_TASKS)
-    return fail(nullptr, "slot/task counts out of range");
-  if (h.nslot > 0 && (h.root_slot < 0 || h.root_slot >= h.nslot)) return fail(nullptr, "root_slot out of range");
-  const size_t nb = h.nbody, ns = h.nslot;
-  bool ok = range_ok(h, h.off_parent, nb * 4) && range_ok(h, h.off_jnt_type, nb * 4) && range_ok(h, h.off_qpos_adr, nb * 4) &&
-            range_ok(h, h.off_dof_adr, nb * 4) && range_ok(h, h.off_jnt_limited, nb * 4) && range_ok(h, h.off_body_pos, nb * 24) &&
-            range_ok(h, h.off_body_quat, nb * 32) && range_ok(h, h.off_body_quat_raw, nb * 32) && range_ok(h, h.off_jnt_axis, nb * 24) &&
-            range_ok(h, h.off_jnt_range, nb * 16) && range_ok(h, h.off_qpos0, (size_t)h.nq * 8) && range_ok(h, h.off_slot_scale, ns * 8) &&
-            range_ok(h, h.off_slot_pos_off, ns * 24) && range_ok(h, h.off_slot_rot_off, ns * 32) && range_ok(h, h.off_slot_is_foot, ns * 4);
-  for (int k = 0; k < 2; ++k)
-    ok = ok && range_ok(h, h.off_task_body[k], (size_t)h.ntask[k] * 4) && range_ok(h, h.off_task_slot[k], (size_t)h.ntask[k] * 4) &&
-         range_ok(h, h.off_task_wp[k], (size_t)h.ntask[k] * 8) && range_ok(h, h.off_task_wr[k], (size_t)h.ntask[k] * 8);
-  if (!ok) return fail(nullptr, "blob array offsets out of range");
+  std::string blob_err;
+  if (gmr::validate_blob(blob, blob_bytes, h, blob_err) != GMR_OK) return fail(nullptr, blob_err.c_str());
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, "no HIP device available (libgmr_amd has no CPU path)");
@@ -1231,20 +534,19 @@ int gmr_model_info_get(const gmr_model *m, gmr_model_info *out) {
 }
 
 // Debug / test hook, host only (no device is touched, so it works on a machine without one; not part of gmr_amd.h): builds the model
-// of a blob as gmr_model_create does up to its first device call and reports which kernel instance a launch of it would take.
+// of a blob as gmr_model_create does (model_plan.h) and reports which kernel instance a launch of it would take.
 // alter_field >= 0: first add alter_delta to that shape field (in GMR_IK_SHAPE_FIELDS order) of the host model.  launch flags as
 // launch_ik sees them.  fields_out: NULL or room for 16 ints, receives the (altered) shape fields.  name_out receives the instance's
-// name ("generic" or the shape's).  Returns the shape's index, -1 for the generic instance, < -1 on a blob that does not build.
+// name ("generic" or the shape's).  Returns the shape's index, -1 for the generic instance, -2 on a blob that does not validate (its
+// header, or an array that does not lie inside it), -3 on one that does not plan.
 int gmr_debug_ik_shape(const void *blob, size_t blob_bytes, int force_generic, int alter_field, int alter_delta, int in_f64,
                        int offset_to_ground, int plain, int *fields_out, char *name_out, size_t name_len) {
-  if (!blob || blob_bytes < sizeof(gmr_blob_header)) return -2;
-  gmr_model m;
-  memcpy(&m.h, blob, sizeof(m.h));
-  if (m.h.magic != GMR_BLOB_MAGIC || m.h.version != GMR_BLOB_VERSION || m.h.total_bytes != blob_bytes) return -2;
-  m.blob.assign(static_cast<const uint8_t *>(blob), static_cast<const uint8_t *>(blob) + blob_bytes);
-  m.force_generic = force_generic != 0;
-  if (build_device_model(&m, true) != GMR_OK) return -3;
-  gmr::DevModel &d = m.dm;
+  gmr_blob_header h;
+  std::string why;
+  if (gmr::validate_blob(blob, blob_bytes, h, why) != GMR_OK) return -2;
+  gmr::ModelPlan plan;
+  if (gmr::plan_model(blob, blob_bytes, 0, force_generic != 0, plan, why) != GMR_OK) return -3;
+  gmr::DevModel &d = plan.dm;
   int k = 0;
 #define GMR_X(f, e) if (k++ == alter_field) (e) += alter_delta;
   GMR_IK_SHAPE_FIELDS(GMR_X)
@@ -1253,8 +555,8 @@ int gmr_debug_ik_shape(const void *blob, size_t blob_bytes, int force_generic, i
 #define GMR_X(f, e) if (fields_out) fields_out[k++] = (e);
   GMR_IK_SHAPE_FIELDS(GMR_X)
 #undef GMR_X
-  const bool sq = d.sq_ok && !m.force_generic;
-  const int shape = ik_launch_shape(ik_shape_of(d, m.nvp, sq), false, plain != 0, in_f64 != 0, offset_to_ground != 0, false);
+  const bool sq = d.sq_ok && !force_generic;
+  const int shape = ik_launch_shape(ik_shape_of(d, plan.nvp, sq), false, plain != 0, in_f64 != 0, offset_to_ground != 0, false);
   if (name_out && name_len) snprintf(name_out, name_len, "%s", ik_shape_name(shape));
   return shape;
 }

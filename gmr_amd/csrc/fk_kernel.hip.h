@@ -26,36 +26,9 @@
 
 #include <type_traits>
 
+#include "dev_model.h"
+
 namespace gmr {
-
-constexpr int kFkThreads = 128;
-#ifndef GMR_FK_GROUP
-#define GMR_FK_GROUP 8
-#endif
-constexpr int kFkGroup = GMR_FK_GROUP;             // bodies per output flush
-constexpr int kFkPosStride = 3 * kFkGroup + 1;    // LDS words per lane of the position stage (odd: conflict-free)
-constexpr int kFkRotStride = 4 * kFkGroup + 1;
-constexpr int kFkMaxSlots = 12;
-
-// Everything the chain needs about one body, in one 80-byte record: read with two scalar loads (s_load_dwordx16 + x4) and
-// fetched one body ahead of its use, instead of a dozen dependent scalar loads per body in front of the wave-uniform branches.
-struct FkBody {
-  int src_slot, dofidx, save_slot, pad0;  // src_slot: -1 = the previous body is the parent; dofidx: -1 = no hinge
-  float lpos[3], pad1;                    // local translation
-  float lrot[4];                          // local rotation xyzw, raw XML values (not normalised)
-  double axis[3], pad2;                   // unit hinge axis in float64 (torch promotes the hinge quaternion to float64)
-};
-static_assert(sizeof(FkBody) == 80, "FkBody layout");
-
-struct FkTree {     // device arrays, [nbody]
-  const int *parent, *dofidx, *src_slot, *save_slot;  // dofidx: -1 if no hinge; src_slot: -1 = previous body
-  const float *lpos;   // [nb][3] local translation
-  const float *lrot;   // [nb][4] local rotation xyzw, raw XML values (not normalised)
-  const float *jaxis;  // [nb][3] hinge axis, unit (double normalised, then rounded)
-  const double *jaxis64;  // [nb][3] unit axis in float64 (torch promotes the hinge quaternion to float64)
-  const FkBody *body;     // [nb] the same, one record per body (what the kernels read)
-  int nbody, ndof, nslots, dof_in_order;  // dof_in_order: dofidx never decreases along the bodies (the register window needs it)
-};
 
 __device__ __forceinline__ void fk_quat_mul(const float a[4], const float b[4], float o[4]) {
 #pragma clang fp contract(off)

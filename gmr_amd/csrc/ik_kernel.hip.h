@@ -37,11 +37,10 @@
 #include <type_traits>
 
 #include "../../include/gmr_amd.h"
+#include "dev_model.h"
 #include "target_blocks.h"
 
 namespace gmr {
-
-typedef unsigned long long u64;
 
 // Measurement instruments (per-phase cycle stamps, ISA phase marks, the phase-duplication builds of tools/build_variant.sh) live in
 // ik_variants.hip.h and exist in variant builds only (-DGMR_IK_VARIANTS); the shipped kernel sees empty macros.
@@ -59,9 +58,6 @@ typedef unsigned long long u64;
 #ifndef GMR_QP_GROUP
 #define GMR_QP_GROUP 6
 #endif
-#ifndef GMR_IK_STAGE_TREE
-#define GMR_IK_STAGE_TREE 1  // joint tree staged in LDS per wavefront; 0 = re-read from L2 (saves 3.3 KB LDS for G1)
-#endif
 #ifndef GMR_IK_TARGET_BLOCKS
 #define GMR_IK_TARGET_BLOCKS 1  // plain instances prepare the targets of four frames per pass (target_blocks.h); 0 = one frame per pass
 #endif
@@ -71,68 +67,14 @@ typedef unsigned long long u64;
                                   // not fit 256 registers, and with 512 (256 VGPRs + AGPRs as their overflow) nothing goes to scratch
                                   // memory -- 480 bytes per lane did for NVP 64 (profiles/r03_generic_qp_*)
 
-// Doubles per task / composite block: LL(6) LA(9) AA(6) g(6) = 27 used, the block sums move 28 (14 lanes x 16 bytes), and the
-// stride is 30 = 15 sixteen-byte slots, odd, so that the blocks of different composites start on different LDS slots: the F
-// phase (every dof lane reads element c of ITS composite) then has no bank conflicts (stride 28 = 14 slots: 91 extra LDS
-// cycles per solve on G1).  Stored "by column": element 3k + s, s = 0..2,
-// (Round 2's mixed-precision variant -- this assembly in float32: -0.5 % time, 5.4e-5 rad -- lives in the history up to commit d74eaa7,
-// profiles/experiment_log_r01_r02.md, round-2 item 7.)
+// Layout of a task / composite block of kBT doubles (dev_model.h), stored "by column": element 3k + s, s = 0..2,
 typedef double blk_t;
-constexpr int kBT = 30, kBTLanes = 14;
 // k: 0 LL(s,s)  1 LL(s,s+1)  2..4 LA(s,s), LA(s,s+1), LA(s,s+2)  5 AA(s,s)  6 AA(s,s+1)  7 gl_s  8 ga_s   (indices mod 3)
 // -- the order in which three lanes per task (one per column s) produce it in task_block_quad
 __host__ __device__ constexpr int bt_ll(int i, int j) { return i == j ? i : ((j - i + 3) % 3 == 1 ? 3 + i : 3 + j); }
 __host__ __device__ constexpr int bt_la(int i, int j) { return 3 * (2 + (j - i + 3) % 3) + i; }
 __host__ __device__ constexpr int bt_aa(int i, int j) { return i == j ? 15 + i : ((j - i + 3) % 3 == 1 ? 18 + i : 18 + j); }
-constexpr int kHPlanRegsSQ = 6;  // rounds of the H pair plan held in registers (even); structured back end only -- the generic one has no registers to spare
-constexpr int kCompRegsSQ = 3;   // passes of the composite plan whose addresses stay in registers for a whole stage (ditto)
-constexpr int kMaxCompPass = 32;  // passes of the composite plan (two composites per pass, children before parents)
 constexpr double kLieEps = 1e-10;  // mink.lie.utils.get_epsilon(float64)
-
-// A compiled model as the kernels see it: ONE struct of fixed-capacity arrays in device memory (filled by api.hip), reached
-// through a single kernel-argument pointer.  Every table is base + compile-time offset, so the model costs two SGPRs instead
-// of two per table (with ~45 tables passed by value the kernel spilled hundreds of SGPRs into VGPR lanes).
-constexpr int kMaxPairsPadded = (GMR_MAX_BODIES * (GMR_MAX_BODIES - 1) / 2 + 127) / 128 * 128;
-struct DevModel {
-  // root_tslot: slot whose prepared target the root body tracks (-1 = none); same_tasks: both tables used, same (body, slot) per task
-  int nbody, nq, nv, nslot, root_slot, n_act, root_tslot, same_tasks;
-  int ntask[2], use_table[2], ncomp[2], ncpass[2];  // ncpass: composite passes per table
-  int npairp, fkrounds, sq_ok, sq_nlimb;              // npairp: entries of hplan (a multiple of 128)
-  int root_planar, pad_[3];                           // 1: planar base (gmr_blob.h root_dof_mask 0x23): rows 2-4 of the QP are null dofs (akind 7)
-  // per active dof [64]
-  int abody[64], akind[64], aqadr[64], alimited[64];  // akind: 0..2 root translation, 3..5 root rotation, 6 hinge, 7 null (a root
-                                                      // dof the model lacks: takes the hinge path with the root's zero axis)
-  double arange[128];                                 // [64][2]
-  int acomp[2 * 64];                                  // composite node of the dof per table
-  // per task, table-major [2][GMR_MAX_TASKS]
-  int tbody[2 * GMR_MAX_TASKS], tslot[2 * GMR_MAX_TASKS];
-  double twp[2 * GMR_MAX_TASKS], twr[2 * GMR_MAX_TASKS];
-  // per body [nbody]
-  int jtype[GMR_MAX_BODIES], qadr[GMR_MAX_BODIES];
-  double bpos[3 * GMR_MAX_BODIES], bquat[4 * GMR_MAX_BODIES], axis[3 * GMR_MAX_BODIES];  // bquat: unit wxyz
-  u64 fkanc[GMR_MAX_BODIES];                          // byte r = ancestor folded in FK round r (0xff: none)
-  double qpos0[GMR_MAX_BODIES + 8];                   // [nq]
-  // per slot [nslot]
-  double sscale[GMR_MAX_SLOTS], spoff[3 * GMR_MAX_SLOTS], sroff[4 * GMR_MAX_SLOTS];
-  int sfoot[GMR_MAX_SLOTS];
-  // structured QP (box_qp_struct): 4 groups of 16 lanes, each = one bin of limb dofs + a copy of the core dofs
-  signed char sq_gdof[64], sq_owner[64];              // dof of a structured lane (-1 padding); 1 if the lane owns that dof
-  int sq_lane_of_dof[64], sq_diag[64];                // per dof: its owner lane; LDS index of its diagonal entry
-  // H assembly plan, one entry per structurally non-zero off-diagonal pair (dof j strictly above dof i), padded to a multiple
-  // of 64 with entries that land in the dummy slots: LDS byte offsets {S_j | F_i << 16, H[i][j] | H[j][i] << 16}
-  uint2 hplan[kMaxPairsPadded];
-  // composite plan per table, pass and quarter-wave: LDS byte offsets of four source blocks and the destination block
-  // {s0|s1<<16, s2|s3<<16, dst, -}; absent sources point at the zero block, an idle quarter at a scratch block
-  uint4 comp_plan[2 * kMaxCompPass * 4];
-};
-
-struct LdsLayout {
-  // offsets in doubles.  zero: block of zeros; hplan / cplan: the staged H-pair and composite plans; Lb (generic QP broadcast
-  // rows) aliases S; Bc aliases the poses; H aliases [B | poses / Bc] (all dead during the QP)
-  int zero, hplan, cplan, q, tp, tq, S, F, Lb, bodyc, xpos, xquat, B, Bc, H, total_doubles;
-  // tring: the ring of kTargetBlockFrames target images [tp | tq] of a model that matches a plain shape (target_blocks.h), else -1
-  int tring;
-};
 
 struct IkLaunch {
   const void *hpos, *hquat;
@@ -186,31 +128,6 @@ __device__ __forceinline__ double kc(double c) {
   asm volatile("" : "+s"(c));
   return c;
 }
-// The shape of a (model, call): everything ik_body reads from DevModel / IkLaunch / the work item that is wave-uniform and never
-// changes for a given model and calling mode.  A shape is a struct of static constexpr ints, one per field below, -1 = "read it at
-// run time"; IkShapeAny (all -1) is the generic instance that serves every model, the group kernels and the session kernel.  A
-// shaped instance is only ever launched for a model and a launch the host has matched field by field (api.hip, ik_shape_of): the
-// kernel does not re-check.  X(field, the value in a host DevModel d).
-#define GMR_IK_SHAPE_FIELDS(X)                                                                                                   \
-  X(nlimb, d.sq_nlimb) X(ntask0, d.ntask[0]) X(ntask1, d.ntask[1]) X(use0, d.use_table[0]) X(use1, d.use_table[1])              \
-  X(same_tasks, d.same_tasks) X(ncpass0, d.ncpass[0]) X(ncpass1, d.ncpass[1]) X(npairp, d.npairp) X(nbody, d.nbody)              \
-  X(fkrounds, d.fkrounds) X(n_act, d.n_act) X(nslot, d.nslot) X(nq, d.nq) X(root_slot, d.root_slot)
-// plain (a property of the launch, not of the model): 1 = float32 key-points, no offset_to_ground, no item with a verification walk
-// (check_stride) or a speculative chunk start (GMR_INIT_ROOT_TARGET), no step cap (IkLaunch::step_cap)
-struct IkShapeAny {
-#define GMR_X(f, e) static constexpr int f = -1;
-  GMR_IK_SHAPE_FIELDS(GMR_X)
-#undef GMR_X
-  static constexpr int plain = -1;
-};
-// unitree_g1 with the smplx config (and whatever else packs to the same counts) in the plain batched call
-struct IkShapeG1Smplx {
-  static constexpr int nlimb = 7, ntask0 = 14, ntask1 = 14, use0 = 1, use1 = 1, same_tasks = 1, ncpass0 = 3, ncpass1 = 3, npairp = 384,
-                       nbody = 32, fkrounds = 4, n_act = 35, nslot = 14, nq = 36, root_slot = 0;
-  // plain is compiled in: the host only sends plain launches here (api.hip, ik_launch_shape), and the target preparation -- the one
-  // block whose contraction used to depend on the float64 / offset_to_ground / walk paths around it -- is pinned (target_prep_slot)
-  static constexpr int plain = 1;
-};
 // The shape's value where it fixes one, else the run-time value (whose load is then dead code).
 template <int V>
 __device__ __forceinline__ int shp(int v) {
@@ -442,7 +359,6 @@ __device__ __forceinline__ void qrot(const double q[4], const double v[3], doubl
   o[1] = fma(2.0, q[0] * cy + (q[3] * cx - q[1] * cz), v[1]);
   o[2] = fma(2.0, q[0] * cz + (q[1] * cy - q[2] * cx), v[2]);
 }
-constexpr int kBodyC = 11;  // doubles per body in the LDS-staged joint tree: pos(3) quat(4) axis(3) {fkanc(6 bytes), jtype, qadr}
 // Stage this lane's body of the joint tree into LDS (once per wavefront).
 // The model is always read through the CONSTANT address space (it is read-only for every launch): a group launch gets its model
 // pointer from memory, and loads through a generic (flat) pointer count as divergent, loads through a global pointer that is not a

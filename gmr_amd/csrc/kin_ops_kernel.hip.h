@@ -26,14 +26,6 @@ namespace gmr {
 constexpr int kKinThreads = 256;
 constexpr int kKinMaxBodies = 64;  // GMR_MAX_BODIES
 
-struct KinTables {            // device arrays
-  const int *dof_body;        // [ndof] body that owns hinge d
-  const float *lim_lo, *lim_hi;  // [ndof] float32 of the XML range (KinematicsModel._dof_lower_limits / _dof_upper_limits)
-  const uint8_t *depth;       // [nb] tree level of body j (0 for the root)
-  const uint8_t *order;       // [nb] bodies sorted by level (stable)
-  int max_depth;
-};
-
 // ---------------------------------------------------------------------------------------------------------------- dof_to_rot
 // Item i = (frame f, joint j = 1 + i % (nb - 1)): out[i] = hinge quaternion of the joint's angle, or the identity.
 __global__ void __launch_bounds__(kKinThreads) dof_to_rot_kernel(FkTree t, const float *__restrict__ dof, int64_t n_frames, float *__restrict__ out) {
