@@ -278,8 +278,12 @@ template <int NVP>
 void launch_ik_sliced(const gmr_model *m, const gmr::IkLaunch &L, const gmr::IkSliceArgs &S, unsigned grid, hipStream_t st, bool plain) {
   const bool sq = m->dm.sq_ok && !m->force_generic;
   const int shape = sq ? ik_launch_shape(m->shape, m->force_generic_shape, plain, L.in_f64 != 0, L.prm.offset_to_ground != 0, L.step_cap != nullptr) : -1;
-  if (getenv("GMR_DEBUG_PLAN"))
-    fprintf(stderr, "gmr: ik launch: sliced instance %s, slice %d frames, %u tickets for %d items\n", ik_shape_name(shape), S.slice_len, grid, L.n_items);
+  if (getenv("GMR_DEBUG_PLAN")) {
+    std::string taper = S.plan.n_taper > 0 ? ", taper" : ", no taper";  // the taper's slice lengths, in order
+    for (int j = 0; j < S.plan.n_taper; ++j) taper += " " + std::to_string(S.plan.taper_end[j] - (j ? S.plan.taper_end[j - 1] : S.plan.t_body));
+    fprintf(stderr, "gmr: ik launch: sliced instance %s, slice %d frames, %u tickets for %d items%s\n", ik_shape_name(shape), S.plan.slice_len, grid,
+            L.n_items, taper.c_str());
+  }
   if (shape >= 0) {
     int idx = 0;
 #define GMR_X(SH, v)                                                                                                                   \
@@ -308,6 +312,12 @@ void launch_ik_sliced(const gmr_model *m, const gmr::IkLaunch &L, const gmr::IkS
 // slice would also take the batches of 512 .. 1023 frames, for which nothing was measured and which the probe policy serves
 // (Engine.PROBE_*, measured down to 300 frames).
 constexpr int kBalanceSlice = 256;
+// Taper floor in frames, 0 = off: the last kBalanceSlice frames of the longest clip run as halving slices down to this length
+// (slice_plan.h), which takes the short last round of a short slice without its set-ups over the whole clip.  Swept on the headline
+// batch (profiles/slice_taper_sweep.md): off / 128 / 64 / 32 / 16 / 8 take 508.6 / 506.5 / 503.2 / 502.1 / 501.3 / 499.8 ms, a uniform
+// 128-frame slice 504.1 ms.  16, not 8: over both visits' rows the two are within the spread of repeated rows (500.7 .. 501.3 against
+// 499.8 .. 501.0 ms), and 16 draws fewer tickets: 256 frames end as 128 64 32 16 16, 16 rounds on 3000 frames against 12.
+constexpr int kBalanceTaperFloor = 16;
 constexpr bool kBalanceDefault = true;          // without GMR_AMD_BALANCE: take the sliced path where the plan says it pays
 constexpr double kBalanceMaxLengthSpread = 0.10;  // "equal lengths": the band Engine.PROBE_MAX_LENGTH_SPREAD uses
 constexpr int kBalanceMinSlices = 4;            // mean item length, in slices, from which slicing pays
@@ -671,7 +681,10 @@ static int ik_run_sliced(gmr_model *m, const gmr::IkLaunch &L, const std::vector
     return GMR_OK;
   }
   const int longest = sorted[0].n_burn + sorted[0].n_out;
-  const int64_t rounds = std::max<int64_t>(1, ((int64_t)longest + slice - 1) / slice), grid = rounds * n_items;
+  int taper_floor = kBalanceTaperFloor;  // GMR_AMD_BALANCE_TAPER: read per call, like the two above
+  if (const char *e = getenv("GMR_AMD_BALANCE_TAPER")) { const long v = strtol(e, nullptr, 10); if (v >= 0 && v <= INT32_MAX) taper_floor = (int)v; }
+  const gmr::SlicePlan plan = gmr::slice_plan_make(longest, slice, taper_floor);
+  const int64_t rounds = gmr::slice_plan_rounds(plan), grid = rounds * n_items;
   const size_t rec = (size_t)m->dm.nq + 7 * (size_t)m->dm.nbody;  // (the kernel's own tree: DevModel::nbody)
   const size_t flag_bytes = (sizeof(unsigned) * ((size_t)n_items + 1) + 15) & ~size_t(15);  // [head | done[n_items]], cleared every call
   const size_t lane_off = flag_bytes, state_off = lane_off + sizeof(int) * 64 * (size_t)n_items;
@@ -691,7 +704,7 @@ static int ik_run_sliced(gmr_model *m, const gmr::IkLaunch &L, const std::vector
   S.timeouts = m->slice_err_dev;
   S.lane_state = reinterpret_cast<int *>(ws + lane_off);
   S.state = reinterpret_cast<double *>(ws + state_off);
-  S.slice_len = slice;
+  S.plan = plan;
   S.rec_doubles = (int)rec;
   // The poll cap, a guard far beyond the longest wait of a correct run.  With more items than slots a predecessor finished rounds ago; with
   // fewer, ceil(slots / n_items) slices of one clip are resident at once and the last of them waits for the whole chain before it.  2048

@@ -38,6 +38,7 @@
 
 #include "../../include/gmr_amd.h"
 #include "dev_model.h"
+#include "slice_plan.h"
 #include "target_blocks.h"
 
 namespace gmr {
@@ -103,8 +104,9 @@ struct IkSliceArgs {
   unsigned *timeouts;  // host memory: set to 1 by a wavefront that gave up (gmr_ik_sliced_timeouts reads and clears it)
   double *state;       // [n_items][rec_doubles]: q [nq], xpos [3 nbody], xquat [4 nbody] at the end of the item's last finished slice
   int *lane_state;     // [n_items][64]: the QP's working set of every lane (sq_status / status)
-  int slice_len, rec_doubles;
-  unsigned max_polls, pad;
+  int rec_doubles;
+  unsigned max_polls;
+  SlicePlan plan;      // which frames round r covers (slice_plan.h)
 };
 constexpr unsigned kSliceGaveUp = 0xffffffffu;
 
@@ -1139,7 +1141,7 @@ struct IkLive {
   unsigned max_polls, max_frames;
 };
 
-// A slice of a plain item (ik_kernel_sliced): frames [r slice_len, (r + 1) slice_len) of sorted item `item`.  A slice that is not
+// A slice of a plain item (ik_kernel_sliced): frames [slice_begin(r), slice_end(r)) of sorted item `item` (slice_plan.h).  A slice that is not
 // the first RESUMES: it waits for its predecessor's record and starts from exactly the state that one ended with -- q, the poses
 // of the last stepped FK and the QP's working set of every lane; nothing else outlives a frame (e, jl_*, sum_r2 are rebuilt at
 // stage-1 entry, solves and qpflag are per frame).  The poses are carried, not recomputed: an entry FK normalises the root
@@ -1291,8 +1293,8 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   bool poses_valid = SLICED && sl.r > 0;
   int kf0 = 0, kend = nfr;  // SLICED: this slice's frames
   if constexpr (SLICED) {
-    kf0 = sl.r * ik_slice_args(sl.Sk)->slice_len;
-    kend = min(nfr, kf0 + ik_slice_args(sl.Sk)->slice_len);
+    kf0 = slice_begin(ik_slice_args(sl.Sk)->plan, sl.r);
+    kend = min(nfr, slice_end(ik_slice_args(sl.Sk)->plan, sl.r));
   }
   // Verification walk (check_stride > 0, gmr_blob.h): the item runs down a clip whose chunks were already solved
   // speculatively.  At every chunk boundary the state is compared with the state B that chunk started its output from: equal
@@ -1813,7 +1815,7 @@ __device__ __forceinline__ void ik_sliced_item(const DevModel *mp, const LdsLayo
   const unsigned n = (unsigned)Lk->n_items;
   const int item = (int)(h % n), r = (int)(h / n);
   const int nfr = Lk->items[item].n_burn + Lk->items[item].n_out;
-  if (r > 0 && (long long)r * Sk->slice_len >= (long long)nfr) return;  // (slice 0 always runs: an empty item still reports frames_done = 0 and its state)
+  if (r > 0 && slice_begin(Sk->plan, r) >= nfr) return;  // (slice 0 always runs: an empty item still reports frames_done = 0 and its state)
   ik_body<NVP, SQ, false, false, SH, true>(*(DevModelG *)mp, Lk, lay, item, IkLive{}, IkSliceRun{Sk, item, r});
 }
 template <int NVP, bool SQ>

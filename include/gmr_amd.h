@@ -155,15 +155,17 @@ int gmr_ik_solve(gmr_model *m, const void *human_pos, const void *human_quat, in
                  int32_t *iters_out, int32_t *frames_done, gmr_ik_stats *stats, void *stream);
 
 /* How gmr_ik_solve launches a batch: whole clips, one wavefront each from start to end, or -- plain clips of (nearly) equal
- * length, more of them than the device has wavefront slots -- cut into slices of a fixed number of frames that wavefronts draw
- * round-robin by ticket, the full solver state handed from slice to slice exactly, so that all clips advance at the same pace and
+ * length, more of them than the device has wavefront slots -- cut into slices that wavefronts draw round-robin by ticket: a fixed
+ * number of frames each through the clip, and ever shorter ones, halving down to a floor, over the last slice length of frames of
+ * the longest clip, so that the launch's last round is short (csrc/slice_plan.h), the full solver state handed from slice to slice exactly, so that all clips advance at the same pace and
  * finish in the same last round whatever each costs.  Results are bit-identical either way.
  * gmr_ik_balance_plan is that choice as a pure host function (no device, no stream): the slice length in frames, or 0 for whole
  * clips.  Nonzero when every item is plain (no check_stride, no burn-in, no GMR_INIT_ROOT_TARGET start), n_items > slots (wavefront
  * slots of the device: 8 per compute unit), the standard deviation of the item lengths is at most 10 % of their mean, and the mean
  * is at least four slices.  Environment: GMR_AMD_BALANCE=0 never slices, GMR_AMD_BALANCE=1 slices every plain batch,
  * GMR_AMD_BALANCE=2 applies the rule above (the default, where DESIGN.md 8 says so), GMR_AMD_BALANCE_SLICE=<frames> overrides the
- * slice length.  gmr_ik_solve_ordered and the group calls always run whole clips.
+ * slice length, GMR_AMD_BALANCE_TAPER=<frames> the floor of the halving slices (0: fixed-length slices to the end; the function's
+ * return value does not depend on it).  gmr_ik_solve_ordered and the group calls always run whole clips.
  * gmr_ik_sliced_timeouts: a waiting slice polls a bounded number of times; the bound only guards against a broken protocol.  A
  * wavefront that reaches it writes no frame and ends, as do the later slices of its clip (their rows of qpos_out and
  * frames_done stay as the caller left them), and this function -- host only, call it after synchronising the stream -- returns 1 if
