@@ -122,6 +122,12 @@ __device__ __forceinline__ FkBody fk_body(const FkTree &t, int j) {
 #endif
 }
 
+// Sixteen bytes of a caller's float array.  Such an array is only element-aligned (include/gmr_amd.h, "Extent and alignment"), so
+// the access is typed with 4-byte alignment: still one global_load / global_store_dwordx4, which the memory pipeline takes at any
+// dword address, but nothing the compiler may assume 16 of.  FkV4 is the same vector in registers and LDS.
+typedef float FkV4 __attribute__((ext_vector_type(4)));
+typedef FkV4 FkV4E __attribute__((aligned(4)));
+
 template <int MODE>
 __global__ void __launch_bounds__(kFkThreads) fk_kernel(FkTree t, const float *__restrict__ root_pos,
                                                         const float *__restrict__ root_rot, const float *__restrict__ dof,
@@ -179,7 +185,7 @@ __global__ void __launch_bounds__(kFkThreads) fk_kernel(FkTree t, const float *_
       for (int i = tid; i < n; i += kFkThreads) {
         const int fr = i / cnt, b = i - fr * cnt;
         const float *sp = rstage + fr * kFkRotStride + 4 * b;
-        *reinterpret_cast<float4 *>(body_rot + ((f0 + fr) * nbody + j0 + b) * 4) = make_float4(sp[0], sp[1], sp[2], sp[3]);
+        *reinterpret_cast<FkV4E *>(body_rot + ((f0 + fr) * nbody + j0 + b) * 4) = FkV4{sp[0], sp[1], sp[2], sp[3]};
       }
     }
     __syncthreads();
@@ -324,9 +330,9 @@ __global__ void __launch_bounds__(kFkWave) fk_pos_kernel(FkTree t, const float *
     __syncthreads();  // (one wavefront: orders the LDS writes of the other lanes before the reads below)
     if (PARTS == 1) {
       const int nwords = nfb * row, n4 = nwords >> 2;
-      float *dst = body_pos + f0 * row;  // 16-byte aligned: 64 rows of 12 nbody bytes per tile
+      float *dst = body_pos + f0 * row;  // element-aligned only, as the caller's array is: 16-byte stores typed FkV4E
       for (int i = lane; i < n4; i += kFkWave)
-        *reinterpret_cast<float4 *>(dst + 4 * i) = *reinterpret_cast<const float4 *>(img + 4 * i);
+        *reinterpret_cast<FkV4E *>(dst + 4 * i) = *reinterpret_cast<const FkV4 *>(img + 4 * i);
       for (int i = 4 * n4 + lane; i < nwords; i += kFkWave) dst[i] = img[i];
     } else {
       const int w = 3 * nb_part;

@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(kKinThreads) dof_to_rot_kernel(FkTree t, const
       const double ax[3] = {s_axis[3 * j], s_axis[3 * j + 1], s_axis[3 * j + 2]};
       fk_hinge_quat(ax, dof[f * ndof + d], q);
     }
-    reinterpret_cast<float4 *>(out)[i] = make_float4(q[0], q[1], q[2], q[3]);
+    reinterpret_cast<FkV4E *>(out)[i] = FkV4{q[0], q[1], q[2], q[3]};  // 16 bytes, typed with the element's alignment
   }
 }
 
@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(kKinThreads) rot_to_dof_kernel(FkTree t, KinTa
   int d = (int)(i0 - f * ndof);
   for (int64_t i = i0; i < n; i += stride, f += sf, d += sd) {
     if (d >= ndof) { d -= ndof; ++f; }
-    const float4 q0 = reinterpret_cast<const float4 *>(rot)[f * nj + (s_body[d] - 1)];
+    const FkV4 q0 = reinterpret_cast<const FkV4E *>(rot)[f * nj + (s_body[d] - 1)];  // 16 bytes, typed with the element's alignment
     const float sg = 1.0f - 2.0f * (q0.w < 0.0f ? 1.0f : 0.0f);
     const float x = sg * q0.x, y = sg * q0.y, z = sg * q0.z, w = sg * q0.w;
     const float len = sqrtf(x * x + y * y + z * z);
@@ -103,7 +103,8 @@ __global__ void __launch_bounds__(kKinThreads) rot_to_dof_kernel(FkTree t, KinTa
 // lane busy, and its parents' results are already in the LDS image of the output from the passes before (a pass that spans several
 // levels takes one round per level).  A batch therefore costs about P + depth rounds of one LDS read, one product and one LDS write --
 // against nb - 1 dependent steps per frame in the reference's loop -- and the results leave in the input's order as dense 16-byte stores.
-typedef float KinV4 __attribute__((ext_vector_type(4)));  // a native 16-byte vector: arrays of it stay in registers
+typedef FkV4 KinV4;    // a native 16-byte vector: arrays of it stay in registers
+typedef FkV4E KinV4E;  // the same in the caller's arrays, which are element-aligned only
 template <int P>
 __global__ void __launch_bounds__(64) local_to_global_kernel(FkTree t, KinTables kt, const float *__restrict__ local, int64_t n_frames,
                                                             float *__restrict__ global_) {
@@ -129,8 +130,8 @@ __global__ void __launch_bounds__(64) local_to_global_kernel(FkTree t, KinTables
     dhi[p] = last >= 0 ? __builtin_amdgcn_readlane(depth[p], last < 0 ? 0 : last) : -1;
   }
   const int64_t n_batches = (n_frames + F - 1) / F;
-  const KinV4 *src = reinterpret_cast<const KinV4 *>(local);
-  KinV4 *dst = reinterpret_cast<KinV4 *>(global_);
+  const KinV4E *src = reinterpret_cast<const KinV4E *>(local);
+  KinV4E *dst = reinterpret_cast<KinV4E *>(global_);
   // the prefetch registers: loads are unconditional (indices clamped to the array's last element) so that they stay registers
   KinV4 nxt[P];
   const int64_t e_last = n_frames * nb - 1;

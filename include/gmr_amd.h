@@ -25,6 +25,14 @@
  * their stream and return results to the host.  All of this is checked behind a busy stream for every entry on ROCm 7
  * (tests/test_gpu_stream_order.py).
  *
+ * Extent and alignment.  Every device and host array is dense and row-major, of exactly the extent its entry states: there is no
+ * padding between rows and none is needed behind the last one.  An array needs only the alignment of its element type (4 bytes
+ * for float32 / int32, 8 for float64 / int64, 1 for text bytes; a struct its natural alignment) -- a slice that starts in the
+ * middle of a larger allocation is as good as the allocation itself, and no entry asks for more.  Nothing outside the stated
+ * extent is read into a result, and nothing outside it is written; inputs are never modified and every element of a non-NULL
+ * output is written unless its entry says otherwise.  Checked for every stream-taking entry inside guarded arrays, 256-byte
+ * aligned and element-aligned (tests/test_gpu_guard_band.py).
+ *
  * What each entry point replaces in the reference (Zudva/GMR):
  *   gmr_model_create   GeneralMotionRetargeting.__init__ + setup_retarget_configuration
  *                      (general_motion_retargeting/motion_retarget.py:13-114): mj.MjModel.from_xml_path,

@@ -279,9 +279,9 @@ def test_motion_library_filters_once_at_construction():
 
 
 # ------------------------------------------------------------------ 8: stream order with the filter on
-def test_late_producer_with_the_filter_on():
-    from tests import stream_order as so
-    from tests.test_gpu_stream_order import DEV, MotionCase
+def FilteredTrack(v):
+    """The gmr_motion_track case of the stream-order tests with the filter on (also run by tests/test_gpu_guard_band.py)."""
+    from tests.test_gpu_stream_order import MotionCase
 
     class FilteredTrack(MotionCase):
         def __init__(self, v):
@@ -292,6 +292,13 @@ def test_late_producer_with_the_filter_on():
             super().fill(st, b, decoy)
             for i in range(len(self.engines)):
                 st["inp"][i].lowpass_hz = 3.0 if decoy else 6.0
+
+    return FilteredTrack(v)
+
+
+def test_late_producer_with_the_filter_on():
+    from tests import stream_order as so
+    from tests.test_gpu_stream_order import DEV, MotionCase
 
     case = FilteredTrack(0)
     ser = so.serial_answers(case, DEV())

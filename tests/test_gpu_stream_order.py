@@ -130,9 +130,11 @@ def _fk_inputs(cm, v, n=N_KIN):
     return {"root_pos": (out[0][0], out[1][0]), "root_rot": (out[0][1], out[1][1]), "dof": (out[0][2], out[1][2])}
 
 
-def case_fk(v, shape=False, min_height=False, offsets=None):
-    eng, lib = _engine(), _lib()
+def case_fk(v, shape=False, min_height=False, offsets=None, n=N_KIN, eng=None, want_rot=True):
+    """n, eng, want_rot: the guard-band tests' other lengths, another model's handle and the call with body_rot = NULL."""
+    eng, lib = eng or _engine(), _lib()
     cm, nb = eng.cm, eng.nbody
+    rot = (lambda b: P(b.out["body_rot"])) if want_rot else (lambda b: None)
     if min_height:
         offs = (KIN_OFFS, KIN_OFFS_DECOY) if offsets is None else offsets
         n_seq = len(offs[0]) - 1
@@ -144,57 +146,63 @@ def case_fk(v, shape=False, min_height=False, offsets=None):
         return c
     elif shape:
         c = Plain("gmr_fk_shape", lambda b, s: lib.gmr_fk_shape(eng._h, P(b.dev["root_pos"]), P(b.dev["root_rot"]), P(b.dev["dof"]), P(b.dev["shape"]), 3,
-                                                                N_KIN, P(b.out["body_pos"]), P(b.out["body_rot"]), s), 2, 0)
+                                                                n, P(b.out["body_pos"]), rot(b), s), 2, 0)
     else:
-        c = Plain("gmr_fk", lambda b, s: lib.gmr_fk(eng._h, P(b.dev["root_pos"]), P(b.dev["root_rot"]), P(b.dev["dof"]), N_KIN, P(b.out["body_pos"]),
-                                                    P(b.out["body_rot"]), s), 1, 0)
-    c.dev_in = _fk_inputs(cm, v)
+        c = Plain("gmr_fk", lambda b, s: lib.gmr_fk(eng._h, P(b.dev["root_pos"]), P(b.dev["root_rot"]), P(b.dev["dof"]), n, P(b.out["body_pos"]),
+                                                    rot(b), s), 1, 0)
+    c.dev_in = _fk_inputs(cm, v, n)
     if shape:
         g = _gen(120 + v)
         c.dev_in["shape"] = tuple((1.0 + 0.2 * torch.rand((nb, 3), generator=g, dtype=F64, device=DEV())).to(F32) for _ in range(2))
     if not min_height:
-        c.out_spec = {"body_pos": ((N_KIN, nb, 3), F32), "body_rot": ((N_KIN, nb, 4), F32)}
+        c.out_spec = {"body_pos": ((n, nb, 3), F32)}
+        if want_rot:
+            c.out_spec["body_rot"] = ((n, nb, 4), F32)
     return c
 
 
-def case_kin(v, name):
+def case_kin(v, name, n=N_KIN):
     eng, lib = _engine(), _lib()
     nb, nd = eng.nbody, eng.nq - 7
-    shapes = {"gmr_dof_to_rot": ((N_KIN, nd), (N_KIN, nb - 1, 4)), "gmr_rot_to_dof": ((N_KIN, nb - 1, 4), (N_KIN, nd)),
-              "gmr_local_rot_to_global": ((N_KIN, nb, 4), (N_KIN, nb, 4))}[name]
+    shapes = {"gmr_dof_to_rot": ((n, nd), (n, nb - 1, 4)), "gmr_rot_to_dof": ((n, nb - 1, 4), (n, nd)),
+              "gmr_local_rot_to_global": ((n, nb, 4), (n, nb, 4))}[name]
     fn = getattr(lib, name)
-    c = Plain(name, lambda b, s: fn(eng._h, P(b.dev["x"]), N_KIN, P(b.out["y"]), s), 1, 0)
+    c = Plain(name, lambda b, s: fn(eng._h, P(b.dev["x"]), n, P(b.out["y"]), s), 1, 0)
     make = (lambda g: _randn(g, shapes[0], F32, 0.5)) if name == "gmr_dof_to_rot" else (lambda g: _unit(g, shapes[0], F32))
     c.dev_in = {"x": (make(_gen(130 + 10 * v)), make(_gen(135 + 10 * v)))}
     c.out_spec = {"y": (shapes[1], F32)}
     return c
 
 
-def case_evaluate(v):
+def case_evaluate(v, n=N_KIN, omit=()):
+    """omit: the outputs passed as NULL (the guard-band tests leave each out in turn)."""
     eng, lib = _engine(), _lib()
     cm = eng.cm
     nt = eng.info.ntask[0] + eng.info.ntask[1]
-    pt, qt = _keypoints(cm, N_KIN, 140 + 10 * v)
-    pd, qd = _keypoints(cm, N_KIN, 145 + 10 * v)
-    c = Plain("gmr_evaluate", lambda b, s: lib.gmr_evaluate(eng._h, P(b.dev["qpos"]), N_KIN, P(b.dev["pos"]), P(b.dev["quat"]), _native.GMR_DTYPE_F64,
-                                                            cm.nslot + 1, H(b.host["slot_col"]), 0, None, P(b.out["err"]), P(b.out["task_err"]),
-                                                            P(b.out["xpos"]), P(b.out["xquat"]), s), 1, 1)
-    c.dev_in = {"qpos": (_qpos(cm, N_KIN, 141 + 10 * v), _qpos(cm, N_KIN, 146 + 10 * v)), "pos": (pt, pd), "quat": (qt, qd)}
+    pt, qt = _keypoints(cm, n, 140 + 10 * v)
+    pd, qd = _keypoints(cm, n, 145 + 10 * v)
+    O = lambda b, k: P(b.out.get(k))  # noqa: E731
+    c = Plain("gmr_evaluate", lambda b, s: lib.gmr_evaluate(eng._h, P(b.dev["qpos"]), n, P(b.dev["pos"]), P(b.dev["quat"]), _native.GMR_DTYPE_F64,
+                                                            cm.nslot + 1, H(b.host["slot_col"]), 0, None, O(b, "err"), O(b, "task_err"),
+                                                            O(b, "xpos"), O(b, "xquat"), s), 1, 1)
+    c.dev_in = {"qpos": (_qpos(cm, n, 141 + 10 * v), _qpos(cm, n, 146 + 10 * v)), "pos": (pt, pd), "quat": (qt, qd)}
     c.host_in = {"slot_col": _slot_cols(cm)}
-    c.out_spec = {"err": ((N_KIN, 2), F64), "task_err": ((N_KIN, nt, 6), F64), "xpos": ((N_KIN, eng.nbody, 3), F64), "xquat": ((N_KIN, eng.nbody, 4), F64)}
+    c.out_spec = {"err": ((n, 2), F64), "task_err": ((n, nt, 6), F64), "xpos": ((n, eng.nbody, 3), F64), "xquat": ((n, eng.nbody, 4), F64)}
+    for k in omit:
+        del c.out_spec[k]
     return c
 
 
 SMPLX_T, SMPLX_TOUT, SMPLX_STRIDE = 130, 65, 60
 
 
-def case_smplx(v, name):
+def case_smplx(v, name, T=SMPLX_T, T_out=SMPLX_TOUT):
     from gmr_amd import synth
     from gmr_amd.smplx_adapter import SMPLX_JOINT_NAMES, SMPLX_PARENTS
     lib = _lib()
     J = 55
     f32 = name == "gmr_smplx_keypoints_in"
-    arrs = [synth.smplx_arrays_torch(SMPLX_T, DEV(), J, SMPLX_STRIDE, seed=150 + 10 * v + k) for k in (0, 5)]
+    arrs = [synth.smplx_arrays_torch(T, DEV(), J, SMPLX_STRIDE, seed=150 + 10 * v + k) for k in (0, 5)]
     if f32:
         arrs = [tuple(a.to(F32) for a in t) for t in arrs]
     rng = np.random.default_rng(150 + v)
@@ -204,33 +212,33 @@ def case_smplx(v, name):
     cols.append(rng.permutation(J)[:n_out].astype(np.int32))
     if name == "gmr_smplx_keypoints":
         B = J
-        call = lambda b, s: lib.gmr_smplx_keypoints(H(b.host["parents"]), J, SMPLX_STRIDE, P(b.dev["go"]), P(b.dev["fp"]), P(b.dev["jt"]), SMPLX_T,  # noqa: E731
-                                                    SMPLX_TOUT, 1, P(b.out["pos"]), P(b.out["quat"]), s)
+        call = lambda b, s: lib.gmr_smplx_keypoints(H(b.host["parents"]), J, SMPLX_STRIDE, P(b.dev["go"]), P(b.dev["fp"]), P(b.dev["jt"]), T,  # noqa: E731
+                                                    T_out, 1, P(b.out["pos"]), P(b.out["quat"]), s)
     elif name == "gmr_smplx_keypoints_cols":
         B = n_out
-        call = lambda b, s: lib.gmr_smplx_keypoints_cols(H(b.host["parents"]), J, SMPLX_STRIDE, P(b.dev["go"]), P(b.dev["fp"]), P(b.dev["jt"]), SMPLX_T,  # noqa: E731
-                                                         SMPLX_TOUT, 1, H(b.host["out_cols"]), n_out, P(b.out["pos"]), P(b.out["quat"]), s)
+        call = lambda b, s: lib.gmr_smplx_keypoints_cols(H(b.host["parents"]), J, SMPLX_STRIDE, P(b.dev["go"]), P(b.dev["fp"]), P(b.dev["jt"]), T,  # noqa: E731
+                                                         T_out, 1, H(b.host["out_cols"]), n_out, P(b.out["pos"]), P(b.out["quat"]), s)
     else:
         B = n_out
         call = lambda b, s: lib.gmr_smplx_keypoints_in(H(b.host["parents"]), J, SMPLX_STRIDE, P(b.dev["go"]), P(b.dev["fp"]), P(b.dev["jt"]),  # noqa: E731
-                                                       _native.GMR_DTYPE_F32, SMPLX_T, SMPLX_TOUT, 1, H(b.host["out_cols"]), n_out, P(b.out["pos"]),
+                                                       _native.GMR_DTYPE_F32, T, T_out, 1, H(b.host["out_cols"]), n_out, P(b.out["pos"]),
                                                        P(b.out["quat"]), s)
     c = Plain(name, call, 1, 0)
     c.dev_in = {k: (arrs[0][i], arrs[1][i]) for i, k in enumerate(("go", "fp", "jt"))}
     c.host_in = {"parents": par}
     if B != J:
         c.host_in["out_cols"] = tuple(cols)
-    c.out_spec = {"pos": ((SMPLX_TOUT, B, 3), F64), "quat": ((SMPLX_TOUT, B, 4), F64)}
+    c.out_spec = {"pos": ((T_out, B, 3), F64), "quat": ((T_out, B, 4), F64)}
     return c
 
 
 BVH_T = 130
 
 
-def case_bvh_fk(v, rows):
+def case_bvh_fk(v, rows, n=BVH_T):
     from gmr_amd import synth
     lib = _lib()
-    data = [synth.lafan_rows_torch(BVH_T, DEV(), seed=160 + 10 * v + k) for k in (0, 5)]
+    data = [synth.lafan_rows_torch(n, DEV(), seed=160 + 10 * v + k) for k in (0, 5)]
     parents, offsets = data[0][1], data[0][2]
     J = len(parents)
     rng = np.random.default_rng(160 + v)
@@ -240,19 +248,19 @@ def case_bvh_fk(v, rows):
         n_out = 14
         host["out_cols"] = (rng.permutation(J + 2)[:n_out].astype(np.int32), rng.permutation(J + 2)[:n_out].astype(np.int32))
         c = Plain("gmr_bvh_fk_rows", lambda b, s: lib.gmr_bvh_fk_rows(H(b.host["parents"]), J, H(b.host["order"]), H(b.host["extra_pos"]), H(b.host["extra_rot"]), 2, 3,
-                                                                      P(b.dev["offsets"]), P(b.dev["rows"]), 3 + 3 * J, BVH_T, 0.01, H(b.host["out_cols"]), n_out,
+                                                                      P(b.dev["offsets"]), P(b.dev["rows"]), 3 + 3 * J, n, 0.01, H(b.host["out_cols"]), n_out,
                                                                       P(b.out["pos"]), P(b.out["quat"]), s), 1, 0)
         off = torch.from_numpy(offsets).to(DEV())
         c.dev_in = {"rows": (data[0][0], data[1][0]), "offsets": (off, off * 1.1)}
     else:
         n_out = J + 2
         c = Plain("gmr_bvh_fk", lambda b, s: lib.gmr_bvh_fk(H(b.host["parents"]), J, H(b.host["order"]), H(b.host["extra_pos"]), H(b.host["extra_rot"]), 2,
-                                                            P(b.dev["lpos"]), P(b.dev["eul"]), BVH_T, 0.01, P(b.out["pos"]), P(b.out["quat"]), s), 1, 0)
+                                                            P(b.dev["lpos"]), P(b.dev["eul"]), n, 0.01, P(b.out["pos"]), P(b.out["quat"]), s), 1, 0)
         g = _gen(165 + v)
-        c.dev_in = {"lpos": (_randn(g, (BVH_T, J, 3), scale=20.0), _randn(g, (BVH_T, J, 3), scale=20.0)),
-                    "eul": (_randn(g, (BVH_T, J, 3)), _randn(g, (BVH_T, J, 3)))}
+        c.dev_in = {"lpos": (_randn(g, (n, J, 3), scale=20.0), _randn(g, (n, J, 3), scale=20.0)),
+                    "eul": (_randn(g, (n, J, 3)), _randn(g, (n, J, 3)))}
     c.host_in = host
-    c.out_spec = {"pos": ((BVH_T, n_out, 3), F64), "quat": ((BVH_T, n_out, 4), F64)}
+    c.out_spec = {"pos": ((n, n_out, 3), F64), "quat": ((n, n_out, 4), F64)}
     return c
 
 
@@ -288,6 +296,10 @@ class BvhParse(so.Case):
     def sort_rows_count(self, b, a):
         return int(min(max(int(b.host_out["n_slow"][0]), 0), self.MAX_SLOW))
 
+    def written(self, b, name):
+        """Leading rows of an output the call writes (None: all): the rows of ``slow`` behind n_slow are left alone."""
+        return self.sort_rows_count(b, None) if name == "host:slow" else None
+
     def invoke(self, b, st, stream):
         h, o = b.host, b.host_out
         return _lib().gmr_bvh_parse_motion_device(P(b.dev["text"]), self.n_bytes, 2, H(h["seg_begin"]), H(h["seg_end"]), H(h["n_lines"]), self.COLS, H(h["row_begin"]),
@@ -313,10 +325,11 @@ class IKCase(so.Case):
 
     struct_values = True
 
-    def __init__(self, v, mode, group):
+    def __init__(self, v, mode, group, dtype=F32):
         super().__init__()
         from gmr_amd import synth
         self.mode, self.group = mode, group
+        self.in_dtype = _native.GMR_DTYPE_F32 if dtype == F32 else _native.GMR_DTYPE_F64
         self.entry = {("solve", False): "gmr_ik_solve", ("plan", False): "gmr_ik_plan_order", ("ordered", False): "gmr_ik_solve_ordered",
                       ("solve", True): "gmr_group_ik_solve", ("plan", True): "gmr_group_plan_order", ("ordered", True): "gmr_group_ik_solve_ordered"}[mode, group]
         self.engines = _group().engines if group else [_engine()]
@@ -328,9 +341,9 @@ class IKCase(so.Case):
             cm = eng.cm
             kp = []
             for seed, hard in ((200 + 10 * v + i, False), (205 + 10 * v + i, True)):
-                pos, quat, _, _ = synth.synth_clips_torch(cm, IK_LENS, seed, DEV(), hard=hard, yaw0=1.0, dtype=F32)
-                pad_p = torch.zeros((IK_FRAMES, 1, 3), dtype=F32, device=DEV())
-                pad_q = torch.zeros((IK_FRAMES, 1, 4), dtype=F32, device=DEV())
+                pos, quat, _, _ = synth.synth_clips_torch(cm, IK_LENS, seed, DEV(), hard=hard, yaw0=1.0, dtype=dtype)
+                pad_p = torch.zeros((IK_FRAMES, 1, 3), dtype=dtype, device=DEV())
+                pad_q = torch.zeros((IK_FRAMES, 1, 4), dtype=dtype, device=DEV())
                 pad_q[..., 0] = 1.0
                 kp.append((torch.cat([pad_p, pos], 1).contiguous(), torch.cat([pad_q, quat], 1).contiguous()))
             self.dev_in[f"pos{i}"], self.dev_in[f"quat{i}"] = (kp[0][0], kp[1][0]), (kp[0][1], kp[1][1])
@@ -353,7 +366,7 @@ class IKCase(so.Case):
         for i, eng in enumerate(self.engines):
             e = st["inp"][i]
             e.human_pos, e.human_quat = b.dev[f"pos{i}"].data_ptr(), b.dev[f"quat{i}"].data_ptr()
-            e.in_dtype, e.n_cols, e.n_frames, e.n_items = _native.GMR_DTYPE_F32, eng.cm.nslot + 1, IK_FRAMES, IK_ITEMS
+            e.in_dtype, e.n_cols, e.n_frames, e.n_items = self.in_dtype, eng.cm.nslot + 1, IK_FRAMES, IK_ITEMS
             e.slot_col, e.items = b.host[f"slot_col{i}"].ctypes.data, b.host[f"items{i}"].ctypes.data
             if self.mode != "plan":
                 e.qpos_out, e.iters_out = b.out[f"qpos{i}"].data_ptr(), b.out[f"iters{i}"].data_ptr()
@@ -368,7 +381,7 @@ class IKCase(so.Case):
                 return lib.gmr_group_plan_order(g, st["inp"], prm, IK_PROBE, P(b.out["order"]), stream)
             return lib.gmr_group_ik_solve_ordered(g, st["inp"], prm, P(b.dev["launch_order"]), stream)
         eng = self.engines[0]
-        batch = (eng._h, P(b.dev["pos0"]), P(b.dev["quat0"]), _native.GMR_DTYPE_F32, eng.cm.nslot + 1, H(b.host["slot_col0"]), IK_FRAMES, H(b.host["items0"]),
+        batch = (eng._h, P(b.dev["pos0"]), P(b.dev["quat0"]), self.in_dtype, eng.cm.nslot + 1, H(b.host["slot_col0"]), IK_FRAMES, H(b.host["items0"]),
                  IK_ITEMS, prm, None)
         if self.mode == "plan":
             return lib.gmr_ik_plan_order(*batch, IK_PROBE, P(b.out["order"]), stream)
@@ -386,11 +399,16 @@ class MotionCase(so.Case):
     """kind: 'epilogue' | 'track' | 'report'; group: the gmr_group_* form.  Struct field names are the keys of the working sets."""
 
     struct_values = True
+    epilogue_flags = _native.MOTION_HEIGHT_ADJUST | _native.MOTION_ROOT_ORIGIN
 
-    def __init__(self, v, kind, group):
+    def __init__(self, v, kind, group, offs=None):
+        """offs: (true, decoy) tables of three clips other than KIN_OFFS (the guard-band tests' other lengths; not for 'track')."""
         super().__init__()
         from gmr_amd.schedule import track_plan
+        assert offs is None or kind != "track"
         self.kind, self.group = kind, group
+        self.offs = (KIN_OFFS, KIN_OFFS_DECOY) if offs is None else offs
+        n = self.n_frames = int(self.offs[0][-1])
         base = {"epilogue": "motion_epilogue", "track": "motion_track", "report": "clip_report"}[kind]
         self.entry = ("gmr_group_" if group else "gmr_") + base
         self.engines = _group().engines if group else [_engine()]
@@ -405,11 +423,11 @@ class MotionCase(so.Case):
         for i, eng in enumerate(self.engines):
             cm, nq, nb, nd = eng.cm, eng.nq, eng.nbody, eng.nq - 7
             nt = eng.info.ntask[0] + eng.info.ntask[1]
-            dev = {"qpos": (_qpos(cm, N_KIN, 300 + 10 * v + i), _qpos(cm, N_KIN, 305 + 10 * v + i))}
-            host = {"seq_offsets": (KIN_OFFS, KIN_OFFS_DECOY)}
+            dev = {"qpos": (_qpos(cm, n, 300 + 10 * v + i), _qpos(cm, n, 305 + 10 * v + i))}
+            host = {"seq_offsets": self.offs}
             if kind == "epilogue":
-                out = {"root_pos_out": ((N_KIN, 3), F64), "root_rot_out": ((N_KIN, 4), F64), "dof_pos_out": ((N_KIN, nd), F64),
-                       "local_body_pos_out": ((N_KIN, nb, 3), F32), "min_z_out": ((3,), F32)}
+                out = {"root_pos_out": ((n, 3), F64), "root_rot_out": ((n, 4), F64), "dof_pos_out": ((n, nd), F64),
+                       "local_body_pos_out": ((n, nb, 3), F32), "min_z_out": ((3,), F32)}
             elif kind == "track":
                 host["out_offsets"] = (self.out_offs, decoy_out)
                 host["ratio"] = (ratio, np.array([0.5, 0.7, 0.61]))
@@ -417,10 +435,10 @@ class MotionCase(so.Case):
                         "body_pos_w": (nb, 3), "body_quat_w": (nb, 4), "body_lin_vel_w": (nb, 3), "body_ang_vel_w": (nb, 3)}
                 out = {k + "_out": ((M,) + t, F32 if k.startswith("body_") else F64) for k, t in tail.items()}
             else:
-                pt, qt = _keypoints(cm, N_KIN, 310 + 10 * v + i)
-                pd, qd = _keypoints(cm, N_KIN, 315 + 10 * v + i)
+                pt, qt = _keypoints(cm, n, 310 + 10 * v + i)
+                pd, qd = _keypoints(cm, n, 315 + 10 * v + i)
                 g = _gen(320 + 10 * v + i)
-                its = tuple(torch.randint(1, 20, (N_KIN,), generator=g, device=DEV(), dtype=I64).to(I32) for _ in range(2))
+                its = tuple(torch.randint(1, 20, (n,), generator=g, device=DEV(), dtype=I64).to(I32) for _ in range(2))
                 dev.update(human_pos=(pt, pd), human_quat=(qt, qd), iters=its)
                 host["slot_col"] = _slot_cols(cm)
                 S = 3
@@ -448,9 +466,9 @@ class MotionCase(so.Case):
                 setattr(e, k, b.host[f"{k}{i}"].ctypes.data)
             for k in self.out_names:
                 setattr(e, k, b.out[f"{k}{i}"].data_ptr())
-            e.n_frames, e.n_seq = N_KIN, 3
+            e.n_frames, e.n_seq = self.n_frames, 3
             if self.kind == "epilogue":
-                e.flags, e.ground_offset = _native.MOTION_HEIGHT_ADJUST | _native.MOTION_ROOT_ORIGIN, 0.05 if decoy else 0.02
+                e.flags, e.ground_offset = self.epilogue_flags, 0.05 if decoy else 0.02
             elif self.kind == "track":
                 e.fps_out = TRACK_FPS_OUT
             else:
@@ -542,6 +560,17 @@ class SmplxBodyCase(so.Case):
         self.host_in["out_cols"] = (cols, rng.permutation(55)[:self.n_out].astype(np.int32))
         N = sum(self.LENS)
         self.out_spec = {"global_orient": ((N, 3), F64), "full_pose": ((N, 55, 3), F64), "joints": ((N, 55, 3), F64), "rest": ((3, 55, 3), F64)}
+
+    def written(self, b, name):
+        """Mask of the elements the call writes (None: all): of full_pose and joints only the named joints and their ancestors
+        (the header: "the other joints' entries of full_pose / joints are left as they are")."""
+        if name not in ("full_pose", "joints"):
+            return None
+        par, live = self.host_in["parents"][0], np.zeros(55, bool)
+        for j in self.host_in["out_cols"][0]:
+            while j >= 0 and not live[j]:
+                live[j], j = True, par[j]
+        return live[:, None]
 
     def new_struct(self):
         return (_native.SmplxBodyClip * 3)()
