@@ -545,7 +545,8 @@ int gmr_model_info_get(const gmr_model *m, gmr_model_info *out) {
 
 // Debug / test hook, host only (no device is touched, so it works on a machine without one; not part of gmr_amd.h): builds the model
 // of a blob as gmr_model_create does (model_plan.h) and reports which kernel instance a launch of it would take.
-// alter_field >= 0: first add alter_delta to that shape field (in GMR_IK_SHAPE_FIELDS order) of the host model.  launch flags as
+// alter_field >= 0: first add alter_delta to that shape field (in GMR_IK_SHAPE_FIELDS order) of the host model; the four indices behind the fields
+// (15 .. 18) add it to one word of table 1 that stage_tables_shared compares: tbody[0], tslot[0], acomp[0], comp_plan[0].x.  launch flags as
 // launch_ik sees them.  fields_out: NULL or room for 16 ints, receives the (altered) shape fields.  name_out receives the instance's
 // name ("generic" or the shape's).  Returns the shape's index, -1 for the generic instance, -2 on a blob that does not validate (its
 // header, or an array that does not lie inside it), -3 on one that does not plan.
@@ -561,6 +562,12 @@ int gmr_debug_ik_shape(const void *blob, size_t blob_bytes, int force_generic, i
 #define GMR_X(f, e) if (k++ == alter_field) (e) += alter_delta;
   GMR_IK_SHAPE_FIELDS(GMR_X)
 #undef GMR_X
+  // behind the fields: one equality of stage_tables_shared each, broken in table 1 (its first task's body and slot, the composite of
+  // its first active dof, the first word of its composite plan)
+  if (alter_field == k) d.tbody[GMR_MAX_TASKS] += alter_delta;
+  if (alter_field == k + 1) d.tslot[GMR_MAX_TASKS] += alter_delta;
+  if (alter_field == k + 2) d.acomp[64] += alter_delta;
+  if (alter_field == k + 3) d.comp_plan[4 * gmr::kMaxCompPass].x += (unsigned)alter_delta;
   k = 0;
 #define GMR_X(f, e) if (fields_out) fields_out[k++] = (e);
   GMR_IK_SHAPE_FIELDS(GMR_X)

@@ -93,6 +93,7 @@ struct IkShapeAny {
   GMR_IK_SHAPE_FIELDS(GMR_X)
 #undef GMR_X
   static constexpr int plain = -1;
+  static constexpr int stage_shared = -1;
 };
 // unitree_g1 with the smplx config (and whatever else packs to the same counts) in the plain batched call
 struct IkShapeG1Smplx {
@@ -101,6 +102,9 @@ struct IkShapeG1Smplx {
   // plain is compiled in: the host only sends plain launches here (api.hip, ik_launch_shape), and the target preparation -- the one
   // block whose contraction used to depend on the float64 / offset_to_ground / walk paths around it -- is pinned (target_prep_slot)
   static constexpr int plain = 1;
+  // the two task tables differ in their weights only (model_plan.h, stage_tables_shared): a property of the model beside the fields
+  // above, matched by ik_shape_matches.  The instance then reads the tables once per work item instead of once per stage.
+  static constexpr int stage_shared = 1;
 };
 
 // ---- forward kinematics in the KinematicsModel convention (fk_kernel.hip.h) ----

@@ -1240,6 +1240,34 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   const int a_body = m.abody[arow], a_kind = real_row ? m.akind[arow] : -1, a_qadr = m.aqadr[arow], a_lim = real_row ? m.alimited[arow] : 0;
   const bool is_slot = lane < nslot;
   const int s_col = Lk->slot_col[is_slot ? lane : 0], root_col = Lk->slot_col[root_slot];
+  // Shared stage tables (SH::stage_shared, model_plan.h stage_tables_shared): the two tables name the same bodies, slots and
+  // composites and have the same composite plan, so everything a stage reads of them is read here, once per work item (per slice),
+  // from table 0 -- beside the set-up loads above, whose wait it shares.  Only the weights differ: both tables' pairs are loaded,
+  // the stage reads sh_wp / sh_wr and the pairs change places at the end of every stage (two stages per frame, never skipped: back
+  // to table 0 at the top of every frame).  Every other instance reads its tables at the stage's entry, as before.
+  constexpr bool kStageShared = SQ && SH::stage_shared > 0;
+  constexpr bool kPrmAtTop = SQ && kPlain;  // the solve's launch parameters in one batch of scalar loads at its top (below)
+  int sh_body = 0, sh_slot = 0, sh_comp = 0;
+  double sh_wp = 0.0, sh_wr = 0.0, sh_wp_next = 0.0, sh_wr_next = 0.0;
+  unsigned sh_cadr[kCompRegs > 0 ? kCompRegs : 1][5] = {};
+  if constexpr (kStageShared) {
+    static_assert(SH::use0 == 1 && SH::use1 == 1 && SH::same_tasks == 1 && SH::ntask0 >= 1 && SH::ntask0 == SH::ntask1 && SH::ncpass0 == SH::ncpass1,
+                  "a shape with shared stage tables runs both stages of every frame on the same tasks");
+    const int tl0 = SH::ntask0 <= 16 ? lane >> 2 : lane;
+    const int trow0 = tl0 < SH::ntask0 ? tl0 : 0;
+    sh_body = m.tbody[trow0]; sh_slot = m.tslot[trow0];
+    sh_wp = m.twp[trow0]; sh_wr = m.twr[trow0];
+    sh_wp_next = m.twp[GMR_MAX_TASKS + trow0]; sh_wr_next = m.twr[GMR_MAX_TASKS + trow0];
+    sh_comp = m.acomp[arow];
+    const unsigned el16 = 16u * (lane & 15);
+#pragma unroll
+    for (int p = 0; p < kCompRegs; ++p) {
+      const uint4 e = p < SH::ncpass0 ? ld_plain(&m.comp_plan[4 * p + (lane >> 4)]) : uint4{0, 0, 0, 0};
+      sh_cadr[p][0] = (e.x & 0xffffu) + el16; sh_cadr[p][1] = (e.x >> 16) + el16;
+      sh_cadr[p][2] = (e.y & 0xffffu) + el16; sh_cadr[p][3] = (e.y >> 16) + el16;
+      sh_cadr[p][4] = e.z + el16;
+    }
+  }
 
   // structured QP: this lane's row in the 4 x 16 layout
   const int sq_g = SQ ? (int)m.sq_gdof[lane] : -1;
@@ -1470,9 +1498,10 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       const int tl = quad ? lane >> 2 : lane, ts = quad ? lane & 3 : 0;
       const bool is_task = tl < nt;
       const int trow = tab * GMR_MAX_TASKS + (is_task ? tl : 0);
-      const int t_body = m.tbody[trow], t_slot = m.tslot[trow];
-      const double t_wp = m.twp[trow], t_wr = m.twr[trow];
-      const int a_comp = m.acomp[tab * 64 + arow];
+      // (shared stage tables: the per-item copies, no load here)
+      const int t_body = kStageShared ? sh_body : m.tbody[trow], t_slot = kStageShared ? sh_slot : m.tslot[trow];
+      const double t_wp = kStageShared ? sh_wp : m.twp[trow], t_wr = kStageShared ? sh_wr : m.twr[trow];
+      const int a_comp = kStageShared ? sh_comp : m.acomp[tab * 64 + arow];
       // composite plan of this table: entry of quarter-wave lane >> 4 per pass = four source block offsets + destination
       // (LDS bytes); this lane moves the 16 bytes at el16 of each block.  The first kCompRegs passes are resolved to addresses here.
       const int np = shp2<SH::ncpass0, SH::ncpass1>(tab, m.ncpass[tab]);
@@ -1481,10 +1510,15 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       unsigned cadr[kCompRegs > 0 ? kCompRegs : 1][5];
 #pragma unroll
       for (int p = 0; p < kCompRegs; ++p) {
-        const uint4 e = p < np ? cplan_tab[4 * p] : uint4{0, 0, 0, 0};
-        cadr[p][0] = (e.x & 0xffffu) + el16; cadr[p][1] = (e.x >> 16) + el16;
-        cadr[p][2] = (e.y & 0xffffu) + el16; cadr[p][3] = (e.y >> 16) + el16;
-        cadr[p][4] = e.z + el16;
+        if constexpr (kStageShared) {
+#pragma unroll
+          for (int i = 0; i < 5; ++i) cadr[p][i] = sh_cadr[p][i];
+        } else {
+          const uint4 e = p < np ? cplan_tab[4 * p] : uint4{0, 0, 0, 0};
+          cadr[p][0] = (e.x & 0xffffu) + el16; cadr[p][1] = (e.x >> 16) + el16;
+          cadr[p][2] = (e.y & 0xffffu) + el16; cadr[p][3] = (e.y >> 16) + el16;
+          cadr[p][4] = e.z + el16;
+        }
       }
 
       // q has not moved since the FK that closed the previous solve (previous stage or previous frame): the poses in LDS
@@ -1525,6 +1559,17 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
         }
         const double diag = ik_args(Lk)->prm.damping + ik_args(Lk)->prm.lm_damping * sum_mu;
         const double lgain_generic = SQ ? 0.0 : ik_args(Lk)->prm.limit_gain;  // (read here, in uniform control flow)
+        // Plain shaped instances: the three parameters the rest of the solve reads -- limit_gain in front of the QP, tol and max_iter
+        // directly in front of the loop's closing branch -- are loaded here, with damping and lm_damping, and held in scalar registers
+        // (pinned: the loads must not sink back to their uses, where each waits for the scalar cache alone).  The static spill report
+        // does not grow for it (profiles/stage_shared_isa.txt); every other instance loads them where it uses them, as before.
+        double top_tol = 0.0, top_lgain = 0.0;
+        int top_max_iter = 0;
+        if constexpr (kPrmAtTop) {
+          IkLaunchK *Lt = ik_args(Lk);
+          top_tol = Lt->prm.tol; top_lgain = Lt->prm.limit_gain; top_max_iter = Lt->prm.max_iter;
+          asm volatile("" : "+s"(top_tol), "+s"(top_lgain), "+s"(top_max_iter));
+        }
         GMR_STAMP(3);
         // ---- screws S_i (world frame, about the origin) ----
         double Si[6] = {0, 0, 0, 0, 0, 0};
@@ -1670,7 +1715,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
           const double s_ci = sq_own ? c_in : 0.0;
           // mink ConfigurationLimit, evaluated by the lane that owns the dof in the QP layout: -gain (q - lower) <= dq <= gain (upper - q)
           const double qv = q[sq_qadr];
-          const double lgain = ik_args(Lk)->prm.limit_gain;
+          const double lgain = kPrmAtTop ? top_lgain : ik_args(Lk)->prm.limit_gain;
           double s_lo = fmax(-lgain * (qv - sq_rlo), -1e30), s_hi = fmin(lgain * (sq_rhi - qv), 1e30);
           if constexpr (kCap) { s_lo = fmax(s_lo, -sq_cap); s_hi = fmin(s_hi, sq_cap); }
           double xs;
@@ -1711,8 +1756,13 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
         GMR_STAMP(2);
         if (!first) ++num_iter;
         first = false;
-        if (!(curr - next > ik_args(Lk)->prm.tol && num_iter < ik_args(Lk)->prm.max_iter)) break;
+        if (!(curr - next > (kPrmAtTop ? top_tol : ik_args(Lk)->prm.tol) && num_iter < (kPrmAtTop ? top_max_iter : ik_args(Lk)->prm.max_iter))) break;
         curr = next;
+      }
+      if constexpr (kStageShared) {  // the next stage runs with the other table's weights
+        const double wp = sh_wp, wr = sh_wr;
+        sh_wp = sh_wp_next; sh_wr = sh_wr_next;
+        sh_wp_next = wp; sh_wr_next = wr;
       }
     }
     if constexpr (PROBE) cost_acc += solves;

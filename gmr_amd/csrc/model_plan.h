@@ -40,13 +40,30 @@ namespace gmr {
 // instance at compile time; a model that matches none runs the generic instance.  The structs are defined beside IkShapeAny.
 #define GMR_FOR_EACH_IK_SHAPE(X) X(IkShapeG1Smplx, 36)
 
-// Does the host copy of a model carry exactly the values the shape SH fixes?  (SH::plain is the launch's side: launch_ik.)
+// Do the two task tables of a model differ in their weights (twp, twr) only?  Both used on the same (body, slot) per task, the same
+// composite per active dof and the same composite plan, entry for entry: everything else a stage of ik_body reads of its table.
+inline bool stage_tables_shared(const DevModel &d) {
+  if (!d.use_table[0] || !d.use_table[1] || !d.same_tasks) return false;
+  if (d.ntask[0] != d.ntask[1] || d.ncpass[0] != d.ncpass[1]) return false;
+  for (int t = 0; t < d.ntask[0]; ++t)
+    if (d.tbody[t] != d.tbody[GMR_MAX_TASKS + t] || d.tslot[t] != d.tslot[GMR_MAX_TASKS + t]) return false;
+  for (int i = 0; i < d.n_act; ++i)
+    if (d.acomp[i] != d.acomp[64 + i]) return false;
+  for (int i = 0; i < 4 * d.ncpass[0]; ++i) {
+    const uint4 &a = d.comp_plan[i], &b = d.comp_plan[4 * kMaxCompPass + i];
+    if (a.x != b.x || a.y != b.y || a.z != b.z || a.w != b.w) return false;
+  }
+  return true;
+}
+
+// Does the host copy of a model carry exactly the values the shape SH fixes, and the properties it assumes?  (SH::plain is the
+// launch's side: launch_ik.)
 template <class SH>
 inline bool ik_shape_matches(const DevModel &d) {
 #define GMR_X(f, e) if (SH::f >= 0 && SH::f != (e)) return false;
   GMR_IK_SHAPE_FIELDS(GMR_X)
 #undef GMR_X
-  return true;
+  return SH::stage_shared <= 0 || stage_tables_shared(d);
 }
 // The shape (index into GMR_FOR_EACH_IK_SHAPE) of a model built for kernel variant nvp with the structured QP, or -1.
 inline int ik_shape_of(const DevModel &d, int nvp, bool sq) {
