@@ -31,7 +31,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
-           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock"]
+           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics"]
 
 
 class IKParams(C.Structure):
@@ -133,6 +133,23 @@ class FootlockInput(C.Structure):
         ("iterations", C.c_int32), ("reserved", C.c_int32), ("damping", C.c_double), ("step_cap", C.c_double),
         ("stream", C.c_void_p),
     ] + [(k + "_out", C.c_void_p) for k in FOOTLOCK_OUTPUTS]
+
+
+DYNAMICS_FRAME_OUTPUTS = ("tau", "root_wrench", "com", "zmp", "qvel", "qacc")   # gmr_dynamics_input's output pointers, in order:
+DYNAMICS_STATS = ("tau_abs_max", "tau_rms", "tau_ratio_max", "frames_over_limit", "frames_any_over_limit", "fz_ratio_max", "fz_ratio_min",
+                  "unloaded_frames", "nonfinite_frames")                         # per frame, then per clip
+DYNAMICS_OUTPUTS = DYNAMICS_FRAME_OUTPUTS + DYNAMICS_STATS
+DYNAMICS_TABLE = ("body_parent", "body_mass", "body_com", "body_inertia", "armature", "torque_limit")  # the inertial table's arrays
+
+
+class DynamicsInput(C.Structure):
+    """``gmr_dynamics_input`` (include/gmr_amd.h): the whole call of the inverse dynamics, its stream included."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("qvel", C.c_void_p), ("qacc", C.c_void_p),
+        ("n_seq", C.c_int32), ("nbody", C.c_int32), ("fps", C.c_double),
+        ("gravity_x", C.c_double), ("gravity_y", C.c_double), ("gravity_z", C.c_double), ("ground_z", C.c_double), ("fz_min", C.c_double),
+    ] + [(k, C.c_void_p) for k in DYNAMICS_TABLE] + [("stream", C.c_void_p)] + [(k + "_out", C.c_void_p) for k in DYNAMICS_OUTPUTS]
 
 
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
@@ -259,6 +276,8 @@ def load():
     L.gmr_motion_contacts.argtypes = [vp, C.POINTER(ContactInput)]
     L.gmr_motion_footlock.restype = C.c_int
     L.gmr_motion_footlock.argtypes = [vp, C.POINTER(FootlockInput)]
+    L.gmr_motion_dynamics.restype = C.c_int
+    L.gmr_motion_dynamics.argtypes = [vp, C.POINTER(DynamicsInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

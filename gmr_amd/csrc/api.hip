@@ -33,6 +33,7 @@
 #include "sample_kernel.hip.h"
 #include "report_kernel.hip.h"
 #include "contact_kernel.hip.h"
+#include "dynamics_kernel.hip.h"
 #include "footlock_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
@@ -1703,6 +1704,71 @@ int gmr_motion_footlock(gmr_model *m, const gmr_footlock_input *in) {
   if (!in->qpos || !in->seq_offsets || !in->contact || !in->qpos_out || !in->pos_out || !in->shift_out) { set_err(m, "null argument"); return GMR_EINVAL; }
   if ((int64_t)gmr::motion_qpitch(m->fk.ndof + 7) * gmr::kFkWave * 8 > 64 * 1024) { set_err(m, "the row tile needs more than 64 KiB of LDS"); return GMR_EUNSUPPORTED; }
   return footlock_run(m, *in, a, lds_doubles, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ inverse dynamics (dynamics_kernel.hip.h)
+// The two launches of gmr_motion_dynamics, and nothing else: no allocation, no copy, no synchronisation.  Every array is a device
+// array and everything else travels in the kernels' argument.
+static int dynamics_run(gmr_model *m, const gmr_dynamics_input &in, bool stats, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::DynamicsArgs a{};
+  a.dm = m->dm_eval_dev;
+  a.qpos = in.qpos; a.qvel = in.qvel; a.qacc = in.qacc; a.seq_offsets = in.seq_offsets; a.n_frames = in.n_frames;
+  a.n_seq = in.n_seq; a.nbody = m->fk.nbody; a.nq = m->fk.ndof + 7; a.nh = m->fk.ndof;
+  a.dt = 1.0 / in.fps; a.gx = in.gravity_x; a.gy = in.gravity_y; a.gz = in.gravity_z;
+  a.gnorm = std::sqrt(in.gravity_x * in.gravity_x + in.gravity_y * in.gravity_y + in.gravity_z * in.gravity_z);
+  a.ground_z = in.ground_z; a.fz_min = in.fz_min;
+  a.parent = in.body_parent; a.mass = in.body_mass; a.com = in.body_com; a.inertia = in.body_inertia;
+  a.armature = in.armature; a.limit = in.torque_limit;
+  a.tau = in.tau_out; a.wrench = in.root_wrench_out; a.comw = in.com_out; a.zmp = in.zmp_out;
+  a.qvel_out = in.qvel_out; a.qacc_out = in.qacc_out;
+  a.tau_abs_max = in.tau_abs_max_out; a.tau_rms = in.tau_rms_out; a.tau_ratio_max = in.tau_ratio_max_out;
+  a.frames_over = in.frames_over_limit_out; a.any_over = in.frames_any_over_limit_out;
+  a.fz_max = in.fz_ratio_max_out; a.fz_min_out = in.fz_ratio_min_out;
+  a.unloaded = in.unloaded_frames_out; a.nonfinite = in.nonfinite_frames_out;
+  // Wavefronts per clip: enough for about kDynTargetWaves in the whole launch (four rounds of a 256-CU device at two wavefronts per
+  // SIMD), at most one per frame slot of the mean clip.  A wavefront strides over its clip's slots, so its per-launch set-up (depth,
+  // subtree end, the body's constants) is paid once for many frames: 2 048 clips x 3 000 frames run 4 wavefronts of 750 frames each.
+  const int groups = gmr::chain_geom(a.nbody).groups;
+  const int64_t slots = (in.n_frames + groups - 1) / groups, mean = (slots + in.n_seq - 1) / in.n_seq;
+  const int64_t want = (gmr::kDynTargetWaves + in.n_seq - 1) / in.n_seq;
+  const unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean), 65535));
+  hipLaunchKernelGGL(gmr::motion_dynamics_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
+  if (stats) hipLaunchKernelGGL(gmr::motion_dynamics_stats_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_dynamics(gmr_model *m, const gmr_dynamics_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (!std::isfinite(in->fps) || !(in->fps > 0.0)) { set_err(m, "fps must be finite and > 0"); return GMR_EINVAL; }
+  if (!std::isfinite(in->gravity_x) || !std::isfinite(in->gravity_y) || !std::isfinite(in->gravity_z) || !std::isfinite(in->ground_z)) {
+    set_err(m, "gravity and ground_z must be finite"); return GMR_EINVAL;
+  }
+  if (in->gravity_x == 0.0 && in->gravity_y == 0.0 && in->gravity_z == 0.0) { set_err(m, "gravity must not be zero"); return GMR_EINVAL; }
+  if (!std::isfinite(in->fz_min) || in->fz_min < 0.0) { set_err(m, "fz_min must be finite and >= 0"); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "inverse dynamics needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int nb = m->h.nbody;
+  if (in->nbody != nb) { set_err(m, "the inertial table holds %d bodies, the model %d", in->nbody, nb); return GMR_EUNSUPPORTED; }
+  if (nb > gmr::kFkWave || gmr::kDynLdsBytes > 160 * 1024) { set_err(m, "a model of %d bodies does not fit the dynamics tile", nb); return GMR_EUNSUPPORTED; }
+  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
+  for (int b = 1; b < nb; ++b) {   // depth-first order: the parent of b is b - 1 or one of its ancestors
+    int j = b - 1;
+    while (j >= 0 && j != parent[b]) j = parent[j];
+    if (j < 0) { set_err(m, "body %d does not follow its parent's subtree: the bodies are not in depth-first order", b); return GMR_EUNSUPPORTED; }
+  }
+  const bool stats = in->tau_abs_max_out || in->tau_rms_out || in->tau_ratio_max_out || in->frames_over_limit_out ||
+                     in->frames_any_over_limit_out || in->fz_ratio_max_out || in->fz_ratio_min_out || in->unloaded_frames_out ||
+                     in->nonfinite_frames_out;
+  if (stats && (!in->tau_out || !in->root_wrench_out)) { set_err(m, "the statistics are reduced from tau_out and root_wrench_out: both are required"); return GMR_EINVAL; }
+  if (in->n_frames == 0 || in->n_seq == 0) return GMR_OK;
+  if (!in->qpos || !in->seq_offsets || !in->body_parent || !in->body_mass || !in->body_com || !in->body_inertia || !in->armature || !in->torque_limit) {
+    set_err(m, "null argument"); return GMR_EINVAL;
+  }
+  return dynamics_run(m, *in, stats, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

@@ -83,7 +83,7 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                    height_adjust: bool = True, root_origin_offset: bool = True, chunk: int = 0, burn_in: int = 0,
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
                    track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
-                   contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False):
+                   contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False, dynamics: bool = False):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -93,7 +93,8 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     With ``lowpass_hz`` the solved qpos is smoothed once (``smooth_qpos`` at ``fps``), and the motions, the report and the tracks
     are all made from the smoothed qpos.  ``contact_bodies`` / ``contact`` (with ``track_fps``): ``tracking_from_qpos``'s contact
     labels on the tracking dicts; ``lock_feet``: ``tracking_from_qpos``'s foot locking of those bodies (the tracking dicts only: the
-    motions and the report are made from the qpos as solved)."""
+    motions and the report are made from the qpos as solved).  With ``dynamics`` the ``dynamics_report`` of the same qpos follows
+    the clip report (or the motions, without ``report``) and precedes the tracks."""
     if contact_bodies is not None and track_fps is None:
         raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
     if lock_feet and contact_bodies is None:
@@ -114,6 +115,8 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
             qpos = smooth_qpos(gmr, qpos, seq_offsets, fps, lowpass_hz)
         rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
         res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset), rep.numpy())
+    if dynamics:
+        res += (dynamics_report(gmr, qpos, seq_offsets, fps),)
     if track_fps is not None:
         lock_kw = {"lock_feet": lock_feet} if lock_feet else {}  # (absent without the flag: nothing changes then)
         res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps, contact_bodies=contact_bodies, contact=contact, **lock_kw),)
@@ -367,6 +370,86 @@ def _smooth_qpos(eng, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, lowpa
         else:
             res.index_copy_(0, rows, sm)
     return res
+
+
+# ------------------------------------------------------------------ inverse dynamics
+DYNAMICS_CSV_FIELDS = ("frames_any_over_limit", "fz_ratio_max", "fz_ratio_min", "unloaded_frames", "nonfinite_frames")
+
+
+def dynamics_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, lowpass_hz: float = 0.0,
+                       table=None, **dynamics_kwargs) -> List[Dict]:
+    """Inverse dynamics of qpos ``[N, nq]`` float64 on the GPU (concatenated clips at the one rate ``fps``) -> one dict of host
+    arrays per clip: ``tau`` ``[T, nh]``, ``root_wrench`` ``[T, 6]``, ``com`` ``[T, 3]``, ``zmp`` ``[T, 2]``, ``qvel`` / ``qacc``
+    ``[T, nv]``, the clip's row of every statistic of ``Engine.motion_dynamics``, and ``joint_names``, ``torque_limit``, ``fps``
+    (the definition is the contract above ``gmr_dynamics_input`` in include/gmr_amd.h).  Velocities and accelerations are central
+    and second differences of qpos.  Second differences of unfiltered IK output are noisy -- the torques of a raw clip are
+    dominated by frame-to-frame jitter of the solve -- so ``lowpass_hz > 0`` routes qpos through ``smooth_qpos`` first; the default
+    0 leaves qpos as it is and the choice to the caller.  ``dynamics_kwargs``: ``gravity``, ``ground_z``, ``fz_min`` (a
+    convention, not measured on any robot)."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("inverse dynamics assumes a free-joint root; a planar-base robot is not supported")
+    eng = gmr._engine
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    if lowpass_hz:
+        qpos = _smooth_qpos(eng, qpos, offs, fps, lowpass_hz)
+    got = eng.motion_dynamics(qpos, offs, float(fps), table=table, **dynamics_kwargs)
+    host = {k: v.cpu().numpy() for k, v in got.items()}
+    names = [gmr.model.jnt_names[b] for b in gmr.model.hinge_bodies()]
+    limit = eng.inertial_device(table)["torque_limit"].cpu().numpy()
+    out = []
+    for s in range(offs.size - 1):
+        a, b = int(offs[s]), int(offs[s + 1])
+        d = {k: host[k][a:b] for k in ("tau", "root_wrench", "com", "zmp", "qvel", "qacc")}
+        d.update((k, host[k][s]) for k in got.stats)
+        d.update(joint_names=names, torque_limit=limit, fps=float(fps))
+        out.append(d)
+    return out
+
+
+def dynamics_report(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, lowpass_hz: float = 0.0,
+                    table=None, **dynamics_kwargs) -> Dict:
+    """The per-clip statistics of ``dynamics_from_qpos`` alone, as host arrays with one row per clip, plus ``joint_names`` and
+    ``torque_limit``: ``tau_abs_max``, ``tau_rms``, ``tau_ratio_max``, ``frames_over_limit`` ``[S, nh]``; ``frames_any_over_limit``,
+    ``fz_ratio_max``, ``fz_ratio_min``, ``unloaded_frames``, ``nonfinite_frames`` ``[S]``."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("inverse dynamics assumes a free-joint root; a planar-base robot is not supported")
+    return _dynamics_report(gmr._engine, qpos, seq_offsets, fps, lowpass_hz, table, dynamics_kwargs)
+
+
+def _dynamics_report(eng, qpos, seq_offsets, fps, lowpass_hz=0.0, table=None, dynamics_kwargs=None) -> Dict:
+    """``dynamics_report`` on an ``Engine`` (a free-joint model)."""
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    if lowpass_hz:
+        qpos = _smooth_qpos(eng, qpos, offs, fps, lowpass_hz)
+    got = eng.motion_dynamics(qpos, offs, float(fps), table=table, **(dynamics_kwargs or {}))
+    rep = {k: v.cpu().numpy() for k, v in got.stats.items()}
+    model = eng.cm.robot
+    rep["joint_names"] = [model.jnt_names[b] for b in model.hinge_bodies()]
+    rep["torque_limit"] = eng.inertial_device(table)["torque_limit"].cpu().numpy()
+    return rep
+
+
+def write_dynamics_csv(path: str, names: Sequence[str], report: Dict, append: bool = False) -> None:
+    """One row per clip of a ``dynamics_report``: the per-clip fields, then the worst joint -- the hinge with the largest
+    ``tau_ratio_max``, or with the largest ``tau_abs_max`` where no hinge has a limit -- its name, its ratio and its peak torque."""
+    import csv
+    ratio, peak = np.asarray(report["tau_ratio_max"]), np.asarray(report["tau_abs_max"])
+    if len(names) != ratio.shape[0]:
+        raise ValueError("one name per clip is required")
+    with open(path, "a" if append else "w", newline="") as f:
+        w = csv.writer(f)
+        if not append:
+            w.writerow(("clip",) + DYNAMICS_CSV_FIELDS + ("worst_joint", "worst_ratio", "worst_tau_abs_max"))
+        for s, n in enumerate(names):
+            j = int(np.argmax(ratio[s])) if ratio.shape[1] and ratio[s].max() > 0.0 else (int(np.argmax(peak[s])) if peak.shape[1] else -1)
+            w.writerow([n] + [repr(report[k][s].item()) for k in DYNAMICS_CSV_FIELDS]
+                       + ([report["joint_names"][j], repr(float(ratio[s, j])), repr(float(peak[s, j]))] if j >= 0 else ["", "0.0", "0.0"]))
+
+
+def dynamics_hard_mask(report: Dict, max_torque_ratio: float) -> np.ndarray:
+    """Clips in which some hinge needs more than ``max_torque_ratio`` times its torque limit."""
+    r = np.asarray(report["tau_ratio_max"])
+    return (r.max(axis=1) > float(max_torque_ratio)) if r.shape[1] else np.zeros(r.shape[0], dtype=bool)
 
 
 # ------------------------------------------------------------------ the motion library

@@ -6,6 +6,7 @@ PyTorch is plumbing here: device buffers, the current HIP stream, and (elsewhere
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import Optional
 
 import numpy as np
@@ -443,6 +444,83 @@ def _footlock_input(eng: "Engine", qpos, seq_offsets, contact, body_ids, blend_f
     return fi, MotionFootlock(res), [qpos, offs, contact, ids]
 
 
+DYNAMICS_FIELDS = _native.DYNAMICS_OUTPUTS   # the arrays of the inverse dynamics, in gmr_dynamics_input's order
+DYNAMICS_STATS = _native.DYNAMICS_STATS     # of them the per-clip statistics
+# Parameters of the inverse dynamics when none are given.  fz_min -- a frame whose ground reaction is below 5 % of the robot's weight
+# counts as unloaded and gets no ZMP -- is a convention, not measured on any robot.
+DYNAMICS_DEFAULTS = {"gravity": (0.0, 0.0, -9.81), "ground_z": 0.0, "fz_min": 0.05}
+
+
+class MotionDynamics(dict):
+    """Result of ``motion_dynamics``: the device tensors by name (``DYNAMICS_FIELDS``).  Per frame, float64: ``tau`` ``[N, nq - 7]``
+    (N m, hinges in qpos order), ``root_wrench`` ``[N, 6]`` (the force and the moment about the root's position the contacts must
+    supply, world frame), ``com`` ``[N, 3]``, ``zmp`` ``[N, 2]`` (NaN in an unloaded frame), ``qvel`` / ``qacc`` ``[N, nv]`` (what was
+    used; the root's angular part in the world frame).  Per clip (``DYNAMICS_STATS``): ``tau_abs_max``, ``tau_rms``,
+    ``tau_ratio_max`` float64 and ``frames_over_limit`` int32 ``[S, nq - 7]``; ``frames_any_over_limit``, ``unloaded_frames``,
+    ``nonfinite_frames`` int32 and ``fz_ratio_max``, ``fz_ratio_min`` float64 ``[S]``."""
+
+    @property
+    def stats(self):
+        return {k: self[k] for k in DYNAMICS_STATS if k in self}
+
+
+def _dynamics_input(eng: "Engine", qpos, seq_offsets, fps, qvel, qacc, gravity, ground_z, fz_min, table, out):
+    """Check the arguments of one inverse-dynamics call and fill its ``DynamicsInput`` (all but the stream).  Returns (input,
+    MotionDynamics, keep-alive)."""
+    dev = eng.device
+    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or int(qpos.shape[1]) != eng.nq or not qpos.is_contiguous():
+        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
+    N, nv, nh = int(qpos.shape[0]), eng.nq - 1, eng.nq - 7
+    for name, t in (("qvel", qvel), ("qacc", qacc)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != (N, nv)
+                              or not t.is_contiguous()):
+            raise EngineError(f"{name} must be a contiguous float64 [{N}, {nv}] tensor on the engine's device (or None)")
+    if isinstance(seq_offsets, torch.Tensor):
+        offs = seq_offsets
+        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
+            raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
+    else:
+        o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+        if o.ndim != 1 or o.size < 1:
+            raise ValueError("seq_offsets must hold n_seq + 1 entries")
+        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    S = int(offs.shape[0]) - 1
+    g = np.asarray(gravity, dtype=np.float64)
+    if g.shape != (3,) or not np.all(np.isfinite(g)) or not np.any(g != 0.0):
+        raise ValueError("gravity must hold three finite numbers, not all zero")
+    if not (np.isfinite(fps) and fps > 0.0 and np.isfinite(ground_z) and np.isfinite(fz_min) and fz_min >= 0.0):
+        raise ValueError("fps > 0, a finite ground_z and fz_min >= 0 are required")
+    dev_table = eng.inertial_device(table)
+    f64, i32 = torch.float64, torch.int32
+    shapes = {"tau": ((N, nh), f64), "root_wrench": ((N, 6), f64), "com": ((N, 3), f64), "zmp": ((N, 2), f64), "qvel": ((N, nv), f64),
+              "qacc": ((N, nv), f64), "tau_abs_max": ((S, nh), f64), "tau_rms": ((S, nh), f64), "tau_ratio_max": ((S, nh), f64),
+              "frames_over_limit": ((S, nh), i32), "frames_any_over_limit": ((S,), i32), "fz_ratio_max": ((S,), f64),
+              "fz_ratio_min": ((S,), f64), "unloaded_frames": ((S,), i32), "nonfinite_frames": ((S,), i32)}
+    if out is None:
+        # rows outside every clip are not written, and a call without rows launches nothing: zeros
+        res = {k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}
+    else:
+        res = {k: out[k] for k in DYNAMICS_FIELDS if k in out}
+        if set(out) - set(DYNAMICS_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                                  or t.device != dev or not t.is_contiguous() for k, t in res.items()):
+            raise EngineError("out must map names of DYNAMICS_FIELDS to contiguous tensors of the call's shapes on the engine's device")
+        if set(res) & set(DYNAMICS_STATS) and not {"tau", "root_wrench"} <= set(res):
+            raise EngineError("out must hold tau and root_wrench when it holds a statistic: the statistics are reduced from them")
+    di = _native.DynamicsInput()
+    di.qpos, di.n_frames, di.seq_offsets, di.n_seq = qpos.data_ptr(), N, offs.data_ptr(), S
+    di.qvel = qvel.data_ptr() if qvel is not None else None
+    di.qacc = qacc.data_ptr() if qacc is not None else None
+    di.nbody, di.fps = int(dev_table["body_mass"].shape[0]), float(fps)
+    di.gravity_x, di.gravity_y, di.gravity_z = float(g[0]), float(g[1]), float(g[2])
+    di.ground_z, di.fz_min = float(ground_z), float(fz_min)
+    for k in _native.DYNAMICS_TABLE:
+        setattr(di, k, dev_table[k].data_ptr())
+    for k, t in res.items():
+        setattr(di, k + "_out", t.data_ptr())
+    return di, MotionDynamics(res), [qpos, offs, qvel, qacc, dev_table]
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -592,6 +670,7 @@ class Engine:
         self._lib.gmr_model_info_get(self._h, C.byref(info))
         self.info = info
         self.nq, self.nv, self.nbody = info.nq, info.nv, info.nbody
+        self._inertial_dev = {}   # inertial tables on the device (inertial_device): None -> the robot's own, id(table) -> an explicit one
         if getattr(cm, "step_cap", None) is not None:  # the model's velocity limit (model.step_cap): part of the handle from here on
             self.set_step_cap(cm.step_cap)
 
@@ -1071,6 +1150,48 @@ class Engine:
         fi, res, keep = _footlock_input(self, qpos, seq_offsets, contact, body_ids, blend_frames, min_run, iterations, damping, step_cap, out)
         fi.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self._lib.gmr_motion_footlock(self._h, C.byref(fi)), "gmr_motion_footlock")
+        return res
+
+    def inertial_device(self, table=None):
+        """The inertial table on the engine's device, by the field names of ``gmr_dynamics_input``: uploaded once per engine (or
+        once per explicit ``table``, a :class:`gmr_amd.inertial.InertialTable`) and cached.  ``table=None`` reads the robot's own
+        MJCF file (``gmr_amd.inertial.inertial_table``)."""
+        cache = self._inertial_dev
+        key = id(table) if table is not None else None
+        if key not in cache:
+            from .inertial import inertial_table
+            t = table if table is not None else inertial_table(self.cm.robot)
+            nh = self.nq - 7
+            if t.nbody != self.nbody or t.armature.shape != (nh,) or t.torque_limit.shape != (nh,):
+                raise EngineError(f"the inertial table holds {t.nbody} bodies and {t.armature.shape[0]} hinges, the model {self.nbody} and {nh}")
+            I = t.inertia
+            host = {"body_parent": np.ascontiguousarray(t.parent, dtype=np.int32), "body_mass": np.ascontiguousarray(t.mass, dtype=np.float64),
+                    "body_com": np.ascontiguousarray(t.com, dtype=np.float64),
+                    "body_inertia": np.ascontiguousarray(np.stack([I[:, 0, 0], I[:, 1, 1], I[:, 2, 2], I[:, 0, 1], I[:, 0, 2], I[:, 1, 2]], -1)),
+                    "armature": np.ascontiguousarray(t.armature, dtype=np.float64), "torque_limit": np.ascontiguousarray(t.torque_limit, dtype=np.float64)}
+            cache[key] = ({k: torch.from_numpy(v).to(self.device) for k, v in host.items()},)
+            if table is not None:   # an explicit table's upload lives as long as the table does: its id is the key
+                weakref.finalize(table, cache.pop, key, None)
+        return cache[key][0]
+
+    def motion_dynamics(self, qpos: torch.Tensor, seq_offsets, fps: float, qvel: Optional[torch.Tensor] = None,
+                        qacc: Optional[torch.Tensor] = None, gravity=DYNAMICS_DEFAULTS["gravity"], ground_z: float = DYNAMICS_DEFAULTS["ground_z"],
+                        fz_min: float = DYNAMICS_DEFAULTS["fz_min"], out=None, table=None) -> MotionDynamics:
+        """Floating-base inverse dynamics of qpos ``[N, nq]`` float64 (engine layout, concatenated clips) in two kernels
+        (``gmr_motion_dynamics``; the definition is the contract in include/gmr_amd.h): joint torques, the wrench the contacts must
+        supply on the root, centre of mass and ZMP per frame, torque-limit and ground-reaction statistics per clip.
+        ``seq_offsets`` ``[S + 1]``: the clips' rows, a host sequence (uploaded once) or a device int64 tensor.  ``fps``: the one
+        frame rate of the call.  ``qvel`` / ``qacc`` ``[N, nv]``: generalized velocity and acceleration with the root's angular
+        part in the WORLD frame (what ``motion_track`` writes as ``root_ang_vel``, not MuJoCo's local-frame convention); ``None``:
+        the tracking export's central differences, and second differences, of qpos.  ``fz_min`` (a fraction of the robot's
+        weight below which a frame is unloaded and has no ZMP) is a convention, not measured on any robot.  ``table``: an
+        :class:`gmr_amd.inertial.InertialTable` instead of the one read from the robot's MJCF file.  Returns a
+        :class:`MotionDynamics` of device tensors; ``out``: caller-owned result tensors by name (a name left out is not computed;
+        a statistic needs ``tau`` and ``root_wrench``).  A planar base is refused (``GMR_EUNSUPPORTED``).  Asynchronous on the current
+        stream; with ``out`` and a device ``seq_offsets`` no allocation, no copy, no synchronisation."""
+        di, res, keep = _dynamics_input(self, qpos, seq_offsets, fps, qvel, qacc, gravity, ground_z, fz_min, table, out)
+        di.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.gmr_motion_dynamics(self._h, C.byref(di)), "gmr_motion_dynamics")
         return res
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,

@@ -3,8 +3,8 @@
 Reads only what the retarget hot path needs from a MuJoCo XML model: the body
 tree (``pos``/``quat``), hinge ``axis``/``range``/``limited``, the free root
 joint (or the planar base of galaxea_r1pro: slide x, slide y, hinge z on the root body), ``<include>``,
-``<compiler angle=... autolimits=...>`` and default-class inheritance for joint attributes.  Inertials, geoms, meshes, actuators,
-sensors and keyframes are ignored.
+``<compiler angle=... autolimits=...>`` and default-class inheritance for joint attributes.  Geoms, meshes, sensors and keyframes are ignored
+(SURVEY.md section 2 row 10, Appendix B); inertials and actuator limits are read by ``gmr_amd.inertial``, not here.
 
 It replaces two reference loaders at once:
 
@@ -81,6 +81,8 @@ class RobotModel:
     # translate to MuJoCo's ``[x, y, yaw, hinges]``.
     root_dofs: int = ROOT_DOFS_FREE
     root_jnt_names: Optional[List[str]] = None
+    # Where the MJCF file lies when the model was read from one: gmr_amd.inertial reads masses, inertias and actuator limits from it.
+    xml_path: Optional[str] = dataclasses.field(default=None, compare=False, repr=False)
 
     # ------------------------------------------------------------------
     @property
@@ -406,7 +408,9 @@ def load_mjcf(path: str, name: Optional[str] = None) -> RobotModel:
             add_body(child, idx, childclass)
 
     add_body(robot_roots[0], -1, None)
-    return _assemble(name or root.attrib.get("model", os.path.basename(path)), os.path.basename(path), recs, timestep, angle_unit)
+    robot = _assemble(name or root.attrib.get("model", os.path.basename(path)), os.path.basename(path), recs, timestep, angle_unit)
+    robot.xml_path = os.path.abspath(path)
+    return robot
 
 
 def _assemble(name: str, source: str, recs: List[_BodyRec], timestep: float, angle_unit: str) -> RobotModel:

@@ -422,6 +422,13 @@ class GeneralMotionRetargeting:
         return self._engine.clip_report(tq, offs, tpos, tquat, cols, height_scale=hs, iters=it, offset_to_ground=offset_to_ground,
                                         limit_eps=CLIP_REPORT_LIMIT_EPS if limit_eps is None else limit_eps, segment_frames=segment_frames)
 
+    def dynamics_report(self, qpos, seq_offsets, fps, lowpass_hz: float = 0.0, **dynamics_kwargs):
+        """Per-clip torque-limit and ground-reaction statistics of retargeted qpos ``[N, nq]`` (numpy or CUDA torch, engine layout,
+        concatenated clips at the one rate ``fps``), reduced on the GPU (``dataset.dynamics_report``, ``Engine.motion_dynamics``)."""
+        from .dataset import dynamics_report
+        tq = (torch.from_numpy(np.ascontiguousarray(qpos)) if isinstance(qpos, np.ndarray) else qpos).to(self.device, torch.float64).contiguous()
+        return dynamics_report(self, tq, seq_offsets, fps, lowpass_hz, **dynamics_kwargs)
+
     def fk_batch(self, root_pos, root_rot_xyzw, dof_pos, want_rot: bool = False):
         """Batched FK in the ``KinematicsModel.forward_kinematics`` convention (float32, xyzw; kinematics_model.py:213-246) on this
         object's robot: ``root_pos [T,3]``, ``root_rot_xyzw [T,4]``, ``dof_pos [T,ndof]`` -> ``body_pos [T,nbody,3]`` (and

@@ -5,6 +5,8 @@ import os
 import re
 from typing import Callable, List, Sequence, Tuple
 
+import numpy as np
+
 
 def natural_key(name: str):
     """natsort's default order for plain file names (scripts/smplx_to_robot_dataset.py:207 sorts with natsorted): digit runs compare as numbers."""
@@ -97,6 +99,8 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--report_csv", default=None, type=str, help="write the per-clip quality report (stage and task errors, joint-limit and step statistics; one row per clip) to this CSV; with --robots one file per robot, <stem>.<robot><ext>; under --shard_by_rank one per rank, <stem>[.<robot>].rank<k><ext>")
     ap.add_argument("--hard_out", default=None, type=str, help="write the clips that exceed --max_pos_err / --max_dof_step as a hard-motion list (the format --hard_motions reads); with --robots one file per robot, under --shard_by_rank one per rank (named like --report_csv)")
     ap.add_argument("--max_pos_err", default=None, type=float, help="metres: a clip whose largest task position error exceeds this is not written and is listed in --hard_out")
+    ap.add_argument("--dynamics_csv", default=None, type=str, help="write the per-clip inverse-dynamics statistics (frames over a torque limit, ground-reaction ratios, unloaded and non-finite frames, the worst joint and its torque ratio; one row per clip) to this CSV, named like --report_csv; needs the robot's MJCF file (GMR_ROOT) for masses and torque limits")
+    ap.add_argument("--max_torque_ratio", default=None, type=float, help="a clip in which some joint needs more than this many times its torque limit is not written and is listed in --hard_out (with the clip report's difficulty: this flag computes the clip report too; --dynamics_csv alone does not)")
     ap.add_argument("--max_dof_step", default=None, type=float, help="radians: a clip whose largest joint step between consecutive frames exceeds this is not written and is listed in --hard_out")
     ap.add_argument("--track_fps", default=None, type=float, help="with --track_folder: also write every clip's tracking export (resampled root, joints and world body poses with their velocities, dataset.tracking_from_qpos) at this rate")
     ap.add_argument("--track_folder", default=None, type=str, help="with --track_fps: where the tracking exports go, <track_folder>/<relative path>.npz (with --robots <track_folder>/<robot>/...); the pickles are unchanged")
@@ -171,8 +175,18 @@ def track_path(args, target: str) -> str:
 
 
 def wants_report(args) -> bool:
-    """Whether any of the report flags is given: only then is the clip report computed at all."""
-    return any(getattr(args, k, None) is not None for k in ("report_csv", "hard_out", "max_pos_err", "max_dof_step"))
+    """Whether the clip report is needed: one of its own flags is given, or ``--max_torque_ratio``, whose clips go to the hard list
+    with the clip report's difficulty.  ``--dynamics_csv`` alone does not compute it."""
+    return any(getattr(args, k, None) is not None for k in ("report_csv", "hard_out", "max_pos_err", "max_dof_step", "max_torque_ratio"))
+
+
+def wants_dynamics(args) -> bool:
+    """Whether the inverse-dynamics statistics are asked for."""
+    return any(getattr(args, k, None) is not None for k in ("dynamics_csv", "max_torque_ratio"))
+
+
+def wants_sink(args) -> bool:
+    return wants_report(args) or wants_dynamics(args)
 
 
 def report_path(path: str, robot=None, rank=None) -> str:
@@ -190,15 +204,21 @@ class ReportSink:
         self.args = args
         self.csv = report_path(args.report_csv, robot, rank) if args.report_csv else None
         self.hard = report_path(args.hard_out, robot, rank) if args.hard_out else None
+        self.dyn_csv = report_path(args.dynamics_csv, robot, rank) if getattr(args, "dynamics_csv", None) else None
         self.withheld, self._started = 0, False
 
-    def take(self, dataset, targets: Sequence[str], motions: list, report):
-        """One batch: returns the (motions, targets) that are to be written."""
+    def take(self, dataset, targets: Sequence[str], motions: list, report, dynamics=None):
+        """One batch: returns the (motions, targets) that are to be written.  ``dynamics``: the batch's ``dynamics_report``."""
         names = [os.path.splitext(os.path.basename(t))[0] for t in targets]
-        mask = dataset.report_hard_mask(report, self.args.max_pos_err, self.args.max_dof_step)
-        if self.csv:
+        mask = dataset.report_hard_mask(report, self.args.max_pos_err, self.args.max_dof_step) if report is not None else np.zeros(len(names), dtype=bool)
+        if dynamics is not None:
+            if getattr(self.args, "max_torque_ratio", None) is not None:
+                mask |= dataset.dynamics_hard_mask(dynamics, self.args.max_torque_ratio)
+            if self.dyn_csv:
+                dataset.write_dynamics_csv(self.dyn_csv, names, dynamics, append=self._started)
+        if self.csv and report is not None:
             dataset.write_report_csv(self.csv, names, report, append=self._started)
-        if self.hard:
+        if self.hard and report is not None:
             dataset.write_hard_list(self.hard, names, report, mask, append=self._started)
         self._started = True
         self.withheld += int(mask.sum())
@@ -206,7 +226,7 @@ class ReportSink:
 
     def close(self):
         if self.withheld:
-            print(f"{self.withheld} clips withheld (--max_pos_err / --max_dof_step)" + (f", listed in {self.hard}" if self.hard else ""))
+            print(f"{self.withheld} clips withheld (--max_pos_err / --max_dof_step / --max_torque_ratio)" + (f", listed in {self.hard}" if self.hard else ""))
 
 
 def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callable, retarget_kw: Callable, workers: int, done: str) -> int:
@@ -227,12 +247,14 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         from .. import GeneralMotionRetargeting as GMR, dataset
         g = GMR(src_human=src_human, tgt_robot=args.robot, device=args.device, use_velocity_limit=args.use_velocity_limit, velocity_limits=args.velocity_limit)
         target_of, failed = dict(pairs), 0
-        sink = ReportSink(args, rank=args.report_rank) if wants_report(args) else None
+        sink = ReportSink(args, rank=args.report_rank) if wants_sink(args) else None
+        rep_on = wants_report(args)
         track_fps = getattr(args, "track_fps", None)
         track_kw = {}if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
         if getattr(args, "lowpass_hz", None) is not None:
             track_kw["lowpass_hz"] = args.lowpass_hz
         track_kw.update(getattr(args, "contact_kw", {}))
+        dyn_kw = {"dynamics": True} if wants_dynamics(args) else {}  # (absent without the flags: nothing changes then)
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -242,12 +264,12 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
                     continue
                 targets = [target_of[f] for f in batch.files]
                 res = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                             clip_start=args.clip_start, report=sink is not None, **retarget_kw(batch), **track_kw)
+                                             clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw)
                 res = res if isinstance(res, tuple) else (res,)
                 motions = res[0]
                 track_of = dict(zip(targets, res[-1])) if track_fps is not None else None
                 if sink is not None:
-                    motions, targets = sink.take(dataset, targets, motions, res[1])
+                    motions, targets = sink.take(dataset, targets, motions, res[1] if rep_on else None, res[1 + rep_on] if dyn_kw else None)
                 writer.submit(motions, targets)
                 if track_of is not None:  # (a withheld clip has no tracking export either)
                     writer.submit([track_of[t] for t in targets], [track_path(args, t) for t in targets])
@@ -264,12 +286,14 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
     from .. import MultiRobotRetargeting, dataset
     mr = MultiRobotRetargeting(src_human, args.robot_list, device=args.device, use_velocity_limit=args.use_velocity_limit, velocity_limits=args.velocity_limit)
     target_of, failed = dict(pairs), 0
-    sinks = {r: ReportSink(args, r, getattr(args, "report_rank", None)) for r in mr.robots} if wants_report(args) else None
+    sinks = {r: ReportSink(args, r, getattr(args, "report_rank", None)) for r in mr.robots} if wants_sink(args) else None
+    rep_on = wants_report(args)
     track_fps = getattr(args, "track_fps", None)
     track_kw = {} if track_fps is None else {"track_fps": track_fps}  # (absent without the flags: nothing changes then)
     if getattr(args, "lowpass_hz", None) is not None:
         track_kw["lowpass_hz"] = args.lowpass_hz
     track_kw.update(getattr(args, "contact_kw", {}))
+    dyn_kw = {"dynamics": True} if wants_dynamics(args) else {}
     with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
         for batch in batches([s for s, _ in pairs], mr.ik_columns):
             for f, why in batch.skipped:
@@ -278,14 +302,15 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
             if not len(batch):
                 continue
             res = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                    clip_start=args.clip_start, report=sinks is not None, **retarget_kw(batch), **track_kw)
+                                    clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw)
             res = res if isinstance(res, tuple) else (res,)
-            motions, reps = res[0], res[1] if sinks is not None else None
+            motions, reps = res[0], res[1] if rep_on else None
+            dyns = res[1 + rep_on] if dyn_kw else None
             for i, r in enumerate(mr.robots):
                 ms, ts = motions[r], [target_of[f][i] for f in batch.files]
                 track_of = dict(zip(ts, res[-1][r])) if track_fps is not None else None
-                if reps is not None:
-                    ms, ts = sinks[r].take(dataset, ts, ms, reps[r])
+                if sinks is not None:
+                    ms, ts = sinks[r].take(dataset, ts, ms, reps[r] if reps is not None else None, dyns[r] if dyns is not None else None)
                 writer.submit(ms, ts)
                 if track_of is not None:
                     writer.submit([track_of[t] for t in ts], [track_path(args, t) for t in ts])

@@ -65,6 +65,9 @@
  *                      from the export in a host loop, and the foot-slide and ground-penetration figures of a retargeted clip
  *   gmr_motion_footlock  (no counterpart in the reference) the foot-slide clean-up such a pipeline runs on the host: a loop over
  *                      contact phases with a small leg IK per frame, here a post-pass from qpos to qpos
+ *   gmr_motion_dynamics  (no counterpart in the reference) what the consumers of the clips run on the host to filter them, MuJoCo's
+ *                      inverse dynamics per frame: joint torques, the contact wrench on the root, centre of mass and ZMP, and per
+ *                      clip torque-limit and ground-reaction statistics
  *   gmr_dof_to_rot     KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -570,6 +573,90 @@ typedef struct gmr_footlock_input {
   int32_t       *limit_frames_out;
 } gmr_footlock_input;
 int gmr_motion_footlock(gmr_model *m, const gmr_footlock_input *in);
+
+/* Inverse dynamics of retargeted qpos with a floating base: per frame the joint torques the motion needs, the wrench the contacts
+ * must supply on the root, the centre of mass and the zero-moment point; per clip torque-limit and ground-reaction statistics.
+ * All arithmetic is float64 without floating-point contraction; a + b + c means (a + b) + c.
+ *
+ * The whole call is this struct, its stream included (in->stream, in the sense of the stream-order paragraph at the top of this
+ * file); the struct is read completely before the call returns.  The call enqueues two kernels on in->stream (one when no
+ * statistic is asked for) and nothing else: no allocation, no copy, no synchronisation.  All arrays are device arrays.
+ *   qpos          f64 [n_frames][nq], free-joint layout (x y z, qw qx qy qz, hinges), concatenated clips (N = n_frames)
+ *   seq_offsets   int64 [n_seq+1]: clip s owns the rows a = clamp(seq_offsets[s], 0, N) to b = clamp(seq_offsets[s+1], a, N), T = b - a
+ *   fps           one rate for the call, h = 1 / fps
+ *   gravity_x/y/z the gravity vector g in m/s^2, usually (0, 0, -9.81);  ground_z: the height of the ground plane of the ZMP
+ *   fz_min        a frame whose F_z is below fz_min (sum m) |g| is "unloaded".  0.05 is a convention, not measured on any robot
+ *   qvel, qacc    f64 [n_frames][nv] or NULL, nv = nq - 1: entries 0..2 the root's linear part in the world frame, 3..5 the root's
+ *                 angular part IN THE WORLD FRAME -- the convention gmr_motion_track writes, not MuJoCo's local-frame qvel[3..5] --
+ *                 then the hinges.
+ * The inertial table, in the model's body order (nbody must equal the model's): body_parent int32 [nbody] (-1 for the root; the
+ * bodies are in depth-first order, so a subtree is a run of indices), body_mass [nbody], body_com [nbody][3] (centre of mass in the
+ * body frame), body_inertia [nbody][6] (xx yy zz xy xz yz about the centre of mass, body frame), armature [nq-7] and torque_limit
+ * [nq-7] in qpos order (> 0, +inf for none).  Trusted, as body_ids are in gmr_motion_sample; the kernel only clamps body_parent.
+ * Velocity when qvel is NULL: the tracking export's central differences.  Frame k of a clip: km = max(k-1, 0), kp = min(k+1, T-1),
+ * hv = (double)(kp - km) h; linear and hinge parts (x[kp] - x[km]) / hv, angular part rotvec(q[kp] (x) conj(q[km])) / hv with
+ * gmr_motion_track's rotvec on the rows as they are (wxyz); all 0 when hv = 0.
+ * Acceleration when qacc is NULL: 0 for T < 3; else with kc = clamp(k, 1, T-2) (the first and last frame take their neighbour's)
+ * linear and hinge parts ((x[kc+1] - 2 x[kc]) + x[kc-1]) / (h h), angular part (w+ - w-) / h with
+ * w+ = rotvec(q[kc+1] (x) conj(q[kc])) / h and w- = rotvec(q[kc] (x) conj(q[kc-1])) / h.
+ * Poses are gmr_motion_footlock's FK (MuJoCo's convention, the root quaternion divided by its norm), not the float32 gmr_fk.  Body i
+ * has mass m_i, world centre of mass c_i, world rotation R_i, body-frame inertia I_i and angular velocity w_i; the velocity (v, w)
+ * and acceleration of the root above and the hinge rates carry down the tree as rigid-body kinematics.  For a point p let
+ *   W(p, set) = sum over i in set of (c_i - p) x m_i (c_i'' - g) + d/dt(R_i I_i R_i^T w_i).
+ * Outputs per frame, any may be NULL:
+ *   tau_out [n_frames][nq-7]       a_j . W(p_j, subtree(j)) + armature_j theta_j'', a_j the hinge's world axis, p_j its world anchor
+ *   root_wrench_out [n_frames][6]  (F, M): F = sum over all i of m_i (c_i'' - g), M = W(p_root, all).  Dual to the root's (v, w): the
+ *                                  power of the motion is F . v + M . w + tau . theta'
+ *   com_out [n_frames][3]          sum m_i c_i / sum m_i
+ *   zmp_out [n_frames][2]          ((ground_z F_x - Mo_y) / F_z, (Mo_x + ground_z F_y) / F_z) with Mo = M + p_root x F; both NaN in
+ *                                  an unloaded frame
+ *   qvel_out, qacc_out [n_frames][nv]   the velocity and acceleration used, given or differenced
+ * Every sum over bodies runs in body order from 0.0, moments are gathered about p_root; how the kernel walks the tree is its own
+ * business and results agree with the formula to rounding.
+ * Per-clip statistics, any may be NULL, reduced by the second kernel from tau_out and root_wrench_out (both are required when a
+ * statistic is asked for).  A frame with a non-finite entry in its tau or root_wrench row is counted in nonfinite_frames and takes
+ * part in no other statistic.  Over the other frames of the clip, hinges in qpos order:
+ *   tau_abs_max_out, tau_rms_out [n_seq][nq-7] f64   max |tau|; sqrt(sum tau^2 / frames), the sum added frame by frame from 0.0
+ *   tau_ratio_max_out [n_seq][nq-7] f64              max |tau| / torque_limit (0 for a hinge without a limit)
+ *   frames_over_limit_out [n_seq][nq-7] i32          frames with |tau| > torque_limit
+ *   frames_any_over_limit_out [n_seq] i32            frames in which any hinge is over its limit
+ *   fz_ratio_max_out, fz_ratio_min_out [n_seq] f64   extremes of F_z / ((sum m) |g|), 0 without a finite frame
+ *   unloaded_frames_out, nonfinite_frames_out [n_seq] i32
+ * A clip without frames reports 0.  Rows outside every clip are not written.  Two calls give identical bytes.  Non-finite input: a
+ * non-finite entry of a qpos row reaches only the frames whose stencil reads that row, and only its own clip's statistics; no byte
+ * of another clip changes.
+ * GMR_EINVAL: fps, gravity, ground_z or fz_min not finite, fps <= 0, fz_min < 0, a zero gravity, NULL arrays with work to do, a
+ * statistic without tau_out and root_wrench_out, negative counts.  GMR_EUNSUPPORTED: a planar-base model, nbody that is not the
+ * model's, a model of more than 64 bodies (its work unit does not fit one wavefront's LDS tile), a model whose bodies are not in
+ * depth-first order.  n_frames = 0 or n_seq = 0 returns GMR_OK without a launch.  Asynchronous on in->stream; the handle's device
+ * is selected.
+ * Layout (LP64): sizeof 272; offsets qpos 0, n_frames 8, seq_offsets 16, qvel 24, qacc 32, n_seq 40, nbody 44, fps 48,
+ * gravity_x 56, gravity_y 64, gravity_z 72, ground_z 80, fz_min 88, body_parent 96, body_mass 104, body_com 112,
+ * body_inertia 120, armature 128, torque_limit 136, stream 144, tau_out 152, root_wrench_out 160, com_out 168, zmp_out 176,
+ * qvel_out 184, qacc_out 192, tau_abs_max_out 200, tau_rms_out 208, tau_ratio_max_out 216, frames_over_limit_out 224,
+ * frames_any_over_limit_out 232, fz_ratio_max_out 240, fz_ratio_min_out 248, unloaded_frames_out 256,
+ * nonfinite_frames_out 264.  */
+typedef struct gmr_dynamics_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  const double  *qvel, *qacc;     /* device [n_frames][nq-1] f64, or NULL = differences of qpos */
+  int32_t        n_seq, nbody;    /* nbody: bodies of the inertial table */
+  double         fps;
+  double         gravity_x, gravity_y, gravity_z;
+  double         ground_z, fz_min;
+  const int32_t *body_parent;     /* device [nbody] */
+  const double  *body_mass, *body_com, *body_inertia;   /* device [nbody], [nbody][3], [nbody][6] */
+  const double  *armature, *torque_limit;               /* device [nq-7] */
+  void          *stream;          /* the call's stream */
+  double        *tau_out, *root_wrench_out, *com_out, *zmp_out;
+  double        *qvel_out, *qacc_out;
+  double        *tau_abs_max_out, *tau_rms_out, *tau_ratio_max_out;
+  int32_t       *frames_over_limit_out, *frames_any_over_limit_out;
+  double        *fz_ratio_max_out, *fz_ratio_min_out;
+  int32_t       *unloaded_frames_out, *nonfinite_frames_out;
+} gmr_dynamics_input;
+int gmr_motion_dynamics(gmr_model *m, const gmr_dynamics_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
