@@ -31,7 +31,8 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_group_plan_order", "gmr_group_ik_solve_ordered", "gmr_motion_epilogue", "gmr_group_motion_epilogue",
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
-           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics"]
+           "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics",
+           "gmr_motion_self_collision"]
 
 
 class IKParams(C.Structure):
@@ -150,6 +151,24 @@ class DynamicsInput(C.Structure):
         ("n_seq", C.c_int32), ("nbody", C.c_int32), ("fps", C.c_double),
         ("gravity_x", C.c_double), ("gravity_y", C.c_double), ("gravity_z", C.c_double), ("ground_z", C.c_double), ("fz_min", C.c_double),
     ] + [(k, C.c_void_p) for k in DYNAMICS_TABLE] + [("stream", C.c_void_p)] + [(k + "_out", C.c_void_p) for k in DYNAMICS_OUTPUTS]
+
+
+SELF_COLLISION_FRAME_OUTPUTS = ("clearance", "pair", "hits")   # gmr_self_collision_input's output pointers, in order: per frame,
+SELF_COLLISION_STATS = ("clearance_min", "worst_frame", "worst_pair", "colliding_frames", "longest_run", "hits_sum",
+                        "nonfinite_frames")                     # then per clip
+SELF_COLLISION_OUTPUTS = SELF_COLLISION_FRAME_OUTPUTS + SELF_COLLISION_STATS
+SELF_COLLISION_TABLE = ("cap_body", "cap_p0", "cap_p1", "cap_radius", "pairs")   # the proxy tables' arrays
+SELF_COLLISION_MAX_CAPS, SELF_COLLISION_MAX_PAIRS = 256, 32768
+
+
+class SelfCollisionInput(C.Structure):
+    """``gmr_self_collision_input`` (include/gmr_amd.h): the whole call of the self-collision report, its stream included."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("n_seq", C.c_int32), ("n_caps", C.c_int32),
+        ("n_pairs", C.c_int32), ("reserved", C.c_int32),
+    ] + [(k, C.c_void_p) for k in SELF_COLLISION_TABLE] + [("margin", C.c_double), ("stream", C.c_void_p)] \
+      + [(k + "_out", C.c_void_p) for k in SELF_COLLISION_OUTPUTS]
 
 
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
@@ -278,6 +297,8 @@ def load():
     L.gmr_motion_footlock.argtypes = [vp, C.POINTER(FootlockInput)]
     L.gmr_motion_dynamics.restype = C.c_int
     L.gmr_motion_dynamics.argtypes = [vp, C.POINTER(DynamicsInput)]
+    L.gmr_motion_self_collision.restype = C.c_int
+    L.gmr_motion_self_collision.argtypes = [vp, C.POINTER(SelfCollisionInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

@@ -35,6 +35,7 @@
 #include "contact_kernel.hip.h"
 #include "dynamics_kernel.hip.h"
 #include "footlock_kernel.hip.h"
+#include "self_collision_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
 #include "model_plan.h"
@@ -1769,6 +1770,72 @@ int gmr_motion_dynamics(gmr_model *m, const gmr_dynamics_input *in) {
     set_err(m, "null argument"); return GMR_EINVAL;
   }
   return dynamics_run(m, *in, stats, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ self-collision (self_collision_kernel.hip.h)
+// The two launches of gmr_motion_self_collision, and nothing else: no allocation, no copy, no synchronisation.  Every array is a
+// device array and everything else -- the tree's parents and depths included -- travels in the kernels' argument.
+static int self_collision_run(gmr_model *m, const gmr_self_collision_input &in, bool stats, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::SelfCollisionArgs a{};
+  a.dm = m->dm_eval_dev;
+  a.qpos = in.qpos; a.seq_offsets = in.seq_offsets; a.n_frames = in.n_frames;
+  a.n_seq = in.n_seq; a.nbody = m->h.nbody; a.nq = m->fk.ndof + 7; a.n_caps = in.n_caps; a.n_pairs = in.n_pairs;
+  a.cap_body = in.cap_body; a.cap_p0 = in.cap_p0; a.cap_p1 = in.cap_p1; a.cap_radius = in.cap_radius; a.pairs = in.pairs;
+  a.margin = in.margin;
+  a.clearance = in.clearance_out; a.pair = in.pair_out; a.hits = in.hits_out;
+  a.clearance_min = in.clearance_min_out; a.worst_frame = in.worst_frame_out; a.worst_pair = in.worst_pair_out;
+  a.colliding = in.colliding_frames_out; a.longest_run = in.longest_run_out; a.hits_sum = in.hits_sum_out;
+  a.nonfinite = in.nonfinite_frames_out;
+  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
+  for (int b = 0; b < a.nbody; ++b) {   // (a parent precedes its child: gmr_motion_self_collision checked)
+    a.parent[b] = parent[b] < 0 ? 0xff : (uint8_t)parent[b];
+    a.depth[b] = parent[b] < 0 ? 0 : (uint8_t)(a.depth[parent[b]] + 1);
+  }
+  // Wavefronts per clip as in dynamics_run: about kColTargetWaves in the whole launch, at most one per frame slot of the mean clip;
+  // a wavefront's set-up (its body's and capsules' constants, the staged radii and pairs) is paid once for many frames.
+  // GMR_AMD_COLLISION_WAVES forces a number (the results do not depend on it).
+  const int groups = gmr::chain_geom(a.nbody).groups;
+  const int64_t slots = (in.n_frames + groups - 1) / groups, mean = (slots + in.n_seq - 1) / in.n_seq;
+  const int64_t want = (gmr::kColTargetWaves + in.n_seq - 1) / in.n_seq;
+  unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean), 65535));
+  if (const char *e = getenv("GMR_AMD_COLLISION_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) ty = (unsigned)v; }
+  // Where the pair indices live: staged in LDS as 16-bit words while the table is small, re-read from L2 in every
+  // frame otherwise.  GMR_AMD_COLLISION_PAIRS=lds / global forces one (lds only where it fits).
+  bool lds = in.n_pairs <= gmr::kColPairsLdsMax;
+  if (const char *e = getenv("GMR_AMD_COLLISION_PAIRS")) lds = lds && e[0] != 'g';
+  const unsigned bytes = (unsigned)gmr::self_collision_lds_bytes(in.n_caps, in.n_pairs, lds);
+  if (lds) hipLaunchKernelGGL(gmr::motion_self_collision_kernel<true>, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), bytes, st, a);
+  else hipLaunchKernelGGL(gmr::motion_self_collision_kernel<false>, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), bytes, st, a);
+  if (stats) hipLaunchKernelGGL(gmr::motion_self_collision_stats_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0 || in->n_caps < 0 || in->n_pairs < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (!std::isfinite(in->margin)) { set_err(m, "margin must be finite"); return GMR_EINVAL; }
+  const int nb = m->h.nbody;
+  if (nb > gmr::kFkWave) { set_err(m, "a model of %d bodies does not fit the self-collision tile", nb); return GMR_EUNSUPPORTED; }
+  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
+  for (int b = 1; b < nb; ++b)
+    if (parent[b] < 0 || parent[b] >= b) { set_err(m, "body %d does not follow its parent", b); return GMR_EUNSUPPORTED; }
+  if (in->n_caps > gmr::kColMaxCaps) { set_err(m, "at most %d capsules per call", gmr::kColMaxCaps); return GMR_EUNSUPPORTED; }
+  if (in->n_pairs > gmr::kColMaxPairs) { set_err(m, "at most %d pairs per call", gmr::kColMaxPairs); return GMR_EUNSUPPORTED; }
+  const bool stats = in->clearance_min_out || in->worst_frame_out || in->worst_pair_out || in->colliding_frames_out ||
+                     in->longest_run_out || in->hits_sum_out || in->nonfinite_frames_out;
+  if (in->n_frames == 0 || in->n_seq == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (stats && (!in->clearance_out || !in->pair_out || !in->hits_out)) {
+    set_err(m, "the statistics are reduced from clearance_out, pair_out and hits_out: all three are required"); return GMR_EINVAL;
+  }
+  if (in->n_caps < 1 || in->n_pairs < 1) { set_err(m, "n_caps and n_pairs must be at least 1"); return GMR_EINVAL; }
+  if (!in->qpos || !in->seq_offsets || !in->cap_body || !in->cap_p0 || !in->cap_p1 || !in->cap_radius || !in->pairs) {
+    set_err(m, "null argument"); return GMR_EINVAL;
+  }
+  return self_collision_run(m, *in, stats, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

@@ -83,7 +83,8 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                    height_adjust: bool = True, root_origin_offset: bool = True, chunk: int = 0, burn_in: int = 0,
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
                    track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
-                   contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False, dynamics: bool = False):
+                   contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False, dynamics: bool = False,
+                   collision=None):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -94,7 +95,9 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     are all made from the smoothed qpos.  ``contact_bodies`` / ``contact`` (with ``track_fps``): ``tracking_from_qpos``'s contact
     labels on the tracking dicts; ``lock_feet``: ``tracking_from_qpos``'s foot locking of those bodies (the tracking dicts only: the
     motions and the report are made from the qpos as solved).  With ``dynamics`` the ``dynamics_report`` of the same qpos follows
-    the clip report (or the motions, without ``report``) and precedes the tracks."""
+    the clip report (or the motions, without ``report``) and precedes the tracks.  With ``collision`` (``True``, or a dict of
+    ``self_collision_report``'s keywords: ``radius``, ``capsules``, ``pairs``, ``margin``) the ``self_collision_report`` of the same
+    qpos follows the dynamics report (or what precedes it) and precedes the tracks."""
     if contact_bodies is not None and track_fps is None:
         raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
     if lock_feet and contact_bodies is None:
@@ -117,6 +120,8 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
         res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset), rep.numpy())
     if dynamics:
         res += (dynamics_report(gmr, qpos, seq_offsets, fps),)
+    if collision:
+        res += (self_collision_report(gmr, qpos, seq_offsets, **(collision if isinstance(collision, dict) else {})),)
     if track_fps is not None:
         lock_kw = {"lock_feet": lock_feet} if lock_feet else {}  # (absent without the flag: nothing changes then)
         res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps, contact_bodies=contact_bodies, contact=contact, **lock_kw),)
@@ -450,6 +455,74 @@ def dynamics_hard_mask(report: Dict, max_torque_ratio: float) -> np.ndarray:
     """Clips in which some hinge needs more than ``max_torque_ratio`` times its torque limit."""
     r = np.asarray(report["tau_ratio_max"])
     return (r.max(axis=1) > float(max_torque_ratio)) if r.shape[1] else np.zeros(r.shape[0], dtype=bool)
+
+
+# ------------------------------------------------------------------ self-collision
+COLLISION_CSV_FIELDS = ("clearance_min", "penetration_max", "worst_frame", "colliding_frames", "longest_run", "hits_sum", "nonfinite_frames")
+
+
+def self_collision_from_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], capsules=None, pairs=None,
+                             margin: float = 0.0, radius: float = 0.03) -> List[Dict]:
+    """Capsule clearance of qpos ``[N, nq]`` float64 on the GPU (concatenated clips) -> one dict of host arrays per clip:
+    ``clearance`` ``[T]`` (metres, negative = penetration), ``pair`` ``[T]`` (row of the pair table), ``hits`` ``[T]``, the clip's
+    row of every statistic of ``Engine.motion_self_collision``, and ``pair_names`` (the two capsule names of every pair of the
+    table).  The definition is the contract above ``gmr_self_collision_input`` in include/gmr_amd.h.  ``capsules`` / ``pairs``:
+    ``gmr_amd.collision`` tables; ``None``: the skeleton's capsules of ``radius`` along the links and their default pairs -- the
+    radius is a convention, not measured on any robot, and the skeleton is not the robot's collision geometry."""
+    from .collision import pair_names
+    eng = gmr._engine
+    capsules, pairs = eng.resolve_proxies(capsules, pairs, radius)
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    got = eng.motion_self_collision(qpos, offs, capsules, pairs, margin=margin)
+    host = {k: v.cpu().numpy() for k, v in got.items()}
+    names = pair_names(capsules, pairs)
+    out = []
+    for s in range(offs.size - 1):
+        a, b = int(offs[s]), int(offs[s + 1])
+        d = {k: host[k][a:b] for k in ("clearance", "pair", "hits")}
+        d.update((k, host[k][s]) for k in got.stats)
+        d["pair_names"] = names
+        out.append(d)
+    return out
+
+
+def self_collision_report(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], capsules=None, pairs=None,
+                          margin: float = 0.0, radius: float = 0.03) -> Dict:
+    """The per-clip statistics of ``self_collision_from_qpos`` alone, as host arrays with one row per clip: ``clearance_min``,
+    ``worst_frame``, ``worst_pair``, ``colliding_frames``, ``longest_run``, ``hits_sum``, ``nonfinite_frames``; plus
+    ``worst_pair_names`` (the two capsule names of ``worst_pair``, ``("", "")`` where there is none) and ``penetration_max =
+    max(0, -clearance_min)``."""
+    return _self_collision_report(gmr._engine, qpos, seq_offsets, capsules, pairs, margin, radius)
+
+
+def _self_collision_report(eng, qpos, seq_offsets, capsules=None, pairs=None, margin=0.0, radius=0.03) -> Dict:
+    """``self_collision_report`` on an ``Engine``."""
+    capsules, pairs = eng.resolve_proxies(capsules, pairs, radius)
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    got = eng.motion_self_collision(qpos, offs, capsules, pairs, margin=margin)
+    rep = {k: v.cpu().numpy() for k, v in got.stats.items()}
+    rep["worst_pair_names"] = [(capsules.names[int(pairs.pairs[p, 0])], capsules.names[int(pairs.pairs[p, 1])]) if p >= 0 else ("", "")
+                               for p in rep["worst_pair"]]
+    rep["penetration_max"] = np.maximum(0.0, -rep["clearance_min"])
+    return rep
+
+
+def write_collision_csv(path: str, names: Sequence[str], report: Dict, append: bool = False) -> None:
+    """One row per clip of a ``self_collision_report``: the per-clip fields, then the two capsule names of the worst pair."""
+    import csv
+    if len(names) != len(report["clearance_min"]):
+        raise ValueError("one name per clip is required")
+    with open(path, "a" if append else "w", newline="") as f:
+        w = csv.writer(f)
+        if not append:
+            w.writerow(("clip",) + COLLISION_CSV_FIELDS + ("worst_capsule_a", "worst_capsule_b"))
+        for s, n in enumerate(names):
+            w.writerow([n] + [repr(report[k][s].item()) for k in COLLISION_CSV_FIELDS] + list(report["worst_pair_names"][s]))
+
+
+def collision_hard_mask(report: Dict, max_penetration: float) -> np.ndarray:
+    """Clips whose deepest penetration exceeds ``max_penetration`` metres."""
+    return np.asarray(report["penetration_max"]) > float(max_penetration)
 
 
 # ------------------------------------------------------------------ the motion library

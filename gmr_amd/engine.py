@@ -521,6 +521,68 @@ def _dynamics_input(eng: "Engine", qpos, seq_offsets, fps, qvel, qacc, gravity, 
     return di, MotionDynamics(res), [qpos, offs, qvel, qacc, dev_table]
 
 
+SELF_COLLISION_FIELDS = _native.SELF_COLLISION_OUTPUTS   # the arrays of the self-collision report, in gmr_self_collision_input's order
+SELF_COLLISION_STATS = _native.SELF_COLLISION_STATS      # of them the per-clip statistics
+
+
+class MotionSelfCollision(dict):
+    """Result of ``motion_self_collision``: the device tensors by name (``SELF_COLLISION_FIELDS``).  Per frame ``[N]``:
+    ``clearance`` float64 (metres, negative = penetration; NaN for a non-finite frame), ``pair`` int32 (row of the pair table, -1
+    in a NaN frame), ``hits`` int32.  Per clip ``[S]`` (``SELF_COLLISION_STATS``): ``clearance_min`` float64, ``worst_frame``,
+    ``worst_pair``, ``colliding_frames``, ``longest_run``, ``nonfinite_frames`` int32 and ``hits_sum`` int64."""
+
+    @property
+    def stats(self):
+        return {k: self[k] for k in SELF_COLLISION_STATS if k in self}
+
+
+def _self_collision_input(eng: "Engine", qpos, seq_offsets, capsules, pairs, margin, out, stats):
+    """Check the arguments of one self-collision call and fill its ``SelfCollisionInput`` (all but the stream).  Returns (input,
+    MotionSelfCollision, keep-alive)."""
+    dev = eng.device
+    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or int(qpos.shape[1]) != eng.nq or not qpos.is_contiguous():
+        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
+    N = int(qpos.shape[0])
+    if isinstance(seq_offsets, torch.Tensor):
+        offs = seq_offsets
+        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
+            raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
+    else:
+        o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+        if o.ndim != 1 or o.size < 1:
+            raise ValueError("seq_offsets must hold n_seq + 1 entries")
+        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    S = int(offs.shape[0]) - 1
+    if not np.isfinite(margin):
+        raise ValueError("margin must be finite")
+    dev_table = eng.collision_device(capsules, pairs)
+    f64, i32, i64 = torch.float64, torch.int32, torch.int64
+    shapes = {"clearance": ((N,), f64), "pair": ((N,), i32), "hits": ((N,), i32), "clearance_min": ((S,), f64), "worst_frame": ((S,), i32),
+              "worst_pair": ((S,), i32), "colliding_frames": ((S,), i32), "longest_run": ((S,), i32), "hits_sum": ((S,), i64),
+              "nonfinite_frames": ((S,), i32)}
+    if out is None:
+        # rows outside every clip are not written, and a call without rows launches nothing: what an empty clip reports
+        fill = {"clearance": float("nan"), "pair": -1, "clearance_min": float("inf"), "worst_frame": -1, "worst_pair": -1}
+        res = {k: torch.full(sh, fill.get(k, 0), dtype=dt, device=dev) for k, (sh, dt) in shapes.items()
+               if stats or k in _native.SELF_COLLISION_FRAME_OUTPUTS}
+    else:
+        res = {k: out[k] for k in SELF_COLLISION_FIELDS if k in out}
+        if set(out) - set(SELF_COLLISION_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                                        or t.device != dev or not t.is_contiguous() for k, t in res.items()):
+            raise EngineError("out must map names of SELF_COLLISION_FIELDS to contiguous tensors of the call's shapes on the engine's device")
+        if set(res) & set(SELF_COLLISION_STATS) and not set(_native.SELF_COLLISION_FRAME_OUTPUTS) <= set(res):
+            raise EngineError("out must hold clearance, pair and hits when it holds a statistic: the statistics are reduced from them")
+    ci = _native.SelfCollisionInput()
+    ci.qpos, ci.n_frames, ci.seq_offsets, ci.n_seq = qpos.data_ptr(), N, offs.data_ptr(), S
+    ci.n_caps, ci.n_pairs, ci.margin = int(dev_table["cap_body"].shape[0]), int(dev_table["pairs"].shape[0]), float(margin)
+    for k in _native.SELF_COLLISION_TABLE:
+        setattr(ci, k, dev_table[k].data_ptr())
+    for k, t in res.items():
+        setattr(ci, k + "_out", t.data_ptr())
+    return ci, MotionSelfCollision(res), [qpos, offs, dev_table]
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -671,6 +733,8 @@ class Engine:
         self.info = info
         self.nq, self.nv, self.nbody = info.nq, info.nv, info.nbody
         self._inertial_dev = {}   # inertial tables on the device (inertial_device): None -> the robot's own, id(table) -> an explicit one
+        self._collision_dev = {}      # collision proxies on the device (collision_device): (id(capsules), id(pairs)) -> the upload
+        self._collision_default = {}  # the skeleton's proxies by radius (default_proxies), default pairs of explicit capsules
         if getattr(cm, "step_cap", None) is not None:  # the model's velocity limit (model.step_cap): part of the handle from here on
             self.set_step_cap(cm.step_cap)
 
@@ -1192,6 +1256,65 @@ class Engine:
         di, res, keep = _dynamics_input(self, qpos, seq_offsets, fps, qvel, qacc, gravity, ground_z, fz_min, table, out)
         di.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self._lib.gmr_motion_dynamics(self._h, C.byref(di)), "gmr_motion_dynamics")
+        return res
+
+    def default_proxies(self, radius=None):
+        """``(CapsuleTable, PairTable)`` of the robot's skeleton at ``radius`` (``gmr_amd.collision.skeleton_capsules`` and
+        ``default_pairs``; ``None``: 0.03 m, a convention, not measured on any robot), built once per engine and radius."""
+        from . import collision
+        r = collision.DEFAULT_RADIUS if radius is None else radius
+        key = tuple(sorted(r.items())) if isinstance(r, dict) else float(r)
+        if key not in self._collision_default:
+            self._collision_default[key] = collision.proxies(self.cm.robot, radius=r)
+        return self._collision_default[key]
+
+    def resolve_proxies(self, capsules=None, pairs=None, radius=None):
+        """``(capsules, pairs)`` with the defaults filled in, each default built once: without ``capsules`` the skeleton's at
+        ``radius`` (:meth:`default_proxies`), without ``pairs`` the ``default_pairs`` of ``capsules``."""
+        if capsules is None:
+            capsules, default = self.default_proxies(radius)
+            return capsules, (default if pairs is None else pairs)
+        if pairs is None:
+            key = ("pairs", id(capsules))
+            if key not in self._collision_default:
+                from . import collision
+                self._collision_default[key] = collision.default_pairs(self.cm.robot, capsules)[0]
+                weakref.finalize(capsules, self._collision_default.pop, key, None)
+            pairs = self._collision_default[key]
+        return capsules, pairs
+
+    def collision_device(self, capsules, pairs):
+        """The proxy tables on the engine's device, by the field names of ``gmr_self_collision_input``: uploaded once per
+        ``(capsules, pairs)`` (a :class:`gmr_amd.collision.CapsuleTable` and a :class:`gmr_amd.collision.PairTable`; their
+        identity is the key, so a table changed in place needs a new object) and cached as long as both live."""
+        cache = self._collision_dev
+        key = (id(capsules), id(pairs))
+        if key not in cache:
+            from . import collision
+            collision.check_tables(self.nbody, capsules, pairs)
+            host = {"cap_body": capsules.body, "cap_p0": capsules.p0, "cap_p1": capsules.p1, "cap_radius": capsules.radius, "pairs": pairs.pairs}
+            cache[key] = ({k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in host.items()},)
+            for t in (capsules, pairs):
+                weakref.finalize(t, cache.pop, key, None)
+        return cache[key][0]
+
+    def motion_self_collision(self, qpos: torch.Tensor, seq_offsets, capsules=None, pairs=None, margin: float = 0.0, out=None,
+                              stats: bool = True) -> MotionSelfCollision:
+        """Capsule clearance of qpos ``[N, nq]`` float64 (engine layout, concatenated clips) in two kernels
+        (``gmr_motion_self_collision``; the definition is the contract in include/gmr_amd.h): per frame the smallest clearance over
+        the pair table, the pair that attains it and the number of pairs below ``margin``; per clip the deepest frame, its pair,
+        the colliding frames and their longest run.  ``seq_offsets`` ``[S + 1]``: the clips' rows, a host sequence (uploaded once)
+        or a device int64 tensor.  ``capsules`` / ``pairs``: a :class:`gmr_amd.collision.CapsuleTable` and
+        :class:`gmr_amd.collision.PairTable`; ``None``: the skeleton's (:meth:`default_proxies` -- capsules of 0.03 m along the
+        links, a convention, not the robot's collision geometry), and ``pairs=None`` alone: ``default_pairs`` of ``capsules``.
+        ``stats=False`` leaves the per-clip statistics out (one kernel).  Returns a :class:`MotionSelfCollision` of device tensors;
+        ``out``: caller-owned result tensors by name (a name left out is not computed; a statistic needs ``clearance``, ``pair``
+        and ``hits``).  Asynchronous on the current stream; with ``out``, cached tables and a device ``seq_offsets`` no allocation,
+        no copy, no synchronisation."""
+        capsules, pairs = self.resolve_proxies(capsules, pairs)
+        ci, res, keep = _self_collision_input(self, qpos, seq_offsets, capsules, pairs, margin, out, stats)
+        ci.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self._lib.gmr_motion_self_collision(self._h, C.byref(ci)), "gmr_motion_self_collision")
         return res
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,

@@ -429,6 +429,15 @@ class GeneralMotionRetargeting:
         tq = (torch.from_numpy(np.ascontiguousarray(qpos)) if isinstance(qpos, np.ndarray) else qpos).to(self.device, torch.float64).contiguous()
         return dynamics_report(self, tq, seq_offsets, fps, lowpass_hz, **dynamics_kwargs)
 
+    def self_collision_report(self, qpos, seq_offsets, capsules=None, pairs=None, margin: float = 0.0, radius: float = 0.03):
+        """Per-clip self-collision statistics of retargeted qpos ``[N, nq]`` (numpy or CUDA torch, engine layout, concatenated
+        clips), reduced on the GPU (``dataset.self_collision_report``, ``Engine.motion_self_collision``): the deepest penetration of
+        the capsule proxies, its frame and pair, the colliding frames and their longest run.  The default proxies are capsules of
+        ``radius`` along the skeleton's links: a convention, not the robot's collision geometry."""
+        from .dataset import self_collision_report
+        tq = (torch.from_numpy(np.ascontiguousarray(qpos)) if isinstance(qpos, np.ndarray) else qpos).to(self.device, torch.float64).contiguous()
+        return self_collision_report(self, tq, seq_offsets, capsules, pairs, margin, radius)
+
     def fk_batch(self, root_pos, root_rot_xyzw, dof_pos, want_rot: bool = False):
         """Batched FK in the ``KinematicsModel.forward_kinematics`` convention (float32, xyzw; kinematics_model.py:213-246) on this
         object's robot: ``root_pos [T,3]``, ``root_rot_xyzw [T,4]``, ``dof_pos [T,ndof]`` -> ``body_pos [T,nbody,3]`` (and

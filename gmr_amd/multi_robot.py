@@ -238,7 +238,7 @@ class MultiRobotRetargeting:
                        root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
                        clip_start: str = "qpos0", report: bool = False, track_fps: Optional[float] = None,
                        lowpass_hz: Optional[float] = None, contact_bodies: Optional[Dict[str, Sequence[str]]] = None, contact=None,
-                       lock_feet=False, dynamics: bool = False):
+                       lock_feet=False, dynamics: bool = False, collision=None):
         """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
         solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
         ``dataset.MotionWriter.submit`` as they are.  With ``report`` a second value is returned: ``{robot: engine.ClipReport}``
@@ -247,7 +247,8 @@ class MultiRobotRetargeting:
         every robot's solved qpos is smoothed once (``dataset.smooth_qpos`` at ``fps``) and everything is made from that.
         ``contact_bodies`` / ``contact`` (with ``track_fps``): :meth:`tracking_from_qpos`'s contact labels; ``lock_feet``: its foot
         locking (the tracking dicts only).  With ``dynamics`` :meth:`dynamics_report` of the same qpos follows the clip reports (or
-        the motions) and precedes the tracks."""
+        the motions) and precedes the tracks.  With ``collision`` (``True`` or a dict of :meth:`self_collision_report`'s keywords)
+        that report follows the dynamics reports (or what precedes them) and precedes the tracks."""
         self._refuse_planar()
         if contact_bodies is not None and track_fps is None:
             raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
@@ -269,6 +270,9 @@ class MultiRobotRetargeting:
         res = (motions, {r: rep.numpy() for r, rep in reps.items()}) if report else (motions,)
         if dynamics:
             res += (self.dynamics_report({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps),)
+        if collision:
+            res += (self.self_collision_report({r: q for r, (q, _) in zip(self.robots, outs)}, offs,
+                                               **(collision if isinstance(collision, dict) else {})),)
         if track_fps is not None:
             res += (self.tracking_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, track_fps,
                                             contact_bodies=contact_bodies, contact=contact, **({"lock_feet": lock_feet} if lock_feet else {})),)
@@ -282,6 +286,15 @@ class MultiRobotRetargeting:
         from .dataset import _dynamics_report
         self._refuse_planar()
         return {r: _dynamics_report(eng, qpos[r], seq_offsets, fps, lowpass_hz, (tables or {}).get(r), dynamics_kwargs)
+                for r, eng in zip(self.robots, self.group.engines) if r in qpos}
+
+    def self_collision_report(self, qpos: Dict[str, torch.Tensor], seq_offsets: Sequence[int], capsules=None, pairs=None,
+                              margin: float = 0.0, radius: float = 0.03) -> Dict[str, Dict]:
+        """``dataset.self_collision_report`` per robot: ``{robot: statistics}`` of ``{robot: qpos [N, nq]}`` on the device, one
+        ``Engine.motion_self_collision`` call per member (the members share no grid).  ``capsules`` / ``pairs``: ``{robot: table}``
+        instead of the skeletons' at ``radius`` (a convention, not measured on any robot)."""
+        from .dataset import _self_collision_report
+        return {r: _self_collision_report(eng, qpos[r], seq_offsets, (capsules or {}).get(r), (pairs or {}).get(r), margin, radius)
                 for r, eng in zip(self.robots, self.group.engines) if r in qpos}
 
     def _solve(self, pos, quat, body_names, seq_offsets, chunk, burn_in, offset_to_ground, verify, human_heights, check, clip_start):

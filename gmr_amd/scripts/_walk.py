@@ -101,6 +101,10 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--max_pos_err", default=None, type=float, help="metres: a clip whose largest task position error exceeds this is not written and is listed in --hard_out")
     ap.add_argument("--dynamics_csv", default=None, type=str, help="write the per-clip inverse-dynamics statistics (frames over a torque limit, ground-reaction ratios, unloaded and non-finite frames, the worst joint and its torque ratio; one row per clip) to this CSV, named like --report_csv; needs the robot's MJCF file (GMR_ROOT) for masses and torque limits")
     ap.add_argument("--max_torque_ratio", default=None, type=float, help="a clip in which some joint needs more than this many times its torque limit is not written and is listed in --hard_out (with the clip report's difficulty: this flag computes the clip report too; --dynamics_csv alone does not)")
+    ap.add_argument("--collision_csv", default=None, type=str, help="write the per-clip self-collision statistics (smallest clearance and deepest penetration of the capsule proxies, its frame and pair, colliding frames and their longest run; one row per clip) to this CSV, named like --report_csv")
+    ap.add_argument("--max_penetration", default=None, type=float, metavar="M", help="metres: a clip whose capsule proxies penetrate each other deeper than this is not written and is listed in --hard_out (with the clip report's difficulty: this flag computes the clip report too; --collision_csv alone does not)")
+    ap.add_argument("--collision_radius", default=None, type=float, metavar="R", help="radius of the default proxies, capsules along the skeleton's links (default 0.03 m, a convention, not measured on any robot; the skeleton is not the robot's collision geometry)")
+    ap.add_argument("--collision_proxies", default=None, type=str, metavar="FILE.json", help="capsules (and optionally pairs) from this file instead of the skeleton's (gmr_amd.collision.save_proxies writes one); with --robots: robot:file;robot2:file2")
     ap.add_argument("--max_dof_step", default=None, type=float, help="radians: a clip whose largest joint step between consecutive frames exceeds this is not written and is listed in --hard_out")
     ap.add_argument("--track_fps", default=None, type=float, help="with --track_folder: also write every clip's tracking export (resampled root, joints and world body poses with their velocities, dataset.tracking_from_qpos) at this rate")
     ap.add_argument("--track_folder", default=None, type=str, help="with --track_fps: where the tracking exports go, <track_folder>/<relative path>.npz (with --robots <track_folder>/<robot>/...); the pickles are unchanged")
@@ -175,9 +179,9 @@ def track_path(args, target: str) -> str:
 
 
 def wants_report(args) -> bool:
-    """Whether the clip report is needed: one of its own flags is given, or ``--max_torque_ratio``, whose clips go to the hard list
-    with the clip report's difficulty.  ``--dynamics_csv`` alone does not compute it."""
-    return any(getattr(args, k, None) is not None for k in ("report_csv", "hard_out", "max_pos_err", "max_dof_step", "max_torque_ratio"))
+    """Whether the clip report is needed: one of its own flags is given, or ``--max_torque_ratio`` / ``--max_penetration``, whose
+    clips go to the hard list with the clip report's difficulty.  ``--dynamics_csv`` or ``--collision_csv`` alone does not compute it."""
+    return any(getattr(args, k, None) is not None for k in ("report_csv", "hard_out", "max_pos_err", "max_dof_step", "max_torque_ratio", "max_penetration"))
 
 
 def wants_dynamics(args) -> bool:
@@ -185,8 +189,41 @@ def wants_dynamics(args) -> bool:
     return any(getattr(args, k, None) is not None for k in ("dynamics_csv", "max_torque_ratio"))
 
 
+def wants_collision(args) -> bool:
+    """Whether the self-collision statistics are asked for."""
+    return any(getattr(args, k, None) is not None for k in ("collision_csv", "max_penetration"))
+
+
+def collision_kw(args, model=None) -> dict:
+    """The ``collision`` argument of ``retarget_clips`` from the flags ({} without them: nothing changes then).  ``model``: the
+    ``RobotModel`` (a proxies file may name bodies), or with ``--robots`` ``{robot: RobotModel}``: the tables are then
+    ``{robot: table}`` and ``--collision_proxies`` reads ``robot:file;robot2:file2``."""
+    if not wants_collision(args):
+        return {}
+    from ..collision import load_proxies
+    kw = {}
+    if getattr(args, "collision_radius", None) is not None:
+        kw["radius"] = args.collision_radius
+    spec = getattr(args, "collision_proxies", None)
+    if spec is not None:
+        if isinstance(model, dict):   # --robots
+            caps, prs = {}, {}
+            for part in (p for p in spec.split(";") if p.strip()):
+                r, sep, path = part.partition(":")
+                if not sep or r.strip() not in model:
+                    raise ValueError("--collision_proxies with --robots takes robot:file;robot2:file2, each robot one of --robots")
+                caps[r.strip()], pr = load_proxies(path.strip(), model[r.strip()])
+                if pr is not None:
+                    prs[r.strip()] = pr
+            kw.update(capsules=caps, pairs=prs)
+        else:
+            caps, pr = load_proxies(spec, model)
+            kw.update(capsules=caps, pairs=pr)
+    return {"collision": kw or True}
+
+
 def wants_sink(args) -> bool:
-    return wants_report(args) or wants_dynamics(args)
+    return wants_report(args) or wants_dynamics(args) or wants_collision(args)
 
 
 def report_path(path: str, robot=None, rank=None) -> str:
@@ -205,10 +242,12 @@ class ReportSink:
         self.csv = report_path(args.report_csv, robot, rank) if args.report_csv else None
         self.hard = report_path(args.hard_out, robot, rank) if args.hard_out else None
         self.dyn_csv = report_path(args.dynamics_csv, robot, rank) if getattr(args, "dynamics_csv", None) else None
+        self.col_csv = report_path(args.collision_csv, robot, rank) if getattr(args, "collision_csv", None) else None
         self.withheld, self._started = 0, False
 
-    def take(self, dataset, targets: Sequence[str], motions: list, report, dynamics=None):
-        """One batch: returns the (motions, targets) that are to be written.  ``dynamics``: the batch's ``dynamics_report``."""
+    def take(self, dataset, targets: Sequence[str], motions: list, report, dynamics=None, collision=None):
+        """One batch: returns the (motions, targets) that are to be written.  ``dynamics``: the batch's ``dynamics_report``;
+        ``collision``: its ``self_collision_report``."""
         names = [os.path.splitext(os.path.basename(t))[0] for t in targets]
         mask = dataset.report_hard_mask(report, self.args.max_pos_err, self.args.max_dof_step) if report is not None else np.zeros(len(names), dtype=bool)
         if dynamics is not None:
@@ -216,6 +255,11 @@ class ReportSink:
                 mask |= dataset.dynamics_hard_mask(dynamics, self.args.max_torque_ratio)
             if self.dyn_csv:
                 dataset.write_dynamics_csv(self.dyn_csv, names, dynamics, append=self._started)
+        if collision is not None:
+            if getattr(self.args, "max_penetration", None) is not None:
+                mask |= dataset.collision_hard_mask(collision, self.args.max_penetration)
+            if self.col_csv:
+                dataset.write_collision_csv(self.col_csv, names, collision, append=self._started)
         if self.csv and report is not None:
             dataset.write_report_csv(self.csv, names, report, append=self._started)
         if self.hard and report is not None:
@@ -226,7 +270,7 @@ class ReportSink:
 
     def close(self):
         if self.withheld:
-            print(f"{self.withheld} clips withheld (--max_pos_err / --max_dof_step / --max_torque_ratio)" + (f", listed in {self.hard}" if self.hard else ""))
+            print(f"{self.withheld} clips withheld (--max_pos_err / --max_dof_step / --max_torque_ratio / --max_penetration)" + (f", listed in {self.hard}" if self.hard else ""))
 
 
 def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callable, retarget_kw: Callable, workers: int, done: str) -> int:
@@ -255,6 +299,7 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
             track_kw["lowpass_hz"] = args.lowpass_hz
         track_kw.update(getattr(args, "contact_kw", {}))
         dyn_kw = {"dynamics": True} if wants_dynamics(args) else {}  # (absent without the flags: nothing changes then)
+        col_kw = collision_kw(args, model=g.model) if wants_collision(args) else {}  # (ditto)
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -264,12 +309,13 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
                     continue
                 targets = [target_of[f] for f in batch.files]
                 res = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                             clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw)
+                                             clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw)
                 res = res if isinstance(res, tuple) else (res,)
                 motions = res[0]
                 track_of = dict(zip(targets, res[-1])) if track_fps is not None else None
                 if sink is not None:
-                    motions, targets = sink.take(dataset, targets, motions, res[1] if rep_on else None, res[1 + rep_on] if dyn_kw else None)
+                    motions, targets = sink.take(dataset, targets, motions, res[1] if rep_on else None, res[1 + rep_on] if dyn_kw else None,
+                                                 res[1 + rep_on + bool(dyn_kw)] if col_kw else None)
                 writer.submit(motions, targets)
                 if track_of is not None:  # (a withheld clip has no tracking export either)
                     writer.submit([track_of[t] for t in targets], [track_path(args, t) for t in targets])
@@ -294,6 +340,7 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
         track_kw["lowpass_hz"] = args.lowpass_hz
     track_kw.update(getattr(args, "contact_kw", {}))
     dyn_kw = {"dynamics": True} if wants_dynamics(args) else {}
+    col_kw = collision_kw(args, model=dict(zip(mr.robots, mr.models))) if wants_collision(args) else {}
     with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
         for batch in batches([s for s, _ in pairs], mr.ik_columns):
             for f, why in batch.skipped:
@@ -302,15 +349,17 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
             if not len(batch):
                 continue
             res = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                    clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw)
+                                    clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw)
             res = res if isinstance(res, tuple) else (res,)
             motions, reps = res[0], res[1] if rep_on else None
             dyns = res[1 + rep_on] if dyn_kw else None
+            cols = res[1 + rep_on + bool(dyn_kw)] if col_kw else None
             for i, r in enumerate(mr.robots):
                 ms, ts = motions[r], [target_of[f][i] for f in batch.files]
                 track_of = dict(zip(ts, res[-1][r])) if track_fps is not None else None
                 if sinks is not None:
-                    ms, ts = sinks[r].take(dataset, ts, ms, reps[r] if reps is not None else None, dyns[r] if dyns is not None else None)
+                    ms, ts = sinks[r].take(dataset, ts, ms, reps[r] if reps is not None else None, dyns[r] if dyns is not None else None,
+                                             cols[r] if cols is not None else None)
                 writer.submit(ms, ts)
                 if track_of is not None:
                     writer.submit([track_of[t] for t in ts], [track_path(args, t) for t in ts])

@@ -68,7 +68,10 @@
  *   gmr_motion_dynamics  (no counterpart in the reference) what the consumers of the clips run on the host to filter them, MuJoCo's
  *                      inverse dynamics per frame: joint torques, the contact wrench on the root, centre of mass and ZMP, and per
  *                      clip torque-limit and ground-reaction statistics
- *   gmr_dof_to_rot     KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
+ *   gmr_motion_self_collision  (no counterpart in the reference) the self-penetration filter the consumers of the clips run on the
+ *                      host in a Python loop: FK plus a segment-segment distance per capsule pair and frame, and per clip the
+ *                      deepest penetration, where it happens and for how long
+ *   gmr_dof_to_rot    KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
  *   gmr_smplx_keypoints, gmr_smplx_keypoints_cols, gmr_smplx_keypoints_in  the numeric part of get_smplx_data_offline_fast (general_motion_retargeting/utils/smpl.py:109-198)
@@ -657,6 +660,81 @@ typedef struct gmr_dynamics_input {
   int32_t       *unloaded_frames_out, *nonfinite_frames_out;
 } gmr_dynamics_input;
 int gmr_motion_dynamics(gmr_model *m, const gmr_dynamics_input *in);
+
+/* Self-collision of retargeted qpos: per frame the smallest clearance over a list of capsule pairs, the pair that attains it and
+ * the number of pairs in collision; per clip the deepest frame, its pair, and how many frames collide and for how long in a row.
+ * A capsule is a segment fixed to a body plus a radius (a sphere when its ends coincide); which capsules and which pairs is the
+ * caller's table (gmr_amd/collision.py builds a default from the kinematic tree -- not the robot's collision geometry).
+ * All arithmetic is float64 without floating-point contraction, in the written order; a dot product u.v is (u_x v_x + u_y v_y) + u_z v_z.
+ *
+ * The whole call is this struct, its stream included (in->stream, in the sense of the stream-order paragraph at the top of this
+ * file); the struct is read completely before the call returns.  The call enqueues two kernels on in->stream (one when no
+ * statistic is asked for) and nothing else: no allocation, no copy, no synchronisation.  All arrays are device arrays.
+ *   qpos          f64 [n_frames][nq], free-joint layout (x y z, qw qx qy qz, hinges), concatenated clips (N = n_frames)
+ *   seq_offsets   int64 [n_seq+1]: clip s owns the rows a = clamp(seq_offsets[s], 0, N) to b = clamp(seq_offsets[s+1], a, N), T = b - a
+ *                 (gmr_motion_dynamics' rule)
+ *   cap_body      int32 [n_caps]: the body a capsule is fixed to.  Trusted; the kernel only clamps it into [0, nbody)
+ *   cap_p0, cap_p1   f64 [n_caps][3]: the ends in the body frame.  Trusted
+ *   cap_radius    f64 [n_caps].  Trusted
+ *   pairs         int32 [n_pairs][2]: the capsule pairs (A, B) that are tested.  Trusted; the kernel only clamps into [0, n_caps)
+ *   margin        a pair is a hit when its clearance is below margin (0: touching does not count)
+ * Poses are gmr_motion_footlock's FK (MuJoCo's convention, the root quaternion divided by its norm), not the float32 gmr_fk.  With
+ * x_j and the unit quaternion of body j, the world ends of capsule i on body j are P = x_j + R_j p0 and Q = x_j + R_j p1, R v
+ * evaluated as t = 2 (u x v), v + w t + (u x t) for the quaternion (w, u).
+ * Clearance of the pair (A, B) with ends (p1, q1) and (p2, q2):
+ *   d1 = q1 - p1, d2 = q2 - p2, r = p1 - p2;  a = d1.d1, e = d2.d2, f = d2.r, c = d1.r, b = d1.d2, den = a e - b b
+ *   s = den > 0 ? clamp01((b f - c e) / den) : 0;   t = e > 0 ? (b s + f) / e : 0
+ *   if not e > 0 or t < 0:  t = 0, s = a > 0 ? clamp01(-c / a) : 0;   else if t > 1:  t = 1, s = a > 0 ? clamp01((b - c) / a) : 0
+ *   (not e > 0: B is a sphere, and s is the point of A nearest its centre)
+ *   w = (p1 + s d1) - (p2 + t d2);   clearance = sqrt(w.w) - (r_A + r_B)
+ * clamp01(x) = x > 0 ? (x < 1 ? x : 1) : 0, which is 0 for a NaN.
+ * Outputs per frame, any may be NULL:
+ *   clearance_out [n_frames] f64   the minimum over the pairs; NaN when any pair's clearance is NaN (torch.min's rule, as the
+ *                                  clip minimum of gmr_motion_contacts)
+ *   pair_out [n_frames] i32        the lowest pair index that attains the minimum; -1 in a NaN frame
+ *   hits_out [n_frames] i32        pairs with clearance < margin; 0 in a NaN frame
+ * The minimum and its index are properties of the pair table: they do not depend on how the kernel spreads the pairs over its
+ * lanes or the frames over its wavefronts.
+ * Per-clip statistics, any may be NULL, reduced by the second kernel from the three per-frame outputs (all three are required when
+ * a statistic is asked for).  Frames are counted from 0 at the clip's first row:
+ *   clearance_min_out [n_seq] f64      the minimum over the clip's frames whose clearance is not NaN; +inf when there is none
+ *   worst_frame_out [n_seq] i32        the earliest frame of the clip at that minimum; -1 when there is none (T < 2^31)
+ *   worst_pair_out [n_seq] i32         that frame's pair_out; -1 when there is none
+ *   colliding_frames_out [n_seq] i32   frames with hits > 0
+ *   longest_run_out [n_seq] i32        the longest run of consecutive such frames (a NaN frame has no hits and ends a run)
+ *   hits_sum_out [n_seq] i64           the sum of hits over the clip
+ *   nonfinite_frames_out [n_seq] i32   frames whose clearance is NaN
+ * A clip without frames reports +inf, -1, -1, 0, 0, 0, 0.  Rows outside every clip are not written.  Two calls give identical
+ * bytes.  Non-finite input: a non-finite entry of a qpos row reaches only its own frame and its own clip's statistics; no byte of
+ * another frame's outputs or another clip's statistics changes.  A zero root quaternion gives a NaN frame.
+ * GMR_EINVAL: a non-finite margin, negative counts, and with work to do: n_caps < 1 or n_pairs < 1, NULL arrays, a statistic
+ * without the three per-frame outputs.  GMR_EUNSUPPORTED: a model of more than 64 bodies (its poses do not fit one
+ * wavefront's tile), a model in which a body precedes its parent, n_caps > 256, n_pairs > 32768.  n_frames = 0 or n_seq = 0
+ * returns GMR_OK without a launch.  A planar-base model is accepted: internally it carries a free-joint qpos, and nothing here is
+ * physics.  Asynchronous on in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 176; offsets qpos 0, n_frames 8, seq_offsets 16, n_seq 24, n_caps 28, n_pairs 32, reserved 36,
+ * cap_body 40, cap_p0 48, cap_p1 56, cap_radius 64, pairs 72, margin 80, stream 88, clearance_out 96, pair_out 104,
+ * hits_out 112, clearance_min_out 120, worst_frame_out 128, worst_pair_out 136, colliding_frames_out 144,
+ * longest_run_out 152, hits_sum_out 160, nonfinite_frames_out 168.  */
+typedef struct gmr_self_collision_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  int32_t        n_seq, n_caps;
+  int32_t        n_pairs, reserved;
+  const int32_t *cap_body;        /* device [n_caps] */
+  const double  *cap_p0, *cap_p1, *cap_radius;   /* device [n_caps][3], [n_caps][3], [n_caps] */
+  const int32_t *pairs;           /* device [n_pairs][2] */
+  double         margin;
+  void          *stream;          /* the call's stream */
+  double        *clearance_out;
+  int32_t       *pair_out, *hits_out;
+  double        *clearance_min_out;
+  int32_t       *worst_frame_out, *worst_pair_out, *colliding_frames_out, *longest_run_out;
+  int64_t       *hits_sum_out;
+  int32_t       *nonfinite_frames_out;
+} gmr_self_collision_input;
+int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
