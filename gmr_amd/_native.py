@@ -32,7 +32,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
            "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics",
-           "gmr_motion_self_collision"]
+           "gmr_motion_self_collision", "gmr_motion_mirror"]
 
 
 class IKParams(C.Structure):
@@ -171,6 +171,18 @@ class SelfCollisionInput(C.Structure):
       + [(k + "_out", C.c_void_p) for k in SELF_COLLISION_OUTPUTS]
 
 
+MIRROR_WORLD, MIRROR_CLIP_START = 0, 1    # GMR_MIRROR_WORLD, GMR_MIRROR_CLIP_START
+MIRROR_MODES = {"world": MIRROR_WORLD, "start": MIRROR_CLIP_START}
+MIRROR_MAX_NQ = 64
+
+
+class MirrorInput(C.Structure):
+    """``gmr_mirror_input`` (include/gmr_amd.h): the whole call of the mirror augmentation, its stream included."""
+
+    _fields_ = [("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("n_seq", C.c_int32), ("mode", C.c_int32),
+                ("col_src", C.c_void_p), ("col_sign", C.c_void_p), ("stream", C.c_void_p), ("qpos_out", C.c_void_p), ("reserved", C.c_int64)]
+
+
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
 CLIP_REPORT_LIMIT_EPS = 1e-3    # GMR_CLIP_REPORT_LIMIT_EPS
 
@@ -299,6 +311,8 @@ def load():
     L.gmr_motion_dynamics.argtypes = [vp, C.POINTER(DynamicsInput)]
     L.gmr_motion_self_collision.restype = C.c_int
     L.gmr_motion_self_collision.argtypes = [vp, C.POINTER(SelfCollisionInput)]
+    L.gmr_motion_mirror.restype = C.c_int
+    L.gmr_motion_mirror.argtypes = [vp, C.POINTER(MirrorInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

@@ -36,6 +36,7 @@
 #include "dynamics_kernel.hip.h"
 #include "footlock_kernel.hip.h"
 #include "self_collision_kernel.hip.h"
+#include "mirror_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
 #include "model_plan.h"
@@ -1836,6 +1837,40 @@ int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in) 
     set_err(m, "null argument"); return GMR_EINVAL;
   }
   return self_collision_run(m, *in, stats, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ mirror augmentation (mirror_kernel.hip.h)
+// The one launch of gmr_motion_mirror, and nothing else: no allocation, no copy, no synchronisation.  The grid is (clips, wavefronts
+// per clip): about kMirrorTargetWaves in the whole launch, at most one per tile of the mean clip; a clip's rows come from
+// seq_offsets on the device, so a longer clip makes its wavefronts walk further.  GMR_AMD_MIRROR_WAVES forces a number (the results
+// do not depend on it).
+static int mirror_run(gmr_model *m, const gmr_mirror_input &in, int nq, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::MirrorArgs a{};
+  a.qpos = in.qpos; a.out = in.qpos_out; a.seq_offsets = in.seq_offsets; a.col_src = in.col_src; a.col_sign = in.col_sign;
+  a.n_frames = in.n_frames; a.n_seq = in.n_seq; a.nq = nq; a.mode = in.mode;
+  const int64_t mean = (in.n_frames + in.n_seq - 1) / in.n_seq, tiles = (mean + gmr::kMirrorTile - 1) / gmr::kMirrorTile;
+  const int64_t want = (gmr::kMirrorTargetWaves + in.n_seq - 1) / in.n_seq;
+  unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, tiles), 65535));
+  if (const char *e = getenv("GMR_AMD_MIRROR_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) ty = (unsigned)v; }
+  hipLaunchKernelGGL(gmr::motion_mirror_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_mirror(gmr_model *m, const gmr_mirror_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (in->mode != GMR_MIRROR_WORLD && in->mode != GMR_MIRROR_CLIP_START) { set_err(m, "unknown mode %d", (int)in->mode); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "mirroring needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int nq = m->fk.ndof + 7;
+  if (nq > gmr::kMirrorMaxNq) { set_err(m, "a row of %d columns does not fit one wavefront", nq); return GMR_EUNSUPPORTED; }
+  if (in->n_frames == 0 || in->n_seq == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (!in->qpos || !in->qpos_out || !in->seq_offsets || !in->col_src || !in->col_sign) { set_err(m, "null argument"); return GMR_EINVAL; }
+  if (in->qpos_out == in->qpos) { set_err(m, "qpos_out must not be qpos: a row is permuted"); return GMR_EINVAL; }
+  return mirror_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

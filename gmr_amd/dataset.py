@@ -84,7 +84,7 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
                    track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
                    contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False, dynamics: bool = False,
-                   collision=None):
+                   collision=None, mirror=False):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -97,7 +97,13 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     motions and the report are made from the qpos as solved).  With ``dynamics`` the ``dynamics_report`` of the same qpos follows
     the clip report (or the motions, without ``report``) and precedes the tracks.  With ``collision`` (``True``, or a dict of
     ``self_collision_report``'s keywords: ``radius``, ``capsules``, ``pairs``, ``margin``) the ``self_collision_report`` of the same
-    qpos follows the dynamics report (or what precedes it) and precedes the tracks."""
+    qpos follows the dynamics report (or what precedes it) and precedes the tracks.  With ``mirror`` (``True``, or a dict of
+    ``augment_mirror``'s keywords ``about`` and ``plan``) the motions and the tracks are made from ``augment_mirror`` of the (smoothed)
+    qpos: twice the clips, clip ``S + i`` the mirror image of clip ``i``; the reports stay those of the ``S`` solved clips (a
+    mirrored clip has no human targets to be compared with).  A robot that is not symmetric raises ``SymmetryError`` before the solve."""
+    mirror_kw = dict(mirror) if isinstance(mirror, dict) else {}
+    if mirror and mirror_kw.get("plan") is None:
+        gmr.symmetry_plan()  # (SymmetryError here, before any solve)
     if contact_bodies is not None and track_fps is None:
         raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
     if lock_feet and contact_bodies is None:
@@ -110,21 +116,24 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                                   human_heights=human_heights, clip_start=clip_start)  # (raises on non-finite qpos / a capped QP)
         if lowpass_hz:
             qpos = smooth_qpos(gmr, qpos, seq_offsets, fps, lowpass_hz)
-        res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset),)
+        rep = None
     else:
         qpos, iters = gmr.retarget_batch(tpos, tquat, body_names, seq_offsets=seq_offsets, chunk=chunk, burn_in=burn_in,
                                          human_heights=human_heights, clip_start=clip_start, return_iters=True)
         if lowpass_hz:
             qpos = smooth_qpos(gmr, qpos, seq_offsets, fps, lowpass_hz)
         rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
-        res = (motions_from_qpos(gmr, qpos, seq_offsets, fps, height_adjust=height_adjust, root_origin_offset=root_origin_offset), rep.numpy())
+    q_all, offs_all, fps_all = augment_mirror(gmr, qpos, seq_offsets, fps, **mirror_kw) if mirror else (qpos, seq_offsets, fps)
+    res = (motions_from_qpos(gmr, q_all, offs_all, fps_all, height_adjust=height_adjust, root_origin_offset=root_origin_offset),)
+    if rep is not None:
+        res += (rep.numpy(),)
     if dynamics:
         res += (dynamics_report(gmr, qpos, seq_offsets, fps),)
     if collision:
         res += (self_collision_report(gmr, qpos, seq_offsets, **(collision if isinstance(collision, dict) else {})),)
     if track_fps is not None:
         lock_kw = {"lock_feet": lock_feet} if lock_feet else {}  # (absent without the flag: nothing changes then)
-        res += (tracking_from_qpos(gmr, qpos, seq_offsets, fps, track_fps, contact_bodies=contact_bodies, contact=contact, **lock_kw),)
+        res += (tracking_from_qpos(gmr, q_all, offs_all, fps_all, track_fps, contact_bodies=contact_bodies, contact=contact, **lock_kw),)
     return res[0] if len(res) == 1 else res
 
 
@@ -525,6 +534,47 @@ def collision_hard_mask(report: Dict, max_penetration: float) -> np.ndarray:
     return np.asarray(report["penetration_max"]) > float(max_penetration)
 
 
+# ------------------------------------------------------------------ mirror augmentation
+def mirror_qpos(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], about: str = "world", plan=None) -> torch.Tensor:
+    """The left-right mirrored copy of qpos ``[N, nq]`` float64 on the GPU (concatenated clips), one kernel
+    (``Engine.motion_mirror``; the definition is the contract above ``gmr_mirror_input`` in include/gmr_amd.h).  ``about="world"``:
+    the reflection in the world plane y = 0; ``"start"``: per clip in the vertical plane through its first root position along its
+    heading.  ``plan``: a ``gmr_amd.symmetry.SymmetryPlan``; ``None``: the robot's own at the default tolerances, which raises
+    ``SymmetryError`` for a robot that is not symmetric (pass looser tolerances to ``gmr.symmetry_plan`` or a plan of your own).
+    No clamp to the joint ranges: a symmetric robot's ranges mirror onto each other."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("mirroring assumes a free-joint root; a planar-base robot is not supported")
+    return gmr._engine.motion_mirror(qpos, np.ascontiguousarray(seq_offsets, dtype=np.int64), plan=plan, about=about)
+
+
+def augment_mirror(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, about: str = "start", plan=None):
+    """A batch of clips and its mirror images: ``(qpos2 [2N, nq], seq_offsets2 [2S + 1], fps2)``, the originals first, then the
+    mirrors in the same order, so clip ``S + i`` is the mirror of clip ``i``.  ``fps``: one rate (returned as it is) or one per clip
+    (returned twice over).  The result feeds ``tracking_from_qpos``, ``lock_feet``, ``dynamics_report`` and ``MotionLibrary``
+    unchanged; body names that go with a mirrored clip (``contact_bodies``) are ``plan.mirror_names(names)``."""
+    return _augment_mirror(gmr._engine, qpos, seq_offsets, fps, about, plan, planar=gmr.model.planar_base)
+
+
+def _augment_mirror(eng, qpos, seq_offsets, fps, about="start", plan=None, planar=False):
+    """``augment_mirror`` on an ``Engine``."""
+    if planar:
+        raise NotImplementedError("mirroring assumes a free-joint root; a planar-base robot is not supported")
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1 or offs[0] != 0 or offs[-1] != qpos.shape[0] or np.any(np.diff(offs) < 0):
+        raise ValueError("seq_offsets must span [0, N] without going back")
+    N = int(qpos.shape[0])
+    both = torch.empty((2 * N, int(qpos.shape[1])), dtype=qpos.dtype, device=qpos.device)
+    both[:N].copy_(qpos)
+    eng.motion_mirror(qpos, offs, plan=plan, about=about, out=both[N:])
+    if isinstance(fps, torch.Tensor):
+        f2 = torch.cat([fps, fps]) if fps.dim() else fps
+    elif np.ndim(fps) == 0:
+        f2 = fps
+    else:  # (a list stays a list of the same objects: what motions_from_qpos writes into the clips' dicts)
+        f2 = np.concatenate([fps, fps]) if isinstance(fps, np.ndarray) else list(fps) * 2
+    return both, np.concatenate([offs, offs[1:] + N]).astype(np.int64), f2
+
+
 # ------------------------------------------------------------------ the motion library
 class MotionLibrary:
     """A set of retargeted clips of one robot kept on the GPU as qpos (288 B per G1 frame) and sampled at arbitrary times: what a
@@ -534,9 +584,12 @@ class MotionLibrary:
     ``qpos`` ``[N, nq]`` float64 (free-joint layout ``[x y z qw qx qy qz hinges]``, concatenated clips) and ``seq_offsets``
     ``[S + 1]`` as numpy arrays or device tensors; ``fps``: one rate, or one per clip.  Attributes: ``num_clips``, ``num_frames``,
     ``durations`` (device float64 ``[S]``: ``(T - 1) / fps``, 0 for a clip of one frame or none).  ``lowpass_hz``: the clips are
-    filtered once at construction (``smooth_qpos``); ``None``: kept as they are."""
+    filtered once at construction (``smooth_qpos``); ``None``: kept as they are.  ``mirror=True``: the library stores
+    ``augment_mirror``'s result -- the (filtered) clips and then their mirror images about ``mirror_about`` -- so ``num_clips``
+    doubles and clip ``S + i`` is the mirror of clip ``i``; the sampling kernel knows nothing of it."""
 
-    def __init__(self, gmr: GeneralMotionRetargeting, qpos, seq_offsets, fps, lowpass_hz: Optional[float] = None):
+    def __init__(self, gmr: GeneralMotionRetargeting, qpos, seq_offsets, fps, lowpass_hz: Optional[float] = None, mirror: bool = False,
+                 mirror_about: str = "start", mirror_plan=None):
         if gmr.model.planar_base:
             raise NotImplementedError("the motion library assumes a free-joint root; a planar-base robot is not supported")
         from .schedule import clip_durations
@@ -557,6 +610,9 @@ class MotionLibrary:
         self.qpos = q.to(dev).contiguous()
         if lowpass_hz:  # filtered once, here: the queries read the smoothed clips
             self.qpos = smooth_qpos(gmr, self.qpos, offs, f, lowpass_hz)
+        if mirror:
+            self.qpos, offs, f = augment_mirror(gmr, self.qpos, offs, f, about=mirror_about, plan=mirror_plan)
+            dur, S = np.concatenate([dur, dur]), 2 * S
         self.seq_offsets = offs
         self.fps = f
         self.num_clips, self.num_frames = S, int(offs[-1])
@@ -569,7 +625,7 @@ class MotionLibrary:
         self._bodies = {}
 
     @classmethod
-    def from_motions(cls, gmr: GeneralMotionRetargeting, motions: Sequence[Dict], lowpass_hz: Optional[float] = None) -> "MotionLibrary":
+    def from_motions(cls, gmr: GeneralMotionRetargeting, motions: Sequence[Dict], lowpass_hz: Optional[float] = None, **mirror_kw) -> "MotionLibrary":
         """From motion dicts (``retarget_clips`` / the dict of ``load_robot_motion``): ``root_pos``, xyzw ``root_rot``, ``dof_pos``
         and ``fps`` of every clip, checked with ``validate_motion``."""
         nq = gmr._engine.nq
@@ -583,7 +639,7 @@ class MotionLibrary:
             fps.append(float(m["fps"]))
         qpos = np.concatenate(rows) if rows else np.zeros((0, nq))
         return cls(gmr, qpos, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), np.asarray(fps, dtype=np.float64),
-                   lowpass_hz=lowpass_hz)
+                   lowpass_hz=lowpass_hz, **mirror_kw)
 
     def sample_ids(self, n: int, generator=None) -> torch.Tensor:
         """``n`` clip ids (device int64) drawn in proportion to the durations; a clip without frames is never drawn."""

@@ -735,6 +735,8 @@ class Engine:
         self._inertial_dev = {}   # inertial tables on the device (inertial_device): None -> the robot's own, id(table) -> an explicit one
         self._collision_dev = {}      # collision proxies on the device (collision_device): (id(capsules), id(pairs)) -> the upload
         self._collision_default = {}  # the skeleton's proxies by radius (default_proxies), default pairs of explicit capsules
+        self._symmetry_default = None  # plan_symmetry(robot) at the default tolerances (symmetry_plan), made once
+        self._symmetry_dev = {}        # symmetry plans on the device (symmetry_device): id(plan) -> the upload
         if getattr(cm, "step_cap", None) is not None:  # the model's velocity limit (model.step_cap): part of the handle from here on
             self.set_step_cap(cm.step_cap)
 
@@ -1316,6 +1318,68 @@ class Engine:
         ci.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self._lib.gmr_motion_self_collision(self._h, C.byref(ci)), "gmr_motion_self_collision")
         return res
+
+    def symmetry_plan(self):
+        """``gmr_amd.symmetry.plan_symmetry`` of the robot at the default tolerances, made once per engine.  Raises
+        ``gmr_amd.symmetry.SymmetryError`` for a robot that is not left-right symmetric within them."""
+        if self._symmetry_default is None:
+            from .symmetry import plan_symmetry
+            self._symmetry_default = plan_symmetry(self.cm.robot)
+        return self._symmetry_default
+
+    def symmetry_device(self, plan):
+        """``col_src`` (int32) and ``col_sign`` (float64) of a :class:`gmr_amd.symmetry.SymmetryPlan` on the engine's device, checked
+        (the involution and ``7 <= col_src[c] < nq``: what ``gmr_motion_mirror`` trusts) and uploaded once per plan; its identity is
+        the key, so a plan changed in place needs a new object."""
+        cache = self._symmetry_dev
+        key = id(plan)
+        if key not in cache:
+            plan.check()
+            plan.check_robot(self.cm.robot)
+            cache[key] = ({"col_src": torch.from_numpy(np.ascontiguousarray(plan.col_src, dtype=np.int32)).to(self.device),
+                           "col_sign": torch.from_numpy(np.ascontiguousarray(plan.col_sign, dtype=np.float64)).to(self.device)},)
+            weakref.finalize(plan, cache.pop, key, None)
+        return cache[key][0]
+
+    def motion_mirror(self, qpos: torch.Tensor, seq_offsets, plan=None, about: str = "world", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The left-right mirrored copy of qpos ``[N, nq]`` float64 (engine layout, concatenated clips) in one kernel
+        (``gmr_motion_mirror``; the definition is the contract in include/gmr_amd.h): the hinge columns permuted with signs by
+        ``plan`` (a :class:`gmr_amd.symmetry.SymmetryPlan`; ``None``: :meth:`symmetry_plan`, which refuses an asymmetric robot), the
+        root reflected in the world plane y = 0 (``about="world"``) or, per clip, in the vertical plane through the clip's first
+        root position along its heading (``about="start"``: the mirrored clip starts where the original does, facing the same way).
+        ``seq_offsets`` ``[S + 1]``: a host sequence (uploaded once) or a device int64 tensor.  Rows outside every clip are not
+        written: without ``out`` they hold a copy of the input.  ``out``: a caller-owned ``[N, nq]`` tensor, not ``qpos``.
+        Asynchronous on the current stream; with ``out``, a cached plan and a device ``seq_offsets`` no allocation, no copy, no
+        synchronisation."""
+        dev = self.device
+        if about not in _native.MIRROR_MODES:
+            raise ValueError(f"about must be one of {sorted(_native.MIRROR_MODES)}")
+        if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+                or int(qpos.shape[1]) != self.nq or not qpos.is_contiguous():
+            raise EngineError(f"qpos must be a contiguous float64 [N, {self.nq}] tensor on the engine's device")
+        if isinstance(seq_offsets, torch.Tensor):
+            offs = seq_offsets
+            if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
+                raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
+        else:
+            o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+            if o.ndim != 1 or o.size < 1:
+                raise ValueError("seq_offsets must hold n_seq + 1 entries")
+            offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+        tab = self.symmetry_device(self.symmetry_plan() if plan is None else plan)
+        if out is None:
+            out = qpos.clone()  # rows outside every clip are not written
+        elif not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.float64 or tuple(out.shape) != tuple(qpos.shape) \
+                or not out.is_contiguous():
+            raise EngineError("out must be a contiguous float64 tensor of qpos's shape on the engine's device")
+        elif out.numel() and out.data_ptr() == qpos.data_ptr():
+            raise EngineError("out must not be qpos: a row is permuted, so the call cannot work in place")
+        mi = _native.MirrorInput()
+        mi.qpos, mi.n_frames, mi.seq_offsets, mi.n_seq = qpos.data_ptr(), int(qpos.shape[0]), offs.data_ptr(), int(offs.shape[0]) - 1
+        mi.mode, mi.col_src, mi.col_sign, mi.qpos_out = _native.MIRROR_MODES[about], tab["col_src"].data_ptr(), tab["col_sign"].data_ptr(), out.data_ptr()
+        mi.stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.gmr_motion_mirror(self._h, C.byref(mi)), "gmr_motion_mirror")
+        return out
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,
                     slot_col: Optional[np.ndarray] = None, height_scale=None, iters: Optional[torch.Tensor] = None,

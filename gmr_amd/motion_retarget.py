@@ -438,6 +438,23 @@ class GeneralMotionRetargeting:
         tq = (torch.from_numpy(np.ascontiguousarray(qpos)) if isinstance(qpos, np.ndarray) else qpos).to(self.device, torch.float64).contiguous()
         return self_collision_report(self, tq, seq_offsets, capsules, pairs, margin, radius)
 
+    def symmetry_plan(self, **tol):
+        """The robot's left-right symmetry plan (``gmr_amd.symmetry.plan_symmetry``): which body mirrors which, and the permutation
+        and signs of the hinge columns.  Without arguments the engine's cached plan at the default tolerances; ``tol_pos``,
+        ``tol_axis``, ``tol_range`` (conventions, 1e-3) make a new one.  Raises ``SymmetryError`` for a robot that is not symmetric
+        within them."""
+        if not tol:
+            return self._engine.symmetry_plan()
+        from .symmetry import plan_symmetry
+        return plan_symmetry(self.model, **tol)
+
+    def mirror_qpos(self, qpos, seq_offsets, about: str = "world", plan=None):
+        """The left-right mirrored copy of retargeted qpos ``[N, nq]`` (numpy or CUDA torch, engine layout, concatenated clips) on
+        the GPU (``dataset.mirror_qpos``, ``Engine.motion_mirror``) -> device float64 ``[N, nq]``."""
+        from .dataset import mirror_qpos
+        tq = (torch.from_numpy(np.ascontiguousarray(qpos)) if isinstance(qpos, np.ndarray) else qpos).to(self.device, torch.float64).contiguous()
+        return mirror_qpos(self, tq, seq_offsets, about=about, plan=plan)
+
     def fk_batch(self, root_pos, root_rot_xyzw, dof_pos, want_rot: bool = False):
         """Batched FK in the ``KinematicsModel.forward_kinematics`` convention (float32, xyzw; kinematics_model.py:213-246) on this
         object's robot: ``root_pos [T,3]``, ``root_rot_xyzw [T,4]``, ``dof_pos [T,ndof]`` -> ``body_pos [T,nbody,3]`` (and

@@ -238,7 +238,7 @@ class MultiRobotRetargeting:
                        root_origin_offset: bool = True, chunk=0, burn_in: int = 0, human_heights: Optional[Sequence[float]] = None,
                        clip_start: str = "qpos0", report: bool = False, track_fps: Optional[float] = None,
                        lowpass_hz: Optional[float] = None, contact_bodies: Optional[Dict[str, Sequence[str]]] = None, contact=None,
-                       lock_feet=False, dynamics: bool = False, collision=None):
+                       lock_feet=False, dynamics: bool = False, collision=None, mirror=False):
         """``dataset.retarget_clips`` for every robot: one solve (:meth:`retarget_batch`'s), then :meth:`motions_from_qpos` on the
         solved qpos, which stays on the device.  Returns ``{robot: [motion dict per clip]}``; each robot's clips feed
         ``dataset.MotionWriter.submit`` as they are.  With ``report`` a second value is returned: ``{robot: engine.ClipReport}``
@@ -248,8 +248,16 @@ class MultiRobotRetargeting:
         ``contact_bodies`` / ``contact`` (with ``track_fps``): :meth:`tracking_from_qpos`'s contact labels; ``lock_feet``: its foot
         locking (the tracking dicts only).  With ``dynamics`` :meth:`dynamics_report` of the same qpos follows the clip reports (or
         the motions) and precedes the tracks.  With ``collision`` (``True`` or a dict of :meth:`self_collision_report`'s keywords)
-        that report follows the dynamics reports (or what precedes them) and precedes the tracks."""
+        that report follows the dynamics reports (or what precedes them) and precedes the tracks.  With ``mirror`` (``True``, or a
+        dict: ``about``, and ``plan`` as ``{robot: SymmetryPlan}``) the motions and the tracks are made from
+        ``dataset.augment_mirror`` of every robot's qpos, one ``Engine.motion_mirror`` call per robot (the robots share no grid):
+        twice the clips per robot, clip ``S + i`` the mirror image of clip ``i``; the reports stay those of the solved clips.  A
+        robot whose symmetry plan is refused raises ``SymmetryError`` before any solve."""
         self._refuse_planar()
+        mirror_kw = dict(mirror) if isinstance(mirror, dict) else {}
+        plans = mirror_kw.pop("plan", None) or {}
+        if mirror:
+            plans = {r: plans[r] if plans.get(r) is not None else eng.symmetry_plan() for r, eng in zip(self.robots, self.group.engines)}
         if contact_bodies is not None and track_fps is None:
             raise ValueError("contact_bodies needs track_fps: the labels are made on the tracking export")
         if lock_feet and contact_bodies is None:
@@ -265,8 +273,12 @@ class MultiRobotRetargeting:
         if report:
             reps = self.clip_report({r: q for r, (q, _) in zip(self.robots, outs)}, tpos, tquat, body_names, offs, human_heights,
                                     iters={r: it for r, (_, it) in zip(self.robots, outs)})
-        motions = self.motions_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, height_adjust=height_adjust,
-                                         root_origin_offset=root_origin_offset)
+        q_all, offs_all, fps_all = {r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps
+        if mirror:
+            from .dataset import _augment_mirror
+            for r, eng in zip(self.robots, self.group.engines):
+                q_all[r], offs_all, fps_all = _augment_mirror(eng, q_all[r], offs, fps, plan=plans[r], **mirror_kw)
+        motions = self.motions_from_qpos(q_all, offs_all, fps_all, height_adjust=height_adjust, root_origin_offset=root_origin_offset)
         res = (motions, {r: rep.numpy() for r, rep in reps.items()}) if report else (motions,)
         if dynamics:
             res += (self.dynamics_report({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps),)
@@ -274,7 +286,7 @@ class MultiRobotRetargeting:
             res += (self.self_collision_report({r: q for r, (q, _) in zip(self.robots, outs)}, offs,
                                                **(collision if isinstance(collision, dict) else {})),)
         if track_fps is not None:
-            res += (self.tracking_from_qpos({r: q for r, (q, _) in zip(self.robots, outs)}, offs, fps, track_fps,
+            res += (self.tracking_from_qpos(q_all, offs_all, fps_all, track_fps,
                                             contact_bodies=contact_bodies, contact=contact, **({"lock_feet": lock_feet} if lock_feet else {})),)
         return res[0] if len(res) == 1 else res
 

@@ -115,6 +115,9 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--contact_speed_on", default=None, type=float, metavar="M_PER_S", help="a body enters contact at or below this speed (default 0.3)")
     ap.add_argument("--contact_speed_off", default=None, type=float, metavar="M_PER_S", help="... and leaves it above this speed (default 0.6)")
     ap.add_argument("--lock_feet", default=False, action="store_true", help="with --contact_bodies: remove the foot slide of those bodies from qpos before the tracking exports are made (dataset.lock_feet, on the GPU; the .npz gain footlock_stats_*); the pickles are unchanged; default: off")
+    ap.add_argument("--mirror", default=False, action="store_true", help="also write the left-right mirrored copy of every clip, X_mirror.pkl beside X.pkl (and X_mirror.npz beside a tracking export), made on the GPU from the solved qpos (dataset.augment_mirror) with the same post-processing; a robot that is not symmetric within 1e-3 (gmr_amd.symmetry.plan_symmetry) ends the run before any file is read; the reports stay those of the solved clips; default: off")
+    ap.add_argument("--mirror_about", default="start", choices=["world", "start"], help="with --mirror: reflect in the world plane y = 0 (world), or each clip in the vertical plane through its first root position along its heading, so that the mirrored clip starts where the original does (start, the default)")
+    ap.add_argument("--mirror_plan", default=None, type=str, metavar="FILE.json", help="with --mirror: the symmetry plan from this file (gmr_amd.symmetry.save_plan writes one) instead of the robot's own; with --robots: robot:file;robot2:file2")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -127,6 +130,49 @@ def resolve_track(ap, args) -> None:
     if getattr(args, "lowpass_hz", None) is not None and not args.lowpass_hz > 0:
         ap.error("--lowpass_hz must be positive")
     resolve_contact(ap, args)
+    resolve_mirror(ap, args)
+
+
+def mirror_path(target: str) -> str:
+    """Where the mirrored copy of a clip goes: ``X_mirror.pkl`` beside ``X.pkl``."""
+    root, ext = os.path.splitext(target)
+    return root + "_mirror" + ext
+
+
+def resolve_mirror(ap, args) -> None:
+    """``--mirror``: plans every robot's symmetry on the host, before a file is read or a GPU is touched, and ends the run with the
+    ``SymmetryError`` text for a robot that is refused.  Sets ``args.mirror_kw``: the ``mirror`` argument of ``retarget_clips``
+    (empty without the flag: nothing changes then)."""
+    args.mirror_kw = {}
+    spec = getattr(args, "mirror_plan", None)
+    if not getattr(args, "mirror", False):
+        if spec is not None:
+            ap.error("--mirror_plan needs --mirror")
+        return
+    from .. import params
+    from ..mjcf import load_robot
+    from ..symmetry import SymmetryError, load_plan, plan_symmetry
+    robots = getattr(args, "robot_list", None)
+    files = {}
+    if spec is not None and robots is None:
+        files[args.robot] = spec
+    elif spec is not None:
+        for part in (p for p in spec.split(";") if p.strip()):
+            r, sep, path = part.partition(":")
+            if not sep or r.strip() not in robots or r.strip() in files:
+                ap.error("--mirror_plan with --robots takes robot:file;robot2:file2, each robot one of --robots and named once")
+            files[r.strip()] = path.strip()
+    plans = {}
+    for r in (robots if robots is not None else [args.robot]):
+        if r not in params.ROBOT_XML_DICT:
+            ap.error(f"--mirror: unknown robot {r!r}")
+        try:
+            model = load_robot(params.ROBOT_XML_DICT[r], name=r)
+            plans[r] = load_plan(files[r]) if r in files else plan_symmetry(model)
+            plans[r].check_robot(model)
+        except (SymmetryError, NotImplementedError) as e:
+            ap.error(f"--mirror: {e}")
+    args.mirror_kw = {"mirror": {"about": args.mirror_about, "plan": plans if robots is not None else plans[args.robot]}}
 
 
 _CONTACT_THRESHOLDS = ("height_on", "height_off", "speed_on", "speed_off")
@@ -300,6 +346,7 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         track_kw.update(getattr(args, "contact_kw", {}))
         dyn_kw = {"dynamics": True} if wants_dynamics(args) else {}  # (absent without the flags: nothing changes then)
         col_kw = collision_kw(args, model=g.model) if wants_collision(args) else {}  # (ditto)
+        mir_kw = getattr(args, "mirror_kw", {})  # (ditto)
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -309,16 +356,22 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
                     continue
                 targets = [target_of[f] for f in batch.files]
                 res = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                             clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw)
+                                             clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw, **mir_kw)
                 res = res if isinstance(res, tuple) else (res,)
-                motions = res[0]
-                track_of = dict(zip(targets, res[-1])) if track_fps is not None else None
+                S = len(targets)
+                motions, mirror_of = res[0][:S], dict(zip(targets, res[0][S:]))  # (with --mirror clip S + i is the mirror of clip i)
+                track_of = dict(zip(targets, res[-1][:S])) if track_fps is not None else None
+                track_mirror_of = dict(zip(targets, res[-1][S:])) if track_fps is not None else {}
                 if sink is not None:
                     motions, targets = sink.take(dataset, targets, motions, res[1] if rep_on else None, res[1 + rep_on] if dyn_kw else None,
                                                  res[1 + rep_on + bool(dyn_kw)] if col_kw else None)
                 writer.submit(motions, targets)
                 if track_of is not None:  # (a withheld clip has no tracking export either)
                     writer.submit([track_of[t] for t in targets], [track_path(args, t) for t in targets])
+                if mirror_of:  # (nor a mirrored copy)
+                    writer.submit([mirror_of[t] for t in targets], [mirror_path(t) for t in targets])
+                if track_mirror_of:
+                    writer.submit([track_mirror_of[t] for t in targets], [mirror_path(track_path(args, t)) for t in targets])
         if sink is not None:
             sink.close()
         print(f"{writer.written} files written, {failed} could not be loaded")
@@ -341,6 +394,7 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
     track_kw.update(getattr(args, "contact_kw", {}))
     dyn_kw = {"dynamics": True} if wants_dynamics(args) else {}
     col_kw = collision_kw(args, model=dict(zip(mr.robots, mr.models))) if wants_collision(args) else {}
+    mir_kw = getattr(args, "mirror_kw", {})
     with dataset.MotionWriter(workers=max(1, workers), override=args.override) as writer:
         for batch in batches([s for s, _ in pairs], mr.ik_columns):
             for f, why in batch.skipped:
@@ -349,20 +403,27 @@ def _convert_robots(args, pairs, src_human: str, batches: Callable, retarget_kw:
             if not len(batch):
                 continue
             res = mr.retarget_clips(batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                    clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw)
+                                    clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw, **mir_kw)
             res = res if isinstance(res, tuple) else (res,)
             motions, reps = res[0], res[1] if rep_on else None
             dyns = res[1 + rep_on] if dyn_kw else None
             cols = res[1 + rep_on + bool(dyn_kw)] if col_kw else None
             for i, r in enumerate(mr.robots):
-                ms, ts = motions[r], [target_of[f][i] for f in batch.files]
-                track_of = dict(zip(ts, res[-1][r])) if track_fps is not None else None
+                ts = [target_of[f][i] for f in batch.files]
+                S = len(ts)
+                ms, mirror_of = motions[r][:S], dict(zip(ts, motions[r][S:]))  # (with --mirror clip S + i is the mirror of clip i)
+                track_of = dict(zip(ts, res[-1][r][:S])) if track_fps is not None else None
+                track_mirror_of = dict(zip(ts, res[-1][r][S:])) if track_fps is not None else {}
                 if sinks is not None:
                     ms, ts = sinks[r].take(dataset, ts, ms, reps[r] if reps is not None else None, dyns[r] if dyns is not None else None,
                                              cols[r] if cols is not None else None)
                 writer.submit(ms, ts)
                 if track_of is not None:
                     writer.submit([track_of[t] for t in ts], [track_path(args, t) for t in ts])
+                if mirror_of:
+                    writer.submit([mirror_of[t] for t in ts], [mirror_path(t) for t in ts])
+                if track_mirror_of:
+                    writer.submit([track_mirror_of[t] for t in ts], [mirror_path(track_path(args, t)) for t in ts])
     if sinks is not None:
         for sink in sinks.values():
             sink.close()

@@ -71,6 +71,8 @@
  *   gmr_motion_self_collision  (no counterpart in the reference) the self-penetration filter the consumers of the clips run on the
  *                      host in a Python loop: FK plus a segment-segment distance per capsule pair and frame, and per clip the
  *                      deepest penetration, where it happens and for how long
+ *   gmr_motion_mirror  (no counterpart in the reference) the left-right mirrored copy of every clip, the augmentation a tracking or
+ *                      AMP pipeline doubles its data with: a signed permutation of the hinge columns and the reflected root
  *   gmr_dof_to_rot    KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -735,6 +737,68 @@ typedef struct gmr_self_collision_input {
   int32_t       *nonfinite_frames_out;
 } gmr_self_collision_input;
 int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in);
+
+/* The left-right mirrored copy of retargeted qpos: every row's hinge columns permuted with signs, its root reflected.  Which
+ * column is the image of which is the caller's table (gmr_amd/symmetry.py derives it from the kinematic tree and refuses a
+ * robot that is not symmetric); the entry does not judge it.
+ *
+ * The whole call is this struct, its stream included (in->stream, in the sense of the stream-order paragraph at the top of this
+ * file); the struct is read completely before the call returns.  The call enqueues one kernel on in->stream and nothing else: no
+ * allocation, no copy, no synchronisation, no scratch.  All arrays are device arrays; loads and stores are element-wise, so every
+ * array needs the alignment of its element type only.
+ *   qpos          f64 [n_frames][nq], free-joint layout (x y z, qw qx qy qz, hinges), concatenated clips (N = n_frames)
+ *   seq_offsets   int64 [n_seq+1]: clip s owns the rows a = clamp(seq_offsets[s], 0, N) to b = clamp(seq_offsets[s+1], a, N), T = b - a
+ *                 (gmr_motion_dynamics' rule).  Clips are expected not to overlap
+ *   col_src       int32 [nq], col_sign f64 [nq]: only the elements 7 .. nq-1 are read.  Trusted: the caller guarantees
+ *                 7 <= col_src[c] < nq (gmr_amd.symmetry.SymmetryPlan checks it, and that the map is an involution, before the
+ *                 Python layer uploads a table); the kernel only clamps col_src[c] into [7, nq-1] and reads no more of col_sign[c]
+ *                 than whether it is < 0
+ *   mode          GMR_MIRROR_WORLD or GMR_MIRROR_CLIP_START
+ *   qpos_out      f64 [n_frames][nq], not qpos: a row is permuted, so the call cannot work in place
+ * Per row q with root position p = q[0:3] and root quaternion r = q[3:7] (w x y z):
+ *   hinges, both modes:  out[c] = q[col_src[c]] for c >= 7, negated when col_sign[c] < 0.  A copy and a sign flip: with
+ *   col_sign[c] = +-1 this is col_sign[c] * q[col_src[c]], and no arithmetic touches the value (a NaN keeps its payload).
+ *   GMR_MIRROR_WORLD (0), the reflection in the world plane y = 0:  p' = (p_x, -p_y, p_z),  r' = (w, -x, y, -z).  The whole call is
+ *   copies and sign flips: the output is bit-exact against this definition, and with a table that is an involution mirroring
+ *   twice returns the input bytes (a negation flips the sign bit, so -0.0 comes back as -0.0 too).
+ *   GMR_MIRROR_CLIP_START (1), the reflection of each clip in the vertical plane through its first row's root position p0 along
+ *   that row's heading, so that the mirrored clip starts where the original started, facing the same way.  With the first row's
+ *   root (p0, r0), f = R(r0 / |r0|) e_x and the heading psi = atan2(f_y, f_x):
+ *     p'_xy = p0_xy + [[cos 2psi, sin 2psi], [sin 2psi, -cos 2psi]] (p - p0)_xy,  p'_z = p_z (a copy)
+ *     r'    = r_z(2 psi) (x) (w, -x, y, -z),  r_z(2 psi) = (cos psi, 0, 0, sin psi)
+ *   psi = 0 when f_x^2 + f_y^2 < 1e-12: a convention for a root that points straight up, where the heading is not defined.
+ *   The map is linear in r, so sign continuity and the norm carry over; nothing is normalised.  No trigonometric function is
+ *   evaluated.  All arithmetic is float64 without floating-point contraction, in this order:
+ *     n = sqrt(((w0 w0 + x0 x0) + y0 y0) + z0 z0);  (w, x, y, z) = r0 / n, element-wise
+ *     f_x = 1 - 2 (y y + z z);  f_y = 2 (x y + w z);  h2 = f_x f_x + f_y f_y
+ *     h2 < 1e-12:  cp = 1, sp = 0, c2 = 1, s2 = 0;   otherwise  h = sqrt(h2), cp = f_x / h, sp = f_y / h,
+ *                  c2 = (f_x f_x - f_y f_y) / h2, s2 = (2 f_x f_y) / h2      (cos psi, sin psi, cos 2psi, sin 2psi)
+ *     d = p - p0:  p'_x = p0_x + (c2 d_x + s2 d_y),  p'_y = p0_y + ((-c2) d_y + s2 d_x)
+ *     r'_w = cp w + sp z,  r'_x = (-cp) x + (-sp) y,  r'_y = cp y + (-sp) x,  r'_z = (-cp) z + sp w       (of the row's r)
+ * Rows outside every clip are not written.  A clip without frames does no work.  Two calls give identical bytes.
+ * Non-finite input: in GMR_MIRROR_WORLD a non-finite entry reaches exactly the output element it is copied to.  In
+ * GMR_MIRROR_CLIP_START a non-finite root entry of a clip's first row reaches root columns of that clip's rows only, a non-finite
+ * root entry of another row reaches root columns of that row only.  Hinge columns are never affected by the root, and no other
+ * clip changes, in either mode.
+ * GMR_EINVAL: negative counts, an unknown mode, and with work to do: NULL arrays, qpos_out == qpos.  GMR_EUNSUPPORTED: nq > 64 (a
+ * row does not fit one wavefront), a planar-base model.  n_frames = 0 or n_seq = 0 returns GMR_OK without a launch.
+ * Asynchronous on in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 72; offsets qpos 0, n_frames 8, seq_offsets 16, n_seq 24, mode 28, col_src 32, col_sign 40, stream 48,
+ * qpos_out 56, reserved 64.  */
+#define GMR_MIRROR_WORLD 0
+#define GMR_MIRROR_CLIP_START 1
+typedef struct gmr_mirror_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  int32_t        n_seq, mode;
+  const int32_t *col_src;         /* device [nq] */
+  const double  *col_sign;        /* device [nq] */
+  void          *stream;          /* the call's stream */
+  double        *qpos_out;        /* device [n_frames][nq] f64, not qpos */
+  int64_t        reserved;        /* 0 */
+} gmr_mirror_input;
+int gmr_motion_mirror(gmr_model *m, const gmr_mirror_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
