@@ -30,6 +30,9 @@ def __getattr__(name):
     if name == "load_robot_motion":
         from .dataset import load_robot_motion
         return load_robot_motion
+    if name in ("compose_clips", "repeat_clip"):
+        from . import dataset
+        return getattr(dataset, name)
     if name == "RobotMotionViewer":
         raise AttributeError("gmr_amd has no RobotMotionViewer: the MuJoCo viewer is outside this engine's scope (use the reference's with the qpos this engine returns)")
     raise AttributeError(name)

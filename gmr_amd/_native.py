@@ -32,7 +32,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
            "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics",
-           "gmr_motion_self_collision", "gmr_motion_mirror"]
+           "gmr_motion_self_collision", "gmr_motion_mirror", "gmr_motion_compose"]
 
 
 class IKParams(C.Structure):
@@ -183,6 +183,17 @@ class MirrorInput(C.Structure):
                 ("col_src", C.c_void_p), ("col_sign", C.c_void_p), ("stream", C.c_void_p), ("qpos_out", C.c_void_p), ("reserved", C.c_int64)]
 
 
+COMPOSE_MAX_NQ = 64
+
+
+class ComposeInput(C.Structure):
+    """``gmr_compose_input`` (include/gmr_amd.h): the whole call of the clip composition, its stream included."""
+
+    _fields_ = [("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seg_src", C.c_void_p), ("seg_len", C.c_void_p), ("seg_blend", C.c_void_p),
+                ("seg_out", C.c_void_p), ("clip_segs", C.c_void_p), ("n_seg", C.c_int32), ("n_out", C.c_int32), ("n_out_frames", C.c_int64),
+                ("stream", C.c_void_p), ("qpos_out", C.c_void_p), ("seg_transform", C.c_void_p), ("reserved", C.c_int64)]
+
+
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
 CLIP_REPORT_LIMIT_EPS = 1e-3    # GMR_CLIP_REPORT_LIMIT_EPS
 
@@ -313,6 +324,8 @@ def load():
     L.gmr_motion_self_collision.argtypes = [vp, C.POINTER(SelfCollisionInput)]
     L.gmr_motion_mirror.restype = C.c_int
     L.gmr_motion_mirror.argtypes = [vp, C.POINTER(MirrorInput)]
+    L.gmr_motion_compose.restype = C.c_int
+    L.gmr_motion_compose.argtypes = [vp, C.POINTER(ComposeInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

@@ -37,6 +37,7 @@
 #include "footlock_kernel.hip.h"
 #include "self_collision_kernel.hip.h"
 #include "mirror_kernel.hip.h"
+#include "compose_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
 #include "model_plan.h"
@@ -1871,6 +1872,45 @@ int gmr_motion_mirror(gmr_model *m, const gmr_mirror_input *in) {
   if (!in->qpos || !in->qpos_out || !in->seq_offsets || !in->col_src || !in->col_sign) { set_err(m, "null argument"); return GMR_EINVAL; }
   if (in->qpos_out == in->qpos) { set_err(m, "qpos_out must not be qpos: a row is permuted"); return GMR_EINVAL; }
   return mirror_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ composed clips (compose_kernel.hip.h)
+// The two launches of gmr_motion_compose, and nothing else: no allocation, no copy, no synchronisation.  The plan kernel takes one
+// wavefront per output clip.  The grid of the other is (segments, wavefronts per segment): about kComposeTargetWaves in the whole
+// launch, at most one per tile of the mean segment; a segment's rows come from the tables on the device, so a longer segment makes
+// its wavefronts walk further.  GMR_AMD_COMPOSE_WAVES forces a number (the results do not depend on it).
+static int compose_run(gmr_model *m, const gmr_compose_input &in, int nq, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::ComposeArgs a{};
+  a.qpos = in.qpos; a.out = in.qpos_out; a.seg_transform = in.seg_transform; a.seg_src = in.seg_src; a.seg_len = in.seg_len;
+  a.seg_blend = in.seg_blend; a.seg_out = in.seg_out; a.clip_segs = in.clip_segs;
+  a.n_frames = in.n_frames; a.n_out_frames = in.n_out_frames; a.n_seg = in.n_seg; a.n_out = in.n_out; a.nq = nq;
+  const int64_t mean = (in.n_out_frames + in.n_seg - 1) / in.n_seg, tiles = (mean + gmr::kComposeTile - 1) / gmr::kComposeTile;
+  const int64_t want = (gmr::kComposeTargetWaves + in.n_seg - 1) / in.n_seg;
+  unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, tiles), 65535));
+  if (const char *e = getenv("GMR_AMD_COMPOSE_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) ty = (unsigned)v; }
+  hipLaunchKernelGGL(gmr::motion_compose_plan_kernel, dim3((unsigned)in.n_out), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  hipLaunchKernelGGL(gmr::motion_compose_kernel, dim3((unsigned)in.n_seg, ty), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_compose(gmr_model *m, const gmr_compose_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seg < 0 || in->n_out < 0 || in->n_out_frames < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "composing needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int nq = m->fk.ndof + 7;
+  if (nq > gmr::kComposeMaxNq) { set_err(m, "a row of %d columns does not fit one wavefront", nq); return GMR_EUNSUPPORTED; }
+  if (in->n_seg == 0 || in->n_out == 0 || in->n_out_frames == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (!in->qpos || !in->qpos_out || !in->seg_transform || !in->seg_src || !in->seg_len || !in->seg_blend || !in->seg_out || !in->clip_segs) {
+    set_err(m, "null argument"); return GMR_EINVAL;
+  }
+  if (in->n_frames == 0) { set_err(m, "segments of a motion without frames"); return GMR_EINVAL; }
+  if (in->qpos_out == in->qpos) { set_err(m, "qpos_out must not be qpos: an output row reads other rows"); return GMR_EINVAL; }
+  return compose_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

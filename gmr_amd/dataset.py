@@ -575,6 +575,27 @@ def _augment_mirror(eng, qpos, seq_offsets, fps, about="start", plan=None, plana
     return both, np.concatenate([offs, offs[1:] + N]).astype(np.int64), f2
 
 
+# ------------------------------------------------------------------ composed clips
+def compose_clips(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], sequences, blend=8):
+    """Long reference motions from segments of the clips, on the GPU (``Engine.motion_compose``; the definition is the contract
+    above ``gmr_compose_input`` in include/gmr_amd.h): ``sequences`` is a list of output clips, each a list of
+    ``gmr_amd.compose.Segment(clip, begin, length)``; every segment but the first of its output clip is turned and shifted in the
+    plane onto the end of the one before it and cross-faded into it over ``blend`` frames (one int, or one per transition).
+    Returns ``(qpos_out, seq_offsets_out, seg_transform)``: ordinary qpos and offsets for ``lock_feet`` (which removes the slide a
+    cross-fade puts into planted feet), ``tracking_from_qpos``, ``dynamics_report`` and ``MotionLibrary``, and every segment's
+    placement ``(c, s, tx, ty, hw, hz)``.  A plan that breaks an invariant raises ``gmr_amd.compose.ComposeError``."""
+    from .compose import ComposePlan
+    plan = ComposePlan(seq_offsets, sequences, blend)
+    qpos_out, seg_transform = gmr._engine.motion_compose(qpos, plan)
+    return qpos_out, np.array(plan.out_offsets), seg_transform  # (a copy: the plan's arrays are read-only)
+
+
+def repeat_clip(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], clip: int, times: int, blend=8):
+    """One output clip: clip ``clip`` ``times`` times over, each pass starting where the last one ended (``compose_clips``)."""
+    frames = int(seq_offsets[clip + 1]) - int(seq_offsets[clip])
+    return compose_clips(gmr, qpos, seq_offsets, [[(clip, 0, frames)] * int(times)], blend)
+
+
 # ------------------------------------------------------------------ the motion library
 class MotionLibrary:
     """A set of retargeted clips of one robot kept on the GPU as qpos (288 B per G1 frame) and sampled at arbitrary times: what a

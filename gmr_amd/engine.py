@@ -737,6 +737,7 @@ class Engine:
         self._collision_default = {}  # the skeleton's proxies by radius (default_proxies), default pairs of explicit capsules
         self._symmetry_default = None  # plan_symmetry(robot) at the default tolerances (symmetry_plan), made once
         self._symmetry_dev = {}        # symmetry plans on the device (symmetry_device): id(plan) -> the upload
+        self._compose_dev = {}         # composition plans on the device (compose_device): id(plan) -> the upload
         if getattr(cm, "step_cap", None) is not None:  # the model's velocity limit (model.step_cap): part of the handle from here on
             self.set_step_cap(cm.step_cap)
 
@@ -1380,6 +1381,57 @@ class Engine:
         mi.stream = torch.cuda.current_stream(dev).cuda_stream
         self._check(self._lib.gmr_motion_mirror(self._h, C.byref(mi)), "gmr_motion_mirror")
         return out
+
+    def compose_device(self, plan):
+        """The five tables of a :class:`gmr_amd.compose.ComposePlan` on the engine's device, uploaded once per plan (the plan
+        checked its invariants when it was made: what ``gmr_motion_compose`` trusts); its identity is the key."""
+        cache = self._compose_dev
+        key = id(plan)
+        if key not in cache:
+            cache[key] = ({k: torch.from_numpy(np.array(v)).to(self.device) for k, v in plan.tables().items()},)  # (a copy: the plan's are read-only)
+            weakref.finalize(plan, cache.pop, key, None)
+        return cache[key][0]
+
+    def motion_compose(self, qpos: torch.Tensor, plan, stream=None, out: Optional[torch.Tensor] = None,
+                       transform_out: Optional[torch.Tensor] = None):
+        """Composed clips from qpos ``[N, nq]`` float64 (engine layout, concatenated clips) in two kernels
+        (``gmr_motion_compose``; the definition is the contract in include/gmr_amd.h): every segment of ``plan`` (a
+        :class:`gmr_amd.compose.ComposePlan` made for these ``N`` rows) moved in the plane onto the end of the segment before it
+        and cross-faded into it over their overlap.  Returns ``(qpos_out [plan.n_out_frames, nq], seg_transform [plan.n_seg, 6])``:
+        the clips of ``plan.out_offsets``, and ``(c, s, tx, ty, hw, hz)`` of every segment's placement.  ``stream``: a
+        ``torch.cuda.Stream`` (``None``: the current one).  ``out`` / ``transform_out``: caller-owned tensors of those shapes.
+        The plan's tables are uploaded once per plan.  Asynchronous; with ``out``, ``transform_out`` and a cached plan no
+        allocation, no copy, no synchronisation."""
+        dev = self.device
+        if self.cm.robot.planar_base:
+            raise NotImplementedError("composing assumes a free-joint root; a planar-base robot is not supported")
+        if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+                or int(qpos.shape[1]) != self.nq or not qpos.is_contiguous():
+            raise EngineError(f"qpos must be a contiguous float64 [N, {self.nq}] tensor on the engine's device")
+        if int(qpos.shape[0]) != plan.n_frames:
+            raise EngineError(f"the plan was made for {plan.n_frames} source rows, qpos has {int(qpos.shape[0])}")
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(st):
+            tab = self.compose_device(plan)
+            shapes = {"out": (plan.n_out_frames, self.nq), "transform_out": (plan.n_seg, 6)}
+            res = {}
+            for name, t in (("out", out), ("transform_out", transform_out)):
+                if t is None:
+                    t = torch.empty(shapes[name], dtype=torch.float64, device=dev)
+                elif not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != shapes[name] \
+                        or not t.is_contiguous():
+                    raise EngineError(f"{name} must be a contiguous float64 {list(shapes[name])} tensor on the engine's device")
+                res[name] = t
+        if res["out"].numel() and res["out"].data_ptr() == qpos.data_ptr():
+            raise EngineError("out must not be qpos: an output row reads other rows")
+        ci = _native.ComposeInput()
+        ci.qpos, ci.n_frames = qpos.data_ptr(), int(qpos.shape[0])
+        for k, t in tab.items():
+            setattr(ci, k, t.data_ptr())
+        ci.n_seg, ci.n_out, ci.n_out_frames = plan.n_seg, plan.n_out, plan.n_out_frames
+        ci.qpos_out, ci.seg_transform, ci.stream = res["out"].data_ptr(), res["transform_out"].data_ptr(), st.cuda_stream
+        self._check(self._lib.gmr_motion_compose(self._h, C.byref(ci)), "gmr_motion_compose")
+        return res["out"], res["transform_out"]
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,
                     slot_col: Optional[np.ndarray] = None, height_scale=None, iters: Optional[torch.Tensor] = None,

@@ -73,6 +73,8 @@
  *                      deepest penetration, where it happens and for how long
  *   gmr_motion_mirror  (no counterpart in the reference) the left-right mirrored copy of every clip, the augmentation a tracking or
  *                      AMP pipeline doubles its data with: a signed permutation of the hinge columns and the reflected root
+ *   gmr_motion_compose (no counterpart in the reference) long reference motions from segments of the clips: each segment moved
+ *                      onto the end of the one before it in the plane and cross-faded into it
  *   gmr_dof_to_rot    KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -799,6 +801,90 @@ typedef struct gmr_mirror_input {
   int64_t        reserved;        /* 0 */
 } gmr_mirror_input;
 int gmr_motion_mirror(gmr_model *m, const gmr_mirror_input *in);
+
+/* Composed clips: long reference motions made of segments of the source clips, each segment moved by a planar rigid map onto the
+ * end of the one before it and cross-faded into it over the frames they share.  What a trainer needs for references longer than
+ * a capture take (walk -> turn -> run, a cycle repeated) and for transitions that do not teleport the robot.  The result is
+ * ordinary qpos: it feeds gmr_motion_footlock (which removes the slide a cross-fade puts into planted feet), gmr_motion_track
+ * and the reports unchanged.  Which segments follow which is the caller's plan (gmr_amd/compose.py builds and checks it); the
+ * entry does not judge it.
+ *
+ * The whole call is this struct, its stream included (in->stream, in the sense of the stream-order paragraph at the top of this
+ * file); the struct is read completely before the call returns.  The call enqueues two kernels on in->stream and nothing else: no
+ * allocation, no copy, no synchronisation, no hidden scratch (seg_transform is the hand-over between the two kernels).  All
+ * arrays are device arrays; loads and stores are element-wise, so every array needs the alignment of its element type only.
+ *   qpos          f64 [n_frames][nq], free-joint layout (x y z, qw qx qy qz, hinges).  The plan addresses absolute rows, so the
+ *                 clips' seq_offsets are not needed here
+ *   seg_src       int64 [n_seg]: the absolute source row of segment k's first frame
+ *   seg_len       int32 [n_seg]: its frames, at least 1
+ *   seg_blend     int32 [n_seg]: the frames it overlaps with the segment before it in the same output clip: 0 exactly for the first
+ *                 segment of an output clip, at least 1 for every other
+ *   seg_out       int64 [n_seg]: the absolute output row of its first frame, seg_out[k] = seg_out[k-1] + seg_len[k-1] - seg_blend[k]
+ *   clip_segs     int64 [n_out+1]: output clip o is the chain of the segments clip_segs[o] .. clip_segs[o+1]-1 (none: an empty clip)
+ *   qpos_out      f64 [n_out_frames][nq], not qpos
+ *   seg_transform f64 [n_seg][6] = (c, s, tx, ty, hw, hz): where each segment was placed.  A result, and what the second kernel reads
+ * Plan invariants: seg_blend[k] <= seg_len[k-1], and seg_blend[k] + seg_blend[k+1] <= seg_len[k], so every output row reads at
+ * most two source rows.  Segment k writes the output rows seg_out[k] + j, 0 <= j < seg_len[k] - seg_blend[k+1], where
+ * seg_blend[k+1] counts as 0 for the last segment of an output clip.  The tables are trusted as gmr_mirror_input's col_src is
+ * (gmr_amd.compose.ComposePlan checks every invariant before the Python layer uploads a table): the kernels only clamp source
+ * rows into [0, n_frames-1] and segment indices into [0, n_seg], and drop output rows outside [0, n_out_frames), so that a wrong
+ * table cannot leave the arrays.
+ *
+ * Placement.  Segment k has a planar rigid map T_k = (c_k, s_k, tx_k, ty_k) and a half-angle quaternion (hw_k, 0, 0, hz_k).  A
+ * row with root position p and root quaternion r (w x y z) is placed as
+ *   p'_x = (c p_x - s p_y) + tx,  p'_y = (s p_x + c p_y) + ty,  p'_z = p_z (a copy)
+ *   r'   = (hw, 0, 0, hz) (x) r:  r'_w = hw w - hz z,  r'_x = hw x - hz y,  r'_y = hw y + hz x,  r'_z = hw z + hz w
+ * which is linear in r: nothing is normalised.  Hinges are untouched.  The first segment of an output clip has the identity
+ * (1, 0, 0, 0, 1, 0) and its rows are used without arithmetic: outside an overlap they are copied bit for bit.
+ * For any other segment, with B = seg_blend[k], the anchor is a = B / 2 (integer division) and the anchor pair is the previous
+ * segment's source row A = seg_src[k-1] + seg_len[k-1] - B + a and this segment's row Bk = seg_src[k] + a.  The heading of a row
+ * is the mirror contract's: n = sqrt(((w w + x x) + y y) + z z), (w, x, y, z) = r / n, f_x = 1 - 2 (y y + z z),
+ * f_y = 2 (x y + w z), h2 = f_x f_x + f_y f_y;  h2 < 1e-12: (cos, sin) = (1, 0) (a root pointing straight up);  otherwise
+ * h = sqrt(h2), (cos, sin) = (f_x / h, f_y / h).  No trigonometric function is evaluated.  With (ca, sa) of row A and (cb, sb) of
+ * row Bk the relative map D_k turns this segment's anchor heading and xy onto the previous segment's:
+ *   cd = ca cb + sa sb,  sd = sa cb - ca sb,  tdx = pa_x - (cd pb_x - sd pb_y),  tdy = pa_y - (sd pb_x + cd pb_y)
+ * and T_k = T_{k-1} o D_k, composed sequentially in segment order (c, s, tx, ty, hw, hz of segment k-1 on the right-hand sides):
+ *   nx = (c tdx - s tdy) + tx,  ny = (s tdx + c tdy) + ty,  c1 = c cd - s sd,  s1 = s cd + c sd,  n = sqrt(c1 c1 + s1 s1)
+ *   c_k = c1 / n,  s_k = s1 / n,  tx_k = nx,  ty_k = ny
+ * The half angle, without a trigonometric function, hw >= 0 in both branches:
+ *   c_k < 0:   m = sqrt((1 - c_k) 0.5),  hw = |s_k| / (2 m),  hz = -m if s_k < 0, else m      (a turn of pi: (0, +-1) to rounding)
+ *   otherwise: hw = sqrt((1 + c_k) 0.5),  hz = s_k / (2 hw)
+ * Then the sign: with qa = (hw_{k-1}, 0, 0, hz_{k-1}) (x) r_A and qb = (hw, 0, 0, hz) (x) r_Bk, if
+ * ((qa_w qb_w + qa_x qb_x) + qa_y qb_y) + qa_z qb_z < 0 then (hw_k, hz_k) = (-hw, -hz).  So the placed quaternions of the two
+ * segments have a non-negative dot product at the anchor row: sign continuity across a transition is guaranteed there.  In the
+ * rest of the overlap the slerp below takes the shortest arc, whichever signs its two rows have.
+ *
+ * Blend.  Row j < B of segment k combines the previous segment's frame seg_len[k-1] - B + j placed by T_{k-1} (x0) and this
+ * segment's frame j placed by T_k (x1):  u = (j + 1) / (B + 1),  w = (u u) (3 - 2 u), never 0 or 1 (no frame of the overlap is
+ * wasted).  Root xy, root z (the raw values) and every hinge: x0 + w (x1 - x0).  Root quaternion: the shortest-arc slerp of the
+ * two placed quaternions at w, normalised (the tracking export's: acos, sin).  Row j >= B is this segment's own, placed.
+ * All arithmetic is float64 without floating-point contraction, in the order written here.  Two calls give identical bytes.
+ *
+ * Non-finite input: a non-finite hinge entry reaches only the output rows that read its row, in that column.  A non-finite root
+ * entry of a row that is no anchor reaches root columns of the output rows that read it.  A non-finite root entry of an anchor
+ * row reaches root columns of that segment (for row A: of the next one) and of the later segments of the same output clip.  No
+ * other output clip changes, and no hinge column is affected by a root.
+ * GMR_EINVAL: negative counts, and with work to do: NULL arrays, n_frames = 0, qpos_out == qpos.  GMR_EUNSUPPORTED: nq > 64 (a
+ * row does not fit one wavefront), a planar-base model.  n_seg = 0, n_out = 0 or n_out_frames = 0 returns GMR_OK without a launch.
+ * Asynchronous on in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 104; offsets qpos 0, n_frames 8, seg_src 16, seg_len 24, seg_blend 32, seg_out 40, clip_segs 48, n_seg 56,
+ * n_out 60, n_out_frames 64, stream 72, qpos_out 80, seg_transform 88, reserved 96.  */
+typedef struct gmr_compose_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seg_src;         /* device [n_seg] */
+  const int32_t *seg_len;         /* device [n_seg] */
+  const int32_t *seg_blend;       /* device [n_seg] */
+  const int64_t *seg_out;         /* device [n_seg] */
+  const int64_t *clip_segs;       /* device [n_out+1] */
+  int32_t        n_seg, n_out;
+  int64_t        n_out_frames;
+  void          *stream;          /* the call's stream */
+  double        *qpos_out;        /* device [n_out_frames][nq] f64, not qpos */
+  double        *seg_transform;   /* device [n_seg][6] f64 */
+  int64_t        reserved;        /* 0 */
+} gmr_compose_input;
+int gmr_motion_compose(gmr_model *m, const gmr_compose_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
