@@ -32,7 +32,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
            "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics",
-           "gmr_motion_self_collision", "gmr_motion_mirror", "gmr_motion_compose"]
+           "gmr_motion_self_collision", "gmr_motion_mirror", "gmr_motion_compose", "gmr_motion_transitions"]
 
 
 class IKParams(C.Structure):
@@ -194,6 +194,20 @@ class ComposeInput(C.Structure):
                 ("stream", C.c_void_p), ("qpos_out", C.c_void_p), ("seg_transform", C.c_void_p), ("reserved", C.c_int64)]
 
 
+TRANSITIONS_MAX_BODIES, TRANSITIONS_MAX_WINDOW, TRANSITIONS_MOMENTS = 64, 32, 6
+TRANSITIONS_OUTPUTS = ("points", "moments", "best_cost", "best_frame", "cost_out")   # gmr_transitions_input's output pointers, in order
+
+
+class TransitionsInput(C.Structure):
+    """``gmr_transitions_input`` (include/gmr_amd.h): the whole call of the transition search, its stream included."""
+
+    _fields_ = [("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("n_seq", C.c_int32), ("n_bodies", C.c_int32),
+                ("body_ids", C.c_void_p), ("weights", C.c_void_p), ("window", C.c_int32), ("src_stride", C.c_int32),
+                ("min_gap", C.c_int32), ("n_src_clips", C.c_int32), ("n_dst_clips", C.c_int32), ("reserved", C.c_int32),
+                ("src_clips", C.c_void_p), ("src_offsets", C.c_void_p), ("dst_clips", C.c_void_p), ("dst_offsets", C.c_void_p),
+                ("n_sources", C.c_int64), ("n_targets", C.c_int64), ("stream", C.c_void_p)] + [(k, C.c_void_p) for k in TRANSITIONS_OUTPUTS]
+
+
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
 CLIP_REPORT_LIMIT_EPS = 1e-3    # GMR_CLIP_REPORT_LIMIT_EPS
 
@@ -326,6 +340,8 @@ def load():
     L.gmr_motion_mirror.argtypes = [vp, C.POINTER(MirrorInput)]
     L.gmr_motion_compose.restype = C.c_int
     L.gmr_motion_compose.argtypes = [vp, C.POINTER(ComposeInput)]
+    L.gmr_motion_transitions.restype = C.c_int
+    L.gmr_motion_transitions.argtypes = [vp, C.POINTER(TransitionsInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

@@ -38,6 +38,7 @@
 #include "self_collision_kernel.hip.h"
 #include "mirror_kernel.hip.h"
 #include "compose_kernel.hip.h"
+#include "transitions_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
 #include "model_plan.h"
@@ -446,6 +447,7 @@ int build_device_model(gmr_model *m) {
   GMR_LDS_OPT_IN(gmr::motion_track_kernel)
   GMR_LDS_OPT_IN(gmr::motion_sample_kernel)
   GMR_LDS_OPT_IN(gmr::clip_report_kernel)
+  GMR_LDS_OPT_IN(gmr::motion_transitions_pair_kernel<8>) GMR_LDS_OPT_IN(gmr::motion_transitions_pair_kernel<gmr::kTrMaxWindow>)
 #undef GMR_LDS_OPT_IN
   (void)hipGetLastError();
   return GMR_OK;
@@ -1911,6 +1913,75 @@ int gmr_motion_compose(gmr_model *m, const gmr_compose_input *in) {
   if (in->n_frames == 0) { set_err(m, "segments of a motion without frames"); return GMR_EINVAL; }
   if (in->qpos_out == in->qpos) { set_err(m, "qpos_out must not be qpos: an output row reads other rows"); return GMR_EINVAL; }
   return compose_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ transition search (transitions_kernel.hip.h)
+// The three launches of gmr_motion_transitions, and nothing else: no allocation, no copy, no synchronisation.  Kernels a and b take
+// (clips, wavefronts per clip) as the self-collision kernel does.  Kernel c takes one wavefront per work item (a run of `tile`
+// sources, a target clip), at most kTrPairWaves of them: each strides over the items.  GMR_AMD_TRANSITIONS_WAVES forces the
+// wavefronts per clip of a and b and the wavefronts of c, GMR_AMD_TRANSITIONS_TILE the sources of a work item (the results depend
+// on neither).
+static int transitions_run(gmr_model *m, const gmr_transitions_input &in, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::TransitionsArgs a{};
+  a.dm = m->dm_eval_dev;
+  a.qpos = in.qpos; a.seq_offsets = in.seq_offsets; a.n_frames = in.n_frames;
+  a.n_seq = in.n_seq; a.nbody = m->h.nbody; a.nq = m->fk.ndof + 7; a.P = in.n_bodies; a.L = in.window; a.stride = in.src_stride;
+  a.min_gap = in.min_gap; a.n_src = in.n_src_clips; a.n_dst = in.n_dst_clips; a.tile = gmr::kTrTile;
+  a.body_ids = in.body_ids; a.weights = in.weights; a.src_clips = in.src_clips; a.dst_clips = in.dst_clips;
+  a.src_offsets = in.src_offsets; a.dst_offsets = in.dst_offsets; a.n_sources = in.n_sources; a.n_targets = in.n_targets;
+  a.points = in.points; a.moments = in.moments; a.best_cost = in.best_cost; a.best_frame = in.best_frame; a.cost_out = in.cost_out;
+  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
+  for (int b = 0; b < a.nbody; ++b) {   // (a parent precedes its child: gmr_motion_transitions checked)
+    a.parent[b] = parent[b] < 0 ? 0xff : (uint8_t)parent[b];
+    a.depth[b] = parent[b] < 0 ? 0 : (uint8_t)(a.depth[parent[b]] + 1);
+  }
+  long forced = 0;
+  if (const char *e = getenv("GMR_AMD_TRANSITIONS_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) forced = v; }
+  if (const char *e = getenv("GMR_AMD_TRANSITIONS_TILE")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= gmr::kTrMaxTile) a.tile = (int)v; }
+  const int groups = gmr::chain_geom(a.nbody).groups;
+  const int64_t want = (gmr::kTrTargetWaves + in.n_seq - 1) / in.n_seq;
+  const int64_t slots = (in.n_frames + groups - 1) / groups, mean_a = (slots + in.n_seq - 1) / in.n_seq;
+  const int64_t mean_b = ((in.n_frames + in.n_seq - 1) / in.n_seq + gmr::kFkWave - 1) / gmr::kFkWave;
+  unsigned ta = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean_a), 65535));
+  unsigned tb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean_b), 65535));
+  const int64_t items = ((in.n_sources + a.tile - 1) / a.tile) * in.n_dst_clips;
+  unsigned tc = (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, gmr::kTrPairWaves));
+  if (forced) ta = tb = tc = (unsigned)forced;
+  const unsigned bytes = (unsigned)gmr::transitions_pair_lds_bytes(a.P, a.tile);
+  hipLaunchKernelGGL(gmr::motion_transitions_points_kernel, dim3((unsigned)in.n_seq, ta), dim3(gmr::kFkWave), 0, st, a);
+  hipLaunchKernelGGL(gmr::motion_transitions_window_kernel, dim3((unsigned)in.n_seq, tb), dim3(gmr::kFkWave), 0, st, a);
+  if (in.window <= 8) hipLaunchKernelGGL(gmr::motion_transitions_pair_kernel<8>, dim3(tc), dim3(gmr::kFkWave), bytes, st, a);
+  else hipLaunchKernelGGL(gmr::motion_transitions_pair_kernel<gmr::kTrMaxWindow>, dim3(tc), dim3(gmr::kFkWave), bytes, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_transitions(gmr_model *m, const gmr_transitions_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0 || in->n_src_clips < 0 || in->n_dst_clips < 0 || in->n_sources < 0 || in->n_targets < 0) {
+    set_err(m, "negative count"); return GMR_EINVAL;
+  }
+  if (in->window < 1) { set_err(m, "window must be at least 1"); return GMR_EINVAL; }
+  if (in->src_stride < 1) { set_err(m, "src_stride must be at least 1"); return GMR_EINVAL; }
+  if (in->n_bodies < 1) { set_err(m, "n_bodies must be at least 1"); return GMR_EINVAL; }
+  if (in->min_gap < 0) { set_err(m, "min_gap must not be negative"); return GMR_EINVAL; }
+  const int nb = m->h.nbody;
+  if (nb > gmr::kFkWave) { set_err(m, "a model of %d bodies does not fit the transition search's pose tile", nb); return GMR_EUNSUPPORTED; }
+  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
+  for (int b = 1; b < nb; ++b)
+    if (parent[b] < 0 || parent[b] >= b) { set_err(m, "body %d does not follow its parent", b); return GMR_EUNSUPPORTED; }
+  if (in->n_bodies > gmr::kTrMaxBodies) { set_err(m, "at most %d bodies per call", gmr::kTrMaxBodies); return GMR_EUNSUPPORTED; }
+  if (in->window > gmr::kTrMaxWindow) { set_err(m, "a window of at most %d frames", gmr::kTrMaxWindow); return GMR_EUNSUPPORTED; }
+  if (in->n_frames == 0 || in->n_seq == 0 || in->n_src_clips == 0 || in->n_dst_clips == 0 || in->n_sources == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (!in->qpos || !in->seq_offsets || !in->body_ids || !in->weights || !in->src_clips || !in->src_offsets || !in->dst_clips ||
+      !in->points || !in->moments || !in->best_cost || !in->best_frame) {
+    set_err(m, "null argument"); return GMR_EINVAL;
+  }
+  if (in->cost_out && !in->dst_offsets) { set_err(m, "null argument: cost_out needs dst_offsets"); return GMR_EINVAL; }
+  return transitions_run(m, *in, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

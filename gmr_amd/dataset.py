@@ -596,6 +596,35 @@ def repeat_clip(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: 
     return compose_clips(gmr, qpos, seq_offsets, [[(clip, 0, frames)] * int(times)], blend)
 
 
+# ------------------------------------------------------------------ transitions between clips
+def find_transitions(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], bodies=None, weights=None,
+                     window: int = 8, stride: int = 1, src_clips=None, dst_clips=None, min_gap=None, threshold=None, radius=None):
+    """Where a segment of one clip may follow a segment of another, on the GPU (``Engine.motion_transitions``; the definition is the
+    contract above ``gmr_transitions_input`` in include/gmr_amd.h): the motion-graph distance of every ``stride``-th window of
+    ``window`` frames of the clips ``src_clips`` to every window of the clips ``dst_clips`` (``None``: all clips), and of those the
+    transitions worth taking (``gmr_amd.transitions.select_transitions``).  ``bodies``: body names or indices (``None``: all bodies);
+    ``weights``: one per body (``None``: equal).  ``min_gap=None`` means ``window``: inside one clip a window is not matched with
+    itself or an overlapping neighbour.  ``threshold=None`` and ``radius=None`` mean ``gmr_amd.transitions.DEFAULT_THRESHOLD``
+    (m^2) and ``window``: conventions, not measured on a robot.  The default ``window`` is ``compose_clips``' default ``blend``.
+    Returns ``(transitions, best_cost [E, D], best_frame [E, D])``: a list of ``gmr_amd.transitions.Transition`` and the host
+    arrays it was chosen from, source ``e`` as in ``gmr_amd.transitions.search_tables``.  ``gmr_amd.transitions.transition_walks``
+    turns the list into ``sequences`` for ``compose_clips(..., blend=window)``."""
+    from .transitions import DEFAULT_THRESHOLD, select_transitions
+    eng = gmr._engine
+    names = list(eng.cm.robot.body_names)
+    if bodies is None:
+        ids = np.arange(eng.nbody, dtype=np.int32)
+    else:
+        ids = np.asarray([names.index(b) if isinstance(b, str) else int(b) for b in bodies], dtype=np.int32)
+    w = np.ones(ids.size) if weights is None else np.asarray(weights, dtype=np.float64)
+    got = eng.motion_transitions(qpos, seq_offsets, ids, w, int(window), src_clips, dst_clips, int(stride),
+                                 int(window) if min_gap is None else int(min_gap))
+    best_cost, best_frame = got["best_cost"].cpu().numpy(), got["best_frame"].cpu().numpy()
+    trans = select_transitions(best_cost, best_frame, got.src_clips, got.src_offsets, got.stride, got.dst_clips,
+                               DEFAULT_THRESHOLD if threshold is None else float(threshold), int(window) if radius is None else int(radius))
+    return trans, best_cost, best_frame
+
+
 # ------------------------------------------------------------------ the motion library
 class MotionLibrary:
     """A set of retargeted clips of one robot kept on the GPU as qpos (288 B per G1 frame) and sampled at arbitrary times: what a

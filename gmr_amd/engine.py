@@ -583,6 +583,14 @@ def _self_collision_input(eng: "Engine", qpos, seq_offsets, capsules, pairs, mar
     return ci, MotionSelfCollision(res), [qpos, offs, dev_table]
 
 
+class MotionTransitions(dict):
+    """Result of ``motion_transitions``: the device tensors by name -- ``points`` ``[N, P, 3]`` and ``moments`` ``[N, 6]`` float64,
+    ``best_cost`` ``[E, D]`` float64 (``inf`` where a source has no target frame), ``best_frame`` ``[E, D]`` int32 (``-1`` there) and,
+    when asked for, ``cost_out`` ``[E, n_targets]`` -- and as attributes the host tables of the call (``src_clips``, ``src_offsets``,
+    ``dst_clips``, ``dst_offsets``: ``gmr_amd.transitions.search_tables``), ``window``, ``stride``, ``min_gap`` and the normalised
+    ``weights``.  Source ``src_offsets[a] + u`` is frame ``u * stride`` of clip ``src_clips[a]``."""
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -1432,6 +1440,75 @@ class Engine:
         ci.qpos_out, ci.seg_transform, ci.stream = res["out"].data_ptr(), res["transform_out"].data_ptr(), st.cuda_stream
         self._check(self._lib.gmr_motion_compose(self._h, C.byref(ci)), "gmr_motion_compose")
         return res["out"], res["transform_out"]
+
+    def motion_transitions(self, qpos: torch.Tensor, seq_offsets, body_ids, weights, window: int, src_clips=None, dst_clips=None,
+                           stride: int = 1, min_gap: int = 0, dense: bool = False, stream=None, out=None) -> "MotionTransitions":
+        """The transition search over qpos ``[N, nq]`` float64 (engine layout, concatenated clips) in three kernels
+        (``gmr_motion_transitions``; the definition is the contract in include/gmr_amd.h): for every ``stride``-th frame of the
+        clips ``src_clips`` the motion-graph cost of its window of ``window`` frames against every window of every clip of
+        ``dst_clips`` (``None``: all clips), reduced to the best target frame per (source, target clip).  ``seq_offsets`` ``[S + 1]``
+        is a host sequence: the source and target tables are made from it (``gmr_amd.transitions.search_tables``).  ``body_ids``
+        ``[P]``: the bodies whose positions are the points; ``weights`` ``[P]`` >= 0, normalised here to sum 1.  Same clip on both
+        sides: pairs with ``|j - i| < min_gap`` are excluded.  Returns a :class:`MotionTransitions` of device tensors ``points``
+        ``[N, P, 3]``, ``moments`` ``[N, 6]``, ``best_cost`` ``[E, D]`` float64, ``best_frame`` ``[E, D]`` int32 and, with
+        ``dense=True``, ``cost_out`` ``[E, n_targets]``, with the host tables as attributes.  ``stream``: a ``torch.cuda.Stream``
+        (``None``: the current one).  ``out``: caller-owned tensors by those names.  Asynchronous; the tables (a few integers per
+        clip) are uploaded in every call."""
+        from .transitions import search_tables
+        dev = self.device
+        if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+                or int(qpos.shape[1]) != self.nq or not qpos.is_contiguous():
+            raise EngineError(f"qpos must be a contiguous float64 [N, {self.nq}] tensor on the engine's device")
+        N = int(qpos.shape[0])
+        offs = np.ascontiguousarray(seq_offsets.cpu().numpy() if isinstance(seq_offsets, torch.Tensor) else seq_offsets, dtype=np.int64)
+        src, src_offs, dst, dst_offs = search_tables(offs, src_clips, dst_clips, window, stride)
+        if int(offs[-1]) > N:
+            raise EngineError(f"seq_offsets ends at row {int(offs[-1])}, qpos has {N}")
+        ids = np.ascontiguousarray(body_ids, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if ids.size < 1 or ids.size != w.size or ids.size > _native.TRANSITIONS_MAX_BODIES:
+            raise ValueError(f"body_ids and weights must hold the same 1 .. {_native.TRANSITIONS_MAX_BODIES} entries")
+        if ids.min() < 0 or ids.max() >= self.nbody:
+            raise ValueError(f"body_ids must lie in [0, {self.nbody})")
+        if not np.all(np.isfinite(w)) or np.any(w < 0.0) or not w.sum() > 0.0:
+            raise ValueError("weights must be finite, not negative, and not all zero")
+        if int(min_gap) < 0:
+            raise ValueError("min_gap must not be negative")
+        w = w / w.sum()
+        E, D, NT, P = int(src_offs[-1]), int(dst.size), int(dst_offs[-1]), int(ids.size)
+        f64, i32 = torch.float64, torch.int32
+        shapes = {"points": ((N, P, 3), f64), "moments": ((N, _native.TRANSITIONS_MOMENTS), f64), "best_cost": ((E, D), f64),
+                  "best_frame": ((E, D), i32)}
+        if dense:
+            shapes["cost_out"] = ((E, NT), f64)
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(st):
+            tabs = {k: torch.from_numpy(v).to(dev) for k, v in (("seq_offsets", offs), ("body_ids", ids), ("weights", w), ("src_clips", src),
+                                                                ("src_offsets", src_offs), ("dst_clips", dst), ("dst_offsets", dst_offs))}
+            if out is None:
+                # a call without work launches nothing, and rows outside every clip are not written
+                fill = {"points": float("nan"), "moments": float("nan"), "best_cost": float("inf"), "best_frame": -1, "cost_out": float("inf")}
+                res = {k: torch.full(sh, fill[k], dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}
+            else:
+                if set(out) != set(shapes) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                                  or t.device != dev or not t.is_contiguous() for k, t in out.items()):
+                    raise EngineError(f"out must map {sorted(shapes)} to contiguous tensors of the call's shapes on the engine's device")
+                res = {k: out[k] for k in shapes}
+        ti = _native.TransitionsInput()
+        ti.qpos, ti.n_frames, ti.seq_offsets, ti.n_seq, ti.n_bodies = qpos.data_ptr(), N, tabs["seq_offsets"].data_ptr(), int(offs.size) - 1, P
+        ti.window, ti.src_stride, ti.min_gap, ti.n_src_clips, ti.n_dst_clips = int(window), int(stride), int(min_gap), int(src.size), D
+        for k in ("body_ids", "weights", "src_clips", "src_offsets", "dst_clips", "dst_offsets"):
+            setattr(ti, k, tabs[k].data_ptr())
+        ti.n_sources, ti.n_targets, ti.stream = E, NT, st.cuda_stream
+        for k, t in res.items():
+            setattr(ti, k, t.data_ptr())
+        self._check(self._lib.gmr_motion_transitions(self._h, C.byref(ti)), "gmr_motion_transitions")
+        for t in tabs.values():
+            t.record_stream(st)
+        mt = MotionTransitions(res)
+        mt.src_clips, mt.src_offsets, mt.dst_clips, mt.dst_offsets = src, src_offs, dst, dst_offs
+        mt.window, mt.stride, mt.min_gap, mt.weights = int(window), int(stride), int(min_gap), w
+        return mt
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,
                     slot_col: Optional[np.ndarray] = None, height_scale=None, iters: Optional[torch.Tensor] = None,

@@ -75,6 +75,8 @@
  *                      AMP pipeline doubles its data with: a signed permutation of the hinge columns and the reflected root
  *   gmr_motion_compose (no counterpart in the reference) long reference motions from segments of the clips: each segment moved
  *                      onto the end of the one before it in the plane and cross-faded into it
+ *   gmr_motion_transitions (no counterpart in the reference) where such a segment may follow another: the motion-graph distance of
+ *                      every window of the source clips to every window of the target clips, reduced to the best frame per pair
  *   gmr_dof_to_rot    KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -885,6 +887,99 @@ typedef struct gmr_compose_input {
   int64_t        reserved;        /* 0 */
 } gmr_compose_input;
 int gmr_motion_compose(gmr_model *m, const gmr_compose_input *in);
+
+/* Transition search: for windows of L frames of the clips, the motion-graph distance of Kovar, Gleicher and Pighin (2002) -- the
+ * weighted squared distance of two windows of body positions after the best rotation about z and shift in xy of one of them -- for
+ * every source frame against every frame of every target clip, reduced where it is computed to the best target frame per (source
+ * frame, target clip).  What a caller needs in front of gmr_motion_compose to choose which frame of which clip follows which
+ * (gmr_amd/transitions.py turns the result into transitions and into plans for gmr_amd.compose.ComposePlan).
+ *
+ * The whole call is this struct, its stream included (in->stream, in the sense of the stream-order paragraph at the top of this
+ * file); the struct is read completely before the call returns.  The call enqueues three kernels on in->stream and nothing else: no
+ * allocation, no copy, no synchronisation, no hidden scratch (points and moments are the hand-over between the kernels, and
+ * results).  All arrays are device arrays; loads and stores are element-wise, so every array needs the alignment of its element
+ * type only.
+ *   qpos          f64 [n_frames][nq], free-joint layout (x y z, qw qx qy qz, hinges), concatenated clips (N = n_frames)
+ *   seq_offsets   int64 [n_seq+1]: clip s owns the rows a = clamp(seq_offsets[s], 0, N) to b = clamp(seq_offsets[s+1], a, N), T = b - a
+ *                 (gmr_motion_dynamics' rule; T < 2^30).  Clips are expected not to overlap
+ *   body_ids      int32 [n_bodies]: point p lies on body body_ids[p] (its frame origin).  Trusted; the kernel only clamps into [0, nbody)
+ *   weights       f64 [n_bodies]: w_p >= 0.  The caller normalises them to sum 1; the kernels use them as given
+ *   window        L >= 1 frames, uniform frame weights; src_stride s >= 1; min_gap >= 0
+ *   src_clips     int32 [n_src_clips], dst_clips int32 [n_dst_clips]: clips of seq_offsets.  Trusted; clamped into [0, n_seq)
+ *   src_offsets   int64 [n_src_clips+1]: source clip a owns the sources src_offsets[a] .. src_offsets[a+1]-1, source u of it being the
+ *                 frame i = u s of the clip: the frames 0, s, 2s, ... <= T_A - L, none for a clip shorter than L.  From 0, ascending,
+ *                 to n_sources = E.  Trusted; a source the clip does not have reports +inf and -1
+ *   dst_offsets   int64 [n_dst_clips+1]: target clip b owns the columns dst_offsets[b] + j of cost_out, j = 0 .. T_B - L: every frame
+ *                 that starts a full window, stride 1; to n_targets.  Read only when cost_out is given
+ * Points.  x[f][p] in R^3 is the position of body body_ids[p] in row f: gmr_motion_footlock's FK in float64 (MuJoCo's convention, the
+ * root quaternion divided by its norm), exactly as gmr_motion_self_collision evaluates poses; then the clip's first-row root (x, y)
+ * -- qpos columns 0 and 1 of its first row -- is subtracted from x and y of every row of that clip (z is kept), so that magnitudes
+ * stay at the clip's own extent and the cost does not depend on where the clip lies.
+ *   points        f64 [n_frames][n_bodies][3], written for every row of every clip of seq_offsets.  Scratch and a result
+ *   moments       f64 [n_frames][6] = (m.x, m.y, q, M.x, M.y, V).  Scratch and a result; the last three only for rows that start a
+ *                 full window of their clip
+ * All sums start from 0 and add their terms in ascending order, s = s + term.  Per row, over p:
+ *   m_f = sum w_p (x, y)            terms w_p x and w_p y
+ *   q_f = sum w_p (x x + y y)
+ * Per pair of rows (f of the source clip, g of the target clip), over p:
+ *   Gd(f,g) = sum w_p (x_f x_g + y_f y_g)
+ *   Gc(f,g) = sum w_p (x_f y_g - y_f x_g)
+ *   Gz(f,g) = sum w_p ((z_f - z_g) (z_f - z_g))
+ * Per window, sums over k = 0 .. L-1, then one division by L (the double of L):
+ *   M_i = (sum m_{i+k}) / L per component,  Q_i = (sum q_{i+k}) / L,  V_i = Q_i - (M_i.x M_i.x + M_i.y M_i.y)
+ *   D(i,j) = (sum Gd(i+k, j+k)) / L - (M_i.x M_j.x + M_i.y M_j.y)
+ *   C(i,j) = (sum Gc(i+k, j+k)) / L - (M_i.x M_j.y - M_i.y M_j.x)
+ *   Z(i,j) = (sum Gz(i+k, j+k)) / L
+ *   cost(i,j) = ((V_i + V_j) - 2 sqrt(D D + C C)) + Z;   a cost < 0 is replaced by 0, a NaN stays a NaN
+ * which is the minimum over a rotation R about z and a shift t in xy of  mean_k sum_p w_p |a_{i+k,p} - (R b_{j+k,p} + t)|^2  for
+ * weights that sum to 1 (a the source's points, b the target's); the best rotation has (cos, sin) proportional to (D, -C).
+ * Float64, no floating-point contraction, IEEE sqrt and division, the operations in the order written: given the same points a
+ * numpy restatement equals the kernels bit for bit.
+ * In a composition, pair (i, j) is the overlap of Segment(A, a0, i + L - a0) followed by Segment(B, j, n) with blend = L: rows
+ * A[i+k] are cross-faded with B[j+k].
+ * Exclusion: where src_clips[a] == dst_clips[b] (after clamping), the pairs with |j - i| < min_gap are excluded; min_gap = 0
+ * excludes nothing.
+ * Outputs:
+ *   best_cost     f64 [E][n_dst_clips]: the minimum over the target clip's frames that are not excluded and whose cost is not NaN
+ *   best_frame    i32 [E][n_dst_clips]: the lowest frame j at that minimum, counted from the clip's first row;  +inf and -1 when
+ *                 there is no such frame
+ *   cost_out      f64 [E][n_targets], may be NULL: the dense matrix, for small inputs, plots and tests; an excluded pair is +inf
+ * Two calls give identical bytes, and no output depends on how the pairs are spread over lanes, wavefronts or workgroups
+ * (GMR_AMD_TRANSITIONS_WAVES and GMR_AMD_TRANSITIONS_TILE force the launch geometry).  Non-finite input: a non-finite entry of a
+ * qpos row reaches the points and (m, q) of that row, the (M, V) of the windows that contain it, and the pairs whose windows contain
+ * it; a non-finite root (x, y) of a clip's first row reaches every row of that clip; no other output byte changes.
+ * GMR_EINVAL: window < 1, src_stride < 1, n_bodies < 1, min_gap < 0, negative counts, and with work to do: NULL arrays (cost_out
+ * without dst_offsets included).  GMR_EUNSUPPORTED: a model of more than 64 bodies, a model in which a body precedes its parent
+ * (as gmr_motion_self_collision), n_bodies > 64, window > 32 (the windowed sums live in a register ring).  n_frames = 0,
+ * n_seq = 0, n_src_clips = 0, n_dst_clips = 0 or n_sources = 0 returns GMR_OK without a launch.  A planar-base model is accepted, as
+ * in gmr_motion_self_collision.  Asynchronous on in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 168; offsets qpos 0, n_frames 8, seq_offsets 16, n_seq 24, n_bodies 28, body_ids 32, weights 40, window 48,
+ * src_stride 52, min_gap 56, n_src_clips 60, n_dst_clips 64, reserved 68, src_clips 72, src_offsets 80, dst_clips 88,
+ * dst_offsets 96, n_sources 104, n_targets 112, stream 120, points 128, moments 136, best_cost 144, best_frame 152, cost_out 160.  */
+typedef struct gmr_transitions_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  int32_t        n_seq, n_bodies;
+  const int32_t *body_ids;        /* device [n_bodies] */
+  const double  *weights;         /* device [n_bodies] */
+  int32_t        window, src_stride;
+  int32_t        min_gap, n_src_clips;
+  int32_t        n_dst_clips, reserved;
+  const int32_t *src_clips;       /* device [n_src_clips] */
+  const int64_t *src_offsets;     /* device [n_src_clips+1] */
+  const int32_t *dst_clips;       /* device [n_dst_clips] */
+  const int64_t *dst_offsets;     /* device [n_dst_clips+1], for cost_out */
+  int64_t        n_sources;       /* E = src_offsets[n_src_clips] */
+  int64_t        n_targets;       /* dst_offsets[n_dst_clips] */
+  void          *stream;          /* the call's stream */
+  double        *points;          /* device [n_frames][n_bodies][3] f64 */
+  double        *moments;         /* device [n_frames][6] f64 */
+  double        *best_cost;       /* device [E][n_dst_clips] f64 */
+  int32_t       *best_frame;      /* device [E][n_dst_clips] i32 */
+  double        *cost_out;        /* device [E][n_targets] f64, or NULL */
+} gmr_transitions_input;
+int gmr_motion_transitions(gmr_model *m, const gmr_transitions_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
