@@ -1768,9 +1768,12 @@ int gmr_motion_dynamics(gmr_model *m, const gmr_dynamics_input *in) {
   const bool stats = in->tau_abs_max_out || in->tau_rms_out || in->tau_ratio_max_out || in->frames_over_limit_out ||
                      in->frames_any_over_limit_out || in->fz_ratio_max_out || in->fz_ratio_min_out || in->unloaded_frames_out ||
                      in->nonfinite_frames_out;
-  if (stats && (!in->tau_out || !in->root_wrench_out)) { set_err(m, "the statistics are reduced from tau_out and root_wrench_out: both are required"); return GMR_EINVAL; }
+  // A model without a hinge (a floating base alone) has arrays of no columns: tau_out, armature and torque_limit may be NULL.
+  const bool hinges = m->fk.ndof > 0;
+  if (stats && ((hinges && !in->tau_out) || !in->root_wrench_out)) { set_err(m, "the statistics are reduced from tau_out and root_wrench_out: both are required"); return GMR_EINVAL; }
   if (in->n_frames == 0 || in->n_seq == 0) return GMR_OK;
-  if (!in->qpos || !in->seq_offsets || !in->body_parent || !in->body_mass || !in->body_com || !in->body_inertia || !in->armature || !in->torque_limit) {
+  if (!in->qpos || !in->seq_offsets || !in->body_parent || !in->body_mass || !in->body_com || !in->body_inertia ||
+      (hinges && (!in->armature || !in->torque_limit))) {
     set_err(m, "null argument"); return GMR_EINVAL;
   }
   return dynamics_run(m, *in, stats, static_cast<hipStream_t>(in->stream));

@@ -639,6 +639,9 @@ int gmr_motion_footlock(gmr_model *m, const gmr_footlock_input *in);
  * model's, a model of more than 64 bodies (its work unit does not fit one wavefront's LDS tile), a model whose bodies are not in
  * depth-first order.  n_frames = 0 or n_seq = 0 returns GMR_OK without a launch.  Asynchronous on in->stream; the handle's device
  * is selected.
+ * A model without a hinge (a floating base alone, nq = 7) is answered, not refused: root_wrench, com, zmp and the ground-reaction
+ * statistics are those of one rigid body; tau_out, armature, torque_limit and the per-hinge statistics are arrays of no columns,
+ * may be NULL (a statistic then needs root_wrench_out only) and are not touched.
  * Layout (LP64): sizeof 272; offsets qpos 0, n_frames 8, seq_offsets 16, qvel 24, qacc 32, n_seq 40, nbody 44, fps 48,
  * gravity_x 56, gravity_y 64, gravity_z 72, ground_z 80, fz_min 88, body_parent 96, body_mass 104, body_com 112,
  * body_inertia 120, armature 128, torque_limit 136, stream 144, tau_out 152, root_wrench_out 160, com_out 168, zmp_out 176,

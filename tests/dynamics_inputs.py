@@ -7,6 +7,10 @@ the analytic trajectory of seed s (dynamics_reference.Trajectory), so its veloci
   explicit   qpos with the analytic qvel and qacc
   diff       the same qpos rounded to multiples of 2^-16 with qvel = qacc = None: differences of such rows over 1/64 s are exact in
              float64, so the linear and hinge parts of the contract's differences have one correct value, bit for bit
+
+ROBOTS is the registry list.  Every function here takes a model by name, and dynamics_reference.model resolves a name of the form
+``tree/<shape>/<nbody>`` to a synthetic tree of tests/synthetic_trees.py, so tests/test_gpu_tree_packing.py runs the same cases on
+trees of every wavefront packing.
 """
 import dataclasses
 import functools
@@ -66,7 +70,7 @@ def margins(robot, ref, table=None):
     ok = np.all(np.isfinite(ref["tau"]), axis=1) & np.all(np.isfinite(ref["root_wrench"]), axis=1)
     lim = np.where(np.isfinite(tab.torque_limit), tab.torque_limit, np.inf)
     with np.errstate(all="ignore"):
-        m_tau = np.min(np.abs(np.abs(ref["tau"][ok]) / lim - 1.0)) if ok.any() else np.inf
+        m_tau = np.min(np.abs(np.abs(ref["tau"][ok]) / lim - 1.0)) if ok.any() and lim.size else np.inf   # (a model without a hinge has no torque)
     weight = tab.total_mass * 9.81
     m_fz = np.min(np.abs(ref["root_wrench"][ok, 2] / weight - R.FZ_MIN)) if ok.any() else np.inf
     return float(m_tau), float(m_fz)
@@ -116,7 +120,7 @@ def floor_rows(robot, per_kind=4):
     is worst conditioned) and the largest |zmp|, plus every clip's first row."""
     ref = reference(robot, "explicit")
     loaded = ~np.isnan(ref["zmp"]).any(axis=1)
-    keys = [np.abs(ref["tau"]).max(axis=1), np.abs(ref["root_wrench"]).max(axis=1), np.where(loaded, -ref["root_wrench"][:, 2], -np.inf),
+    keys = [np.abs(ref["tau"]).max(axis=1, initial=0.0), np.abs(ref["root_wrench"]).max(axis=1), np.where(loaded, -ref["root_wrench"][:, 2], -np.inf),
             np.where(loaded, np.abs(np.nan_to_num(ref["zmp"])).max(axis=1), -np.inf)]
     rows = set(int(OFFS[s]) for s, T in enumerate(LENS) if T)
     for key in keys:
@@ -138,5 +142,5 @@ def measure_floor(robot, rows=None):
         for k in worst:
             if k == "zmp" and np.isnan(ref[k][row]).any():
                 continue
-            worst[k] = max(worst[k], float(np.abs(ref[k][row] - want[k]).max()))
+            worst[k] = max(worst[k], float(np.abs(ref[k][row] - want[k]).max(initial=0.0)))   # (no tau without a hinge)
     return worst

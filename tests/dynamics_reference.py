@@ -43,6 +43,55 @@ mpf = mp.mpf
 FLOAT_WORST = {"unitree_g1": {"tau": 2e-13, "root_wrench": 4e-13, "com": 4e-15, "zmp": 6e-13},
                "booster_k1": {"tau": 1e-13, "root_wrench": 3e-13, "com": 4e-15, "zmp": 2e-13},
                "unitree_g1_with_hands": {"tau": 5e-13, "root_wrench": 2e-12, "com": 6e-15, "zmp": 8e-13}}
+# The same for the synthetic trees of tests/synthetic_trees.py (TREES), measured the same way over all 332 frames of each tree's
+# explicit case (x86-64, numpy float64; 86 s for the slowest, the chain of 64 bodies) and rounded up to one digit; re-measured on
+# dynamics_inputs.floor_rows by tests/test_synthetic_trees_host.py.  A chain's figures grow with its depth: the reference sums one
+# term per ancestor hinge, and the 64-body chain's last body has 48.  tree/chain/1 has no hinge and so no tau.
+#     tree/chain/1   tau 0.00e+00   root_wrench 1.70e-15   com 1.78e-15   zmp 2.70e-13
+#     tree/chain/2   tau 8.53e-16   root_wrench 1.98e-14   com 1.78e-15   zmp 4.83e-13
+#     tree/chain/3   tau 6.00e-15   root_wrench 2.13e-14   com 1.78e-15   zmp 4.26e-13
+#     tree/chain/4   tau 1.17e-14   root_wrench 1.15e-13   com 1.78e-15   zmp 1.79e-12
+#     tree/chain/5   tau 1.75e-14   root_wrench 1.24e-13   com 3.55e-15   zmp 4.69e-13
+#     tree/chain/8   tau 6.39e-14   root_wrench 1.88e-13   com 3.55e-15   zmp 6.11e-13
+#     tree/chain/9   tau 1.74e-13   root_wrench 2.98e-13   com 3.55e-15   zmp 8.38e-13
+#     tree/chain/16  tau 3.87e-13   root_wrench 6.25e-13   com 3.55e-15   zmp 3.34e-13
+#     tree/chain/17  tau 3.41e-13   root_wrench 5.74e-13   com 7.11e-15   zmp 2.88e-13
+#     tree/chain/32  tau 1.39e-12   root_wrench 4.18e-12   com 7.11e-15   zmp 3.58e-12
+#     tree/chain/33  tau 2.10e-12   root_wrench 4.32e-12   com 5.33e-15   zmp 2.27e-12
+#     tree/chain/64  tau 3.91e-11   root_wrench 6.37e-11   com 7.11e-15   zmp 9.56e-11
+#     tree/star/5    tau 4.62e-15   root_wrench 3.64e-14   com 1.78e-15   zmp 5.12e-13
+#     tree/star/9    tau 9.60e-15   root_wrench 6.13e-14   com 2.66e-15   zmp 4.26e-13
+#     tree/star/17   tau 8.62e-15   root_wrench 1.03e-13   com 1.78e-15   zmp 4.41e-13
+#     tree/star/33   tau 9.05e-15   root_wrench 2.27e-13   com 3.55e-15   zmp 1.56e-13
+#     tree/star/64   tau 9.64e-15   root_wrench 4.55e-13   com 5.33e-15   zmp 3.13e-13
+#     tree/comb/5    tau 4.58e-15   root_wrench 2.66e-14   com 1.78e-15   zmp 3.27e-13
+#     tree/comb/9    tau 9.46e-15   root_wrench 7.46e-14   com 3.55e-15   zmp 4.97e-13
+#     tree/comb/17   tau 6.75e-14   root_wrench 2.84e-13   com 3.55e-15   zmp 1.15e-12
+#     tree/comb/33   tau 2.13e-13   root_wrench 4.55e-13   com 3.55e-15   zmp 3.41e-13
+#     tree/comb/64   tau 6.22e-13   root_wrench 4.87e-12   com 8.88e-15   zmp 9.66e-13
+FLOAT_WORST.update({
+    "tree/chain/1": {"tau": 0.0, "root_wrench": 2e-15, "com": 2e-15, "zmp": 3e-13},
+    "tree/chain/2": {"tau": 9e-16, "root_wrench": 2e-14, "com": 2e-15, "zmp": 5e-13},
+    "tree/chain/3": {"tau": 6e-15, "root_wrench": 3e-14, "com": 2e-15, "zmp": 5e-13},
+    "tree/chain/4": {"tau": 2e-14, "root_wrench": 2e-13, "com": 2e-15, "zmp": 2e-12},
+    "tree/chain/5": {"tau": 2e-14, "root_wrench": 2e-13, "com": 4e-15, "zmp": 5e-13},
+    "tree/chain/8": {"tau": 7e-14, "root_wrench": 2e-13, "com": 4e-15, "zmp": 7e-13},
+    "tree/chain/9": {"tau": 2e-13, "root_wrench": 3e-13, "com": 4e-15, "zmp": 9e-13},
+    "tree/chain/16": {"tau": 4e-13, "root_wrench": 7e-13, "com": 4e-15, "zmp": 4e-13},
+    "tree/chain/17": {"tau": 4e-13, "root_wrench": 6e-13, "com": 8e-15, "zmp": 3e-13},
+    "tree/chain/32": {"tau": 2e-12, "root_wrench": 5e-12, "com": 8e-15, "zmp": 4e-12},
+    "tree/chain/33": {"tau": 3e-12, "root_wrench": 5e-12, "com": 6e-15, "zmp": 3e-12},
+    "tree/chain/64": {"tau": 4e-11, "root_wrench": 7e-11, "com": 8e-15, "zmp": 1e-10},
+    "tree/star/5": {"tau": 5e-15, "root_wrench": 4e-14, "com": 2e-15, "zmp": 6e-13},
+    "tree/star/9": {"tau": 1e-14, "root_wrench": 7e-14, "com": 3e-15, "zmp": 5e-13},
+    "tree/star/17": {"tau": 9e-15, "root_wrench": 2e-13, "com": 2e-15, "zmp": 5e-13},
+    "tree/star/33": {"tau": 1e-14, "root_wrench": 3e-13, "com": 4e-15, "zmp": 2e-13},
+    "tree/star/64": {"tau": 1e-14, "root_wrench": 5e-13, "com": 6e-15, "zmp": 4e-13},
+    "tree/comb/5": {"tau": 5e-15, "root_wrench": 3e-14, "com": 2e-15, "zmp": 4e-13},
+    "tree/comb/9": {"tau": 1e-14, "root_wrench": 8e-14, "com": 4e-15, "zmp": 5e-13},
+    "tree/comb/17": {"tau": 7e-14, "root_wrench": 3e-13, "com": 4e-15, "zmp": 2e-12},
+    "tree/comb/33": {"tau": 3e-13, "root_wrench": 5e-13, "com": 4e-15, "zmp": 4e-13},
+    "tree/comb/64": {"tau": 7e-13, "root_wrench": 5e-12, "com": 9e-15, "zmp": 1e-12}})
 GPU_FACTOR = 10.0
 
 
@@ -54,7 +103,11 @@ def bound(robot, output):
 
 @functools.lru_cache(maxsize=None)
 def model(robot):
-    """(RobotModel, InertialTable) of a registry robot, from the MJCF files under tests/golden."""
+    """(RobotModel, InertialTable) of a registry robot, from the MJCF files under tests/golden; a name ``tree/<shape>/<nbody>`` is a
+    synthetic tree of tests/synthetic_trees.py."""
+    if robot.startswith("tree/"):
+        from tests import synthetic_trees
+        return synthetic_trees.model(robot)
     path = os.path.join(ASSETS, XML[robot])
     return load_mjcf(path, name=robot), load_inertial(path)
 

@@ -2,7 +2,8 @@
 
 The trajectories are tests/dynamics_inputs.explicit: clips of 0, 1, 2, 3, 4, 63, 64, 65 and 130 frames (332 rows) -- the empty clip,
 the short ones and the 64-frame edges of the per-clip kernel's tiles.  The proxies are the skeleton's (gmr_amd.collision) at a
-radius per robot chosen so that colliding and free frames both occur (asserted below)."""
+radius per robot chosen so that colliding and free frames both occur (asserted below).  ROBOTS is the registry list; a name
+``tree/<shape>/<nbody>`` (tests/synthetic_trees.py) is accepted by every function here as well."""
 import functools
 
 import numpy as np
@@ -11,11 +12,17 @@ from gmr_amd import collision
 from tests import dynamics_inputs as di
 from tests import dynamics_reference as R
 from tests import self_collision_reference as SR
+from tests import synthetic_trees as ST
 
 LENS, OFFS, N, S, FPS = di.LENS, di.OFFS, di.N, di.S, di.FPS
 RADIUS = {"unitree_g1": 0.03, "booster_k1": 0.05, "unitree_g1_with_hands": 0.01}
 ROBOTS = list(RADIUS)
 MARGIN = 0.0
+
+
+def case_radius(robot):
+    """The capsule radius of a model's case: RADIUS for a registry robot, tests/synthetic_trees.radius for a synthetic tree."""
+    return ST.radius(robot) if ST.is_tree(robot) else RADIUS[robot]
 
 
 def robot_model(robot):
@@ -26,7 +33,7 @@ def robot_model(robot):
 def tables(robot, radius=None):
     """(CapsuleTable, PairTable): the skeleton's proxies at the case's radius and their default pairs."""
     rob = robot_model(robot)
-    caps = collision.skeleton_capsules(rob, RADIUS[robot] if radius is None else radius)
+    caps = collision.skeleton_capsules(rob, case_radius(robot) if radius is None else radius)
     return caps, collision.default_pairs(rob, caps)[0]
 
 
@@ -40,7 +47,9 @@ def reference(robot):
     caps, pairs = tables(robot)
     ref = SR.self_collision(robot_model(robot), caps, pairs, qpos(robot), OFFS, MARGIN)
     hit = ref["hits"] > 0
-    assert hit.any() and not hit.all(), f"{robot}: the case needs colliding and free frames, got {int(hit.sum())} of {N}"
+    both = hit.any() and not hit.all()
+    # (a synthetic star never collides and a tree of fewer than 9 bodies has too few pairs: synthetic_trees.collides drops it there)
+    assert both or (ST.is_tree(robot) and not ST.collides(robot)), f"{robot}: the case needs colliding and free frames, got {int(hit.sum())} of {N}"
     assert not np.isnan(ref["clearance"]).any()
     for v in ref.values():
         v.setflags(write=False)
@@ -63,7 +72,9 @@ def floor_rows(robot, per_kind=6):
     """The rows at which the numpy reference is measured against 50 digits: every clip's first row and, per kind, the `per_kind` rows
     with the smallest |clearance - margin|, the smallest clearance, and the smallest gap between the best and the second-best pair."""
     ref = reference(robot)
-    keys = [np.abs(ref["clearance"] - MARGIN), ref["clearance"], second_gap(ref["pair_clearance"])]
+    keys = [np.abs(ref["clearance"] - MARGIN), ref["clearance"]]
+    if ref["pair_clearance"].shape[1] > 1:                 # (a table of one pair has no second-best)
+        keys.append(second_gap(ref["pair_clearance"]))
     rows = set(int(OFFS[s]) for s, T in enumerate(LENS) if T)
     for key in keys:
         rows.update(int(i) for i in np.argsort(key)[:per_kind])
@@ -81,6 +92,22 @@ def measure_floor(robot, rows=None):
         tr = trajs.setdefault(s, R.Trajectory(rob, s))
         want = SR.mp_pair_clearance(tr, caps, pairs, R.mpf(row - int(OFFS[s])) / R.mpf(FPS))
         worst = max(worst, float(np.abs(cl[row] - want).max()))
+    return worst
+
+
+def measure_origin_floor(robot, rows=None):
+    """Worst |numpy FK - 50-digit evaluator| of a body origin over `rows` (None: all of them).  The floor of a model without a
+    capsule pair (a tree of two bodies), whose points the transition search's test still compares."""
+    rob = robot_model(robot)
+    zero = np.zeros((rob.nbody, 3))
+    caps = collision.CapsuleTable(np.arange(rob.nbody, dtype=np.int32), zero, zero, np.zeros(rob.nbody), list(rob.body_names))
+    X = R.fk(rob, np.asarray(qpos(robot)))[0]
+    worst, trajs = 0.0, {}
+    for row in (range(N) if rows is None else rows):
+        s = int(np.searchsorted(OFFS, row, side="right")) - 1
+        tr = trajs.setdefault(s, R.Trajectory(rob, s))
+        want = SR.mp_ends(tr, caps, R.mpf(row - int(OFFS[s])) / R.mpf(FPS))[0]
+        worst = max(worst, float(np.abs(X[row] - np.array([[float(c) for c in p] for p in want])).max()))
     return worst
 
 

@@ -24,6 +24,27 @@ mp, mpf = R.mp, R.mpf
 #     unitree_g1_with_hands (0.01 m)  1.11e-15   (25 rows x 1 633 pairs)
 # tests/test_self_collision_host.py re-measures them and fails if a recorded figure is smaller than what it measures.
 FLOAT_WORST = {"unitree_g1": 3e-15, "booster_k1": 2e-15, "unitree_g1_with_hands": 2e-15}
+# The same for the synthetic trees of tests/synthetic_trees.py at each tree's radius, the worst over ALL pairs of ALL 332 rows
+# (self_collision_inputs.measure_floor(tree, range(332)); 193 s for the slowest, the 64-body star), rounded up to one digit;
+# tests/test_synthetic_trees_host.py re-measures the rows of floor_rows.  tree/chain/2 has no pair: its figure is the worst
+# |numpy FK - 50 digits| of a body origin over the 332 rows (self_collision_inputs.measure_origin_floor), which the transition
+# search's test holds that tree's points to.
+#     tree/chain/2   origins   1.78e-15
+#     tree/chain/3   (0.01 m)  3.12e-16   (1 pair)         tree/star/5    (0.01 m)  1.89e-15   (18 pairs)
+#     tree/chain/4   (0.01 m)  1.36e-15   (3 pairs)        tree/star/9    (0.01 m)  1.59e-15   (81 pairs)
+#     tree/chain/5   (0.01 m)  1.72e-15   (6 pairs)        tree/star/17   (0.01 m)  1.72e-15   (354 pairs)
+#     tree/chain/8   (0.01 m)  3.11e-15   (21 pairs)       tree/star/33   (0.01 m)  1.97e-15   (1 471 pairs)
+#     tree/chain/9   (0.01 m)  2.14e-15   (27 pairs)       tree/star/64   (0.01 m)  2.07e-15   (5 815 pairs)
+#     tree/chain/16  (0.01 m)  3.55e-15   (105 pairs)      tree/comb/5    (0.01 m)  2.02e-15   (18 pairs)
+#     tree/chain/17  (0.01 m)  3.36e-15   (120 pairs)      tree/comb/9    (0.03 m)  2.32e-15   (45 pairs)
+#     tree/chain/32  (0.01 m)  5.19e-15   (458 pairs)      tree/comb/17   (0.01 m)  3.66e-15   (165 pairs)
+#     tree/chain/33  (0.01 m)  4.27e-15   (494 pairs)      tree/comb/33   (0.01 m)  6.11e-15   (586 pairs)
+#     tree/chain/64  (0.01 m)  7.02e-15   (1 948 pairs)    tree/comb/64   (0.01 m)  7.27e-15   (2 136 pairs)
+FLOAT_WORST.update({
+    "tree/chain/2": 2e-15, "tree/chain/3": 4e-16, "tree/chain/4": 2e-15, "tree/chain/5": 2e-15, "tree/chain/8": 4e-15, "tree/chain/9": 3e-15,
+    "tree/chain/16": 4e-15, "tree/chain/17": 4e-15, "tree/chain/32": 6e-15, "tree/chain/33": 5e-15, "tree/chain/64": 8e-15,
+    "tree/star/5": 2e-15, "tree/star/9": 2e-15, "tree/star/17": 2e-15, "tree/star/33": 2e-15, "tree/star/64": 3e-15,
+    "tree/comb/5": 3e-15, "tree/comb/9": 3e-15, "tree/comb/17": 4e-15, "tree/comb/33": 7e-15, "tree/comb/64": 8e-15})
 GPU_FACTOR = 10.0
 
 

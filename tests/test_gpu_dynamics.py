@@ -32,9 +32,11 @@ def DEV():
 
 @functools.lru_cache(maxsize=None)
 def engine(robot):
-    """The engine of the robot pack, checked to be the tree the reference reads from the MJCF file."""
+    """The engine of the robot pack (of a synthetic tree: tests/synthetic_trees.py), checked to be the tree the reference reads from
+    the MJCF file."""
     from gmr_amd.engine import Engine
-    cm = compiled("smplx", robot)
+    from tests import synthetic_trees
+    cm = synthetic_trees.compiled(robot) if synthetic_trees.is_tree(robot) else compiled("smplx", robot)
     rob = R.model(robot)[0]
     assert cm.robot.to_dict() == rob.to_dict()
     return Engine(cm, device=0)
@@ -85,34 +87,45 @@ def _bytes(a):
 
 
 # ------------------------------------------------------------------ 1: accuracy
-@pytest.mark.parametrize("case", ["explicit", "diff"])
-@pytest.mark.parametrize("robot", di.ROBOTS)
-def test_frames_equal_the_reference(robot, case):
+def check_frames(robot, case):
+    """The per-frame comparison of a named case: equal shapes and NaN patterns, every output within its bound of the numpy
+    reference.  Prints the worst |GPU - numpy| per output and its share of the bound."""
     got, ref = gpu(robot, case), di.reference(robot, case)
     bounds = {k: R.bound(robot, k) for k in FRAME}
-    assert R.model(robot)[0].nbody == {"unitree_g1": 38, "booster_k1": 23, "unitree_g1_with_hands": 52}[robot]
     report = []
     for k in FRAME:
         assert got[k].shape == ref[k].shape and np.array_equal(np.isnan(got[k]), np.isnan(ref[k])), k
         with np.errstate(all="ignore"):
             err = np.abs(got[k] - ref[k])
-        report.append(f"{k} {np.nanmax(err):.2e} ({np.nanmax(err) / bounds[k]:.2f} of its bound)")
+        worst = float(np.nanmax(err)) if np.isfinite(err).any() else 0.0     # (tau of a model without a hinge has no column)
+        report.append(f"{k} {worst:.2e} ({worst / bounds[k] if bounds[k] else 0.0:.2f} of its bound)")
     print(f"{robot} {case}: worst |GPU - numpy|: " + ", ".join(report))
     for k in FRAME:
         with np.errstate(all="ignore"):
             assert not np.any(np.abs(got[k] - ref[k]) > bounds[k]), k
+    return got, ref
+
+
+@pytest.mark.parametrize("case", ["explicit", "diff"])
+@pytest.mark.parametrize("robot", di.ROBOTS)
+def test_frames_equal_the_reference(robot, case):
+    assert R.model(robot)[0].nbody == {"unitree_g1": 38, "booster_k1": 23, "unitree_g1_with_hands": 52}[robot]
+    _, ref = check_frames(robot, case)
     assert np.isnan(ref["zmp"]).any() and not np.isnan(ref["zmp"]).all()     # both kinds of frame are in the case
 
 
-@pytest.mark.parametrize("robot", di.ROBOTS)
-def test_explicit_velocities_pass_through_bit_for_bit(robot):
+def check_pass_through(robot):
     got = gpu(robot, "explicit")
     _, v, a = di.explicit(robot)
     assert np.array_equal(_bytes(got["qvel"]), _bytes(v)) and np.array_equal(_bytes(got["qacc"]), _bytes(a))
 
 
 @pytest.mark.parametrize("robot", di.ROBOTS)
-def test_differences_are_the_numpy_restatements_bit_for_bit(robot):
+def test_explicit_velocities_pass_through_bit_for_bit(robot):
+    check_pass_through(robot)
+
+
+def check_differences(robot):
     """On rows that are multiples of 2^-16 at 64 Hz every difference of the linear and hinge parts is exact, so there is one correct
     value and the kernel must give its bits.  The angular part goes through atan2 of two different libraries: it is held to 8
     epsilons of the rate (velocity), and for the acceleration -- a difference of two rates over h -- to 16 epsilons of the rate
@@ -134,10 +147,13 @@ def test_differences_are_the_numpy_restatements_bit_for_bit(robot):
             assert not got["qacc"][rows].any()
 
 
-# ------------------------------------------------------------------ 2: statistics
-@pytest.mark.parametrize("case", ["explicit", "diff"])
 @pytest.mark.parametrize("robot", di.ROBOTS)
-def test_statistics_equal_the_reference(robot, case):
+def test_differences_are_the_numpy_restatements_bit_for_bit(robot):
+    check_differences(robot)
+
+
+# ------------------------------------------------------------------ 2: statistics
+def check_statistics(robot, case):
     """Counts equal the numpy reference's (its own values keep a relative distance of more than 1e-9 from every threshold, asserted
     here).  Maxima and counts are exactly the reference reduction of the GPU's own tau and root_wrench rows, and within the frames'
     bound of the numpy reference.  tau_rms: its sum is added frame by frame in both, so it differs by the rows' own error (the rms
@@ -153,11 +169,19 @@ def test_statistics_equal_the_reference(robot, case):
         assert np.array_equal(_bytes(got[k]), _bytes(own[k])), k
     n = np.array(di.LENS, dtype=np.float64)[:, None]
     slack = R.bound(robot, "tau") + n * EPS * ref["tau_rms"]
-    print(f"{robot} {case}: tau_rms worst {np.abs(got['tau_rms'] - ref['tau_rms']).max():.2e}, against its own rows "
-          f"{np.abs(got['tau_rms'] - own['tau_rms']).max():.2e}")
+    print(f"{robot} {case}: tau_rms worst {np.abs(got['tau_rms'] - ref['tau_rms']).max(initial=0.0):.2e}, against its own rows "
+          f"{np.abs(got['tau_rms'] - own['tau_rms']).max(initial=0.0):.2e}")
     assert np.all(np.abs(got["tau_rms"] - ref["tau_rms"]) <= slack) and np.all(np.abs(got["tau_rms"] - own["tau_rms"]) <= n * EPS * own["tau_rms"])
     assert np.all(np.abs(got["tau_abs_max"] - ref["tau_abs_max"]) <= R.bound(robot, "tau"))
     assert not got["tau_abs_max"][:1].any() and not got["tau_rms"][:1].any()     # the empty clip reports 0
+    return got, ref
+
+
+@pytest.mark.parametrize("case", ["explicit", "diff"])
+@pytest.mark.parametrize("robot", di.ROBOTS)
+def test_statistics_equal_the_reference(robot, case):
+    """check_statistics, on a case that has frames over a torque limit and unloaded frames."""
+    _, ref = check_statistics(robot, case)
     if robot != "booster_k1":   # (its MJCF gives no torque limits: nothing can be over)
         assert ref["frames_any_over_limit"].sum() > 0
     assert ref["unloaded_frames"].sum() > 0
@@ -288,6 +312,7 @@ def test_bad_arguments_are_refused_with_their_code():
     for kw, code, word in (({"fps": 0.0}, EINVAL, b"fps"), ({"fps": float("nan")}, EINVAL, b"fps"), ({"gravity_z": 0.0}, EINVAL, b"zero"),
                            ({"gravity_x": float("inf")}, EINVAL, b"finite"), ({"fz_min": -0.1}, EINVAL, b"fz_min"),
                            ({"n_frames": -1}, EINVAL, b"negative"), ({"body_mass": None}, EINVAL, b"null"),
+                           ({"armature": None}, EINVAL, b"null"), ({"torque_limit": None}, EINVAL, b"null"),   # (NULL only without a hinge)
                            ({"tau_out": None}, EINVAL, b"tau_out"), ({"nbody": eng.nbody - 1}, EUNSUPPORTED, b"bodies")):
         rc, msg = call(**kw)
         assert rc == code and word in msg, (kw, rc, msg)
