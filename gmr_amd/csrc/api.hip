@@ -41,6 +41,7 @@
 #include "transitions_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
+#include "clip_launch.h"
 #include "model_plan.h"
 
 using gmr::u64;
@@ -332,8 +333,7 @@ int balance_plan(const gmr_work_item *items, int n_items, int slots) {
   const char *sw = getenv("GMR_AMD_BALANCE");
   const int mode = sw && sw[0] == '0' ? 0 : sw && sw[0] == '1' ? 1 : sw && sw[0] == '2' ? 2 : (kBalanceDefault ? 2 : 0);  // 0 off, 1 forced, 2 where it pays
   if (mode == 0) return 0;
-  int slice = kBalanceSlice;
-  if (const char *e = getenv("GMR_AMD_BALANCE_SLICE")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= INT32_MAX) slice = (int)v; }
+  const int slice = (int)gmr::env_int("GMR_AMD_BALANCE_SLICE", 1, INT32_MAX, kBalanceSlice);
   double sum = 0.0, sum2 = 0.0;
   for (int i = 0; i < n_items; ++i) {
     const gmr_work_item &w = items[i];
@@ -694,8 +694,7 @@ static int ik_run_sliced(gmr_model *m, const gmr::IkLaunch &L, const std::vector
     return GMR_OK;
   }
   const int longest = sorted[0].n_burn + sorted[0].n_out;
-  int taper_floor = kBalanceTaperFloor;  // GMR_AMD_BALANCE_TAPER: read per call, like the two above
-  if (const char *e = getenv("GMR_AMD_BALANCE_TAPER")) { const long v = strtol(e, nullptr, 10); if (v >= 0 && v <= INT32_MAX) taper_floor = (int)v; }
+  const int taper_floor = (int)gmr::env_int("GMR_AMD_BALANCE_TAPER", 0, INT32_MAX, kBalanceTaperFloor);  // read per call, like the two above
   const gmr::SlicePlan plan = gmr::slice_plan_make(longest, slice, taper_floor);
   const int64_t rounds = gmr::slice_plan_rounds(plan), grid = rounds * n_items;
   const size_t rec = (size_t)m->dm.nq + 7 * (size_t)m->dm.nbody;  // (the kernel's own tree: DevModel::nbody)
@@ -1675,9 +1674,7 @@ static int footlock_run(gmr_model *m, const gmr_footlock_input &in, gmr::Footloc
   a.qpos_out = in.qpos_out; a.pos = in.pos_out; a.shift = in.shift_out;
   a.runs = in.runs_out; a.locked = in.locked_frames_out; a.shift_max = in.shift_max_out; a.resid_max = in.residual_max_out;
   a.limit_frames = in.limit_frames_out;
-  // tiles of one clip in flight: four times the mean clip's, so that long clips stride and short ones launch few idle wavefronts
-  const int64_t tiles = (in.n_frames + gmr::kFkWave - 1) / gmr::kFkWave;
-  const unsigned ty = (unsigned)std::min<int64_t>(std::min<int64_t>(tiles, 4 * ((tiles + in.n_seq - 1) / in.n_seq)), 65535);
+  const unsigned ty = gmr::footlock_clip_waves(in.n_frames, in.n_seq, gmr::kFkWave);  // tiles of one clip in flight
   const unsigned lds_a = (unsigned)(gmr::motion_qpitch(nq) * gmr::kFkWave * sizeof(double));
   const unsigned lds_c = (unsigned)(lds_doubles * gmr::kFkWave * sizeof(double));
   hipLaunchKernelGGL(gmr::footlock_pos_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), lds_a, st, a);
@@ -1731,13 +1728,8 @@ static int dynamics_run(gmr_model *m, const gmr_dynamics_input &in, bool stats, 
   a.frames_over = in.frames_over_limit_out; a.any_over = in.frames_any_over_limit_out;
   a.fz_max = in.fz_ratio_max_out; a.fz_min_out = in.fz_ratio_min_out;
   a.unloaded = in.unloaded_frames_out; a.nonfinite = in.nonfinite_frames_out;
-  // Wavefronts per clip: enough for about kDynTargetWaves in the whole launch (four rounds of a 256-CU device at two wavefronts per
-  // SIMD), at most one per frame slot of the mean clip.  A wavefront strides over its clip's slots, so its per-launch set-up (depth,
-  // subtree end, the body's constants) is paid once for many frames: 2 048 clips x 3 000 frames run 4 wavefronts of 750 frames each.
-  const int groups = gmr::chain_geom(a.nbody).groups;
-  const int64_t slots = (in.n_frames + groups - 1) / groups, mean = (slots + in.n_seq - 1) / in.n_seq;
-  const int64_t want = (gmr::kDynTargetWaves + in.n_seq - 1) / in.n_seq;
-  const unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean), 65535));
+  // wavefronts per clip: the grid rule of clip_launch.h over the mean clip's frame slots
+  const unsigned ty = gmr::clip_waves(gmr::kDynTargetWaves, in.n_seq, gmr::mean_clip_slots(in.n_frames, gmr::chain_geom(a.nbody).groups, in.n_seq));
   hipLaunchKernelGGL(gmr::motion_dynamics_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
   if (stats) hipLaunchKernelGGL(gmr::motion_dynamics_stats_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, a);
   if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
@@ -1759,11 +1751,8 @@ int gmr_motion_dynamics(gmr_model *m, const gmr_dynamics_input *in) {
   const int nb = m->h.nbody;
   if (in->nbody != nb) { set_err(m, "the inertial table holds %d bodies, the model %d", in->nbody, nb); return GMR_EUNSUPPORTED; }
   if (nb > gmr::kFkWave || gmr::kDynLdsBytes > 160 * 1024) { set_err(m, "a model of %d bodies does not fit the dynamics tile", nb); return GMR_EUNSUPPORTED; }
-  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
-  for (int b = 1; b < nb; ++b) {   // depth-first order: the parent of b is b - 1 or one of its ancestors
-    int j = b - 1;
-    while (j >= 0 && j != parent[b]) j = parent[j];
-    if (j < 0) { set_err(m, "body %d does not follow its parent's subtree: the bodies are not in depth-first order", b); return GMR_EUNSUPPORTED; }
+  if (const int b = gmr::tree_first_not_depth_first(blob_ptr<int32_t>(m->blob, m->h.off_parent), nb)) {
+    set_err(m, "body %d does not follow its parent's subtree: the bodies are not in depth-first order", b); return GMR_EUNSUPPORTED;
   }
   const bool stats = in->tau_abs_max_out || in->tau_rms_out || in->tau_ratio_max_out || in->frames_over_limit_out ||
                      in->frames_any_over_limit_out || in->fz_ratio_max_out || in->fz_ratio_min_out || in->unloaded_frames_out ||
@@ -1794,23 +1783,13 @@ static int self_collision_run(gmr_model *m, const gmr_self_collision_input &in, 
   a.clearance_min = in.clearance_min_out; a.worst_frame = in.worst_frame_out; a.worst_pair = in.worst_pair_out;
   a.colliding = in.colliding_frames_out; a.longest_run = in.longest_run_out; a.hits_sum = in.hits_sum_out;
   a.nonfinite = in.nonfinite_frames_out;
-  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
-  for (int b = 0; b < a.nbody; ++b) {   // (a parent precedes its child: gmr_motion_self_collision checked)
-    a.parent[b] = parent[b] < 0 ? 0xff : (uint8_t)parent[b];
-    a.depth[b] = parent[b] < 0 ? 0 : (uint8_t)(a.depth[parent[b]] + 1);
-  }
-  // Wavefronts per clip as in dynamics_run: about kColTargetWaves in the whole launch, at most one per frame slot of the mean clip;
-  // a wavefront's set-up (its body's and capsules' constants, the staged radii and pairs) is paid once for many frames.
-  // GMR_AMD_COLLISION_WAVES forces a number (the results do not depend on it).
-  const int groups = gmr::chain_geom(a.nbody).groups;
-  const int64_t slots = (in.n_frames + groups - 1) / groups, mean = (slots + in.n_seq - 1) / in.n_seq;
-  const int64_t want = (gmr::kColTargetWaves + in.n_seq - 1) / in.n_seq;
-  unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean), 65535));
-  if (const char *e = getenv("GMR_AMD_COLLISION_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) ty = (unsigned)v; }
+  gmr::tree_parent_depth(blob_ptr<int32_t>(m->blob, m->h.off_parent), a.nbody, a.parent, a.depth);
+  // Wavefronts per clip as in dynamics_run; GMR_AMD_COLLISION_WAVES forces a number (the results do not depend on it).
+  const unsigned rule = gmr::clip_waves(gmr::kColTargetWaves, in.n_seq, gmr::mean_clip_slots(in.n_frames, gmr::chain_geom(a.nbody).groups, in.n_seq));
+  const unsigned ty = (unsigned)gmr::env_int("GMR_AMD_COLLISION_WAVES", 1, gmr::kGridYMax, rule);
   // Where the pair indices live: staged in LDS as 16-bit words while the table is small, re-read from L2 in every
   // frame otherwise.  GMR_AMD_COLLISION_PAIRS=lds / global forces one (lds only where it fits).
-  bool lds = in.n_pairs <= gmr::kColPairsLdsMax;
-  if (const char *e = getenv("GMR_AMD_COLLISION_PAIRS")) lds = lds && e[0] != 'g';
+  const bool lds = gmr::collision_pairs_in_lds("GMR_AMD_COLLISION_PAIRS", in.n_pairs, gmr::kColPairsLdsMax);
   const unsigned bytes = (unsigned)gmr::self_collision_lds_bytes(in.n_caps, in.n_pairs, lds);
   if (lds) hipLaunchKernelGGL(gmr::motion_self_collision_kernel<true>, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), bytes, st, a);
   else hipLaunchKernelGGL(gmr::motion_self_collision_kernel<false>, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), bytes, st, a);
@@ -1827,9 +1806,6 @@ int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in) 
   if (!std::isfinite(in->margin)) { set_err(m, "margin must be finite"); return GMR_EINVAL; }
   const int nb = m->h.nbody;
   if (nb > gmr::kFkWave) { set_err(m, "a model of %d bodies does not fit the self-collision tile", nb); return GMR_EUNSUPPORTED; }
-  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
-  for (int b = 1; b < nb; ++b)
-    if (parent[b] < 0 || parent[b] >= b) { set_err(m, "body %d does not follow its parent", b); return GMR_EUNSUPPORTED; }
   if (in->n_caps > gmr::kColMaxCaps) { set_err(m, "at most %d capsules per call", gmr::kColMaxCaps); return GMR_EUNSUPPORTED; }
   if (in->n_pairs > gmr::kColMaxPairs) { set_err(m, "at most %d pairs per call", gmr::kColMaxPairs); return GMR_EUNSUPPORTED; }
   const bool stats = in->clearance_min_out || in->worst_frame_out || in->worst_pair_out || in->colliding_frames_out ||
@@ -1847,18 +1823,15 @@ int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in) 
 
 // ------------------------------------------------------------------ mirror augmentation (mirror_kernel.hip.h)
 // The one launch of gmr_motion_mirror, and nothing else: no allocation, no copy, no synchronisation.  The grid is (clips, wavefronts
-// per clip): about kMirrorTargetWaves in the whole launch, at most one per tile of the mean clip; a clip's rows come from
-// seq_offsets on the device, so a longer clip makes its wavefronts walk further.  GMR_AMD_MIRROR_WAVES forces a number (the results
-// do not depend on it).
+// per clip) by the grid rule of clip_launch.h over the mean clip's tiles.  GMR_AMD_MIRROR_WAVES forces a number (the results do not
+// depend on it).
 static int mirror_run(gmr_model *m, const gmr_mirror_input &in, int nq, hipStream_t st) {
   if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
   gmr::MirrorArgs a{};
   a.qpos = in.qpos; a.out = in.qpos_out; a.seq_offsets = in.seq_offsets; a.col_src = in.col_src; a.col_sign = in.col_sign;
   a.n_frames = in.n_frames; a.n_seq = in.n_seq; a.nq = nq; a.mode = in.mode;
-  const int64_t mean = (in.n_frames + in.n_seq - 1) / in.n_seq, tiles = (mean + gmr::kMirrorTile - 1) / gmr::kMirrorTile;
-  const int64_t want = (gmr::kMirrorTargetWaves + in.n_seq - 1) / in.n_seq;
-  unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, tiles), 65535));
-  if (const char *e = getenv("GMR_AMD_MIRROR_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) ty = (unsigned)v; }
+  const unsigned rule = gmr::clip_waves(gmr::kMirrorTargetWaves, in.n_seq, gmr::mean_clip_tiles(in.n_frames, in.n_seq, gmr::kMirrorTile));
+  const unsigned ty = (unsigned)gmr::env_int("GMR_AMD_MIRROR_WAVES", 1, gmr::kGridYMax, rule);
   hipLaunchKernelGGL(gmr::motion_mirror_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
   if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
   return GMR_OK;
@@ -1881,19 +1854,16 @@ int gmr_motion_mirror(gmr_model *m, const gmr_mirror_input *in) {
 
 // ------------------------------------------------------------------ composed clips (compose_kernel.hip.h)
 // The two launches of gmr_motion_compose, and nothing else: no allocation, no copy, no synchronisation.  The plan kernel takes one
-// wavefront per output clip.  The grid of the other is (segments, wavefronts per segment): about kComposeTargetWaves in the whole
-// launch, at most one per tile of the mean segment; a segment's rows come from the tables on the device, so a longer segment makes
-// its wavefronts walk further.  GMR_AMD_COMPOSE_WAVES forces a number (the results do not depend on it).
+// wavefront per output clip.  The grid of the other is (segments, wavefronts per segment) by the grid rule of clip_launch.h, a segment
+// standing for a clip, over the mean segment's tiles.  GMR_AMD_COMPOSE_WAVES forces a number (the results do not depend on it).
 static int compose_run(gmr_model *m, const gmr_compose_input &in, int nq, hipStream_t st) {
   if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
   gmr::ComposeArgs a{};
   a.qpos = in.qpos; a.out = in.qpos_out; a.seg_transform = in.seg_transform; a.seg_src = in.seg_src; a.seg_len = in.seg_len;
   a.seg_blend = in.seg_blend; a.seg_out = in.seg_out; a.clip_segs = in.clip_segs;
   a.n_frames = in.n_frames; a.n_out_frames = in.n_out_frames; a.n_seg = in.n_seg; a.n_out = in.n_out; a.nq = nq;
-  const int64_t mean = (in.n_out_frames + in.n_seg - 1) / in.n_seg, tiles = (mean + gmr::kComposeTile - 1) / gmr::kComposeTile;
-  const int64_t want = (gmr::kComposeTargetWaves + in.n_seg - 1) / in.n_seg;
-  unsigned ty = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, tiles), 65535));
-  if (const char *e = getenv("GMR_AMD_COMPOSE_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) ty = (unsigned)v; }
+  const unsigned rule = gmr::clip_waves(gmr::kComposeTargetWaves, in.n_seg, gmr::mean_clip_tiles(in.n_out_frames, in.n_seg, gmr::kComposeTile));
+  const unsigned ty = (unsigned)gmr::env_int("GMR_AMD_COMPOSE_WAVES", 1, gmr::kGridYMax, rule);
   hipLaunchKernelGGL(gmr::motion_compose_plan_kernel, dim3((unsigned)in.n_out), dim3(gmr::kFkWave), 0, st, a);
   if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
   hipLaunchKernelGGL(gmr::motion_compose_kernel, dim3((unsigned)in.n_seg, ty), dim3(gmr::kFkWave), 0, st, a);
@@ -1930,27 +1900,16 @@ static int transitions_run(gmr_model *m, const gmr_transitions_input &in, hipStr
   a.dm = m->dm_eval_dev;
   a.qpos = in.qpos; a.seq_offsets = in.seq_offsets; a.n_frames = in.n_frames;
   a.n_seq = in.n_seq; a.nbody = m->h.nbody; a.nq = m->fk.ndof + 7; a.P = in.n_bodies; a.L = in.window; a.stride = in.src_stride;
-  a.min_gap = in.min_gap; a.n_src = in.n_src_clips; a.n_dst = in.n_dst_clips; a.tile = gmr::kTrTile;
+  a.min_gap = in.min_gap; a.n_src = in.n_src_clips; a.n_dst = in.n_dst_clips;
   a.body_ids = in.body_ids; a.weights = in.weights; a.src_clips = in.src_clips; a.dst_clips = in.dst_clips;
   a.src_offsets = in.src_offsets; a.dst_offsets = in.dst_offsets; a.n_sources = in.n_sources; a.n_targets = in.n_targets;
   a.points = in.points; a.moments = in.moments; a.best_cost = in.best_cost; a.best_frame = in.best_frame; a.cost_out = in.cost_out;
-  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
-  for (int b = 0; b < a.nbody; ++b) {   // (a parent precedes its child: gmr_motion_transitions checked)
-    a.parent[b] = parent[b] < 0 ? 0xff : (uint8_t)parent[b];
-    a.depth[b] = parent[b] < 0 ? 0 : (uint8_t)(a.depth[parent[b]] + 1);
-  }
-  long forced = 0;
-  if (const char *e = getenv("GMR_AMD_TRANSITIONS_WAVES")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= 65535) forced = v; }
-  if (const char *e = getenv("GMR_AMD_TRANSITIONS_TILE")) { const long v = strtol(e, nullptr, 10); if (v >= 1 && v <= gmr::kTrMaxTile) a.tile = (int)v; }
-  const int groups = gmr::chain_geom(a.nbody).groups;
-  const int64_t want = (gmr::kTrTargetWaves + in.n_seq - 1) / in.n_seq;
-  const int64_t slots = (in.n_frames + groups - 1) / groups, mean_a = (slots + in.n_seq - 1) / in.n_seq;
-  const int64_t mean_b = ((in.n_frames + in.n_seq - 1) / in.n_seq + gmr::kFkWave - 1) / gmr::kFkWave;
-  unsigned ta = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean_a), 65535));
-  unsigned tb = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, mean_b), 65535));
-  const int64_t items = ((in.n_sources + a.tile - 1) / a.tile) * in.n_dst_clips;
-  unsigned tc = (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, gmr::kTrPairWaves));
-  if (forced) ta = tb = tc = (unsigned)forced;
+  gmr::tree_parent_depth(blob_ptr<int32_t>(m->blob, m->h.off_parent), a.nbody, a.parent, a.depth);
+  a.tile = (int)gmr::env_int("GMR_AMD_TRANSITIONS_TILE", 1, gmr::kTrMaxTile, gmr::kTrTile);
+  unsigned ta = gmr::clip_waves(gmr::kTrTargetWaves, in.n_seq, gmr::mean_clip_slots(in.n_frames, gmr::chain_geom(a.nbody).groups, in.n_seq));
+  unsigned tb = gmr::clip_waves(gmr::kTrTargetWaves, in.n_seq, gmr::mean_clip_tiles(in.n_frames, in.n_seq, gmr::kFkWave));
+  unsigned tc = gmr::transitions_pair_waves(in.n_sources, a.tile, in.n_dst_clips, gmr::kTrPairWaves);
+  if (const long forced = gmr::env_int("GMR_AMD_TRANSITIONS_WAVES", 1, gmr::kGridYMax, 0)) ta = tb = tc = (unsigned)forced;
   const unsigned bytes = (unsigned)gmr::transitions_pair_lds_bytes(a.P, a.tile);
   hipLaunchKernelGGL(gmr::motion_transitions_points_kernel, dim3((unsigned)in.n_seq, ta), dim3(gmr::kFkWave), 0, st, a);
   hipLaunchKernelGGL(gmr::motion_transitions_window_kernel, dim3((unsigned)in.n_seq, tb), dim3(gmr::kFkWave), 0, st, a);
@@ -1973,9 +1932,6 @@ int gmr_motion_transitions(gmr_model *m, const gmr_transitions_input *in) {
   if (in->min_gap < 0) { set_err(m, "min_gap must not be negative"); return GMR_EINVAL; }
   const int nb = m->h.nbody;
   if (nb > gmr::kFkWave) { set_err(m, "a model of %d bodies does not fit the transition search's pose tile", nb); return GMR_EUNSUPPORTED; }
-  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent);
-  for (int b = 1; b < nb; ++b)
-    if (parent[b] < 0 || parent[b] >= b) { set_err(m, "body %d does not follow its parent", b); return GMR_EUNSUPPORTED; }
   if (in->n_bodies > gmr::kTrMaxBodies) { set_err(m, "at most %d bodies per call", gmr::kTrMaxBodies); return GMR_EUNSUPPORTED; }
   if (in->window > gmr::kTrMaxWindow) { set_err(m, "a window of at most %d frames", gmr::kTrMaxWindow); return GMR_EUNSUPPORTED; }
   if (in->n_frames == 0 || in->n_seq == 0 || in->n_src_clips == 0 || in->n_dst_clips == 0 || in->n_sources == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)

@@ -27,6 +27,45 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _qpos_rows(qpos, nq: int, device, what: str = "", contiguous: bool = True) -> int:
+    """Check a call's qpos -- a float64 ``[N, nq]`` tensor on ``device``, contiguous unless the caller makes it so -- and return N.
+    ``what`` prefixes the message (a group member)."""
+    if not isinstance(qpos, torch.Tensor) or qpos.device != device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
+            or qpos.shape[1] != nq or (contiguous and not qpos.is_contiguous()):
+        raise EngineError(what + f"qpos must be a {'contiguous ' if contiguous else ''}float64 [N, {nq}] tensor on the engine's device")
+    return int(qpos.shape[0])
+
+
+def _clip_offsets(offsets, device, name: str = "seq_offsets") -> torch.Tensor:
+    """The clips' row offsets ``[S + 1]`` on ``device``: a device int64 tensor as it is, or a host sequence uploaded once.  The
+    messages carry the argument's ``name``: "seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)"."""
+    if isinstance(offsets, torch.Tensor):
+        if offsets.device != device or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous():
+            raise EngineError(f"{name} must be a contiguous 1-D int64 tensor (or a host sequence)")
+        return offsets
+    o = np.ascontiguousarray(offsets, dtype=np.int64)
+    if o.ndim != 1 or o.size < 1:
+        raise ValueError(f"{name} must hold n_seq + 1 entries")
+    return torch.from_numpy(o).to(device)  # the one upload of the call
+
+
+def _named_outputs(inp, out, fields, shapes, device, fields_name: str, alloc, whose: str = "the call's", what: str = "") -> dict:
+    """The result tensors of a call by name, in the order of ``fields``, each bound to ``inp``'s pointer ``name + "_out"``.
+    ``shapes``: ``{name: (shape, dtype)}``.  With ``out`` -- a mapping of caller-owned tensors; a name left out is not computed -- the
+    tensors are checked against it; without, ``alloc(name, shape, dtype)`` makes each (``None``: the name is left out)."""
+    if out is None:
+        made = ((k, alloc(k, *shapes[k])) for k in fields)
+        res = {k: t for k, t in made if t is not None}
+    else:
+        res = {k: out[k] for k in fields if k in out}
+        if set(out) - set(fields) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                         or t.device != device or not t.is_contiguous() for k, t in res.items()):
+            raise EngineError(what + f"out must map names of {fields_name} to contiguous tensors of {whose} shapes on the engine's device")
+    for k, t in res.items():
+        setattr(inp, k + "_out", t.data_ptr())
+    return res
+
+
 def _state_arrays(nq: int, device, items: np.ndarray, qpos_init: Optional[torch.Tensor], qpos_final: Optional[torch.Tensor], n_final: int,
                   frames_done: Optional[torch.Tensor], what: str = ""):
     """Host-side checks of a batch's state arrays against its work items -- the C side cannot check row counts, and on the device a
@@ -137,11 +176,8 @@ def _motion_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, height_adjust:
                   out, min_z: Optional[torch.Tensor], what: str = ""):
     """Check one model's epilogue arguments and fill its ``MotionInput``.  Returns (input, (root_pos, root_rot, dof_pos,
     local_body_pos), keep-alive)."""
-    if not isinstance(qpos, torch.Tensor) or qpos.device != eng.device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-            or qpos.shape[1] != eng.nq:
-        raise EngineError(what + f"qpos must be a float64 [N, {eng.nq}] tensor on the engine's device")
+    N = _qpos_rows(qpos, eng.nq, eng.device, what, contiguous=False)
     qpos = qpos.contiguous()
-    N = int(qpos.shape[0])
     offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
     if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != N:
         raise ValueError(what + "seq_offsets must span [0, N]")
@@ -189,11 +225,8 @@ def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out
     """Check one model's tracking arguments, plan the resampling and fill its ``TrackInput``.  Returns (input, MotionTrack,
     keep-alive)."""
     from .schedule import lowpass_check, track_plan
-    if not isinstance(qpos, torch.Tensor) or qpos.device != eng.device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-            or qpos.shape[1] != eng.nq:
-        raise EngineError(what + f"qpos must be a float64 [N, {eng.nq}] tensor on the engine's device")
+    N = _qpos_rows(qpos, eng.nq, eng.device, what, contiguous=False)
     qpos = qpos.contiguous()
-    N = int(qpos.shape[0])
     offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
     if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != N:
         raise ValueError(what + "seq_offsets must span [0, N]")
@@ -204,25 +237,18 @@ def _track_input(eng: "Engine", qpos: torch.Tensor, seq_offsets, fps_in, fps_out
         raise EngineError(what + f"gmr_motion_track: {_ERR[-1]}: {e}") from None
     M = int(out_offs[-1])
     nd, nb = eng.nq - 7, eng.nbody
-    shapes = {"root_pos": (M, 3), "root_rot": (M, 4), "joint_pos": (M, nd), "root_lin_vel": (M, 3), "root_ang_vel": (M, 3),
-              "joint_vel": (M, nd), "body_pos_w": (M, nb, 3), "body_quat_w": (M, nb, 4), "body_lin_vel_w": (M, nb, 3),
-              "body_ang_vel_w": (M, nb, 3)}
+    f64, f32 = torch.float64, torch.float32
+    shapes = {"root_pos": ((M, 3), f64), "root_rot": ((M, 4), f64), "joint_pos": ((M, nd), f64), "root_lin_vel": ((M, 3), f64),
+              "root_ang_vel": ((M, 3), f64), "joint_vel": ((M, nd), f64), "body_pos_w": ((M, nb, 3), f32), "body_quat_w": ((M, nb, 4), f32),
+              "body_lin_vel_w": ((M, nb, 3), f32), "body_ang_vel_w": ((M, nb, 3), f32)}
     fields = [k for k in TRACK_FIELDS if bodies or k not in _TRACK_BODY_FIELDS]
-    dtype = lambda k: torch.float32 if k in _TRACK_BODY_FIELDS else torch.float64
-    if out is None:
-        res = {k: torch.empty(shapes[k], dtype=dtype(k), device=eng.device) for k in fields}
-    else:
-        res = {k: out[k] for k in fields if k in out}
-        if set(out) - set(fields) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k] or t.dtype != dtype(k)
-                                         or t.device != eng.device or not t.is_contiguous() for k, t in res.items()):
-            raise EngineError(what + "out must map names of TRACK_FIELDS to contiguous tensors of the plan's shapes on the engine's device")
     ti = _native.TrackInput()
+    res = _named_outputs(ti, out, fields, shapes, eng.device, "TRACK_FIELDS", lambda k, sh, dt: torch.empty(sh, dtype=dt, device=eng.device),
+                         whose="the plan's", what=what)
     ti.qpos, ti.n_frames = qpos.data_ptr(), N
     ti.seq_offsets, ti.out_offsets, ti.ratio, ti.n_seq = offs.ctypes.data, out_offs.ctypes.data, ratio.ctypes.data, len(offs) - 1
     ti.fps_out = float(fps_out)
     ti.lowpass_hz = lowpass_hz
-    for k, t in res.items():
-        setattr(ti, k + "_out", t.data_ptr())
     return ti, MotionTrack(res, out_offs, fps_out), (qpos, offs, out_offs, ratio)
 
 
@@ -234,9 +260,7 @@ def _sample_input(eng: "Engine", qpos, seq_offsets_dev, fps_dev, ids, times, k_p
     """Check the arguments of one query call and fill its ``SampleInput``.  Returns (input, MotionSample, keep-alive).  Nothing
     here touches the device: shapes and dtypes only."""
     dev = eng.device
-    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-            or qpos.shape[1] != eng.nq or not qpos.is_contiguous():
-        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
+    N = _qpos_rows(qpos, eng.nq, dev)
     for t, dt, what in ((seq_offsets_dev, torch.int64, "seq_offsets_dev"), (fps_dev, torch.float64, "fps_dev"), (ids, torch.int64, "ids")):
         if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
             raise EngineError(f"{what} must be a contiguous 1-D {dt} tensor on the engine's device")
@@ -276,7 +300,7 @@ def _sample_input(eng: "Engine", qpos, seq_offsets_dev, fps_dev, ids, times, k_p
                        or not t.is_contiguous() for k, t in res.items()):
             raise EngineError("out must map names of TRACK_FIELDS to contiguous tensors of the query's shapes on the engine's device")
     si = _native.SampleInput()
-    si.qpos, si.n_frames = qpos.data_ptr(), int(qpos.shape[0])
+    si.qpos, si.n_frames = qpos.data_ptr(), N
     si.seq_offsets, si.fps, si.n_seq, si.k_per_id = seq_offsets_dev.data_ptr(), fps_dev.data_ptr(), n_seq, k_per_id
     si.ids, si.times, si.n_queries = ids.data_ptr(), times.data_ptr(), Q
     si.time_dtype = _native.GMR_DTYPE_F64 if times.dtype == torch.float64 else _native.GMR_DTYPE_F32
@@ -320,15 +344,7 @@ def _contact_input(eng: "Engine", track_or_arrays, out_offsets, body_ids, height
         raise EngineError("body_pos_w and body_lin_vel_w must hold the same rows")
     if out_offsets is None:
         raise EngineError("out_offsets is needed with plain arrays")
-    if isinstance(out_offsets, torch.Tensor):
-        offs = out_offsets
-        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
-            raise EngineError("out_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
-    else:
-        o = np.ascontiguousarray(out_offsets, dtype=np.int64)
-        if o.ndim != 1 or o.size < 1:
-            raise ValueError("out_offsets must hold n_seq + 1 entries")
-        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    offs = _clip_offsets(out_offsets, dev, "out_offsets")
     S = int(offs.shape[0]) - 1
     if isinstance(body_ids, torch.Tensor):
         ids = body_ids
@@ -358,21 +374,13 @@ def _contact_input(eng: "Engine", track_or_arrays, out_offsets, body_ids, height
     f64, i32 = torch.float64, torch.int32
     shapes = {"contact": ((M, Cn), torch.uint8), "frames": ((S, Cn), i32), "touchdowns": ((S, Cn), i32), "slide_sum": ((S, Cn), f64),
               "slide_step_max": ((S, Cn), f64), "depth_max": ((S, Cn), f64), "airborne_frames": ((S,), i32), "base": ((S,), f64)}
-    if out is None:
-        # zeros: rows outside every clip are not written, and a call without rows launches nothing (every clip is empty then)
-        res = {k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}
-        if M == 0 and S > 0:
-            res["base"].fill_(float("nan") if isinstance(ground, str) else float(ground))
-    else:
-        res = {k: out[k] for k in CONTACT_FIELDS if k in out}
-        if set(out) - set(CONTACT_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
-                                                 or t.device != dev or not t.is_contiguous() for k, t in res.items()):
-            raise EngineError("out must map names of CONTACT_FIELDS to contiguous tensors of the call's shapes on the engine's device")
+    # zeros: rows outside every clip are not written, and a call without rows launches nothing (every clip is empty then)
+    res = _named_outputs(ci, out, CONTACT_FIELDS, shapes, dev, "CONTACT_FIELDS", lambda k, sh, dt: torch.zeros(sh, dtype=dt, device=dev))
+    if out is None and M == 0 and S > 0:
+        res["base"].fill_(float("nan") if isinstance(ground, str) else float(ground))
     ci.body_pos_w, ci.body_lin_vel_w, ci.n_rows = pos.data_ptr(), vel.data_ptr(), M
     ci.out_offsets, ci.body_ids, ci.n_seq, ci.n_contact = offs.data_ptr(), ids.data_ptr(), S, Cn
     ci.height_on, ci.height_off, ci.speed_on, ci.speed_off = float(height_on), float(height_off), float(speed_on), float(speed_off)
-    for k, t in res.items():
-        setattr(ci, k + "_out", t.data_ptr())
     return ci, MotionContacts(res), keep
 
 
@@ -392,19 +400,8 @@ def _footlock_input(eng: "Engine", qpos, seq_offsets, contact, body_ids, blend_f
     """Check the arguments of one foot-locking call and fill its ``FootlockInput`` (all but the stream).  Returns (input,
     MotionFootlock, keep-alive)."""
     dev = eng.device
-    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-            or int(qpos.shape[1]) != eng.nq or not qpos.is_contiguous():
-        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
-    N = int(qpos.shape[0])
-    if isinstance(seq_offsets, torch.Tensor):
-        offs = seq_offsets
-        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
-            raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
-    else:
-        o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
-        if o.ndim != 1 or o.size < 1:
-            raise ValueError("seq_offsets must hold n_seq + 1 entries")
-        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    N = _qpos_rows(qpos, eng.nq, dev)
+    offs = _clip_offsets(seq_offsets, dev)
     S = int(offs.shape[0]) - 1
     ids = np.ascontiguousarray(body_ids, dtype=np.int32)   # a host array: the library reads it before it returns
     if ids.ndim != 1 or not 1 <= ids.size <= _native.FOOTLOCK_MAX_BODIES:
@@ -422,25 +419,18 @@ def _footlock_input(eng: "Engine", qpos, seq_offsets, contact, body_ids, blend_f
     f64, i32 = torch.float64, torch.int32
     shapes = {"qpos": ((N, eng.nq), f64), "pos": ((N, Cn, 3), f64), "shift": ((N, Cn, 3), f64), "runs": ((S, Cn), i32),
               "locked_frames": ((S, Cn), i32), "shift_max": ((S, Cn), f64), "residual_max": ((S, Cn), f64), "limit_frames": ((S, Cn), i32)}
-    if out is None:
-        # rows outside every clip are not written, and a call without rows launches nothing: zeros, and qpos starts as a copy
-        res = {k: (qpos.clone() if k == "qpos" else torch.zeros(sh, dtype=dt, device=dev)) for k, (sh, dt) in shapes.items()}
-    else:
-        res = {k: out[k] for k in FOOTLOCK_FIELDS if k in out}
-        if set(out) - set(FOOTLOCK_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
-                                                  or t.device != dev or not t.is_contiguous() for k, t in res.items()):
-            raise EngineError("out must map names of FOOTLOCK_FIELDS to contiguous tensors of the call's shapes on the engine's device")
-        if not {"qpos", "pos", "shift"} <= set(res):
-            raise EngineError("out must hold qpos, pos and shift: the three are required")
+    fi = _native.FootlockInput()
+    # rows outside every clip are not written, and a call without rows launches nothing: zeros, and qpos starts as a copy
+    res = _named_outputs(fi, out, FOOTLOCK_FIELDS, shapes, dev, "FOOTLOCK_FIELDS",
+                         lambda k, sh, dt: qpos.clone() if k == "qpos" else torch.zeros(sh, dtype=dt, device=dev))
+    if not {"qpos", "pos", "shift"} <= set(res):
+        raise EngineError("out must hold qpos, pos and shift: the three are required")
     if res["qpos"].data_ptr() == qpos.data_ptr() and N > 0:
         raise EngineError("out['qpos'] must not alias qpos")
-    fi = _native.FootlockInput()
     fi.qpos, fi.n_frames, fi.seq_offsets, fi.contact = qpos.data_ptr(), N, offs.data_ptr(), contact.data_ptr()
     fi.body_ids, fi.n_seq, fi.n_contact = ids.ctypes.data, S, Cn
     fi.blend_frames, fi.min_run, fi.iterations = int(blend_frames), int(min_run), int(iterations)
     fi.damping, fi.step_cap = float(damping), float(step_cap)
-    for k, t in res.items():
-        setattr(fi, k + "_out", t.data_ptr())
     return fi, MotionFootlock(res), [qpos, offs, contact, ids]
 
 
@@ -468,23 +458,12 @@ def _dynamics_input(eng: "Engine", qpos, seq_offsets, fps, qvel, qacc, gravity, 
     """Check the arguments of one inverse-dynamics call and fill its ``DynamicsInput`` (all but the stream).  Returns (input,
     MotionDynamics, keep-alive)."""
     dev = eng.device
-    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-            or int(qpos.shape[1]) != eng.nq or not qpos.is_contiguous():
-        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
-    N, nv, nh = int(qpos.shape[0]), eng.nq - 1, eng.nq - 7
+    N, nv, nh = _qpos_rows(qpos, eng.nq, dev), eng.nq - 1, eng.nq - 7
     for name, t in (("qvel", qvel), ("qacc", qacc)):
         if t is not None and (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != (N, nv)
                               or not t.is_contiguous()):
             raise EngineError(f"{name} must be a contiguous float64 [{N}, {nv}] tensor on the engine's device (or None)")
-    if isinstance(seq_offsets, torch.Tensor):
-        offs = seq_offsets
-        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
-            raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
-    else:
-        o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
-        if o.ndim != 1 or o.size < 1:
-            raise ValueError("seq_offsets must hold n_seq + 1 entries")
-        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    offs = _clip_offsets(seq_offsets, dev)
     S = int(offs.shape[0]) - 1
     g = np.asarray(gravity, dtype=np.float64)
     if g.shape != (3,) or not np.all(np.isfinite(g)) or not np.any(g != 0.0):
@@ -497,17 +476,11 @@ def _dynamics_input(eng: "Engine", qpos, seq_offsets, fps, qvel, qacc, gravity, 
               "qacc": ((N, nv), f64), "tau_abs_max": ((S, nh), f64), "tau_rms": ((S, nh), f64), "tau_ratio_max": ((S, nh), f64),
               "frames_over_limit": ((S, nh), i32), "frames_any_over_limit": ((S,), i32), "fz_ratio_max": ((S,), f64),
               "fz_ratio_min": ((S,), f64), "unloaded_frames": ((S,), i32), "nonfinite_frames": ((S,), i32)}
-    if out is None:
-        # rows outside every clip are not written, and a call without rows launches nothing: zeros
-        res = {k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}
-    else:
-        res = {k: out[k] for k in DYNAMICS_FIELDS if k in out}
-        if set(out) - set(DYNAMICS_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
-                                                  or t.device != dev or not t.is_contiguous() for k, t in res.items()):
-            raise EngineError("out must map names of DYNAMICS_FIELDS to contiguous tensors of the call's shapes on the engine's device")
-        if set(res) & set(DYNAMICS_STATS) and not {"tau", "root_wrench"} <= set(res):
-            raise EngineError("out must hold tau and root_wrench when it holds a statistic: the statistics are reduced from them")
     di = _native.DynamicsInput()
+    # rows outside every clip are not written, and a call without rows launches nothing: zeros
+    res = _named_outputs(di, out, DYNAMICS_FIELDS, shapes, dev, "DYNAMICS_FIELDS", lambda k, sh, dt: torch.zeros(sh, dtype=dt, device=dev))
+    if set(res) & set(DYNAMICS_STATS) and not {"tau", "root_wrench"} <= set(res):
+        raise EngineError("out must hold tau and root_wrench when it holds a statistic: the statistics are reduced from them")
     di.qpos, di.n_frames, di.seq_offsets, di.n_seq = qpos.data_ptr(), N, offs.data_ptr(), S
     di.qvel = qvel.data_ptr() if qvel is not None else None
     di.qacc = qacc.data_ptr() if qacc is not None else None
@@ -516,8 +489,6 @@ def _dynamics_input(eng: "Engine", qpos, seq_offsets, fps, qvel, qacc, gravity, 
     di.ground_z, di.fz_min = float(ground_z), float(fz_min)
     for k in _native.DYNAMICS_TABLE:
         setattr(di, k, dev_table[k].data_ptr())
-    for k, t in res.items():
-        setattr(di, k + "_out", t.data_ptr())
     return di, MotionDynamics(res), [qpos, offs, qvel, qacc, dev_table]
 
 
@@ -540,19 +511,8 @@ def _self_collision_input(eng: "Engine", qpos, seq_offsets, capsules, pairs, mar
     """Check the arguments of one self-collision call and fill its ``SelfCollisionInput`` (all but the stream).  Returns (input,
     MotionSelfCollision, keep-alive)."""
     dev = eng.device
-    if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-            or int(qpos.shape[1]) != eng.nq or not qpos.is_contiguous():
-        raise EngineError(f"qpos must be a contiguous float64 [N, {eng.nq}] tensor on the engine's device")
-    N = int(qpos.shape[0])
-    if isinstance(seq_offsets, torch.Tensor):
-        offs = seq_offsets
-        if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
-            raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
-    else:
-        o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
-        if o.ndim != 1 or o.size < 1:
-            raise ValueError("seq_offsets must hold n_seq + 1 entries")
-        offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+    N = _qpos_rows(qpos, eng.nq, dev)
+    offs = _clip_offsets(seq_offsets, dev)
     S = int(offs.shape[0]) - 1
     if not np.isfinite(margin):
         raise ValueError("margin must be finite")
@@ -561,25 +521,18 @@ def _self_collision_input(eng: "Engine", qpos, seq_offsets, capsules, pairs, mar
     shapes = {"clearance": ((N,), f64), "pair": ((N,), i32), "hits": ((N,), i32), "clearance_min": ((S,), f64), "worst_frame": ((S,), i32),
               "worst_pair": ((S,), i32), "colliding_frames": ((S,), i32), "longest_run": ((S,), i32), "hits_sum": ((S,), i64),
               "nonfinite_frames": ((S,), i32)}
-    if out is None:
-        # rows outside every clip are not written, and a call without rows launches nothing: what an empty clip reports
-        fill = {"clearance": float("nan"), "pair": -1, "clearance_min": float("inf"), "worst_frame": -1, "worst_pair": -1}
-        res = {k: torch.full(sh, fill.get(k, 0), dtype=dt, device=dev) for k, (sh, dt) in shapes.items()
-               if stats or k in _native.SELF_COLLISION_FRAME_OUTPUTS}
-    else:
-        res = {k: out[k] for k in SELF_COLLISION_FIELDS if k in out}
-        if set(out) - set(SELF_COLLISION_FIELDS) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
-                                                        or t.device != dev or not t.is_contiguous() for k, t in res.items()):
-            raise EngineError("out must map names of SELF_COLLISION_FIELDS to contiguous tensors of the call's shapes on the engine's device")
-        if set(res) & set(SELF_COLLISION_STATS) and not set(_native.SELF_COLLISION_FRAME_OUTPUTS) <= set(res):
-            raise EngineError("out must hold clearance, pair and hits when it holds a statistic: the statistics are reduced from them")
+    # rows outside every clip are not written, and a call without rows launches nothing: what an empty clip reports
+    fill = {"clearance": float("nan"), "pair": -1, "clearance_min": float("inf"), "worst_frame": -1, "worst_pair": -1}
     ci = _native.SelfCollisionInput()
+    res = _named_outputs(ci, out, SELF_COLLISION_FIELDS, shapes, dev, "SELF_COLLISION_FIELDS",
+                         lambda k, sh, dt: torch.full(sh, fill.get(k, 0), dtype=dt, device=dev)
+                         if stats or k in _native.SELF_COLLISION_FRAME_OUTPUTS else None)
+    if set(res) & set(SELF_COLLISION_STATS) and not set(_native.SELF_COLLISION_FRAME_OUTPUTS) <= set(res):
+        raise EngineError("out must hold clearance, pair and hits when it holds a statistic: the statistics are reduced from them")
     ci.qpos, ci.n_frames, ci.seq_offsets, ci.n_seq = qpos.data_ptr(), N, offs.data_ptr(), S
     ci.n_caps, ci.n_pairs, ci.margin = int(dev_table["cap_body"].shape[0]), int(dev_table["pairs"].shape[0]), float(margin)
     for k in _native.SELF_COLLISION_TABLE:
         setattr(ci, k, dev_table[k].data_ptr())
-    for k, t in res.items():
-        setattr(ci, k + "_out", t.data_ptr())
     return ci, MotionSelfCollision(res), [qpos, offs, dev_table]
 
 
@@ -659,11 +612,8 @@ def _report_names(cm: CompiledModel):
 
 def _report_input(eng: "Engine", qpos, pos, quat, slot_col, seq_offsets, height_scale, iters, what: str = ""):
     """Check one model's clip-report arguments, allocate its outputs and fill its ``ClipReportInput``.  Returns (input, report, keep-alive)."""
-    if not isinstance(qpos, torch.Tensor) or qpos.device != eng.device or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-            or qpos.shape[1] != eng.nq:
-        raise EngineError(what + f"qpos must be a float64 [N, {eng.nq}] tensor on the engine's device")
+    N = _qpos_rows(qpos, eng.nq, eng.device, what, contiguous=False)
     qpos = qpos.contiguous()
-    N = int(qpos.shape[0])
     offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
     if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != N:
         raise ValueError(what + "seq_offsets must span [0, N]")
@@ -1363,18 +1313,8 @@ class Engine:
         dev = self.device
         if about not in _native.MIRROR_MODES:
             raise ValueError(f"about must be one of {sorted(_native.MIRROR_MODES)}")
-        if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-                or int(qpos.shape[1]) != self.nq or not qpos.is_contiguous():
-            raise EngineError(f"qpos must be a contiguous float64 [N, {self.nq}] tensor on the engine's device")
-        if isinstance(seq_offsets, torch.Tensor):
-            offs = seq_offsets
-            if offs.device != dev or offs.dtype != torch.int64 or offs.dim() != 1 or offs.numel() < 1 or not offs.is_contiguous():
-                raise EngineError("seq_offsets must be a contiguous 1-D int64 tensor (or a host sequence)")
-        else:
-            o = np.ascontiguousarray(seq_offsets, dtype=np.int64)
-            if o.ndim != 1 or o.size < 1:
-                raise ValueError("seq_offsets must hold n_seq + 1 entries")
-            offs = torch.from_numpy(o).to(dev)  # the one upload of the call
+        N = _qpos_rows(qpos, self.nq, dev)
+        offs = _clip_offsets(seq_offsets, dev)
         tab = self.symmetry_device(self.symmetry_plan() if plan is None else plan)
         if out is None:
             out = qpos.clone()  # rows outside every clip are not written
@@ -1384,7 +1324,7 @@ class Engine:
         elif out.numel() and out.data_ptr() == qpos.data_ptr():
             raise EngineError("out must not be qpos: a row is permuted, so the call cannot work in place")
         mi = _native.MirrorInput()
-        mi.qpos, mi.n_frames, mi.seq_offsets, mi.n_seq = qpos.data_ptr(), int(qpos.shape[0]), offs.data_ptr(), int(offs.shape[0]) - 1
+        mi.qpos, mi.n_frames, mi.seq_offsets, mi.n_seq = qpos.data_ptr(), N, offs.data_ptr(), int(offs.shape[0]) - 1
         mi.mode, mi.col_src, mi.col_sign, mi.qpos_out = _native.MIRROR_MODES[about], tab["col_src"].data_ptr(), tab["col_sign"].data_ptr(), out.data_ptr()
         mi.stream = torch.cuda.current_stream(dev).cuda_stream
         self._check(self._lib.gmr_motion_mirror(self._h, C.byref(mi)), "gmr_motion_mirror")
@@ -1413,11 +1353,9 @@ class Engine:
         dev = self.device
         if self.cm.robot.planar_base:
             raise NotImplementedError("composing assumes a free-joint root; a planar-base robot is not supported")
-        if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-                or int(qpos.shape[1]) != self.nq or not qpos.is_contiguous():
-            raise EngineError(f"qpos must be a contiguous float64 [N, {self.nq}] tensor on the engine's device")
-        if int(qpos.shape[0]) != plan.n_frames:
-            raise EngineError(f"the plan was made for {plan.n_frames} source rows, qpos has {int(qpos.shape[0])}")
+        N = _qpos_rows(qpos, self.nq, dev)
+        if N != plan.n_frames:
+            raise EngineError(f"the plan was made for {plan.n_frames} source rows, qpos has {N}")
         st = torch.cuda.current_stream(dev) if stream is None else stream
         with torch.cuda.stream(st):
             tab = self.compose_device(plan)
@@ -1433,7 +1371,7 @@ class Engine:
         if res["out"].numel() and res["out"].data_ptr() == qpos.data_ptr():
             raise EngineError("out must not be qpos: an output row reads other rows")
         ci = _native.ComposeInput()
-        ci.qpos, ci.n_frames = qpos.data_ptr(), int(qpos.shape[0])
+        ci.qpos, ci.n_frames = qpos.data_ptr(), N
         for k, t in tab.items():
             setattr(ci, k, t.data_ptr())
         ci.n_seg, ci.n_out, ci.n_out_frames = plan.n_seg, plan.n_out, plan.n_out_frames
@@ -1456,10 +1394,7 @@ class Engine:
         clip) are uploaded in every call."""
         from .transitions import search_tables
         dev = self.device
-        if not isinstance(qpos, torch.Tensor) or qpos.device != dev or qpos.dtype != torch.float64 or qpos.dim() != 2 \
-                or int(qpos.shape[1]) != self.nq or not qpos.is_contiguous():
-            raise EngineError(f"qpos must be a contiguous float64 [N, {self.nq}] tensor on the engine's device")
-        N = int(qpos.shape[0])
+        N = _qpos_rows(qpos, self.nq, dev)
         offs = np.ascontiguousarray(seq_offsets.cpu().numpy() if isinstance(seq_offsets, torch.Tensor) else seq_offsets, dtype=np.int64)
         src, src_offs, dst, dst_offs = search_tables(offs, src_clips, dst_clips, window, stride)
         if int(offs[-1]) > N:
