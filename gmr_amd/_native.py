@@ -32,7 +32,8 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_clip_report", "gmr_group_clip_report", "gmr_motion_track", "gmr_group_motion_track",
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
            "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics",
-           "gmr_motion_self_collision", "gmr_motion_mirror", "gmr_motion_compose", "gmr_motion_transitions"]
+           "gmr_motion_self_collision", "gmr_motion_mirror", "gmr_motion_compose", "gmr_motion_transitions",
+           "gmr_motion_retime_plan", "gmr_motion_retime_apply"]
 
 
 class IKParams(C.Structure):
@@ -208,6 +209,27 @@ class TransitionsInput(C.Structure):
                 ("n_sources", C.c_int64), ("n_targets", C.c_int64), ("stream", C.c_void_p)] + [(k, C.c_void_p) for k in TRANSITIONS_OUTPUTS]
 
 
+RETIME_MAX_NQ, RETIME_MAX_WINDOW, RETIME_MAX_STRETCH, RETIME_Q = 64, 32, 64.0, 1024   # kRetime* (gmr_amd/csrc/retime_kernel.hip.h)
+RETIME_PLAN_OUTPUTS = ("need", "ticks", "cum", "out_len", "clip_stats", "need_max")    # gmr_retime_plan_input's output pointers, in order
+RETIME_STATS = ("stretched_intervals", "capped_intervals", "nonfinite_intervals", "total_ticks")   # the columns of clip_stats
+
+
+class RetimePlanInput(C.Structure):
+    """``gmr_retime_plan_input`` (include/gmr_amd.h): the whole call of the retiming plan, its stream included."""
+
+    _fields_ = [("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("n_seq", C.c_int32), ("window", C.c_int32),
+                ("fps", C.c_double), ("vmax", C.c_void_p), ("max_stretch", C.c_double), ("stream", C.c_void_p)] \
+        + [(k, C.c_void_p) for k in RETIME_PLAN_OUTPUTS] + [("reserved", C.c_int64)]
+
+
+class RetimeApplyInput(C.Structure):
+    """``gmr_retime_apply_input`` (include/gmr_amd.h): the whole call of the resampling along a retiming plan, its stream included."""
+
+    _fields_ = [("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("ticks", C.c_void_p), ("cum", C.c_void_p),
+                ("out_offsets", C.c_void_p), ("n_seq", C.c_int32), ("reserved", C.c_int32), ("n_out_frames", C.c_int64),
+                ("stream", C.c_void_p), ("qpos_out", C.c_void_p), ("src_time", C.c_void_p)]
+
+
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
 CLIP_REPORT_LIMIT_EPS = 1e-3    # GMR_CLIP_REPORT_LIMIT_EPS
 
@@ -342,6 +364,10 @@ def load():
     L.gmr_motion_compose.argtypes = [vp, C.POINTER(ComposeInput)]
     L.gmr_motion_transitions.restype = C.c_int
     L.gmr_motion_transitions.argtypes = [vp, C.POINTER(TransitionsInput)]
+    L.gmr_motion_retime_plan.restype = C.c_int
+    L.gmr_motion_retime_plan.argtypes = [vp, C.POINTER(RetimePlanInput)]
+    L.gmr_motion_retime_apply.restype = C.c_int
+    L.gmr_motion_retime_apply.argtypes = [vp, C.POINTER(RetimeApplyInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

@@ -39,6 +39,7 @@
 #include "mirror_kernel.hip.h"
 #include "compose_kernel.hip.h"
 #include "transitions_kernel.hip.h"
+#include "retime_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
 #include "clip_launch.h"
@@ -1941,6 +1942,77 @@ int gmr_motion_transitions(gmr_model *m, const gmr_transitions_input *in) {
   }
   if (in->cost_out && !in->dst_offsets) { set_err(m, "null argument: cost_out needs dst_offsets"); return GMR_EINVAL; }
   return transitions_run(m, *in, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ retiming to velocity limits (retime_kernel.hip.h)
+// The launches of gmr_motion_retime_plan (three) and gmr_motion_retime_apply (one), and nothing else: no allocation, no copy, no
+// synchronisation.  The need, ticks and apply kernels take the grid (clips, wavefronts per clip) by the grid rule of clip_launch.h
+// over the mean clip's tiles of input (apply: output) rows; the scan kernel takes one wavefront per clip.  GMR_AMD_RETIME_WAVES
+// forces the wavefronts per clip (the results do not depend on it).
+static unsigned retime_clip_waves(int64_t n_rows, int64_t n_seq) {
+  const unsigned rule = gmr::clip_waves(gmr::kRetimeTargetWaves, n_seq, gmr::mean_clip_tiles(n_rows, n_seq, gmr::kRetimeTile));
+  return (unsigned)gmr::env_int("GMR_AMD_RETIME_WAVES", 1, gmr::kGridYMax, rule);
+}
+
+static int retime_plan_run(gmr_model *m, const gmr_retime_plan_input &in, int nq, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::RetimePlanArgs a{};
+  a.qpos = in.qpos; a.seq_offsets = in.seq_offsets; a.vmax = in.vmax; a.need = in.need; a.ticks = in.ticks; a.cum = in.cum;
+  a.out_len = in.out_len; a.clip_stats = in.clip_stats; a.need_max = in.need_max;
+  a.fps = in.fps; a.max_stretch = in.max_stretch; a.n_frames = in.n_frames; a.n_seq = in.n_seq; a.nq = nq; a.window = in.window;
+  if (in.n_frames > 0) {  // (without frames every clip is empty: only the per-clip results are written)
+    const unsigned ty = retime_clip_waves(in.n_frames, in.n_seq);
+    hipLaunchKernelGGL(gmr::motion_retime_need_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
+    hipLaunchKernelGGL(gmr::motion_retime_ticks_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
+  }
+  hipLaunchKernelGGL(gmr::motion_retime_scan_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_retime_plan(gmr_model *m, const gmr_retime_plan_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (in->window < 0 || in->window > gmr::kRetimeMaxWindow) { set_err(m, "window must be 0 .. %d", gmr::kRetimeMaxWindow); return GMR_EINVAL; }
+  if (!(in->max_stretch >= 1.0) || !(in->max_stretch <= 64.0)) { set_err(m, "max_stretch must be 1 .. 64"); return GMR_EINVAL; }
+  if (!std::isfinite(in->fps) || !(in->fps > 0.0)) { set_err(m, "fps must be finite and > 0"); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "retiming needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int nq = m->fk.ndof + 7;
+  if (nq > gmr::kRetimeMaxNq) { set_err(m, "a row of %d columns does not fit one wavefront", nq); return GMR_EUNSUPPORTED; }
+  if (in->n_seq == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (!in->seq_offsets || !in->out_len || !in->clip_stats || !in->need_max) { set_err(m, "null argument"); return GMR_EINVAL; }
+  if (in->n_frames > 0 && (!in->qpos || !in->need || !in->ticks || !in->cum || (nq > 7 && !in->vmax))) { set_err(m, "null argument"); return GMR_EINVAL; }
+  return retime_plan_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
+}
+
+static int retime_apply_run(gmr_model *m, const gmr_retime_apply_input &in, int nq, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::RetimeApplyArgs a{};
+  a.qpos = in.qpos; a.seq_offsets = in.seq_offsets; a.out_offsets = in.out_offsets; a.ticks = in.ticks; a.cum = in.cum;
+  a.out = in.qpos_out; a.src_time = in.src_time;
+  a.n_frames = in.n_frames; a.n_out_frames = in.n_out_frames; a.n_seq = in.n_seq; a.nq = nq;
+  const unsigned ty = retime_clip_waves(in.n_out_frames, in.n_seq);
+  hipLaunchKernelGGL(gmr::motion_retime_apply_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_retime_apply(gmr_model *m, const gmr_retime_apply_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0 || in->n_out_frames < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "retiming needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int nq = m->fk.ndof + 7;
+  if (nq > gmr::kRetimeMaxNq) { set_err(m, "a row of %d columns does not fit one wavefront", nq); return GMR_EUNSUPPORTED; }
+  if (in->n_seq == 0 || in->n_frames == 0 || in->n_out_frames == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (!in->qpos || !in->seq_offsets || !in->ticks || !in->cum || !in->out_offsets || !in->qpos_out || !in->src_time) {
+    set_err(m, "null argument"); return GMR_EINVAL;
+  }
+  if (in->qpos_out == in->qpos) { set_err(m, "qpos_out must not be qpos: an output row reads other rows"); return GMR_EINVAL; }
+  return retime_apply_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

@@ -1,5 +1,5 @@
 // clip_launch.h -- the launch arithmetic of the clip-wise motion calls (foot locking, inverse dynamics, self-collision, mirror,
-// compose, transition search): grids, environment overrides and the body tree's parent / depth bytes.
+// compose, transition search, retiming): grids, environment overrides and the body tree's parent / depth bytes.
 //
 // Plain C++17, host only, no HIP include: api.hip and a stand-alone host test share these functions.  The constants (target
 // wavefronts, tiles, limits) stay with their kernels; the callers pass them in.
@@ -28,7 +28,8 @@ inline unsigned clip_waves(int64_t target, int64_t n_clips, int64_t mean_units) 
 }
 // Units of the mean clip.  Frame slots at `groups` frames side by side (chain_geom), rounded over the whole call first ...
 inline int64_t mean_clip_slots(int64_t n_frames, int groups, int64_t n_clips) { return clip_ceil_div(clip_ceil_div(n_frames, groups), n_clips); }
-// ... and tiles of `tile` rows of the mean clip (kernel b of the transition search: tile = kFkWave).
+// ... and tiles of `tile` rows of the mean clip (kernel b of the transition search: tile = kFkWave; retiming's apply kernel: the
+// mean clip's OUTPUT rows).
 inline int64_t mean_clip_tiles(int64_t n_rows, int64_t n_clips, int tile) { return clip_ceil_div(clip_ceil_div(n_rows, n_clips), tile); }
 
 // Foot locking's own rule, over the `tile`-frame tiles (kFkWave) of its kernels a and c: four times the mean clip's tiles in flight

@@ -84,7 +84,7 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
                    track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
                    contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False, dynamics: bool = False,
-                   collision=None, mirror=False):
+                   collision=None, mirror=False, retime=None):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -100,7 +100,11 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     qpos follows the dynamics report (or what precedes it) and precedes the tracks.  With ``mirror`` (``True``, or a dict of
     ``augment_mirror``'s keywords ``about`` and ``plan``) the motions and the tracks are made from ``augment_mirror`` of the (smoothed)
     qpos: twice the clips, clip ``S + i`` the mirror image of clip ``i``; the reports stay those of the ``S`` solved clips (a
-    mirrored clip has no human targets to be compared with).  A robot that is not symmetric raises ``SymmetryError`` before the solve."""
+    mirrored clip has no human targets to be compared with).  A robot that is not symmetric raises ``SymmetryError`` before the solve.
+    With ``retime`` (``True``, one rate in rad/s, or ``{joint: rad/s}``: ``retime_to_limits``' ``velocity_limits``, ``True`` standing for
+    ``None``) the (smoothed) qpos is retimed to those limits before anything but the clip report is made from it: the motions, the
+    dynamics and self-collision reports, the mirror images and the tracks are those of the retimed clips, which are longer where a
+    hinge was too fast; the clip report stays that of the solved clips (a retimed frame has no human targets to be compared with)."""
     mirror_kw = dict(mirror) if isinstance(mirror, dict) else {}
     if mirror and mirror_kw.get("plan") is None:
         gmr.symmetry_plan()  # (SymmetryError here, before any solve)
@@ -123,6 +127,8 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
         if lowpass_hz:
             qpos = smooth_qpos(gmr, qpos, seq_offsets, fps, lowpass_hz)
         rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
+    if retime is not None and retime is not False:
+        qpos, seq_offsets, _ = retime_to_limits(gmr, qpos, seq_offsets, fps, None if retime is True else retime)
     q_all, offs_all, fps_all = augment_mirror(gmr, qpos, seq_offsets, fps, **mirror_kw) if mirror else (qpos, seq_offsets, fps)
     res = (motions_from_qpos(gmr, q_all, offs_all, fps_all, height_adjust=height_adjust, root_origin_offset=root_origin_offset),)
     if rep is not None:
@@ -594,6 +600,104 @@ def repeat_clip(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: 
     """One output clip: clip ``clip`` ``times`` times over, each pass starting where the last one ended (``compose_clips``)."""
     frames = int(seq_offsets[clip + 1]) - int(seq_offsets[clip])
     return compose_clips(gmr, qpos, seq_offsets, [[(clip, 0, frames)] * int(times)], blend)
+
+
+# ------------------------------------------------------------------ retiming to velocity limits
+# Conventions, not measured on a robot: four intervals on either side spread a stretch over about a tenth of a second at 30 - 60 Hz,
+# and a clip that needs more than eight times its duration somewhere is better looked at than played.
+RETIME_WINDOW = 4
+RETIME_MAX_STRETCH = 8.0
+
+
+def retime_vmax(robot, velocity_limits=None, retargeter_limits=None) -> np.ndarray:
+    """``[nq - 7]`` rad/s per hinge in qpos order for ``retime_to_limits``: ``velocity_limits`` in the forms
+    ``GeneralMotionRetargeting`` takes (one number, or ``{joint: rad/s}``; ``resolve_velocity_limits``); ``None``: the retargeter's own
+    table ``retargeter_limits`` where it has one, else every limited hinge at ``DEFAULT_VELOCITY_LIMIT``.  A hinge the table does not
+    name is ``inf``.  No device is needed."""
+    from .model import resolve_velocity_limits
+    if velocity_limits is not None:
+        table = resolve_velocity_limits(robot, False, velocity_limits)
+    elif retargeter_limits is not None:
+        table = dict(retargeter_limits)
+    else:
+        table = resolve_velocity_limits(robot, True, None)
+    bodies = sorted((int(b) for b in robot.hinge_bodies()), key=lambda b: int(robot.qpos_adr[b]))
+    vmax = np.array([float(table.get(robot.jnt_names[b], np.inf)) for b in bodies], dtype=np.float64)
+    if not np.all(vmax > 0.0):
+        raise ValueError("every velocity limit must be > 0 (inf: no limit)")
+    return vmax
+
+
+def retime_to_limits(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, velocity_limits=None,
+                     window: int = RETIME_WINDOW, max_stretch: float = RETIME_MAX_STRETCH):
+    """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) played slower exactly where a
+    hinge turns faster than its velocity limit, on the GPU (``Engine.motion_retime_plan`` / ``motion_retime_apply``; the definition
+    is the contract above ``gmr_retime_plan_input`` in include/gmr_amd.h): a monotone time warp and a resampling at the clip's own
+    rate.  The joint-space path is kept, unlike ``use_velocity_limit=True`` in the solve, and no clip is dropped.
+    ``velocity_limits``: see ``retime_vmax`` (``None``: ``gmr.velocity_limits``, else ``DEFAULT_VELOCITY_LIMIT`` on every limited
+    hinge).  ``window``: the intervals on either side over which a stretch is widened and averaged; ``max_stretch``: the largest
+    local slow-down, beyond which an interval is counted as capped and still exceeds its limit (``RETIME_WINDOW`` and
+    ``RETIME_MAX_STRETCH`` are conventions, not measured on a robot).
+    Returns ``(qpos_out, seq_offsets_out, info)``: ordinary qpos and offsets at the same ``fps`` for ``lock_feet``,
+    ``tracking_from_qpos``, ``dynamics_report``, ``MotionLibrary`` and ``compose_clips``; ``info`` holds per clip ``stretch`` (output
+    over input duration; 1 for a clip of fewer than two frames), ``stretched_intervals``, ``capped_intervals``,
+    ``nonfinite_intervals`` and ``need_max`` (host arrays ``[S]``), and per frame ``need`` (device ``[N]``: the interval's largest
+    speed over its limit, at its first row) and ``src_time`` (device ``[M]``: the source time of every output row in frames of its
+    clip, for warping per-frame labels such as contacts).
+    The output lengths depend on the data: between the two calls ``out_len`` is read back from the device -- the one host
+    synchronisation, once per distinct rate."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("retiming assumes a free-joint root; a planar-base robot is not supported")
+    eng = gmr._engine
+    vmax = retime_vmax(gmr.model, velocity_limits, getattr(gmr, "velocity_limits", None))
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    S, N = offs.size - 1, int(qpos.shape[0])
+    if offs.ndim != 1 or S < 0 or offs[0] != 0 or offs[-1] != N or np.any(np.diff(offs) < 0):
+        raise ValueError("seq_offsets must span [0, N] and not go back")
+    f = np.asarray(fps.detach().cpu().numpy() if isinstance(fps, torch.Tensor) else fps, dtype=np.float64)
+    f = np.full(S, float(f)) if f.ndim == 0 else f
+    if f.shape != (S,):
+        raise ValueError("fps must be one rate or one rate per clip")
+    lens = np.diff(offs)
+    out_len = np.zeros(S, dtype=np.int64)
+    stats = np.zeros((S, 4), dtype=np.int64)
+    need_max = np.zeros(S)
+    need = torch.zeros(N, dtype=torch.float64, device=qpos.device)
+    vdev = torch.from_numpy(vmax).to(qpos.device)
+    parts = []   # (clips, their plan, their qpos and offsets) per distinct rate
+    for rate in np.unique(f[lens > 0]):
+        sel = np.flatnonzero((f == rate) & (lens > 0))
+        if sel.size == np.count_nonzero(lens > 0):  # one rate: the batch as it is
+            sel, rows, q, o = np.arange(S), None, qpos, offs
+        else:
+            rows = torch.from_numpy(np.concatenate([np.arange(offs[s], offs[s + 1]) for s in sel])).to(qpos.device)
+            q, o = qpos.index_select(0, rows), np.concatenate([[0], np.cumsum(lens[sel])]).astype(np.int64)
+        plan = eng.motion_retime_plan(q, o, float(rate), vdev, window, max_stretch)
+        out_len[sel] = plan["out_len"].cpu().numpy()   # the host synchronisation
+        stats[sel], need_max[sel] = plan["clip_stats"].cpu().numpy(), plan["need_max"].cpu().numpy()
+        if rows is None:
+            need = plan["need"]
+        else:
+            need.index_copy_(0, rows, plan["need"])
+        parts.append((sel, plan, q, o))
+    offs_out = np.concatenate([[0], np.cumsum(out_len)]).astype(np.int64)
+    M = int(offs_out[-1])
+    qpos_out = torch.empty((M, eng.nq), dtype=torch.float64, device=qpos.device)
+    src_time = torch.empty(M, dtype=torch.float64, device=qpos.device)
+    for sel, plan, q, o in parts:
+        oo = np.concatenate([[0], np.cumsum(out_len[sel])]).astype(np.int64)
+        if len(parts) == 1:
+            eng.motion_retime_apply(q, o, plan, oo, out={"qpos": qpos_out, "src_time": src_time})
+        else:
+            part, st, _ = eng.motion_retime_apply(q, o, plan, oo)
+            rows = torch.from_numpy(np.concatenate([np.arange(offs_out[s], offs_out[s + 1]) for s in sel])).to(qpos.device)
+            qpos_out.index_copy_(0, rows, part)
+            src_time.index_copy_(0, rows, st)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        stretch = np.where(lens > 1, (out_len - 1) / np.maximum(lens - 1, 1), 1.0)
+    info = {"stretch": stretch, "stretched_intervals": stats[:, 0], "capped_intervals": stats[:, 1], "nonfinite_intervals": stats[:, 2],
+            "need_max": need_max, "need": need, "src_time": src_time}
+    return qpos_out, offs_out, info
 
 
 # ------------------------------------------------------------------ transitions between clips

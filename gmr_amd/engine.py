@@ -544,6 +544,17 @@ class MotionTransitions(dict):
     ``weights``.  Source ``src_offsets[a] + u`` is frame ``u * stride`` of clip ``src_clips[a]``."""
 
 
+RETIME_FIELDS = _native.RETIME_PLAN_OUTPUTS   # the arrays of a retiming plan, in gmr_retime_plan_input's order
+RETIME_STATS = _native.RETIME_STATS           # the columns of its clip_stats
+
+
+class MotionRetimePlan(dict):
+    """Result of ``motion_retime_plan``: the device tensors by name -- ``need`` ``[N]`` float64, ``ticks`` and ``cum`` ``[N]`` int64
+    (1024 ticks per source frame; an interval's values at its first row), ``out_len`` ``[S]`` int64, ``clip_stats`` ``[S, 4]`` int64
+    (``RETIME_STATS``) and ``need_max`` ``[S]`` float64 -- and as attributes ``seq_offsets`` (the device tensor the call read),
+    ``fps``, ``window`` and ``max_stretch``.  What ``motion_retime_apply`` takes."""
+
+
 CLIP_REPORT_SEGMENT = _native.CLIP_REPORT_SEGMENT      # frames per wavefront of the clip report (GMR_CLIP_REPORT_SEGMENT)
 CLIP_REPORT_LIMIT_EPS = _native.CLIP_REPORT_LIMIT_EPS  # rad: a hinge this close to a limit counts as "near" it
 
@@ -1444,6 +1455,115 @@ class Engine:
         mt.src_clips, mt.src_offsets, mt.dst_clips, mt.dst_offsets = src, src_offs, dst, dst_offs
         mt.window, mt.stride, mt.min_gap, mt.weights = int(window), int(stride), int(min_gap), w
         return mt
+
+    def motion_retime_plan(self, qpos: torch.Tensor, seq_offsets, fps: float, vmax, window: int, max_stretch: float, out=None) -> MotionRetimePlan:
+        """The time warp that plays qpos ``[N, nq]`` float64 (engine layout, concatenated clips at the one rate ``fps``) slower exactly
+        where a hinge turns faster than ``vmax`` ``[nq - 7]`` rad/s (qpos order, every entry > 0, ``inf``: no limit), in three kernels
+        (``gmr_motion_retime_plan``; the definition is the contract in include/gmr_amd.h): per interval the need, the stretch
+        capped at ``max_stretch`` (1 .. 64), widened and averaged over ``window`` (0 .. 32) intervals on either side, as integer ticks
+        of 1/1024 frame; per clip their prefix sum, the output length and the statistics.  ``seq_offsets`` ``[S + 1]``: a host
+        sequence (uploaded once) or a device int64 tensor.  ``vmax``: a host sequence (checked, uploaded) or a device float64
+        tensor (trusted).  Returns a :class:`MotionRetimePlan` of device tensors; ``out``: caller-owned tensors by all its names.
+        Asynchronous on the current stream; with ``out``, a device ``seq_offsets`` and a device ``vmax`` no allocation, no copy, no
+        synchronisation."""
+        dev = self.device
+        if self.cm.robot.planar_base:
+            raise NotImplementedError("retiming assumes a free-joint root; a planar-base robot is not supported")
+        N = _qpos_rows(qpos, self.nq, dev)
+        offs = _clip_offsets(seq_offsets, dev)
+        S, nh = int(offs.shape[0]) - 1, self.nq - 7
+        fps, window, max_stretch = float(fps), int(window), float(max_stretch)
+        if not np.isfinite(fps) or not fps > 0.0:
+            raise ValueError("fps must be finite and > 0")
+        if not 0 <= window <= _native.RETIME_MAX_WINDOW:
+            raise ValueError(f"window must lie in [0, {_native.RETIME_MAX_WINDOW}]")
+        if not 1.0 <= max_stretch <= _native.RETIME_MAX_STRETCH:
+            raise ValueError(f"max_stretch must lie in [1, {_native.RETIME_MAX_STRETCH:g}]")
+        if isinstance(vmax, torch.Tensor):
+            if vmax.device != dev or vmax.dtype != torch.float64 or tuple(vmax.shape) != (nh,) or not vmax.is_contiguous():
+                raise EngineError(f"vmax must be a contiguous float64 [{nh}] tensor on the engine's device (or a host sequence)")
+        else:
+            v = np.ascontiguousarray(vmax, dtype=np.float64)
+            if v.shape != (nh,) or not np.all(v > 0.0):
+                raise ValueError(f"vmax must hold {nh} limits, every one > 0 (inf: no limit)")
+            vmax = torch.from_numpy(v).to(dev)
+        f64, i64 = torch.float64, torch.int64
+        shapes = {"need": ((N,), f64), "ticks": ((N,), i64), "cum": ((N,), i64), "out_len": ((S,), i64), "clip_stats": ((S, 4), i64),
+                  "need_max": ((S,), f64)}
+        if out is None:
+            res = {k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}  # rows outside every clip are not written
+        else:
+            if set(out) != set(shapes) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                              or t.device != dev or not t.is_contiguous() for k, t in out.items()):
+                raise EngineError(f"out must map {sorted(shapes)} to contiguous tensors of the call's shapes on the engine's device")
+            res = {k: out[k] for k in shapes}
+        pi = _native.RetimePlanInput()
+        pi.qpos, pi.n_frames, pi.seq_offsets, pi.n_seq, pi.window = qpos.data_ptr(), N, offs.data_ptr(), S, window
+        pi.fps, pi.vmax, pi.max_stretch = fps, vmax.data_ptr(), max_stretch
+        for k, t in res.items():
+            setattr(pi, k, t.data_ptr())
+        pi.stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.gmr_motion_retime_plan(self._h, C.byref(pi)), "gmr_motion_retime_plan")
+        plan = MotionRetimePlan(res)
+        plan.seq_offsets, plan.fps, plan.window, plan.max_stretch = offs, fps, window, max_stretch
+        return plan
+
+    def motion_retime_apply(self, qpos: torch.Tensor, seq_offsets, plan, out_offsets=None, out=None):
+        """qpos ``[N, nq]`` float64 resampled along ``plan`` (a :class:`MotionRetimePlan` of these clips, or a mapping with its
+        ``ticks`` and ``cum``) in one kernel (``gmr_motion_retime_apply``; the definition is the contract in include/gmr_amd.h).
+        ``out_offsets`` ``[S + 1]``: the output clips' rows, a host sequence or a device int64 tensor; ``None``: the prefix sum of
+        ``plan["out_len"]``, which is READ BACK from the device -- a host synchronisation.  Returns ``(qpos_out [M, nq], src_time [M],
+        out_offsets)``: the retimed clips, per output row the source time in frames of its clip, and the offsets (a host int64 array,
+        or the device tensor that was given).  ``out``: caller-owned ``{"qpos": [M, nq], "src_time": [M]}`` float64 tensors, required
+        with a device ``out_offsets``; with ``out`` M is its number of rows (the offsets are clamped into them), without it the last
+        offset; ``out["qpos"]`` must not be ``qpos``.  Asynchronous on the current
+        stream; with ``out`` and device offsets no allocation, no copy, no synchronisation."""
+        dev = self.device
+        if self.cm.robot.planar_base:
+            raise NotImplementedError("retiming assumes a free-joint root; a planar-base robot is not supported")
+        N = _qpos_rows(qpos, self.nq, dev)
+        offs = _clip_offsets(seq_offsets, dev)
+        S = int(offs.shape[0]) - 1
+        for k in ("ticks", "cum"):
+            t = plan[k]
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.int64 or tuple(t.shape) != (N,) or not t.is_contiguous():
+                raise EngineError(f"plan[{k!r}] must be a contiguous int64 [{N}] tensor on the engine's device")
+        if out_offsets is None:
+            oo = np.concatenate([[0], np.cumsum(plan["out_len"].cpu().numpy())]).astype(np.int64)  # the pair's one host synchronisation
+            if oo.size != S + 1:
+                raise EngineError(f"the plan was made for {oo.size - 1} clips, seq_offsets has {S}")
+            ret_offs, M = oo, int(oo[-1])
+            oo = torch.from_numpy(oo).to(dev)
+        elif isinstance(out_offsets, torch.Tensor):
+            oo = ret_offs = _clip_offsets(out_offsets, dev, "out_offsets")
+            if out is None:
+                raise EngineError("a device out_offsets needs out: its tensors say how many output rows there are")
+            M = -1
+        else:
+            ret_offs = np.array(out_offsets, dtype=np.int64)  # (a copy: the caller's may be read-only)
+            oo = _clip_offsets(ret_offs, dev, "out_offsets")
+            M = int(ret_offs[-1])
+        if out is not None and isinstance(out.get("qpos"), torch.Tensor) and out["qpos"].dim() == 2:
+            M = int(out["qpos"].shape[0])  # (the offsets are clamped into the rows there are, as seq_offsets is)
+        if int(oo.shape[0]) != S + 1:
+            raise EngineError(f"out_offsets must hold {S + 1} entries")
+        shapes = {"qpos": ((M, self.nq), torch.float64), "src_time": ((M,), torch.float64)}
+        if out is None:
+            res = {k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}  # rows outside every clip are not written
+        else:
+            if set(out) != set(shapes) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                              or t.device != dev or not t.is_contiguous() for k, t in out.items()):
+                raise EngineError(f"out must map {sorted(shapes)} to contiguous float64 tensors of {M} rows on the engine's device")
+            res = {k: out[k] for k in shapes}
+        if res["qpos"].numel() and res["qpos"].data_ptr() == qpos.data_ptr():
+            raise EngineError("out must not be qpos: an output row reads other rows")
+        ai = _native.RetimeApplyInput()
+        ai.qpos, ai.n_frames, ai.seq_offsets, ai.n_seq = qpos.data_ptr(), N, offs.data_ptr(), S
+        ai.ticks, ai.cum, ai.out_offsets, ai.n_out_frames = plan["ticks"].data_ptr(), plan["cum"].data_ptr(), oo.data_ptr(), M
+        ai.qpos_out, ai.src_time = res["qpos"].data_ptr(), res["src_time"].data_ptr()
+        ai.stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.gmr_motion_retime_apply(self._h, C.byref(ai)), "gmr_motion_retime_apply")
+        return res["qpos"], res["src_time"], ret_offs
 
     def clip_report(self, qpos: torch.Tensor, seq_offsets, pos: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None,
                     slot_col: Optional[np.ndarray] = None, height_scale=None, iters: Optional[torch.Tensor] = None,

@@ -118,6 +118,7 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--mirror", default=False, action="store_true", help="also write the left-right mirrored copy of every clip, X_mirror.pkl beside X.pkl (and X_mirror.npz beside a tracking export), made on the GPU from the solved qpos (dataset.augment_mirror) with the same post-processing; a robot that is not symmetric within 1e-3 (gmr_amd.symmetry.plan_symmetry) ends the run before any file is read; the reports stay those of the solved clips; default: off")
     ap.add_argument("--mirror_about", default="start", choices=["world", "start"], help="with --mirror: reflect in the world plane y = 0 (world), or each clip in the vertical plane through its first root position along its heading, so that the mirrored clip starts where the original does (start, the default)")
     ap.add_argument("--mirror_plan", default=None, type=str, metavar="FILE.json", help="with --mirror: the symmetry plan from this file (gmr_amd.symmetry.save_plan writes one) instead of the robot's own; with --robots: robot:file;robot2:file2")
+    ap.add_argument("--retime_to_limits", nargs="?", const=True, default=None, type=float, metavar="RAD_PER_S", help="play every solved clip slower exactly where a hinge turns faster than its velocity limit (dataset.retime_to_limits, on the GPU: a monotone time warp, resampled at the clip's rate) before the pickles, the dynamics and collision reports and the tracking exports are made; the clip report stays that of the solved clips; with a number: that limit on every hinge; without: the retargeter's limits (--use_velocity_limit / --velocity_limit), else 3 pi rad/s on every limited hinge; not with --robots; default: off")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -129,6 +130,11 @@ def resolve_track(ap, args) -> None:
         ap.error("--track_fps must be positive")
     if getattr(args, "lowpass_hz", None) is not None and not args.lowpass_hz > 0:
         ap.error("--lowpass_hz must be positive")
+    retime = getattr(args, "retime_to_limits", None)
+    if retime is not None and retime is not True and not retime > 0:
+        ap.error("--retime_to_limits must be positive")
+    if retime is not None and getattr(args, "robots", None):
+        ap.error("--retime_to_limits is not available with --robots")
     resolve_contact(ap, args)
     resolve_mirror(ap, args)
 
@@ -347,6 +353,7 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         dyn_kw = {"dynamics": True} if wants_dynamics(args) else {}  # (absent without the flags: nothing changes then)
         col_kw = collision_kw(args, model=g.model) if wants_collision(args) else {}  # (ditto)
         mir_kw = getattr(args, "mirror_kw", {})  # (ditto)
+        ret_kw = {} if getattr(args, "retime_to_limits", None) is None else {"retime": args.retime_to_limits}  # (ditto)
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:
@@ -356,7 +363,7 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
                     continue
                 targets = [target_of[f] for f in batch.files]
                 res = dataset.retarget_clips(g, batch.pos, batch.quat, batch.body_names, batch.seq_offsets, human_heights=batch.human_heights,
-                                             clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw, **mir_kw)
+                                             clip_start=args.clip_start, report=rep_on, **retarget_kw(batch), **track_kw, **dyn_kw, **col_kw, **mir_kw, **ret_kw)
                 res = res if isinstance(res, tuple) else (res,)
                 S = len(targets)
                 motions, mirror_of = res[0][:S], dict(zip(targets, res[0][S:]))  # (with --mirror clip S + i is the mirror of clip i)

@@ -77,6 +77,9 @@
  *                      onto the end of the one before it in the plane and cross-faded into it
  *   gmr_motion_transitions (no counterpart in the reference) where such a segment may follow another: the motion-graph distance of
  *                      every window of the source clips to every window of the target clips, reduced to the best frame per pair
+ *   gmr_motion_retime_plan, gmr_motion_retime_apply  (no counterpart in the reference) clips played slower exactly where a hinge
+ *                      turns faster than its actuator can: a monotone time warp from per-joint velocity limits, and the clips
+ *                      resampled along it at their own rate
  *   gmr_dof_to_rot    KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -983,6 +986,116 @@ typedef struct gmr_transitions_input {
   double        *cost_out;        /* device [E][n_targets] f64, or NULL */
 } gmr_transitions_input;
 int gmr_motion_transitions(gmr_model *m, const gmr_transitions_input *in);
+
+/* Retiming to joint velocity limits: every clip played slower exactly where a hinge turns faster than its limit, by a monotone time
+ * warp, and resampled along the warp at the clip's own rate.  The joint-space path is kept -- the remedy for a kick or a fall
+ * recovery whose hinges outrun the actuators that neither drops the clip nor lets the pose fall behind its key-points (a velocity
+ * limit inside the IK solve does).  The result is ordinary qpos with its own clip offsets: it feeds gmr_motion_footlock,
+ * gmr_motion_track, gmr_motion_dynamics, gmr_motion_sample and gmr_motion_compose unchanged.
+ *
+ * Two entries, because the output length depends on the data: gmr_motion_retime_plan writes the warp and every clip's output
+ * length, the caller turns the lengths into out_offsets (a prefix sum; reading them back is the one host synchronisation of the
+ * pair, and the caller's) and allocates, gmr_motion_retime_apply resamples.  For each entry the whole call is its struct, the
+ * stream included (in->stream, in the sense of the stream-order paragraph at the top of this file); the struct is read completely
+ * before the call returns.  A call enqueues its kernels on in->stream (plan: three, apply: one) and nothing else: no allocation, no
+ * copy, no synchronisation, no hidden scratch -- need, ticks and cum are the hand-over between the kernels and between the two
+ * entries, and results.  All arrays are device arrays; loads and stores are element-wise, so every array needs the alignment of
+ * its element type only.
+ *
+ * Time is an integer: Q = 1024 ticks per source frame.  The per-clip sums are exact in any order, and two calls give identical
+ * bytes.
+ *
+ * gmr_motion_retime_plan
+ *   qpos          f64 [n_frames][nq], free-joint layout (x y z, qw qx qy qz, hinges), concatenated clips (N = n_frames)
+ *   seq_offsets   int64 [n_seq+1]: clip s owns the rows a = clamp(seq_offsets[s], 0, N) to b = clamp(seq_offsets[s+1], a, N), n = b - a
+ *                 (gmr_motion_dynamics' rule).  Clips are expected not to overlap
+ *   fps           the clips' rate, one per call, finite and > 0
+ *   vmax          f64 [nq-7], rad/s per hinge in qpos order, every entry > 0; +inf: no limit.  Trusted (the Python layer checks it)
+ *   window        W in [0, 32] intervals;  max_stretch in [1, 64]
+ * A clip of n rows has n - 1 intervals; interval i lies between its rows i and i + 1 and its values are stored at row i.  The last
+ * row of every clip gets need = 0 and ticks = 0.  All arithmetic is float64 without floating-point contraction, in the order
+ * written:
+ *   need_ij = (fabs(q[i+1][7+j] - q[i][7+j]) * fps) / vmax[j]     per hinge j
+ *   the interval is NON-FINITE when any need_ij is not < +inf (a NaN or an infinity): then need_i = NaN (0x7ff8000000000000), it
+ *   stretches as 1, and it is counted;  otherwise need_i = max_j need_ij, 0 for a model without hinges.  The root columns do not
+ *   enter: a floating base has no actuator, and its speed scales with the warp anyway
+ *   s_i = min(max(1, need_i), max_stretch)      a clip is never sped up;  the interval is CAPPED when need_i > max_stretch
+ *   d_i = max of s_k over the intervals k in [i-W, i+W] of the clip
+ *   m_i = (the sum of d_k over the same k, in ascending k, starting from the first d_k) / (double)(their number)
+ *         every d_k of the window is at least s_i, so m_i >= s_i: the warp never undercuts a limit (where nothing is capped),
+ *         and the stretch changes by at most (max_stretch - 1) / (2W + 1) per frame
+ *   ticks_i = (int64)ceil(m_i * 1024.0)
+ *   cum[row] = the sum of ticks of the clip's earlier intervals: 0 in its first row, total in its last
+ *   out_len = 0 for a clip without rows, else (total + Q - 1) / Q + 1
+ *   need          f64 [n_frames];  ticks, cum  int64 [n_frames];  rows outside every clip are not written
+ *   out_len       int64 [n_seq]
+ *   clip_stats    int64 [n_seq][4] = (intervals with need_i > 1, capped intervals, non-finite intervals, total)
+ *   need_max      f64 [n_seq]: the largest finite need_i, 0 when there is none
+ * Clips of less than 2^31 rows.
+ *
+ * gmr_motion_retime_apply
+ *   qpos, seq_offsets, ticks, cum   as above: ticks and cum as gmr_motion_retime_plan wrote them for these clips
+ *   out_offsets   int64 [n_seq+1]: clip s owns the output rows out_offsets[s] .. out_offsets[s+1]-1, clamped into
+ *                 [0, n_out_frames] as seq_offsets is.  The caller builds it from out_len
+ *   qpos_out      f64 [n_out_frames][nq], not qpos;  src_time  f64 [n_out_frames]
+ * Output row k of a clip with n >= 1 rows is sampled at tau = k Q:
+ *   tau >= total: a bit-for-bit copy of the clip's last row, src_time = n - 1.  So the clip ends in its exact final pose, and the
+ *   last output interval only runs slower than planned
+ *   otherwise: the interval i with cum[i] <= tau < cum[i+1], u = (double)(tau - cum[i]) / (double)ticks[i], src_time = i + u (it
+ *   lets a caller warp per-frame labels such as contacts alongside the qpos).  Root position and hinges: x0 if u == 0, else
+ *   x0 + u (x1 - x0) (the tracking export's lerp).  Root quaternion: a copy of row i's if u == 0 or if the two rows' quaternions
+ *   are bytewise equal, otherwise the tracking export's shortest-arc slerp of the two at u, normalised, w x y z as stored
+ * A clip given fewer output rows than out_len is truncated; one given more repeats its last row; a clip without rows writes
+ * nothing.  Row and interval indices are clamped into the clip (the search looks only at intervals 0 .. min(k, n-2)), so a wrong
+ * out_offsets, ticks or cum cannot leave the arrays.
+ *
+ * Non-finite qpos.  A non-finite hinge entry reaches only the output rows that interpolate its row (u != 0 next to it, or a copy
+ * of it), in that column; it makes its two intervals non-finite: their need is NaN and they stretch as 1, so ticks change only
+ * within 2 W intervals of them, and only where that interval's clean stretch was above 1.  A non-finite root entry reaches root
+ * columns of the rows that read its row and nothing else: no need, no ticks.  No other clip changes.
+ * GMR_EINVAL: negative counts, NULL arrays with work to do, window outside [0, 32], max_stretch outside [1, 64] (a NaN included),
+ * fps not finite or not > 0, qpos_out == qpos.  GMR_EUNSUPPORTED: nq > 64 (a row does not fit one wavefront), a planar-base
+ * model.  Zero work -- n_seq = 0; for apply also n_frames = 0 or n_out_frames = 0 -- returns GMR_OK without a launch.  With
+ * n_frames = 0 and n_seq > 0 the plan still writes the clips' out_len, clip_stats and need_max (zeros).  Asynchronous on
+ * in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 120; offsets qpos 0, n_frames 8, seq_offsets 16, n_seq 24, window 28, fps 32, vmax 40, max_stretch 48,
+ * stream 56, need 64, ticks 72, cum 80, out_len 88, clip_stats 96, need_max 104, reserved 112.  */
+typedef struct gmr_retime_plan_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  int32_t        n_seq, window;
+  double         fps;
+  const double  *vmax;            /* device [nq-7] f64 */
+  double         max_stretch;
+  void          *stream;          /* the call's stream */
+  double        *need;            /* device [n_frames] f64 */
+  int64_t       *ticks;           /* device [n_frames] i64 */
+  int64_t       *cum;             /* device [n_frames] i64 */
+  int64_t       *out_len;         /* device [n_seq] i64 */
+  int64_t       *clip_stats;      /* device [n_seq][4] i64 */
+  double        *need_max;        /* device [n_seq] f64 */
+  int64_t        reserved;        /* 0 */
+} gmr_retime_plan_input;
+int gmr_motion_retime_plan(gmr_model *m, const gmr_retime_plan_input *in);
+
+/* The second entry of the pair: the contract is above gmr_retime_plan_input.
+ * Layout (LP64): sizeof 88; offsets qpos 0, n_frames 8, seq_offsets 16, ticks 24, cum 32, out_offsets 40, n_seq 48, reserved 52,
+ * n_out_frames 56, stream 64, qpos_out 72, src_time 80.  */
+typedef struct gmr_retime_apply_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  const int64_t *ticks;           /* device [n_frames] i64 */
+  const int64_t *cum;             /* device [n_frames] i64 */
+  const int64_t *out_offsets;     /* DEVICE [n_seq+1] */
+  int32_t        n_seq, reserved;
+  int64_t        n_out_frames;
+  void          *stream;          /* the call's stream */
+  double        *qpos_out;        /* device [n_out_frames][nq] f64, not qpos */
+  double        *src_time;        /* device [n_out_frames] f64 */
+} gmr_retime_apply_input;
+int gmr_motion_retime_apply(gmr_model *m, const gmr_retime_apply_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
