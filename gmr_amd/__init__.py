@@ -30,7 +30,7 @@ def __getattr__(name):
     if name == "load_robot_motion":
         from .dataset import load_robot_motion
         return load_robot_motion
-    if name in ("compose_clips", "repeat_clip", "find_transitions", "retime_to_limits"):
+    if name in ("compose_clips", "repeat_clip", "find_transitions", "retime_to_limits", "retime_to_torque_limits"):
         from . import dataset
         return getattr(dataset, name)
     if name == "RobotMotionViewer":

@@ -33,7 +33,7 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
            "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics",
            "gmr_motion_self_collision", "gmr_motion_mirror", "gmr_motion_compose", "gmr_motion_transitions",
-           "gmr_motion_retime_plan", "gmr_motion_retime_apply"]
+           "gmr_motion_retime_plan", "gmr_motion_retime_apply", "gmr_motion_retime_plan_torque"]
 
 
 class IKParams(C.Structure):
@@ -226,8 +226,21 @@ class RetimeApplyInput(C.Structure):
     """``gmr_retime_apply_input`` (include/gmr_amd.h): the whole call of the resampling along a retiming plan, its stream included."""
 
     _fields_ = [("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("ticks", C.c_void_p), ("cum", C.c_void_p),
-                ("out_offsets", C.c_void_p), ("n_seq", C.c_int32), ("reserved", C.c_int32), ("n_out_frames", C.c_int64),
+                ("out_offsets", C.c_void_p), ("n_seq", C.c_int32), ("interp", C.c_int32), ("n_out_frames", C.c_int64),
                 ("stream", C.c_void_p), ("qpos_out", C.c_void_p), ("src_time", C.c_void_p)]
+
+
+RETIME_INTERP = {"linear": 0, "cubic": 1}   # GMR_RETIME_INTERP_* (include/gmr_amd.h)
+RETIME_TORQUE_OUTPUTS = RETIME_PLAN_OUTPUTS + ("static_over",)   # gmr_retime_torque_input's output pointers, in order
+
+
+class RetimeTorqueInput(C.Structure):
+    """``gmr_retime_torque_input`` (include/gmr_amd.h): the whole call of the retiming plan from joint torques, its stream included."""
+
+    _fields_ = [("tau", C.c_void_p), ("tau_static", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p),
+                ("n_seq", C.c_int32), ("window", C.c_int32), ("torque_limit", C.c_void_p), ("limit_scale", C.c_double),
+                ("max_stretch", C.c_double), ("need_floor", C.c_void_p), ("align_end", C.c_int32), ("reserved", C.c_int32),
+                ("stream", C.c_void_p)] + [(k, C.c_void_p) for k in RETIME_TORQUE_OUTPUTS]
 
 
 CLIP_REPORT_SEGMENT = 32        # GMR_CLIP_REPORT_SEGMENT (include/gmr_amd.h)
@@ -368,6 +381,8 @@ def load():
     L.gmr_motion_retime_plan.argtypes = [vp, C.POINTER(RetimePlanInput)]
     L.gmr_motion_retime_apply.restype = C.c_int
     L.gmr_motion_retime_apply.argtypes = [vp, C.POINTER(RetimeApplyInput)]
+    L.gmr_motion_retime_plan_torque.restype = C.c_int
+    L.gmr_motion_retime_plan_torque.argtypes = [vp, C.POINTER(RetimeTorqueInput)]
     L.gmr_clip_report.restype = C.c_int
     L.gmr_clip_report.argtypes = [vp, C.POINTER(ClipReportInput), C.POINTER(ClipReportParams), vp]
     L.gmr_group_clip_report.restype = C.c_int

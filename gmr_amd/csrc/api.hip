@@ -40,6 +40,7 @@
 #include "compose_kernel.hip.h"
 #include "transitions_kernel.hip.h"
 #include "retime_kernel.hip.h"
+#include "retime_torque_kernel.hip.h"
 #include "bvh_text.h"
 #include "call_block.h"
 #include "clip_launch.h"
@@ -1994,7 +1995,8 @@ static int retime_apply_run(gmr_model *m, const gmr_retime_apply_input &in, int 
   a.out = in.qpos_out; a.src_time = in.src_time;
   a.n_frames = in.n_frames; a.n_out_frames = in.n_out_frames; a.n_seq = in.n_seq; a.nq = nq;
   const unsigned ty = retime_clip_waves(in.n_out_frames, in.n_seq);
-  hipLaunchKernelGGL(gmr::motion_retime_apply_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
+  const auto kernel = in.interp == GMR_RETIME_INTERP_CUBIC ? gmr::motion_retime_apply_cubic_kernel : gmr::motion_retime_apply_kernel;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
   if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
   return GMR_OK;
 }
@@ -2004,6 +2006,7 @@ int gmr_motion_retime_apply(gmr_model *m, const gmr_retime_apply_input *in) {
   m->err.clear();
   if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
   if (in->n_frames < 0 || in->n_seq < 0 || in->n_out_frames < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (in->interp != GMR_RETIME_INTERP_LINEAR && in->interp != GMR_RETIME_INTERP_CUBIC) { set_err(m, "interp must be 0 (linear) or 1 (cubic)"); return GMR_EINVAL; }
   if (m->dm.root_planar) { set_err(m, "retiming needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
   const int nq = m->fk.ndof + 7;
   if (nq > gmr::kRetimeMaxNq) { set_err(m, "a row of %d columns does not fit one wavefront", nq); return GMR_EUNSUPPORTED; }
@@ -2013,6 +2016,55 @@ int gmr_motion_retime_apply(gmr_model *m, const gmr_retime_apply_input *in) {
   }
   if (in->qpos_out == in->qpos) { set_err(m, "qpos_out must not be qpos: an output row reads other rows"); return GMR_EINVAL; }
   return retime_apply_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ retiming to torque limits (retime_torque_kernel.hip.h)
+// The launches of gmr_motion_retime_plan_torque and nothing else: the torque need kernel in the place of the velocity one, the
+// ticks and scan kernels of the velocity plan as they are, and with align_end the alignment kernel, one wavefront per clip.
+static int retime_torque_run(gmr_model *m, const gmr_retime_torque_input &in, int nq, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::RetimeTorqueArgs t{};
+  t.tau = in.tau; t.tau_static = in.tau_static; t.seq_offsets = in.seq_offsets; t.torque_limit = in.torque_limit;
+  t.need_floor = in.need_floor; t.need = in.need; t.static_over = in.static_over;
+  t.limit_scale = in.limit_scale; t.n_frames = in.n_frames; t.n_seq = in.n_seq; t.nh = nq - 7;
+  gmr::RetimePlanArgs a{};  // (qpos, vmax and fps are the velocity need kernel's alone)
+  a.seq_offsets = in.seq_offsets; a.need = in.need; a.ticks = in.ticks; a.cum = in.cum;
+  a.out_len = in.out_len; a.clip_stats = in.clip_stats; a.need_max = in.need_max;
+  a.max_stretch = in.max_stretch; a.n_frames = in.n_frames; a.n_seq = in.n_seq; a.nq = nq; a.window = in.window;
+  if (in.n_frames > 0) {  // (without frames every clip is empty: only the per-clip results are written)
+    const unsigned ty = retime_clip_waves(in.n_frames, in.n_seq);
+    hipLaunchKernelGGL(gmr::motion_retime_torque_need_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, t);
+    hipLaunchKernelGGL(gmr::motion_retime_ticks_kernel, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), 0, st, a);
+  }
+  hipLaunchKernelGGL(gmr::motion_retime_scan_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, a);
+  if (in.align_end && in.n_frames > 0) {
+    gmr::RetimeAlignArgs g{};
+    g.seq_offsets = in.seq_offsets; g.ticks = in.ticks; g.cum = in.cum; g.out_len = in.out_len; g.clip_stats = in.clip_stats;
+    g.n_frames = in.n_frames; g.n_seq = in.n_seq;
+    hipLaunchKernelGGL(gmr::motion_retime_align_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, g);
+  }
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_retime_plan_torque(gmr_model *m, const gmr_retime_torque_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (in->window < 0 || in->window > gmr::kRetimeMaxWindow) { set_err(m, "window must be 0 .. %d", gmr::kRetimeMaxWindow); return GMR_EINVAL; }
+  if (!(in->max_stretch >= 1.0) || !(in->max_stretch <= 64.0)) { set_err(m, "max_stretch must be 1 .. 64"); return GMR_EINVAL; }
+  if (!(in->limit_scale > 0.0) || !(in->limit_scale <= 1.0)) { set_err(m, "limit_scale must be > 0 and <= 1"); return GMR_EINVAL; }
+  if (in->align_end != 0 && in->align_end != 1) { set_err(m, "align_end must be 0 or 1"); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "retiming needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int nq = m->fk.ndof + 7;
+  if (nq > gmr::kRetimeMaxNq) { set_err(m, "a row of %d columns does not fit one wavefront", nq); return GMR_EUNSUPPORTED; }
+  if (in->n_seq == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (!in->seq_offsets || !in->out_len || !in->clip_stats || !in->need_max) { set_err(m, "null argument"); return GMR_EINVAL; }
+  if (in->n_frames > 0 && (!in->need || !in->ticks || !in->cum || (nq > 7 && (!in->tau || !in->tau_static || !in->torque_limit)))) {
+    set_err(m, "null argument"); return GMR_EINVAL;
+  }
+  return retime_torque_run(m, *in, nq, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ clip report (report_kernel.hip.h)

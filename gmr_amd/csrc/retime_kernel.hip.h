@@ -26,6 +26,8 @@
 //                             one after the other.  Then lane = column: the rows go in batches of kRetimeApplyBatch, the row's
 //                             interval, u and quaternion come from its lane through v_readlane, both source rows are loaded
 //                             coalesced (the second is the next row's first: it comes out of the cache) and the row is stored.
+// motion_retime_apply_cubic_kernel, at the end of this file, is the apply with interp = 1: the same structure over a four-row stencil.
+// The two kernels that gmr_motion_retime_plan_torque puts around the ticks and scan kernels are in retime_torque_kernel.hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -303,6 +305,122 @@ __global__ void __launch_bounds__(kFkWave) motion_retime_apply_kernel(RetimeAppl
             if (quat) y = lane == 3 ? qw : lane == 4 ? qx : lane == 5 ? qy : qz;
           } else if (quat) {
             y = v0[b];  // u == 0, or the same quaternion in both rows: a copy
+          }
+          if (live) w[(i0 + b) * nq] = y;
+        }
+      }
+    }
+  }
+}
+
+// The sample point of output row k of a clip of T rows: the interval i and u of the contract, by the linear kernel's search (the
+// last i in [0, min(k, T - 2)] with cum[i] <= tau; every index is inside the clip whatever cum holds).  `top` bounds the search's
+// steps for the whole wavefront.  This is a second copy of the search written out inside motion_retime_apply_kernel, which keeps its
+// own so that its code object stays what it was: the two must stay in step.
+__device__ __forceinline__ void retime_sample_point(const int64_t *cum, const int64_t *ticks, int64_t T, int64_t total, int64_t k,
+                                                    int64_t top, int64_t &i, double &u, bool &end) {
+  const int64_t tau = k * kRetimeQ;
+  end = tau >= total || T < 2;
+  i = T - 1;
+  u = 0.0;
+  const int steps = top < 1 ? 0 : 64 - __builtin_clzll((unsigned long long)top);  // >= log2(top + 1)
+  int64_t lo = 0, hi = k < T - 2 ? k : T - 2;
+  for (int it = 0; it < steps; ++it) {
+    if (!end && lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (cum[mid] <= tau) lo = mid; else hi = mid - 1;
+    }
+  }
+  if (!end) {
+    i = lo;
+    u = (double)(tau - cum[i]) / (double)ticks[i];
+  }
+}
+
+// y of the contract's cubic for one column: Catmull-Rom tangents from the four rows, Horner in u
+__device__ __forceinline__ double retime_cubic(double p0, double p1, double p2, double p3, double u) {
+#pragma clang fp contract(off)
+  const double m1 = 0.5 * (p2 - p0), m2 = 0.5 * (p3 - p1), c = p2 - p1;
+  return p1 + u * (m1 + u * (((3.0 * c - 2.0 * m1) - m2) + u * ((m1 + m2) - 2.0 * c)));
+}
+
+// motion_retime_apply_cubic_kernel  interp = 1 of gmr_motion_retime_apply: the linear kernel's structure with a four-row stencil.
+//                             First lane = output row: the search, src_time and -- where u != 0 -- the row's root quaternion: the
+//                             three neighbours flipped onto row i's hemisphere, the missing neighbour of an end interval reflected,
+//                             the cubic per component, one norm.  Then lane = column: batches of kRetimeApplyBatch rows, four
+//                             coalesced source rows each (three of them are the neighbouring output rows': they come out of the
+//                             cache), and the row is stored.  A row with u == 0 or past the warp's end reads row i alone.
+__global__ void __launch_bounds__(kFkWave) motion_retime_apply_cubic_kernel(RetimeApplyArgs A) {
+#pragma clang fp contract(off)  // the contract's arithmetic exactly
+  constexpr int B = kRetimeApplyBatch;
+  const int lane = threadIdx.x, nq = A.nq;
+  const int s = blockIdx.x;
+  if (s >= A.n_seq) return;
+  int64_t T, M;
+  const int64_t o = retime_clip(A.seq_offsets, s, A.n_frames, T), oo = retime_clip(A.out_offsets, s, A.n_out_frames, M);
+  if (T == 0 || (int64_t)blockIdx.y * kRetimeTile >= M) return;  // (a clip without frames writes nothing)
+  const bool live = lane < nq, quat = lane >= 3 && lane < 7;
+  const int c = live ? lane : nq - 1;
+  const int64_t *cum = A.cum + o, *ticks = A.ticks + o;
+  const int64_t total = cum[T - 1];
+  const double *x = A.qpos + o * nq + c;
+  double *w = A.out + oo * nq + c;
+  for (int64_t t0 = (int64_t)blockIdx.y * kRetimeTile; t0 < M; t0 += (int64_t)gridDim.y * kRetimeTile) {
+    const int64_t t1 = t0 + kRetimeTile < M ? t0 + kRetimeTile : M;
+    // lane = output row (the lanes past the tile's end repeat its last row and store nothing)
+    const int64_t k = t0 + lane < t1 ? t0 + lane : t1 - 1;
+    int64_t i;
+    double u;
+    bool end;
+    retime_sample_point(cum, ticks, T, total, k, T - 2 < t1 - 1 ? T - 2 : t1 - 1, i, u, end);
+    if (t0 + lane < t1) A.src_time[oo + t0 + lane] = (double)i + u;
+    const bool turn = !end && u != 0.0;  // (then i <= T - 2)
+    double qr[4] = {0.0, 0.0, 0.0, 0.0};
+    if (turn) {
+      const double *r1 = A.qpos + (o + i) * nq + 3;
+      const double *r0 = i > 0 ? r1 - nq : r1, *r2 = r1 + nq, *r3 = i + 2 < T ? r2 + nq : r2;
+      double q0[4], q1[4], q2[4], q3[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { q0[j] = r0[j]; q1[j] = r1[j]; q2[j] = r2[j]; q3[j] = r3[j]; }
+      const bool f0 = ((q0[0] * q1[0] + q0[1] * q1[1]) + q0[2] * q1[2]) + q0[3] * q1[3] < 0.0;
+      const bool f2 = ((q2[0] * q1[0] + q2[1] * q1[1]) + q2[2] * q1[2]) + q2[3] * q1[3] < 0.0;
+      const bool f3 = ((q3[0] * q1[0] + q3[1] * q1[1]) + q3[2] * q1[2]) + q3[3] * q1[3] < 0.0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const double b1 = q1[j], b2 = f2 ? -q2[j] : q2[j];
+        const double b0 = i > 0 ? (f0 ? -q0[j] : q0[j]) : b1 + (b1 - b2);
+        const double b3 = i + 2 < T ? (f3 ? -q3[j] : q3[j]) : b2 + (b2 - b1);
+        qr[j] = retime_cubic(b0, b1, b2, b3, u);
+      }
+      const double nrm = sqrt(((qr[0] * qr[0] + qr[1] * qr[1]) + qr[2] * qr[2]) + qr[3] * qr[3]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) qr[j] = qr[j] / nrm;
+    }
+    // lane = column
+    for (int64_t i0 = t0; i0 < t1; i0 += B) {
+      double v0[B], v1[B], v2[B], v3[B];
+#pragma unroll
+      for (int b = 0; b < B; ++b) {  // (rows past the tile's end repeat its last row and are not stored)
+        const int r = (int)((i0 + b < t1 ? i0 + b : t1 - 1) - t0);
+        const int64_t ir = retime_lane64(i, r);
+        const bool tr = __builtin_amdgcn_readlane((int)turn, r) != 0;  // (wave-uniform)
+        v1[b] = x[ir * nq];
+        v0[b] = x[(tr && ir > 0 ? ir - 1 : ir) * nq];
+        v2[b] = x[(tr ? ir + 1 : ir) * nq];
+        v3[b] = x[(tr ? (ir + 2 < T ? ir + 2 : ir + 1) : ir) * nq];
+      }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        if (i0 + b < t1) {  // (wave-uniform)
+          const int r = (int)(i0 + b - t0);
+          double y = v1[b];  // u == 0, or past the warp's end: a copy
+          if (__builtin_amdgcn_readlane((int)turn, r)) {  // (wave-uniform)
+            const int64_t ir = retime_lane64(i, r);
+            const double p0 = ir > 0 ? v0[b] : v1[b] + (v1[b] - v2[b]);
+            const double p3 = ir + 2 < T ? v3[b] : v2[b] + (v2[b] - v1[b]);
+            y = retime_cubic(p0, v1[b], v2[b], p3, rdlane(u, r));
+            const double qw = rdlane(qr[0], r), qx = rdlane(qr[1], r), qy = rdlane(qr[2], r), qz = rdlane(qr[3], r);
+            if (quat) y = lane == 3 ? qw : lane == 4 ? qx : lane == 5 ? qy : qz;
           }
           if (live) w[(i0 + b) * nq] = y;
         }

@@ -84,7 +84,7 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
                    track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
                    contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False, dynamics: bool = False,
-                   collision=None, mirror=False, retime=None):
+                   collision=None, mirror=False, retime=None, retime_torque=None):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -104,7 +104,10 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     With ``retime`` (``True``, one rate in rad/s, or ``{joint: rad/s}``: ``retime_to_limits``' ``velocity_limits``, ``True`` standing for
     ``None``) the (smoothed) qpos is retimed to those limits before anything but the clip report is made from it: the motions, the
     dynamics and self-collision reports, the mirror images and the tracks are those of the retimed clips, which are longer where a
-    hinge was too fast; the clip report stays that of the solved clips (a retimed frame has no human targets to be compared with)."""
+    hinge was too fast; the clip report stays that of the solved clips (a retimed frame has no human targets to be compared with).
+    With ``retime_torque`` (``True``, or ``retime_to_torque_limits``' ``limit_scale``) the (smoothed, velocity-retimed) qpos is then
+    retimed to the robot's torque limits, in the same place.  Torques are second differences of qpos and those of unfiltered IK
+    output are noise (``dynamics_from_qpos``): give ``lowpass_hz`` with it."""
     mirror_kw = dict(mirror) if isinstance(mirror, dict) else {}
     if mirror and mirror_kw.get("plan") is None:
         gmr.symmetry_plan()  # (SymmetryError here, before any solve)
@@ -129,6 +132,9 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
         rep = gmr.clip_report(qpos, tpos, tquat, body_names, seq_offsets, human_heights=human_heights, iters=iters)
     if retime is not None and retime is not False:
         qpos, seq_offsets, _ = retime_to_limits(gmr, qpos, seq_offsets, fps, None if retime is True else retime)
+    if retime_torque is not None and retime_torque is not False:
+        scale = {} if retime_torque is True else {"limit_scale": float(retime_torque)}
+        qpos, seq_offsets, _ = retime_to_torque_limits(gmr, qpos, seq_offsets, fps, **scale)
     q_all, offs_all, fps_all = augment_mirror(gmr, qpos, seq_offsets, fps, **mirror_kw) if mirror else (qpos, seq_offsets, fps)
     res = (motions_from_qpos(gmr, q_all, offs_all, fps_all, height_adjust=height_adjust, root_origin_offset=root_origin_offset),)
     if rep is not None:
@@ -629,7 +635,7 @@ def retime_vmax(robot, velocity_limits=None, retargeter_limits=None) -> np.ndarr
 
 
 def retime_to_limits(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, velocity_limits=None,
-                     window: int = RETIME_WINDOW, max_stretch: float = RETIME_MAX_STRETCH):
+                     window: int = RETIME_WINDOW, max_stretch: float = RETIME_MAX_STRETCH, interp: str = "linear"):
     """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at ``fps``: one rate or one per clip) played slower exactly where a
     hinge turns faster than its velocity limit, on the GPU (``Engine.motion_retime_plan`` / ``motion_retime_apply``; the definition
     is the contract above ``gmr_retime_plan_input`` in include/gmr_amd.h): a monotone time warp and a resampling at the clip's own
@@ -637,7 +643,8 @@ def retime_to_limits(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offs
     ``velocity_limits``: see ``retime_vmax`` (``None``: ``gmr.velocity_limits``, else ``DEFAULT_VELOCITY_LIMIT`` on every limited
     hinge).  ``window``: the intervals on either side over which a stretch is widened and averaged; ``max_stretch``: the largest
     local slow-down, beyond which an interval is counted as capped and still exceeds its limit (``RETIME_WINDOW`` and
-    ``RETIME_MAX_STRETCH`` are conventions, not measured on a robot).
+    ``RETIME_MAX_STRETCH`` are conventions, not measured on a robot).  ``interp``: ``Engine.motion_retime_apply``'s -- ``"cubic"`` gives
+    a C1 path that may overshoot a joint range and, by a little, the limit the plan was made for.
     Returns ``(qpos_out, seq_offsets_out, info)``: ordinary qpos and offsets at the same ``fps`` for ``lock_feet``,
     ``tracking_from_qpos``, ``dynamics_report``, ``MotionLibrary`` and ``compose_clips``; ``info`` holds per clip ``stretch`` (output
     over input duration; 1 for a clip of fewer than two frames), ``stretched_intervals``, ``capped_intervals``,
@@ -687,9 +694,9 @@ def retime_to_limits(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offs
     for sel, plan, q, o in parts:
         oo = np.concatenate([[0], np.cumsum(out_len[sel])]).astype(np.int64)
         if len(parts) == 1:
-            eng.motion_retime_apply(q, o, plan, oo, out={"qpos": qpos_out, "src_time": src_time})
+            eng.motion_retime_apply(q, o, plan, oo, out={"qpos": qpos_out, "src_time": src_time}, interp=interp)
         else:
-            part, st, _ = eng.motion_retime_apply(q, o, plan, oo)
+            part, st, _ = eng.motion_retime_apply(q, o, plan, oo, interp=interp)
             rows = torch.from_numpy(np.concatenate([np.arange(offs_out[s], offs_out[s + 1]) for s in sel])).to(qpos.device)
             qpos_out.index_copy_(0, rows, part)
             src_time.index_copy_(0, rows, st)
@@ -698,6 +705,115 @@ def retime_to_limits(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offs
     info = {"stretch": stretch, "stretched_intervals": stats[:, 0], "capped_intervals": stats[:, 1], "nonfinite_intervals": stats[:, 2],
             "need_max": need_max, "need": need, "src_time": src_time}
     return qpos_out, offs_out, info
+
+
+# ------------------------------------------------------------------ retiming to torque limits
+# Conventions from CPU runs on synthetic G1 trajectories, not measured on a robot: planning against 0.95 of the limit
+# leaves room for the term of a changing stretch that the plan does not model, twelve intervals on either side keep that term small,
+# and four passes were one or two more than those runs needed.
+RETIME_TORQUE_SCALE = 0.95
+RETIME_TORQUE_WINDOW = 12
+RETIME_TORQUE_PASSES = 4
+
+
+def _compose_src_time(prev: torch.Tensor, prev_offs: np.ndarray, st: torch.Tensor, out_len: np.ndarray) -> torch.Tensor:
+    """The source time of the rows of a pass: ``prev`` (the source time of the pass's input rows, clips at ``prev_offs``) read at the
+    pass's own ``st`` (in frames of its input clip), piecewise linearly.  Plumbing: torch indexing."""
+    dev = st.device
+    lens = torch.from_numpy(np.diff(prev_offs)).to(dev)
+    reps = torch.from_numpy(np.ascontiguousarray(out_len)).to(dev)
+    base = torch.repeat_interleave(torch.from_numpy(np.ascontiguousarray(prev_offs[:-1])).to(dev), reps)
+    last = torch.repeat_interleave(lens, reps) - 1
+    i = torch.minimum(st.floor().to(torch.int64), last)
+    u = st - i.to(st.dtype)
+    a, b = prev[base + i], prev[base + torch.minimum(i + 1, last)]
+    return torch.where(u == 0.0, a, a + u * (b - a))
+
+
+def retime_to_torque_limits(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], fps, table=None,
+                            limit_scale: float = RETIME_TORQUE_SCALE, velocity_limits=False, window: int = RETIME_TORQUE_WINDOW,
+                            max_stretch: float = RETIME_MAX_STRETCH, passes: int = RETIME_TORQUE_PASSES, interp: str = "cubic"):
+    """qpos ``[N, nq]`` float64 on the GPU (concatenated clips at the one rate ``fps``) played slower exactly where a hinge needs more
+    torque than its actuator has, on the GPU (the definition is the contract above ``gmr_retime_torque_input`` in
+    include/gmr_amd.h).  Played slower by ``s``, a hinge's torque is ``g + (tau - g) / s^2``, ``g`` the gravity torque of the pose,
+    so per pass ``Engine.motion_dynamics`` runs twice on the current clips -- once differenced, once with zero ``qvel`` / ``qacc`` --
+    then ``Engine.motion_retime_plan_torque`` (against ``limit_scale`` of ``table``'s torque limits; ``None``: the robot's MJCF
+    file's), the one read-back of the pass (``out_len`` and ``clip_stats`` together) and ``Engine.motion_retime_apply`` with
+    ``interp``.  A slower clip has other torques where the stretch changes along it, which the plan does not model: the passes meet
+    that by iteration.  The loop stops when no interval of any clip has need > 1, or after ``passes``; a clip with nothing to
+    stretch gets 1024 ticks per interval, so the later passes copy it bit for bit.  ``velocity_limits``: ``False``: torques alone;
+    ``True``: ``retime_vmax``'s default table, else its ``velocity_limits`` -- each pass then also runs ``Engine.motion_retime_plan``,
+    whose ``need`` becomes the floor of the torque plan, so that one warp meets both limits.
+    Torques are made from second differences of qpos: those of unfiltered IK output are dominated by the frame-to-frame jitter of
+    the solve (``dynamics_from_qpos``), and a warp planned from noise is noise.  Smooth first (``smooth_qpos``).
+    ``limit_scale``, ``window`` and ``passes`` default to ``RETIME_TORQUE_SCALE`` (0.95), ``RETIME_TORQUE_WINDOW`` (12) and
+    ``RETIME_TORQUE_PASSES`` (4): conventions from CPU runs on synthetic trajectories, not measured on a robot.
+    Returns ``(qpos_out, seq_offsets_out, info)``: ordinary qpos and offsets at the same ``fps``.  ``info`` holds per clip (host
+    arrays ``[S]``) ``passes`` (the passes that stretched the clip), ``tau_ratio_before`` and ``tau_ratio_after`` (the largest
+    ``tau_ratio_max`` of the dynamics statistics over the hinges, against the unscaled limits), ``converged`` (``tau_ratio_after <=
+    1``), ``static_over_frames`` (source frames in which gravity alone puts a hinge at or over the scaled limit: no retiming
+    mends those) and ``stretch``; per pass and clip (``[P, S]``) ``stretched_intervals``, ``capped_intervals`` and
+    ``nonfinite_intervals``; and per output row ``src_time`` (device ``[M]``): the source time in frames of its clip, composed over
+    the passes."""
+    if gmr.model.planar_base:
+        raise NotImplementedError("retiming assumes a free-joint root; a planar-base robot is not supported")
+    eng = gmr._engine
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    S, N = offs.size - 1, int(qpos.shape[0])
+    if offs.ndim != 1 or S < 0 or offs[0] != 0 or offs[-1] != N or np.any(np.diff(offs) < 0):
+        raise ValueError("seq_offsets must span [0, N] and not go back")
+    f = np.asarray(fps.detach().cpu().numpy() if isinstance(fps, torch.Tensor) else fps, dtype=np.float64)
+    if f.ndim != 0 and np.unique(f).size > 1:
+        raise ValueError("retiming to torque limits takes one rate per call: the inverse dynamics does")
+    rate = float(f) if f.ndim == 0 else (float(f.flat[0]) if f.size else 30.0)
+    if int(passes) < 1:
+        raise ValueError("passes must be at least 1")
+    dev = qpos.device
+    limit = eng.inertial_device(table)["torque_limit"]
+    vdev = None
+    if velocity_limits is not False:
+        vmax = retime_vmax(gmr.model, None if velocity_limits is True else velocity_limits, getattr(gmr, "velocity_limits", None))
+        vdev = torch.from_numpy(vmax).to(dev)
+    lens0 = np.diff(offs)
+    q, o = qpos, offs
+    src = torch.cat([torch.arange(int(n), dtype=torch.float64, device=dev) for n in lens0]) if N else torch.zeros(0, dtype=torch.float64, device=dev)
+    ratios, per_pass, static_frames = [], [], None
+    used = np.zeros(S, dtype=np.int64)
+    for p in range(int(passes) + 1):
+        n = int(q.shape[0])
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)   # noqa: E731  (the outputs the loop needs, no others)
+        dyn = eng.motion_dynamics(q, o, rate, table=table, out={"tau": z(n, eng.nq - 7), "root_wrench": z(n, 6), "tau_ratio_max": z(S, eng.nq - 7)})
+        ratios.append(dyn["tau_ratio_max"].max(dim=1).values if eng.nq > 7 else torch.zeros(S, dtype=torch.float64, device=dev))
+        if p == int(passes):
+            break
+        zero = z(n, eng.nq - 1)
+        rest = eng.motion_dynamics(q, o, rate, qvel=zero, qacc=zero, table=table, out={"tau": z(n, eng.nq - 7)})
+        floor = eng.motion_retime_plan(q, o, rate, vdev, window, max_stretch)["need"] if vdev is not None else None
+        plan = eng.motion_retime_plan_torque(dyn["tau"], rest["tau"], o, limit, limit_scale, window, max_stretch, floor, True)
+        if static_frames is None:
+            cs = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum((plan["static_over"] > 0).to(torch.int64), 0)])
+            od = plan.seq_offsets
+            static_frames = cs[od[1:]] - cs[od[:-1]]
+        back = torch.cat([plan["out_len"][:, None], plan["clip_stats"]], dim=1).cpu().numpy()   # the pass's one read-back
+        out_len, stats = back[:, 0], back[:, 1:]
+        per_pass.append(stats[:, :3].copy())
+        if not stats[:, 0].any():
+            break
+        used += stats[:, 0] > 0
+        oo = np.concatenate([[0], np.cumsum(out_len)]).astype(np.int64)
+        q_new, st, _ = eng.motion_retime_apply(q, o, plan, oo, interp=interp)
+        src = _compose_src_time(src, o, st, out_len)
+        q, o = q_new, oo
+    before, after = ratios[0].cpu().numpy(), ratios[-1].cpu().numpy()
+    pp = np.stack(per_pass) if per_pass else np.zeros((0, S, 3), dtype=np.int64)
+    lens = np.diff(o)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        stretch = np.where(lens0 > 1, (lens - 1) / np.maximum(lens0 - 1, 1), 1.0)
+    info = {"passes": used, "tau_ratio_before": before, "tau_ratio_after": after, "converged": after <= 1.0,
+            "static_over_frames": static_frames.cpu().numpy() if static_frames is not None else np.zeros(S, dtype=np.int64),
+            "stretch": stretch, "stretched_intervals": pp[:, :, 0], "capped_intervals": pp[:, :, 1], "nonfinite_intervals": pp[:, :, 2],
+            "src_time": src}
+    return q, o, info
 
 
 # ------------------------------------------------------------------ transitions between clips

@@ -1508,9 +1508,77 @@ class Engine:
         plan.seq_offsets, plan.fps, plan.window, plan.max_stretch = offs, fps, window, max_stretch
         return plan
 
-    def motion_retime_apply(self, qpos: torch.Tensor, seq_offsets, plan, out_offsets=None, out=None):
+    def motion_retime_plan_torque(self, tau: torch.Tensor, tau_static: torch.Tensor, seq_offsets, torque_limit, limit_scale: float,
+                                  window: int, max_stretch: float, need_floor=None, align_end: bool = True, out=None) -> MotionRetimePlan:
+        """The time warp that plays clips slower exactly where a hinge needs more torque than ``limit_scale * torque_limit``
+        (``gmr_motion_retime_plan_torque``; the definition is the contract above ``gmr_retime_torque_input`` in include/gmr_amd.h).
+        ``tau`` and ``tau_static`` ``[N, nq - 7]`` float64: ``motion_dynamics``' ``tau`` of the clips, differenced and with zero
+        ``qvel`` / ``qacc``.  ``seq_offsets`` ``[S + 1]``: a host sequence (uploaded once) or a device int64 tensor.  ``torque_limit``
+        ``[nq - 7]`` N m (every entry > 0, ``inf``: no limit): a host sequence (checked, uploaded) or a device float64 tensor
+        (trusted).  ``limit_scale`` in (0, 1]; ``window`` 0 .. 32; ``max_stretch`` 1 .. 64.  ``need_floor`` ``[N]`` float64 on the
+        device or ``None``: the ``need`` of a ``motion_retime_plan`` of the same clips, so that one warp meets both limits.
+        ``align_end``: pad every clip's total to whole frames over its last intervals, so that the last output row is the final pose
+        at its planned time.  Returns a :class:`MotionRetimePlan` for ``motion_retime_apply`` (``fps`` is ``None``) that also holds
+        ``static_over`` ``[N]`` int32: per row the hinges whose gravity torque alone is at or over the scaled limit.  ``out``:
+        caller-owned tensors by all its names.  Asynchronous on the current stream; with ``out`` and device arrays no allocation,
+        no copy, no synchronisation."""
+        dev = self.device
+        if self.cm.robot.planar_base:
+            raise NotImplementedError("retiming assumes a free-joint root; a planar-base robot is not supported")
+        nh = self.nq - 7
+        for name, t in (("tau", tau), ("tau_static", tau_static)):
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != nh \
+                    or t.shape[0] != tau.shape[0] or not t.is_contiguous():
+                raise EngineError(f"{name} must be a contiguous float64 [N, {nh}] tensor on the engine's device")
+        N = int(tau.shape[0])
+        offs = _clip_offsets(seq_offsets, dev)
+        S = int(offs.shape[0]) - 1
+        limit_scale, window, max_stretch = float(limit_scale), int(window), float(max_stretch)
+        if not 0.0 < limit_scale <= 1.0:
+            raise ValueError("limit_scale must lie in (0, 1]")
+        if not 0 <= window <= _native.RETIME_MAX_WINDOW:
+            raise ValueError(f"window must lie in [0, {_native.RETIME_MAX_WINDOW}]")
+        if not 1.0 <= max_stretch <= _native.RETIME_MAX_STRETCH:
+            raise ValueError(f"max_stretch must lie in [1, {_native.RETIME_MAX_STRETCH:g}]")
+        if isinstance(torque_limit, torch.Tensor):
+            if torque_limit.device != dev or torque_limit.dtype != torch.float64 or tuple(torque_limit.shape) != (nh,) or not torque_limit.is_contiguous():
+                raise EngineError(f"torque_limit must be a contiguous float64 [{nh}] tensor on the engine's device (or a host sequence)")
+        else:
+            v = np.array(torque_limit, dtype=np.float64)  # (a copy: the caller's may be read-only)
+            if v.shape != (nh,) or not np.all(v > 0.0):
+                raise ValueError(f"torque_limit must hold {nh} limits, every one > 0 (inf: no limit)")
+            torque_limit = torch.from_numpy(v).to(dev)
+        if need_floor is not None and (not isinstance(need_floor, torch.Tensor) or need_floor.device != dev or need_floor.dtype != torch.float64
+                                       or tuple(need_floor.shape) != (N,) or not need_floor.is_contiguous()):
+            raise EngineError(f"need_floor must be a contiguous float64 [{N}] tensor on the engine's device (or None)")
+        f64, i64 = torch.float64, torch.int64
+        shapes = {"need": ((N,), f64), "ticks": ((N,), i64), "cum": ((N,), i64), "out_len": ((S,), i64), "clip_stats": ((S, 4), i64),
+                  "need_max": ((S,), f64), "static_over": ((N,), torch.int32)}
+        if out is None:
+            res = {k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in shapes.items()}  # rows outside every clip are not written
+        else:
+            if set(out) != set(shapes) or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1]
+                                              or t.device != dev or not t.is_contiguous() for k, t in out.items()):
+                raise EngineError(f"out must map {sorted(shapes)} to contiguous tensors of the call's shapes on the engine's device")
+            res = {k: out[k] for k in shapes}
+        ti = _native.RetimeTorqueInput()
+        ti.tau, ti.tau_static, ti.n_frames, ti.seq_offsets, ti.n_seq, ti.window = tau.data_ptr(), tau_static.data_ptr(), N, offs.data_ptr(), S, window
+        ti.torque_limit, ti.limit_scale, ti.max_stretch = torque_limit.data_ptr(), limit_scale, max_stretch
+        ti.need_floor, ti.align_end = (need_floor.data_ptr() if need_floor is not None else None), int(bool(align_end))
+        for k, t in res.items():
+            setattr(ti, k, t.data_ptr())
+        ti.stream = torch.cuda.current_stream(dev).cuda_stream
+        self._check(self._lib.gmr_motion_retime_plan_torque(self._h, C.byref(ti)), "gmr_motion_retime_plan_torque")
+        plan = MotionRetimePlan(res)
+        plan.seq_offsets, plan.fps, plan.window, plan.max_stretch = offs, None, window, max_stretch
+        plan.limit_scale, plan.align_end = limit_scale, bool(align_end)
+        return plan
+
+    def motion_retime_apply(self, qpos: torch.Tensor, seq_offsets, plan, out_offsets=None, out=None, interp: str = "linear"):
         """qpos ``[N, nq]`` float64 resampled along ``plan`` (a :class:`MotionRetimePlan` of these clips, or a mapping with its
         ``ticks`` and ``cum``) in one kernel (``gmr_motion_retime_apply``; the definition is the contract in include/gmr_amd.h).
+        ``interp``: ``"linear"`` (the lerp and slerp between the two source rows) or ``"cubic"`` (Catmull-Rom over four rows: C1,
+        what a plan from torques needs; it may overshoot a joint range and, by a little, a velocity limit).
         ``out_offsets`` ``[S + 1]``: the output clips' rows, a host sequence or a device int64 tensor; ``None``: the prefix sum of
         ``plan["out_len"]``, which is READ BACK from the device -- a host synchronisation.  Returns ``(qpos_out [M, nq], src_time [M],
         out_offsets)``: the retimed clips, per output row the source time in frames of its clip, and the offsets (a host int64 array,
@@ -1521,6 +1589,8 @@ class Engine:
         dev = self.device
         if self.cm.robot.planar_base:
             raise NotImplementedError("retiming assumes a free-joint root; a planar-base robot is not supported")
+        if interp not in _native.RETIME_INTERP:
+            raise ValueError(f"interp must be one of {sorted(_native.RETIME_INTERP)}")
         N = _qpos_rows(qpos, self.nq, dev)
         offs = _clip_offsets(seq_offsets, dev)
         S = int(offs.shape[0]) - 1
@@ -1560,7 +1630,7 @@ class Engine:
         ai = _native.RetimeApplyInput()
         ai.qpos, ai.n_frames, ai.seq_offsets, ai.n_seq = qpos.data_ptr(), N, offs.data_ptr(), S
         ai.ticks, ai.cum, ai.out_offsets, ai.n_out_frames = plan["ticks"].data_ptr(), plan["cum"].data_ptr(), oo.data_ptr(), M
-        ai.qpos_out, ai.src_time = res["qpos"].data_ptr(), res["src_time"].data_ptr()
+        ai.qpos_out, ai.src_time, ai.interp = res["qpos"].data_ptr(), res["src_time"].data_ptr(), _native.RETIME_INTERP[interp]
         ai.stream = torch.cuda.current_stream(dev).cuda_stream
         self._check(self._lib.gmr_motion_retime_apply(self._h, C.byref(ai)), "gmr_motion_retime_apply")
         return res["qpos"], res["src_time"], ret_offs

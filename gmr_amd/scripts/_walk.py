@@ -119,6 +119,7 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--mirror_about", default="start", choices=["world", "start"], help="with --mirror: reflect in the world plane y = 0 (world), or each clip in the vertical plane through its first root position along its heading, so that the mirrored clip starts where the original does (start, the default)")
     ap.add_argument("--mirror_plan", default=None, type=str, metavar="FILE.json", help="with --mirror: the symmetry plan from this file (gmr_amd.symmetry.save_plan writes one) instead of the robot's own; with --robots: robot:file;robot2:file2")
     ap.add_argument("--retime_to_limits", nargs="?", const=True, default=None, type=float, metavar="RAD_PER_S", help="play every solved clip slower exactly where a hinge turns faster than its velocity limit (dataset.retime_to_limits, on the GPU: a monotone time warp, resampled at the clip's rate) before the pickles, the dynamics and collision reports and the tracking exports are made; the clip report stays that of the solved clips; with a number: that limit on every hinge; without: the retargeter's limits (--use_velocity_limit / --velocity_limit), else 3 pi rad/s on every limited hinge; not with --robots; default: off")
+    ap.add_argument("--retime_to_torque", nargs="?", const=True, default=None, type=float, metavar="SCALE", help="play every solved clip slower exactly where a hinge needs more torque than its actuator has (dataset.retime_to_torque_limits, on the GPU: inverse dynamics, a time warp and a cubic resampling, up to four passes), after --lowpass_hz and --retime_to_limits and before the pickles, the dynamics and collision reports and the tracking exports are made; with a number: the share of the MJCF torque limits the warp is planned against (default 0.95, a convention, not measured on a robot); torques of unfiltered qpos are noise: give --lowpass_hz; not with --robots; default: off")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -135,6 +136,11 @@ def resolve_track(ap, args) -> None:
         ap.error("--retime_to_limits must be positive")
     if retime is not None and getattr(args, "robots", None):
         ap.error("--retime_to_limits is not available with --robots")
+    torque = getattr(args, "retime_to_torque", None)
+    if torque is not None and torque is not True and not 0.0 < torque <= 1.0:
+        ap.error("--retime_to_torque must lie in (0, 1]")
+    if torque is not None and getattr(args, "robots", None):
+        ap.error("--retime_to_torque is not available with --robots")
     resolve_contact(ap, args)
     resolve_mirror(ap, args)
 
@@ -354,6 +360,8 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         col_kw = collision_kw(args, model=g.model) if wants_collision(args) else {}  # (ditto)
         mir_kw = getattr(args, "mirror_kw", {})  # (ditto)
         ret_kw = {} if getattr(args, "retime_to_limits", None) is None else {"retime": args.retime_to_limits}  # (ditto)
+        if getattr(args, "retime_to_torque", None) is not None:
+            ret_kw["retime_torque"] = args.retime_to_torque
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:

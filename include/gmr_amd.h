@@ -80,6 +80,8 @@
  *   gmr_motion_retime_plan, gmr_motion_retime_apply  (no counterpart in the reference) clips played slower exactly where a hinge
  *                      turns faster than its actuator can: a monotone time warp from per-joint velocity limits, and the clips
  *                      resampled along it at their own rate
+ *   gmr_motion_retime_plan_torque  (no counterpart in the reference) the same warp from joint torques: a clip played slower
+ *                      exactly where a hinge needs more torque than its actuator has
  *   gmr_dof_to_rot    KinematicsModel.dof_to_rot (kinematics_model.py:172-182; Joint.dof_to_rot :21-36)
  *   gmr_rot_to_dof     KinematicsModel.rot_to_dof (kinematics_model.py:184-197; Joint.rot_to_dof :38-53), clamped to the joint limits
  *   gmr_local_rot_to_global  KinematicsModel.convert_local_rot_to_global (kinematics_model.py:199-211)
@@ -1045,6 +1047,19 @@ int gmr_motion_transitions(gmr_model *m, const gmr_transitions_input *in);
  *   lets a caller warp per-frame labels such as contacts alongside the qpos).  Root position and hinges: x0 if u == 0, else
  *   x0 + u (x1 - x0) (the tracking export's lerp).  Root quaternion: a copy of row i's if u == 0 or if the two rows' quaternions
  *   are bytewise equal, otherwise the tracking export's shortest-arc slerp of the two at u, normalised, w x y z as stored
+ * interp = GMR_RETIME_INTERP_CUBIC (1; 0 is the linear resampling above, any other value GMR_EINVAL) changes what a row with u != 0
+ * holds and nothing else -- the search, src_time, the bitwise copy of row i at u == 0 and of the last row at tau >= total,
+ * truncation and clamping are the same.  A linearly resampled path has all its acceleration at the source rows; the cubic is C1,
+ * which is what retiming to TORQUE limits needs (below).  Per column, in float64 without contraction, in the order written:
+ *   p1 = row i, p2 = row i+1;  p0 = row i-1, or p1 + (p1 - p2) when i = 0;  p3 = row i+2, or p2 + (p2 - p1) when i+2 is past the clip
+ *   m1 = 0.5 (p2 - p0),  m2 = 0.5 (p3 - p1),  c = p2 - p1                     (Catmull-Rom tangents)
+ *   y  = p1 + u (m1 + u (((3 c - 2 m1) - m2) + u ((m1 + m2) - 2 c)))
+ *   Root quaternion: the stored rows p0, p2 and p3 are negated where their dot product with p1 (((w w' + x x') + y y') + z z') is
+ *   negative -- before any reflection -- the same cubic runs per component, and the result is divided by its norm (the square root
+ *   of ((w w + x x) + y y) + z z, four quotients).
+ *   A clip of two rows gives the lerp to rounding.  A cubic may overshoot a joint range and, by a little, the velocity limit the plan
+ *   was made for; the clip report (gmr_clip_report) of the result shows it.  A non-finite qpos entry reaches the output rows whose
+ *   four-row stencil reads it, in its column -- in the quaternion all four components -- and nothing else.
  * A clip given fewer output rows than out_len is truncated; one given more repeats its last row; a clip without rows writes
  * nothing.  Row and interval indices are clamped into the clip (the search looks only at intervals 0 .. min(k, n-2)), so a wrong
  * out_offsets, ticks or cum cannot leave the arrays.
@@ -1054,7 +1069,7 @@ int gmr_motion_transitions(gmr_model *m, const gmr_transitions_input *in);
  * within 2 W intervals of them, and only where that interval's clean stretch was above 1.  A non-finite root entry reaches root
  * columns of the rows that read its row and nothing else: no need, no ticks.  No other clip changes.
  * GMR_EINVAL: negative counts, NULL arrays with work to do, window outside [0, 32], max_stretch outside [1, 64] (a NaN included),
- * fps not finite or not > 0, qpos_out == qpos.  GMR_EUNSUPPORTED: nq > 64 (a row does not fit one wavefront), a planar-base
+ * fps not finite or not > 0, qpos_out == qpos, interp not 0 or 1.  GMR_EUNSUPPORTED: nq > 64 (a row does not fit one wavefront), a planar-base
  * model.  Zero work -- n_seq = 0; for apply also n_frames = 0 or n_out_frames = 0 -- returns GMR_OK without a launch.  With
  * n_frames = 0 and n_seq > 0 the plan still writes the clips' out_len, clip_stats and need_max (zeros).  Asynchronous on
  * in->stream; the handle's device is selected.
@@ -1079,8 +1094,10 @@ typedef struct gmr_retime_plan_input {
 } gmr_retime_plan_input;
 int gmr_motion_retime_plan(gmr_model *m, const gmr_retime_plan_input *in);
 
+#define GMR_RETIME_INTERP_LINEAR 0
+#define GMR_RETIME_INTERP_CUBIC 1
 /* The second entry of the pair: the contract is above gmr_retime_plan_input.
- * Layout (LP64): sizeof 88; offsets qpos 0, n_frames 8, seq_offsets 16, ticks 24, cum 32, out_offsets 40, n_seq 48, reserved 52,
+ * Layout (LP64): sizeof 88; offsets qpos 0, n_frames 8, seq_offsets 16, ticks 24, cum 32, out_offsets 40, n_seq 48, interp 52,
  * n_out_frames 56, stream 64, qpos_out 72, src_time 80.  */
 typedef struct gmr_retime_apply_input {
   const double  *qpos;            /* device [n_frames][nq] f64 */
@@ -1089,13 +1106,83 @@ typedef struct gmr_retime_apply_input {
   const int64_t *ticks;           /* device [n_frames] i64 */
   const int64_t *cum;             /* device [n_frames] i64 */
   const int64_t *out_offsets;     /* DEVICE [n_seq+1] */
-  int32_t        n_seq, reserved;
+  int32_t        n_seq, interp;   /* interp: GMR_RETIME_INTERP_LINEAR (0, the field's value when it was reserved) or _CUBIC */
   int64_t        n_out_frames;
   void          *stream;          /* the call's stream */
   double        *qpos_out;        /* device [n_out_frames][nq] f64, not qpos */
   double        *src_time;        /* device [n_out_frames] f64 */
 } gmr_retime_apply_input;
 int gmr_motion_retime_apply(gmr_model *m, const gmr_retime_apply_input *in);
+
+/* Retiming to joint TORQUE limits: the plan of gmr_motion_retime_plan with the need taken from joint torques, for a clip that asks a
+ * hinge for more torque than its actuator has.  Played slower by a locally constant factor s, a clip's velocities scale by 1/s and
+ * its accelerations by 1/s^2, so a hinge's torque is tau(s) = g + (tau - g) / s^2, g the gravity torque of the pose: what
+ * gmr_motion_dynamics returns when it is given qvel = qacc = 0.  Two calls of gmr_motion_dynamics on the same clips -- one
+ * differenced, one static -- give tau and tau_static, and from them per row and hinge the exact smallest s that brings the hinge
+ * under its limit.  What this leaves out is the term q' s' / s^2 of a stretch that changes along the clip: the caller meets it by
+ * iteration (plan, gmr_motion_retime_apply with interp = GMR_RETIME_INTERP_CUBIC, dynamics again), which is why this entry has a
+ * planning margin.  The plan feeds gmr_motion_retime_apply unchanged.  The call is its struct, the stream included; it enqueues
+ * three kernels on in->stream (four with align_end) and nothing else: no allocation, no copy, no synchronisation.  All arrays are
+ * device arrays.
+ *   tau, tau_static   f64 [n_frames][nh], nh = nq - 7, hinges in qpos order: the torques of the clips and of their poses at rest
+ *   seq_offsets, n_seq, n_frames, window, max_stretch    as for gmr_motion_retime_plan (the same clamping rule)
+ *   torque_limit      f64 [nh], N m per hinge, every entry > 0; +inf: no limit.  Trusted (the Python layer checks it)
+ *   limit_scale       in (0, 1]: the plan is made against limit_scale * torque_limit (the planning margin)
+ *   need_floor        f64 [n_frames] or NULL: meant to be the need of a gmr_motion_retime_plan of the same clips, so that one
+ *                     warp meets both limits
+ *   align_end         0 or 1
+ * All arithmetic is float64 without floating-point contraction, in the order written.  Per row r and hinge j:
+ *   L = limit_scale * torque_limit[j],  g = tau_static[r][j],  d = tau[r][j] - g
+ *   head = d >= 0 ? L - g : L + g                          what the limit leaves to the dynamic part, on the side it pushes to
+ *   e_rj = 0 when torque_limit[j] is +inf, otherwise head > 0 ? fabs(d) / head : 0
+ *   Gravity alone at or over the limit (head <= 0) is not something a slower clip mends: it contributes no need and is counted
+ * Row r is NON-FINITE when any entry of its tau or tau_static row is not fabs(x) < +inf.
+ *   rho_r = sqrt(max_j e_rj)                               one square root per row; 0 for a model without hinges
+ *   static_over[r] = the number of hinges with a finite limit and fabs(g) >= L; 0 in a non-finite row
+ * Interval i lies between the rows i and i + 1 of its clip and is stored at row i:
+ *   need_i = max(rho_i, rho_{i+1});  with need_floor, need_i = max(need_i, need_floor[i])
+ *   the interval is NON-FINITE when either row is, or when the floor is not < +inf: then need_i = NaN (0x7ff8000000000000), it
+ *   stretches as 1, and it is counted.  The last row of a clip gets need 0 and ticks 0.
+ * From need on -- s, d, m, ticks, cum, out_len, clip_stats and need_max -- the contract is gmr_motion_retime_plan's, word for word,
+ * and so are the kernels.
+ * align_end = 1.  out_len rounds a clip's total up, so the last output row would hold the final pose a fraction of a frame after
+ * the row before it: an abrupt stop, and torques to match.  For a clip of n >= 2 rows with total t:
+ *   r = (1024 - t % 1024) % 1024,  k = min(n - 1, 64)
+ *   interval n - 1 - k + l (l = 0 .. k-1) gains r / k + (l < r % k) ticks; cum of the last k rows, out_len (= t' / 1024 + 1) and
+ *   clip_stats[3] follow
+ * The total is then a whole number of frames and the last output row is the final pose at its planned time.  No interval gains
+ * more than 16 ticks once a clip has 65 rows; a clip of 2 rows rounds its one interval up to whole frames.  ticks may then exceed
+ * 1024 max_stretch, by at most 1023.
+ *   need, ticks, cum, out_len, clip_stats, need_max    as gmr_motion_retime_plan writes them
+ *   static_over       i32 [n_frames], or NULL;  rows outside every clip are not written
+ * GMR_EINVAL: negative counts, NULL arrays with work to do, window outside [0, 32], max_stretch outside [1, 64], limit_scale
+ * outside (0, 1] (a NaN included), align_end not 0 or 1.  GMR_EUNSUPPORTED: nq > 64, a planar-base model.  n_seq = 0 returns
+ * GMR_OK without a launch; with n_frames = 0 and n_seq > 0 the clips' out_len, clip_stats and need_max are written (zeros).
+ * Asynchronous on in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 144; offsets tau 0, tau_static 8, n_frames 16, seq_offsets 24, n_seq 32, window 36, torque_limit 40,
+ * limit_scale 48, max_stretch 56, need_floor 64, align_end 72, reserved 76, stream 80, need 88, ticks 96, cum 104, out_len 112,
+ * clip_stats 120, need_max 128, static_over 136.  */
+typedef struct gmr_retime_torque_input {
+  const double  *tau;             /* device [n_frames][nq-7] f64 */
+  const double  *tau_static;      /* device [n_frames][nq-7] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  int32_t        n_seq, window;
+  const double  *torque_limit;    /* device [nq-7] f64 */
+  double         limit_scale;
+  double         max_stretch;
+  const double  *need_floor;      /* device [n_frames] f64, or NULL */
+  int32_t        align_end, reserved;
+  void          *stream;          /* the call's stream */
+  double        *need;            /* device [n_frames] f64 */
+  int64_t       *ticks;           /* device [n_frames] i64 */
+  int64_t       *cum;             /* device [n_frames] i64 */
+  int64_t       *out_len;         /* device [n_seq] i64 */
+  int64_t       *clip_stats;      /* device [n_seq][4] i64 */
+  double        *need_max;        /* device [n_seq] f64 */
+  int32_t       *static_over;     /* device [n_frames] i32, or NULL */
+} gmr_retime_torque_input;
+int gmr_motion_retime_plan_torque(gmr_model *m, const gmr_retime_torque_input *in);
 
 /* The per-clip quality report: what the reference's users gather by hand -- error1() / error2() per frame
  * (motion_retarget.py:188-200), per-task position errors, joints at their limits (mink.check_limits), the curated hard-motion
