@@ -33,7 +33,8 @@ EXPORTS = ["gmr_abi_version", "gmr_model_create", "gmr_model_destroy", "gmr_last
            "gmr_model_set_step_cap", "gmr_model_get_step_cap", "gmr_motion_sample", "gmr_lowpass_coefficients",
            "gmr_ik_balance_plan", "gmr_ik_sliced_timeouts", "gmr_motion_contacts", "gmr_motion_footlock", "gmr_motion_dynamics",
            "gmr_motion_self_collision", "gmr_motion_mirror", "gmr_motion_compose", "gmr_motion_transitions",
-           "gmr_motion_retime_plan", "gmr_motion_retime_apply", "gmr_motion_retime_plan_torque"]
+           "gmr_motion_retime_plan", "gmr_motion_retime_apply", "gmr_motion_retime_plan_torque",
+           "gmr_motion_self_collision_repair"]
 
 
 class IKParams(C.Structure):
@@ -170,6 +171,24 @@ class SelfCollisionInput(C.Structure):
         ("n_pairs", C.c_int32), ("reserved", C.c_int32),
     ] + [(k, C.c_void_p) for k in SELF_COLLISION_TABLE] + [("margin", C.c_double), ("stream", C.c_void_p)] \
       + [(k + "_out", C.c_void_p) for k in SELF_COLLISION_OUTPUTS]
+
+
+SELF_COLLISION_REPAIR_FRAME_OUTPUTS = ("qpos", "clearance_before", "clearance_after", "move")   # gmr_self_collision_repair_input's
+SELF_COLLISION_REPAIR_STATS = ("repaired_frames", "unresolved_frames", "move_max", "clearance_min_after",
+                               "nonfinite_frames")              # output pointers, in order: per frame, then per clip
+SELF_COLLISION_REPAIR_OUTPUTS = SELF_COLLISION_REPAIR_FRAME_OUTPUTS + SELF_COLLISION_REPAIR_STATS
+SELF_COLLISION_REPAIR_MAX_ITERATIONS = 32
+
+
+class SelfCollisionRepairInput(C.Structure):
+    """``gmr_self_collision_repair_input`` (include/gmr_amd.h): the whole call of the self-collision repair, its stream included."""
+
+    _fields_ = [
+        ("qpos", C.c_void_p), ("n_frames", C.c_int64), ("seq_offsets", C.c_void_p), ("n_seq", C.c_int32), ("n_caps", C.c_int32),
+        ("n_pairs", C.c_int32), ("iterations", C.c_int32),
+    ] + [(k, C.c_void_p) for k in SELF_COLLISION_TABLE] \
+      + [("margin", C.c_double), ("damping", C.c_double), ("step_cap", C.c_double), ("resolve_tol", C.c_double),
+         ("hinge_mask", C.c_uint64), ("stream", C.c_void_p)] + [(k + "_out", C.c_void_p) for k in SELF_COLLISION_REPAIR_OUTPUTS]
 
 
 MIRROR_WORLD, MIRROR_CLIP_START = 0, 1    # GMR_MIRROR_WORLD, GMR_MIRROR_CLIP_START
@@ -371,6 +390,8 @@ def load():
     L.gmr_motion_dynamics.argtypes = [vp, C.POINTER(DynamicsInput)]
     L.gmr_motion_self_collision.restype = C.c_int
     L.gmr_motion_self_collision.argtypes = [vp, C.POINTER(SelfCollisionInput)]
+    L.gmr_motion_self_collision_repair.restype = C.c_int
+    L.gmr_motion_self_collision_repair.argtypes = [vp, C.POINTER(SelfCollisionRepairInput)]
     L.gmr_motion_mirror.restype = C.c_int
     L.gmr_motion_mirror.argtypes = [vp, C.POINTER(MirrorInput)]
     L.gmr_motion_compose.restype = C.c_int

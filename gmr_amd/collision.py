@@ -254,6 +254,34 @@ def proxies(robot, capsules: Optional[CapsuleTable] = None, pairs: Optional[Pair
     return caps, (pairs if pairs is not None else default_pairs(robot, caps)[0])
 
 
+def movable_mask(robot, freeze_joints=(), freeze_bodies=()) -> int:
+    """The ``hinge_mask`` of the self-collision repair (``Engine.motion_self_collision_repair``): bit ``i`` set means that hinge
+    ``i``, in qpos order, may move.  ``freeze_joints``: joint names whose hinges stay.  ``freeze_bodies``: body names (or indices);
+    a frozen body freezes every hinge on its path to the root, so the body stays where it is -- freezing the ankle links keeps a
+    locked foot where ``lock_feet`` put it."""
+    hb = sorted((b for b in robot.hinge_bodies()), key=lambda b: int(robot.qpos_adr[b]))
+    bit = {b: i for i, b in enumerate(hb)}
+    if len(hb) > 64:
+        raise ValueError(f"a hinge mask holds 64 hinges, the robot has {len(hb)}")
+    by_joint = {robot.jnt_names[b]: b for b in hb}
+    frozen = set()
+    for n in freeze_joints:
+        if n not in by_joint:
+            raise ValueError(f"'{n}' is not a hinge joint of {robot.name}")
+        frozen.add(by_joint[n])
+    for n in freeze_bodies:
+        if isinstance(n, str) and n not in robot.body_names:
+            raise ValueError(f"'{n}' is not a body of {robot.name}")
+        j = robot.body_names.index(n) if isinstance(n, str) else int(n)
+        if not 0 <= j < robot.nbody:
+            raise ValueError(f"body {j} is outside the robot's {robot.nbody}")
+        while j >= 0:
+            if j in bit:
+                frozen.add(j)
+            j = int(robot.parent[j])
+    return sum(1 << bit[b] for b in hb if b not in frozen)
+
+
 def check_tables(nbody: int, capsules: CapsuleTable, pairs: PairTable) -> None:
     """What the kernel trusts: bodies and pair entries in range, counts within one call's limits."""
     C, P = len(capsules), len(pairs)

@@ -36,6 +36,7 @@
 #include "dynamics_kernel.hip.h"
 #include "footlock_kernel.hip.h"
 #include "self_collision_kernel.hip.h"
+#include "self_collision_repair_kernel.hip.h"
 #include "mirror_kernel.hip.h"
 #include "compose_kernel.hip.h"
 #include "transitions_kernel.hip.h"
@@ -1821,6 +1822,73 @@ int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in) 
     set_err(m, "null argument"); return GMR_EINVAL;
   }
   return self_collision_run(m, *in, stats, static_cast<hipStream_t>(in->stream));
+}
+
+// ------------------------------------------------------------------ self-collision repair (self_collision_repair_kernel.hip.h)
+// The two launches of gmr_motion_self_collision_repair, and nothing else: no allocation, no copy, no synchronisation.  The tree's
+// parents and depths and, per body, the set of movable hinge bodies on its path from the root -- the caller's hinge mask, which is in
+// qpos order, carried over to body bits here -- travel in the kernels' argument.
+static int self_collision_repair_run(gmr_model *m, const gmr_self_collision_repair_input &in, bool stats, hipStream_t st) {
+  if (hipSetDevice(m->device) != hipSuccess) { set_err(m, "hipSetDevice failed"); return GMR_EDEVICE; }
+  gmr::SelfCollisionRepairArgs a{};
+  a.dm = m->dm_eval_dev; a.lo = m->rep_lo; a.hi = m->rep_hi;
+  a.qpos = in.qpos; a.seq_offsets = in.seq_offsets; a.n_frames = in.n_frames;
+  a.n_seq = in.n_seq; a.nbody = m->h.nbody; a.nq = m->fk.ndof + 7; a.n_caps = in.n_caps; a.n_pairs = in.n_pairs; a.iters = in.iterations;
+  a.cap_body = in.cap_body; a.cap_p0 = in.cap_p0; a.cap_p1 = in.cap_p1; a.cap_radius = in.cap_radius; a.pairs = in.pairs;
+  a.margin = in.margin; a.damping = in.damping; a.step_cap = in.step_cap; a.resolve_tol = in.resolve_tol;
+  a.qpos_out = in.qpos_out; a.before = in.clearance_before_out; a.after = in.clearance_after_out; a.move = in.move_out;
+  a.repaired = in.repaired_frames_out; a.unresolved = in.unresolved_frames_out; a.move_max = in.move_max_out;
+  a.clearance_min_after = in.clearance_min_after_out; a.nonfinite = in.nonfinite_frames_out;
+  const int32_t *parent = blob_ptr<int32_t>(m->blob, m->h.off_parent), *jtype = blob_ptr<int32_t>(m->blob, m->h.off_jnt_type);
+  const int32_t *qadr = blob_ptr<int32_t>(m->blob, m->h.off_qpos_adr);
+  gmr::tree_parent_depth(parent, a.nbody, a.parent, a.depth);
+  for (int b = 0; b < a.nbody; ++b) {   // (a parent precedes its child)
+    const int hcol = jtype[b] == GMR_JNT_HINGE ? qadr[b] - 7 : -1;
+    const uint64_t own = hcol >= 0 && hcol < 64 && ((in.hinge_mask >> hcol) & 1ull) ? 1ull << b : 0ull;
+    a.movable |= own;
+    a.anc[b] = (parent[b] >= 0 ? a.anc[parent[b]] : 0ull) | own;
+  }
+  // Wavefronts per clip by the grid rule of clip_launch.h, one frame per slot; GMR_AMD_COLLISION_REPAIR_WAVES forces a number (the
+  // results do not depend on it).  The pair indices: staged in LDS while the table is small, as in self_collision_run
+  // (GMR_AMD_COLLISION_REPAIR_PAIRS=global forces the other instance).
+  const unsigned rule = gmr::clip_waves(gmr::kScrTargetWaves, in.n_seq, gmr::mean_clip_slots(in.n_frames, 1, in.n_seq));
+  const unsigned ty = (unsigned)gmr::env_int("GMR_AMD_COLLISION_REPAIR_WAVES", 1, gmr::kGridYMax, rule);
+  const bool lds = gmr::collision_pairs_in_lds("GMR_AMD_COLLISION_REPAIR_PAIRS", in.n_pairs, gmr::kScrPairsLdsMax);
+  const unsigned bytes = (unsigned)gmr::self_collision_repair_lds_bytes(in.n_caps, in.n_pairs, lds);
+  if (lds) hipLaunchKernelGGL(gmr::self_collision_repair_kernel<true>, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), bytes, st, a);
+  else hipLaunchKernelGGL(gmr::self_collision_repair_kernel<false>, dim3((unsigned)in.n_seq, ty), dim3(gmr::kFkWave), bytes, st, a);
+  if (stats) hipLaunchKernelGGL(gmr::self_collision_repair_stats_kernel, dim3((unsigned)in.n_seq), dim3(gmr::kFkWave), 0, st, a);
+  if (hipGetLastError() != hipSuccess) { set_err(m, "kernel launch failed"); return GMR_EDEVICE; }
+  return GMR_OK;
+}
+
+int gmr_motion_self_collision_repair(gmr_model *m, const gmr_self_collision_repair_input *in) {
+  if (!m) return GMR_EINVAL;
+  m->err.clear();
+  if (!in) { set_err(m, "null input"); return GMR_EINVAL; }
+  if (in->n_frames < 0 || in->n_seq < 0 || in->n_caps < 0 || in->n_pairs < 0) { set_err(m, "negative count"); return GMR_EINVAL; }
+  if (!std::isfinite(in->margin)) { set_err(m, "margin must be finite"); return GMR_EINVAL; }
+  if (in->iterations < 1 || in->iterations > gmr::kScrMaxIters) { set_err(m, "iterations must be 1 .. %d", gmr::kScrMaxIters); return GMR_EINVAL; }
+  if (!(in->damping > 0.0) || !std::isfinite(in->damping)) { set_err(m, "damping must be finite and > 0"); return GMR_EINVAL; }
+  if (!(in->step_cap > 0.0) || !std::isfinite(in->step_cap)) { set_err(m, "step_cap must be finite and > 0"); return GMR_EINVAL; }
+  if (!(in->resolve_tol >= 0.0) || !std::isfinite(in->resolve_tol)) { set_err(m, "resolve_tol must be finite and >= 0"); return GMR_EINVAL; }
+  if (in->qpos_out && in->qpos_out == in->qpos) { set_err(m, "qpos_out must not alias qpos"); return GMR_EINVAL; }
+  if (m->dm.root_planar) { set_err(m, "the self-collision repair needs a free-joint root; a planar base is not supported"); return GMR_EUNSUPPORTED; }
+  const int nb = m->h.nbody;
+  if (nb > gmr::kFkWave || m->fk.ndof + 7 > gmr::kScrRow) { set_err(m, "a model of %d bodies does not fit the self-collision tile", nb); return GMR_EUNSUPPORTED; }
+  if (in->n_caps > gmr::kScrMaxCaps) { set_err(m, "at most %d capsules per call", gmr::kScrMaxCaps); return GMR_EUNSUPPORTED; }
+  if (in->n_pairs > gmr::kScrMaxPairs) { set_err(m, "at most %d pairs per call", gmr::kScrMaxPairs); return GMR_EUNSUPPORTED; }
+  const bool stats = in->repaired_frames_out || in->unresolved_frames_out || in->move_max_out || in->clearance_min_after_out ||
+                     in->nonfinite_frames_out;
+  if (in->n_frames == 0 || in->n_seq == 0) return GMR_OK;   // (an array of no rows may well be a NULL pointer)
+  if (stats && (!in->clearance_before_out || !in->clearance_after_out || !in->move_out)) {
+    set_err(m, "the statistics are reduced from clearance_before_out, clearance_after_out and move_out: all three are required"); return GMR_EINVAL;
+  }
+  if (in->n_caps < 1 || in->n_pairs < 1) { set_err(m, "n_caps and n_pairs must be at least 1"); return GMR_EINVAL; }
+  if (!in->qpos || !in->seq_offsets || !in->cap_body || !in->cap_p0 || !in->cap_p1 || !in->cap_radius || !in->pairs || !in->qpos_out) {
+    set_err(m, "null argument"); return GMR_EINVAL;
+  }
+  return self_collision_repair_run(m, *in, stats, static_cast<hipStream_t>(in->stream));
 }
 
 // ------------------------------------------------------------------ mirror augmentation (mirror_kernel.hip.h)

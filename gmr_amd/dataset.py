@@ -84,7 +84,7 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
                    human_heights: Optional[Sequence[float]] = None, clip_start: str = "qpos0", report: bool = False,
                    track_fps: Optional[float] = None, lowpass_hz: Optional[float] = None,
                    contact_bodies: Optional[Sequence[str]] = None, contact=None, lock_feet=False, dynamics: bool = False,
-                   collision=None, mirror=False, retime=None, retime_torque=None):
+                   collision=None, mirror=False, retime=None, retime_torque=None, resolve_collisions=False):
     """The whole ``process_file`` compute path for a batch of clips: batched IK, FK, post-processing.  ``human_heights``:
     one ``actual_human_height`` per clip (the per-file ``GMR(..., actual_human_height=...)`` of
     scripts/smplx_to_robot_dataset.py:79-83).  ``clip_start``: ``retarget_batch``'s (``"root_target"`` is the opt-in departure
@@ -107,7 +107,10 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     hinge was too fast; the clip report stays that of the solved clips (a retimed frame has no human targets to be compared with).
     With ``retime_torque`` (``True``, or ``retime_to_torque_limits``' ``limit_scale``) the (smoothed, velocity-retimed) qpos is then
     retimed to the robot's torque limits, in the same place.  Torques are second differences of qpos and those of unfiltered IK
-    output are noise (``dynamics_from_qpos``): give ``lowpass_hz`` with it."""
+    output are noise (``dynamics_from_qpos``): give ``lowpass_hz`` with it.  With ``resolve_collisions`` (``True``, or a dict of
+    ``resolve_self_collisions``' keywords) the (smoothed, retimed) qpos then goes through ``resolve_self_collisions``, before the
+    mirror images, the motions, the dynamics and self-collision reports, the foot locking and the tracks are made from it; the clip
+    report stays that of the solved clips."""
     mirror_kw = dict(mirror) if isinstance(mirror, dict) else {}
     if mirror and mirror_kw.get("plan") is None:
         gmr.symmetry_plan()  # (SymmetryError here, before any solve)
@@ -135,6 +138,8 @@ def retarget_clips(gmr: GeneralMotionRetargeting, pos, quat, body_names: Sequenc
     if retime_torque is not None and retime_torque is not False:
         scale = {} if retime_torque is True else {"limit_scale": float(retime_torque)}
         qpos, seq_offsets, _ = retime_to_torque_limits(gmr, qpos, seq_offsets, fps, **scale)
+    if resolve_collisions:
+        qpos, _ = resolve_self_collisions(gmr, qpos, seq_offsets, **(resolve_collisions if isinstance(resolve_collisions, dict) else {}))
     q_all, offs_all, fps_all = augment_mirror(gmr, qpos, seq_offsets, fps, **mirror_kw) if mirror else (qpos, seq_offsets, fps)
     res = (motions_from_qpos(gmr, q_all, offs_all, fps_all, height_adjust=height_adjust, root_origin_offset=root_origin_offset),)
     if rep is not None:
@@ -526,6 +531,49 @@ def _self_collision_report(eng, qpos, seq_offsets, capsules=None, pairs=None, ma
                                for p in rep["worst_pair"]]
     rep["penetration_max"] = np.maximum(0.0, -rep["clearance_min"])
     return rep
+
+
+def resolve_self_collisions(gmr: GeneralMotionRetargeting, qpos: torch.Tensor, seq_offsets: Sequence[int], radius: float = 0.03,
+                            capsules=None, pairs=None, margin: float = 0.0, freeze_joints: Sequence[str] = (),
+                            freeze_bodies: Sequence[str] = (), **repair_kwargs):
+    """Push the colliding capsule pairs of qpos ``[N, nq]`` float64 on the GPU (concatenated clips) apart
+    (``Engine.motion_self_collision_repair``; the definition is the contract above ``gmr_self_collision_repair_input`` in
+    include/gmr_amd.h) -> ``(qpos_out, info)``: the repaired rows, a device tensor, and host arrays with one row per clip --
+    ``repaired_frames``, ``unresolved_frames``, ``move_max`` (rad), ``clearance_min_after`` (m), ``nonfinite_frames`` -- plus
+    ``clearance_before`` / ``clearance_after`` / ``move`` ``[N]``.  ``capsules`` / ``pairs``: ``gmr_amd.collision`` tables; ``None``: the
+    skeleton's capsules of ``radius`` and ``default_pairs(robot, capsules, rest_margin=margin)``, so that a pair which rests
+    below the margin, and which no hinge changes, does not stay unresolved forever.  ``freeze_joints`` / ``freeze_bodies``:
+    ``gmr_amd.collision.movable_mask`` -- freezing the ankle links keeps a locked foot where ``lock_feet`` put it.
+    ``repair_kwargs``: ``iterations``, ``damping``, ``step_cap``, ``resolve_tol``; their defaults (16 passes, 1e-6 m^2, 0.2 rad,
+    1e-4 m) and the radius are conventions, not measured on a robot.  The velocity of the result has a kink where a pair enters
+    the margin: ``smooth_qpos`` afterwards is the user's tool."""
+    return _resolve_self_collisions(gmr._engine, qpos, seq_offsets, radius, capsules, pairs, margin, freeze_joints, freeze_bodies,
+                                    repair_kwargs)
+
+
+def _resolve_self_collisions(eng, qpos, seq_offsets, radius=0.03, capsules=None, pairs=None, margin=0.0, freeze_joints=(),
+                             freeze_bodies=(), repair_kwargs=None):
+    """``resolve_self_collisions`` on an ``Engine``."""
+    from . import collision
+    if capsules is None:
+        capsules, default = eng.default_proxies(radius)
+        if pairs is None and float(margin) == 0.0:
+            pairs = default
+    if pairs is None:
+        if float(margin) == 0.0:
+            pairs = eng.resolve_proxies(capsules, None)[1]
+        else:   # (built once per capsule table and margin, as the engine's own defaults are)
+            key = ("pairs", id(capsules), float(margin))
+            if key not in eng._collision_default:
+                import weakref
+                eng._collision_default[key] = collision.default_pairs(eng.cm.robot, capsules, rest_margin=float(margin))[0]
+                weakref.finalize(capsules, eng._collision_default.pop, key, None)
+            pairs = eng._collision_default[key]
+    mask = collision.movable_mask(eng.cm.robot, freeze_joints, freeze_bodies)
+    offs = np.ascontiguousarray(seq_offsets, dtype=np.int64)
+    got = eng.motion_self_collision_repair(qpos, offs, capsules, pairs, margin=margin, movable=mask, **(repair_kwargs or {}))
+    info = {k: v.cpu().numpy() for k, v in got.items() if k != "qpos"}
+    return got["qpos"], info
 
 
 def write_collision_csv(path: str, names: Sequence[str], report: Dict, append: bool = False) -> None:

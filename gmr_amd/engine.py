@@ -536,6 +536,74 @@ def _self_collision_input(eng: "Engine", qpos, seq_offsets, capsules, pairs, mar
     return ci, MotionSelfCollision(res), [qpos, offs, dev_table]
 
 
+SELF_COLLISION_REPAIR_FIELDS = _native.SELF_COLLISION_REPAIR_OUTPUTS   # the arrays of the repair, in gmr_self_collision_repair_input's order
+SELF_COLLISION_REPAIR_STATS = _native.SELF_COLLISION_REPAIR_STATS      # of them the per-clip statistics
+# 16 passes, lambda^2 = 1e-6 m^2, steps of at most 0.2 rad, 0.1 mm left over counts as resolved: conventions, not measured on a robot
+SELF_COLLISION_REPAIR_DEFAULTS = {"iterations": 16, "damping": 1e-6, "step_cap": 0.2, "resolve_tol": 1e-4}
+
+
+class MotionSelfCollisionRepair(dict):
+    """Result of ``motion_self_collision_repair``: the device tensors by name (``SELF_COLLISION_REPAIR_FIELDS``).  ``qpos`` ``[N, nq]``
+    float64, the repaired rows.  Per frame ``[N]`` float64: ``clearance_before``, ``clearance_after`` (NaN in a frame that is not
+    evaluated), ``move`` (the largest change of a hinge, rad).  Per clip ``[S]`` (``SELF_COLLISION_REPAIR_STATS``):
+    ``repaired_frames``, ``unresolved_frames``, ``nonfinite_frames`` int32, ``move_max``, ``clearance_min_after`` float64."""
+
+    def statistics(self) -> dict:
+        return {k: self[k] for k in SELF_COLLISION_REPAIR_STATS if k in self}
+
+
+def _self_collision_repair_input(eng: "Engine", qpos, seq_offsets, capsules, pairs, margin, iterations, damping, step_cap, resolve_tol,
+                                 movable, out, stats):
+    """Check the arguments of one repair call and fill its ``SelfCollisionRepairInput`` (all but the stream).  Returns (input,
+    MotionSelfCollisionRepair, keep-alive)."""
+    dev = eng.device
+    if eng.cm.robot.planar_base:
+        raise NotImplementedError("the self-collision repair assumes a free-joint root; a planar-base robot is not supported")
+    N = _qpos_rows(qpos, eng.nq, dev)
+    offs = _clip_offsets(seq_offsets, dev)
+    S = int(offs.shape[0]) - 1
+    if not np.isfinite(margin):
+        raise ValueError("margin must be finite")
+    if not 1 <= int(iterations) <= _native.SELF_COLLISION_REPAIR_MAX_ITERATIONS:
+        raise ValueError(f"iterations must be 1 .. {_native.SELF_COLLISION_REPAIR_MAX_ITERATIONS}")
+    if not (np.isfinite(damping) and damping > 0.0 and np.isfinite(step_cap) and step_cap > 0.0):
+        raise ValueError("damping and step_cap must be finite and > 0")
+    if not (np.isfinite(resolve_tol) and resolve_tol >= 0.0):
+        raise ValueError("resolve_tol must be finite and >= 0")
+    nh = eng.nq - 7
+    mask = (1 << 64) - 1 if movable is None else int(movable)
+    if mask < 0 or mask >> 64:
+        raise ValueError("movable is a 64-bit mask, bit i for hinge i in qpos order (gmr_amd.collision.movable_mask)")
+    dev_table = eng.collision_device(capsules, pairs)
+    f64, i32 = torch.float64, torch.int32
+    shapes = {"qpos": ((N, eng.nq), f64), "clearance_before": ((N,), f64), "clearance_after": ((N,), f64), "move": ((N,), f64),
+              "repaired_frames": ((S,), i32), "unresolved_frames": ((S,), i32), "move_max": ((S,), f64),
+              "clearance_min_after": ((S,), f64), "nonfinite_frames": ((S,), i32)}
+    # rows outside every clip are not written, and a call without rows launches nothing: what an empty clip reports
+    fill = {"clearance_before": float("nan"), "clearance_after": float("nan"), "clearance_min_after": float("inf")}
+
+    def alloc(k, sh, dt):
+        if k == "qpos":
+            return qpos.clone()
+        return torch.full(sh, fill.get(k, 0), dtype=dt, device=dev) if stats or k in _native.SELF_COLLISION_REPAIR_FRAME_OUTPUTS else None
+
+    ri = _native.SelfCollisionRepairInput()
+    res = _named_outputs(ri, out, SELF_COLLISION_REPAIR_FIELDS, shapes, dev, "SELF_COLLISION_REPAIR_FIELDS", alloc)
+    if "qpos" not in res:
+        raise EngineError("out must hold qpos: the repaired rows are the call's result")
+    if res["qpos"].numel() and res["qpos"].data_ptr() == qpos.data_ptr():
+        raise EngineError("out['qpos'] must not be qpos: the call does not work in place")
+    if set(res) & set(SELF_COLLISION_REPAIR_STATS) and not set(_native.SELF_COLLISION_REPAIR_FRAME_OUTPUTS) <= set(res):
+        raise EngineError("out must hold clearance_before, clearance_after and move when it holds a statistic: the statistics are reduced from them")
+    ri.qpos, ri.n_frames, ri.seq_offsets, ri.n_seq = qpos.data_ptr(), N, offs.data_ptr(), S
+    ri.n_caps, ri.n_pairs, ri.margin = int(dev_table["cap_body"].shape[0]), int(dev_table["pairs"].shape[0]), float(margin)
+    ri.iterations, ri.damping, ri.step_cap, ri.resolve_tol = int(iterations), float(damping), float(step_cap), float(resolve_tol)
+    ri.hinge_mask = mask & ((1 << nh) - 1 if nh < 64 else (1 << 64) - 1)
+    for k in _native.SELF_COLLISION_TABLE:
+        setattr(ri, k, dev_table[k].data_ptr())
+    return ri, MotionSelfCollisionRepair(res), [qpos, offs, dev_table]
+
+
 class MotionTransitions(dict):
     """Result of ``motion_transitions``: the device tensors by name -- ``points`` ``[N, P, 3]`` and ``moments`` ``[N, 6]`` float64,
     ``best_cost`` ``[E, D]`` float64 (``inf`` where a source has no target frame), ``best_frame`` ``[E, D]`` int32 (``-1`` there) and,
@@ -1287,6 +1355,33 @@ class Engine:
         ci, res, keep = _self_collision_input(self, qpos, seq_offsets, capsules, pairs, margin, out, stats)
         ci.stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self._lib.gmr_motion_self_collision(self._h, C.byref(ci)), "gmr_motion_self_collision")
+        return res
+
+    def motion_self_collision_repair(self, qpos: torch.Tensor, seq_offsets, capsules=None, pairs=None, margin: float = 0.0,
+                                     iterations: int = SELF_COLLISION_REPAIR_DEFAULTS["iterations"],
+                                     damping: float = SELF_COLLISION_REPAIR_DEFAULTS["damping"],
+                                     step_cap: float = SELF_COLLISION_REPAIR_DEFAULTS["step_cap"],
+                                     resolve_tol: float = SELF_COLLISION_REPAIR_DEFAULTS["resolve_tol"], movable=None, out=None,
+                                     stats: bool = True, stream=None) -> MotionSelfCollisionRepair:
+        """Push the colliding capsule pairs of qpos ``[N, nq]`` float64 (engine layout, concatenated clips) apart in two kernels
+        (``gmr_motion_self_collision_repair``; the definition is the contract in include/gmr_amd.h): in every frame in which a
+        pair of the table is closer than ``margin``, ``iterations`` damped projection passes (``damping`` = lambda^2 in m^2, steps
+        of at most ``step_cap`` rad) over the hinges between the pair's two bodies move it back to the margin; a frame below
+        ``margin - resolve_tol`` afterwards counts as unresolved.  The defaults (16 passes, 1e-6 m^2, 0.2 rad, 1e-4 m) are
+        conventions, not measured on a robot.  ``seq_offsets``, ``capsules`` and ``pairs`` as in :meth:`motion_self_collision`.
+        ``movable``: a 64-bit mask, bit ``i`` for hinge ``i`` in qpos order (``gmr_amd.collision.movable_mask``; ``None``: every
+        hinge).  The root never moves.  ``stats=False`` leaves the per-clip statistics out (one kernel).  Returns a
+        :class:`MotionSelfCollisionRepair` of device tensors; ``out``: caller-owned result tensors by name (``qpos`` is required
+        and must not be the input; a name left out is not computed; a statistic needs the three per-frame arrays).  ``stream``: a
+        ``torch.cuda.Stream`` (``None``: the current one).  Asynchronous; with ``out``, cached tables and a device ``seq_offsets``
+        no allocation, no copy, no synchronisation.  A planar base is refused."""
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        with torch.cuda.stream(st):
+            capsules, pairs = self.resolve_proxies(capsules, pairs)
+            ri, res, keep = _self_collision_repair_input(self, qpos, seq_offsets, capsules, pairs, margin, iterations, damping, step_cap,
+                                                         resolve_tol, movable, out, stats)
+        ri.stream = st.cuda_stream
+        self._check(self._lib.gmr_motion_self_collision_repair(self._h, C.byref(ri)), "gmr_motion_self_collision_repair")
         return res
 
     def symmetry_plan(self):

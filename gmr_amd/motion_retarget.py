@@ -438,6 +438,17 @@ class GeneralMotionRetargeting:
         tq = (torch.from_numpy(np.ascontiguousarray(qpos)) if isinstance(qpos, np.ndarray) else qpos).to(self.device, torch.float64).contiguous()
         return self_collision_report(self, tq, seq_offsets, capsules, pairs, margin, radius)
 
+    def resolve_self_collisions(self, qpos, seq_offsets, radius: float = 0.03, capsules=None, pairs=None, margin: float = 0.0,
+                                freeze_joints=(), freeze_bodies=(), **repair_kwargs):
+        """Push the colliding capsule pairs of retargeted qpos ``[N, nq]`` (numpy or CUDA torch, engine layout, concatenated clips)
+        apart on the GPU (``dataset.resolve_self_collisions``, ``Engine.motion_self_collision_repair``): what
+        ``self_collision_report`` measures, this removes.  Returns ``(qpos_out, info)``: the repaired rows (a CUDA tensor) and the
+        per-clip statistics as host arrays.  The defaults (16 passes, damping 1e-6 m^2, steps of 0.2 rad, 1e-4 m tolerance, capsules
+        of ``radius`` along the skeleton's links) are conventions, not measured on a robot."""
+        from .dataset import resolve_self_collisions
+        tq = (torch.from_numpy(np.ascontiguousarray(qpos)) if isinstance(qpos, np.ndarray) else qpos).to(self.device, torch.float64).contiguous()
+        return resolve_self_collisions(self, tq, seq_offsets, radius, capsules, pairs, margin, freeze_joints, freeze_bodies, **repair_kwargs)
+
     def symmetry_plan(self, **tol):
         """The robot's left-right symmetry plan (``gmr_amd.symmetry.plan_symmetry``): which body mirrors which, and the permutation
         and signs of the hinge columns.  Without arguments the engine's cached plan at the default tolerances; ``tol_pos``,

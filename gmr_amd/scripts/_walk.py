@@ -120,6 +120,7 @@ def add_common_flags(ap) -> None:
     ap.add_argument("--mirror_plan", default=None, type=str, metavar="FILE.json", help="with --mirror: the symmetry plan from this file (gmr_amd.symmetry.save_plan writes one) instead of the robot's own; with --robots: robot:file;robot2:file2")
     ap.add_argument("--retime_to_limits", nargs="?", const=True, default=None, type=float, metavar="RAD_PER_S", help="play every solved clip slower exactly where a hinge turns faster than its velocity limit (dataset.retime_to_limits, on the GPU: a monotone time warp, resampled at the clip's rate) before the pickles, the dynamics and collision reports and the tracking exports are made; the clip report stays that of the solved clips; with a number: that limit on every hinge; without: the retargeter's limits (--use_velocity_limit / --velocity_limit), else 3 pi rad/s on every limited hinge; not with --robots; default: off")
     ap.add_argument("--retime_to_torque", nargs="?", const=True, default=None, type=float, metavar="SCALE", help="play every solved clip slower exactly where a hinge needs more torque than its actuator has (dataset.retime_to_torque_limits, on the GPU: inverse dynamics, a time warp and a cubic resampling, up to four passes), after --lowpass_hz and --retime_to_limits and before the pickles, the dynamics and collision reports and the tracking exports are made; with a number: the share of the MJCF torque limits the warp is planned against (default 0.95, a convention, not measured on a robot); torques of unfiltered qpos are noise: give --lowpass_hz; not with --robots; default: off")
+    ap.add_argument("--resolve_collisions", default=False, action="store_true", help="push the colliding capsule proxies of every solved clip apart (dataset.resolve_self_collisions, on the GPU: 16 damped passes per frame over the hinges between the two capsules, steps of at most 0.2 rad -- conventions, not measured on a robot) after --lowpass_hz and the retiming and before the pickles, the dynamics and collision reports, the foot locking and the tracking exports are made; the clip report stays that of the solved clips; takes --collision_radius and --collision_proxies as --collision_csv does; not with --robots; default: off")
     ap.add_argument("--shard_by_rank", default=False, action="store_true", help="under torch.distributed.run: convert files[RANK::WORLD_SIZE] only (no exchange between ranks)")
 
 
@@ -141,6 +142,8 @@ def resolve_track(ap, args) -> None:
         ap.error("--retime_to_torque must lie in (0, 1]")
     if torque is not None and getattr(args, "robots", None):
         ap.error("--retime_to_torque is not available with --robots")
+    if getattr(args, "resolve_collisions", False) and getattr(args, "robots", None):
+        ap.error("--resolve_collisions is not available with --robots")
     resolve_contact(ap, args)
     resolve_mirror(ap, args)
 
@@ -280,6 +283,21 @@ def collision_kw(args, model=None) -> dict:
     return {"collision": kw or True}
 
 
+def resolve_collisions_kw(args, model=None) -> dict:
+    """The ``resolve_collisions`` argument of ``retarget_clips`` from the flags ({} without ``--resolve_collisions``: nothing changes
+    then): ``--collision_radius`` and ``--collision_proxies`` as ``collision_kw`` reads them."""
+    if not getattr(args, "resolve_collisions", False):
+        return {}
+    from ..collision import load_proxies
+    kw = {}
+    if getattr(args, "collision_radius", None) is not None:
+        kw["radius"] = args.collision_radius
+    if getattr(args, "collision_proxies", None) is not None:
+        caps, pr = load_proxies(args.collision_proxies, model)
+        kw.update(capsules=caps, pairs=pr)
+    return {"resolve_collisions": kw or True}
+
+
 def wants_sink(args) -> bool:
     return wants_report(args) or wants_dynamics(args) or wants_collision(args)
 
@@ -362,6 +380,8 @@ def convert(args, pairs: List[Tuple[str, str]], src_human: str, batches: Callabl
         ret_kw = {} if getattr(args, "retime_to_limits", None) is None else {"retime": args.retime_to_limits}  # (ditto)
         if getattr(args, "retime_to_torque", None) is not None:
             ret_kw["retime_torque"] = args.retime_to_torque
+        if getattr(args, "resolve_collisions", False):
+            ret_kw.update(resolve_collisions_kw(args, model=g.model))
         with dataset.MotionWriter(workers=max(1, workers), override=True) as writer:
             for batch in batches([s for s, _ in pairs], g.ik_columns):
                 for f, why in batch.skipped:

@@ -71,6 +71,8 @@
  *   gmr_motion_self_collision  (no counterpart in the reference) the self-penetration filter the consumers of the clips run on the
  *                      host in a Python loop: FK plus a segment-segment distance per capsule pair and frame, and per clip the
  *                      deepest penetration, where it happens and for how long
+ *   gmr_motion_self_collision_repair  (no counterpart in the reference) what such a consumer does with the colliding frames it
+ *                      does not drop: a host loop that pushes the colliding capsule pairs apart over the hinges between them
  *   gmr_motion_mirror  (no counterpart in the reference) the left-right mirrored copy of every clip, the augmentation a tracking or
  *                      AMP pipeline doubles its data with: a signed permutation of the hinge columns and the reflected root
  *   gmr_motion_compose (no counterpart in the reference) long reference motions from segments of the clips: each segment moved
@@ -749,6 +751,99 @@ typedef struct gmr_self_collision_input {
   int32_t       *nonfinite_frames_out;
 } gmr_self_collision_input;
 int gmr_motion_self_collision(gmr_model *m, const gmr_self_collision_input *in);
+
+/* Self-collision repair of retargeted qpos: every frame in which a capsule pair of gmr_motion_self_collision's tables comes closer
+ * than margin is moved, over the hinges between the two capsules, until the pair is at the margin again -- a fixed number of
+ * damped projection passes per frame, each frame on its own.  What gmr_motion_self_collision measures, this call removes; the
+ * reference has no collision avoidance.  The defaults of the Python layers (16 passes, damping 1e-6 m^2, step_cap 0.2 rad,
+ * resolve_tol 1e-4 m) are conventions, not measured on a robot.
+ * All arithmetic is float64 without floating-point contraction, in the written order; a dot product u.v is (u_x v_x + u_y v_y) +
+ * u_z v_z, a cross product a x b is (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x).
+ *
+ * The whole call is this struct, its stream included (in->stream, in the sense of the stream-order paragraph at the top of this
+ * file); the struct is read completely before the call returns.  The call enqueues two kernels on in->stream (one when no
+ * statistic is asked for) and nothing else: no allocation, no copy, no synchronisation.  All arrays are device arrays.
+ *   qpos, n_frames, seq_offsets, n_seq, cap_body, cap_p0, cap_p1, cap_radius, pairs, n_caps, n_pairs, margin
+ *                 as in gmr_self_collision_input, with its clamping rules (rows a .. b of clip s, cap_body into [0, nbody), pairs
+ *                 into [0, n_caps)) and its FK (gmr_motion_footlock's: MuJoCo's convention, the root quaternion divided by its norm)
+ *   iterations    I, 1 .. 32: the passes of a frame
+ *   damping       lambda^2 > 0, in m^2
+ *   step_cap      > 0, in rad: the largest change of a hinge in one pass
+ *   resolve_tol   >= 0, in m: a frame whose clearance_after is below margin - resolve_tol counts as unresolved
+ *   hinge_mask    by value; bit i set: hinge i, in qpos order (column 7 + i), may move
+ * Definition, per frame of a clip, independently of every other frame.  A frame with a non-finite entry in its row is not
+ * evaluated: its row is copied, clearance_before and clearance_after are NaN, move is 0.  Otherwise q0 is the row's own hinges,
+ * q = q0, and the following pass runs exactly I times:
+ *   1  the poses of all bodies at q (x_j, unit quaternion r_j), the capsule ends, and for every pair p = (A on body X, B on body Y)
+ *      the report's s and t:  a_p = p1 + s d1,  b_p = p2 + t d2,  w = a_p - b_p,  nw = sqrt(w.w),  c_p = nw - (r_A + r_B)
+ *   2  anc(b): the hinges on the path from the root to body b, b's own included.  M_p = (anc(X) xor anc(Y)) and hinge_mask.  (A
+ *      shared ancestor moves both capsules rigidly and is left out by definition.  The root never moves.)
+ *   3  v_p = margin - c_p when that is > 0 and M_p is not empty, else 0 (0 for a NaN).  V = sum_p v_p, pairs in ascending index
+ *      from 0.0.  If V is not > 0, this pass and all later passes change nothing.
+ *   4  n = w / nw when nw > 0, else 0
+ *   5  hinge i on body j has the world axis u_i = rot(r_j, axis_j) and the anchor o_i = x_j.
+ *        g_pi = n . (u_i x (a_p - o_i))      for i in M_p and anc(X)
+ *        g_pi = -(n . (u_i x (b_p - o_i)))   for i in M_p and anc(Y)
+ *        g_pi = 0                            elsewhere
+ *      (the exact derivative of nw with the closest-point parameters s, t held fixed)
+ *   6  rho_p = v_p / (sum_i g_pi g_pi + lambda^2), hinges in ascending qpos order from 0.0;
+ *      dq_i = (sum_p (v_p rho_p) g_pi) / V, pairs in ascending index from 0.0.  (A simultaneous projection with the weights v_p / V,
+ *      which are continuous in the pose; a single colliding pair is moved exactly to the margin of its linearisation.)
+ *   7  m = max_i |dq_i|, scale = m > step_cap ? step_cap / m : 1;  for every hinge of hinge_mask with dq_i != 0:
+ *      q_i = clamp(q_i + scale dq_i, min(lo_i, q0_i), max(hi_i, q0_i)) for a limited hinge, unclamped otherwise (gmr_motion_footlock's
+ *      rule); a hinge with dq_i = 0 keeps its bits.
+ * After the last pass the clearances are evaluated once more at the final q.  The order of the two sums is part of the definition;
+ * how the kernel forms them is its own business and results agree with the definition to rounding (as gmr_motion_dynamics').
+ * Nothing in the map is a discrete choice except v_p > 0, whose contribution vanishes at the threshold: the map is continuous in
+ * the row.  A pair whose segments' axes cross (nw = 0) has no normal and is not moved.
+ * Outputs, device arrays:
+ *   qpos_out [n_frames][nq] f64         required, must not alias qpos.  The rows with the final hinges.  Every other entry -- the
+ *                                       root's seven, hinges outside hinge_mask, frames with V = 0 in the first pass, frames with a
+ *                                       non-finite entry -- is copied bit for bit
+ *   clearance_before_out [n_frames] f64 the minimum of c_p over all pairs at q0; NaN when any c_p is NaN (the report's rule: a zero
+ *                                       root quaternion gives a NaN frame) and in a frame with a non-finite entry.  May be NULL
+ *   clearance_after_out [n_frames] f64  the same at the final q.  May be NULL
+ *   move_out [n_frames] f64             max_i |q_i - q0_i| over the hinges, 0 without one.  May be NULL
+ * Per-clip statistics, any may be NULL, reduced by the second kernel from the three per-frame arrays (all three are required when
+ * a statistic is asked for).  A frame whose clearance_after is NaN is counted in nonfinite_frames and takes part in no other
+ * statistic:
+ *   repaired_frames_out [n_seq] i32       frames with move > 0
+ *   unresolved_frames_out [n_seq] i32     frames with clearance_after < margin - resolve_tol
+ *   move_max_out [n_seq] f64              the maximum of move, 0 without a frame
+ *   clearance_min_after_out [n_seq] f64   the minimum of clearance_after; +inf for a clip without a finite frame
+ *   nonfinite_frames_out [n_seq] i32
+ * A clip without frames reports 0, 0, 0, +inf, 0.  Rows outside every clip are not written.  Two calls give identical bytes.
+ * Non-finite input reaches only its own frame and its own clip's statistics.
+ * GMR_EINVAL: I outside 1 .. 32, damping or step_cap not finite and > 0, a negative or non-finite resolve_tol, a non-finite margin,
+ * qpos_out == qpos, negative counts, and with work to do: NULL arrays, a statistic without the three per-frame arrays, n_caps < 1
+ * or n_pairs < 1.  GMR_EUNSUPPORTED: a model of more than 64 bodies (and with them more than 64 hinges: a hinge is a body's), a
+ * model in which a body precedes its parent, n_caps > 256, n_pairs > 32768, a planar-base model (a planar-base qpos the caller
+ * holds is not in free-joint layout).  These are checked before anything is enqueued.  n_frames = 0 or n_seq = 0 returns GMR_OK
+ * without a launch.  Asynchronous on in->stream; the handle's device is selected.
+ * Layout (LP64): sizeof 200; offsets qpos 0, n_frames 8, seq_offsets 16, n_seq 24, n_caps 28, n_pairs 32, iterations 36,
+ * cap_body 40, cap_p0 48, cap_p1 56, cap_radius 64, pairs 72, margin 80, damping 88, step_cap 96, resolve_tol 104,
+ * hinge_mask 112, stream 120, qpos_out 128, clearance_before_out 136, clearance_after_out 144, move_out 152,
+ * repaired_frames_out 160, unresolved_frames_out 168, move_max_out 176, clearance_min_after_out 184,
+ * nonfinite_frames_out 192.  */
+typedef struct gmr_self_collision_repair_input {
+  const double  *qpos;            /* device [n_frames][nq] f64 */
+  int64_t        n_frames;
+  const int64_t *seq_offsets;     /* DEVICE [n_seq+1] */
+  int32_t        n_seq, n_caps;
+  int32_t        n_pairs, iterations;
+  const int32_t *cap_body;        /* device [n_caps] */
+  const double  *cap_p0, *cap_p1, *cap_radius;   /* device [n_caps][3], [n_caps][3], [n_caps] */
+  const int32_t *pairs;           /* device [n_pairs][2] */
+  double         margin, damping, step_cap, resolve_tol;
+  uint64_t       hinge_mask;      /* bit i: hinge i (qpos column 7 + i) may move */
+  void          *stream;          /* the call's stream */
+  double        *qpos_out;
+  double        *clearance_before_out, *clearance_after_out, *move_out;
+  int32_t       *repaired_frames_out, *unresolved_frames_out;
+  double        *move_max_out, *clearance_min_after_out;
+  int32_t       *nonfinite_frames_out;
+} gmr_self_collision_repair_input;
+int gmr_motion_self_collision_repair(gmr_model *m, const gmr_self_collision_repair_input *in);
 
 /* The left-right mirrored copy of retargeted qpos: every row's hinge columns permuted with signs, its root reflected.  Which
  * column is the image of which is the caller's table (gmr_amd/symmetry.py derives it from the kinematic tree and refuses a
