@@ -686,7 +686,10 @@ __device__ __forceinline__ void cross_t(const T a[3], const T b[3], T o[3]) {
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 // T = double: the block in float64 (T = float was round 2's mixed-precision experiment).
-template <class T>
+// LIT (plain shaped instances, kSolveControl; the caller's s must be lane & 3, the quad layout of the task lanes): the store region
+// `s < 3` -- lanes 0..2 of every quad, the same in every model -- is entered from a literal mask where it is used; as a compare it is hoisted to the top of the work item, and its scalar pair was one of the spilled
+// values a solve reloaded (two v_readlane_b32 per solve).
+template <class T, bool LIT = false>
 __device__ __forceinline__ void task_block_quad(int s, const double e64[6], double kap64, double bet64, const double rs64[3],
                                                 const double xb64[3], double wp64, double wr64, T *out) {
   const T e[6] = {(T)e64[0], (T)e64[1], (T)e64[2], (T)e64[3], (T)e64[4], (T)e64[5]};
@@ -729,7 +732,9 @@ __device__ __forceinline__ void task_block_quad(int s, const double e64[6], doub
   const T wp2 = wp * wp, wr2 = wr * wr;
   const T uu = dot(uc, uc), uu1 = dot(uc, u1);
   const T ev[3] = {wp2 * e[0], wp2 * e[1], wp2 * e[2]}, ew[3] = {wr2 * e[3], wr2 * e[4], wr2 * e[5]};
-  if (s < 3) {
+  bool writes = s < 3;
+  if constexpr (LIT) writes = __builtin_amdgcn_inverse_ballot_w64(kmask<0x77777777u>());
+  if (writes) {
     out[s] = wp2 * uu;                                   // LL(s,s)
     out[3 + s] = wp2 * uu1;                              // LL(s,s+1)
     out[6 + s] = wp2 * dot(uc, vc);                      // LA(s,s)
@@ -972,7 +977,9 @@ __device__ __forceinline__ void static_for_down(F &&f) {  // I = N-1 .. I
   }
 }
 
-template <int NL = -1>  // NL >= 0: the number of limb rows per group as a compile-time value (a shaped instance); nl is then unused
+// NL >= 0: the number of limb rows per group as a compile-time value (a shaped instance); nl is then unused.
+// SEL (plain shaped instances, kSolveControl): the start point and working set are set with selects instead of nested branches.
+template <int NL = -1, bool SEL = false>
 __device__ __forceinline__ int box_qp_struct(int lane, int nl, bool owner, bool pad, const double *Hs, double ci, double lo,
                                              double hi, int &status, double &x_out) {
   const int a = lane & 15;           // local row
@@ -980,7 +987,14 @@ __device__ __forceinline__ int box_qp_struct(int lane, int nl, bool owner, bool 
   const bool core_row = a >= shp<NL>(nl);
   const bool shadow = !owner && !pad;  // copy of a core dof in groups 1..3: mirrors the owner in group 0 (lane a)
   double x = 0.0;
-  if (owner) {
+  if constexpr (SEL) {
+    // The same four cases in the same priority order as selects -- the values are copies of lo / hi / 0 and small
+    // integers, and a nest of four divergent regions (ten branches) in front of every solve becomes straight-line code.
+    const bool at_lo = status == 1, at_hi = !at_lo && status == 2, loose = !at_lo && !at_hi;
+    const bool to_lo = loose && lo > 0.0, to_hi = loose && !to_lo && hi < 0.0;
+    x = owner && (at_lo || to_lo) ? lo : (owner && (at_hi || to_hi) ? hi : 0.0);
+    status = owner && to_lo ? 1 : (owner && to_hi ? 2 : status);
+  } else if (owner) {
     if (status == 1) x = lo;
     else if (status == 2) x = hi;
     else if (lo > 0.0) { x = lo; status = 1; }
@@ -1247,6 +1261,12 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
   // to table 0 at the top of every frame).  Every other instance reads its tables at the stage's entry, as before.
   constexpr bool kStageShared = SQ && SH::stage_shared > 0;
   constexpr bool kPrmAtTop = SQ && kPlain;  // the solve's launch parameters in one batch of scalar loads at its top (below)
+  // Control code of the solve, plain shaped instances: the QP entry as selects (box_qp_struct SEL), the task block's store region from a
+  // literal mask (task_block_quad LIT) and the integrate step's dof-kind predicates compared where they are used.
+  constexpr bool kSolveControl = SQ && kPlain;
+  if constexpr (kSolveControl)
+    static_assert(SH::ntask0 >= 1 && SH::ntask0 <= 16 && SH::ntask1 >= 1 && SH::ntask1 <= 16,
+                  "the literal store mask of task_block_quad is the quad layout's (ts = lane & 3): at most 16 tasks in either table");
   int sh_body = 0, sh_slot = 0, sh_comp = 0;
   double sh_wp = 0.0, sh_wr = 0.0, sh_wp_next = 0.0, sh_wr_next = 0.0;
   unsigned sh_cadr[kCompRegs > 0 ? kCompRegs : 1][5] = {};
@@ -1552,7 +1572,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
       for (;;) {
         // ---- per-task 6x6 blocks ----
         GMR_DUP(3) if (is_task) {
-          if (quad) task_block_quad<blk_t>(ts, e, jl_kap, jl_bet, t_rs, t_xb, t_wp, t_wr, reinterpret_cast<blk_t *>(Bt + kBT * tl));
+          if (quad) task_block_quad<blk_t, kSolveControl>(ts, e, jl_kap, jl_bet, t_rs, t_xb, t_wp, t_wr, reinterpret_cast<blk_t *>(Bt + kBT * tl));
           else {
             task_block(t_body, xpos, xquat, e, jl_kap, jl_bet, t_wp, t_wr, Bt + kBT * tl);
           }
@@ -1720,7 +1740,7 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
           if constexpr (kCap) { s_lo = fmax(s_lo, -sq_cap); s_hi = fmin(s_hi, sq_cap); }
           double xs;
           GMR_DUP_QP_TWICE();
-          qit = box_qp_struct<SH::nlimb>(lane, m.sq_nlimb, sq_own, sq_pad, Hm, s_ci, s_lo, s_hi, sq_status, xs);
+          qit = box_qp_struct<SH::nlimb, kSolveControl>(lane, m.sq_nlimb, sq_own, sq_pad, Hm, s_ci, s_lo, s_hi, sq_status, xs);
           const double x_back = __shfl(xs, sq_owner_lane);
           dq = real_row ? x_back : 0.0;
         } else {
@@ -1739,8 +1759,11 @@ __device__ __forceinline__ void ik_body(DevModelG &m, IkLaunchK *Lk, const LdsLa
         // ---- integrate (mj_integratePos): translations and hinges here, the root rotation inside the FK that follows ----
         const double wx = rdlane(dq, 3), wy = rdlane(dq, 4), wz = rdlane(dq, 5);
         if (real_row) {
-          if (a_kind < 3) q[a_kind] += dq;
-          else if (a_kind == 6) q[a_qadr] += dq;
+          // (plain shaped instances: the two predicates are compared here, from the dof kind in its register; hoisted, their masks
+          // were spilled scalar pairs, reloaded with four v_readlane_b32 per solve)
+          const int kind = kSolveControl ? launder(a_kind) : a_kind;
+          if (kind < 3) q[kind] += dq;
+          else if (kind == 6) q[a_qadr] += dq;
         }
         __syncthreads();
         GMR_STAMP(9);
